@@ -31,7 +31,7 @@
     `python3 bench.py --gpus N` starts the N ranks itself (fresh child processes, one per GPU,
     before anything touches a GPU); under torchrun (WORLD_SIZE set) it is one of the ranks.
 
-    The same line carries BASELINE configs[2] / [3] under "corpus15" (the leg below with at most
+    With --full the same line carries BASELINE configs[2] / [3] under "corpus15" (the leg below with at most
     3 steps; --no-corpus15 skips it): queries/s on the 7.5 GB corpus next to the CPU path.  At N > 1 a
     failure or hang of that leg does not cost the line its configs[1] result ("corpus15": {"error": ...}).
 
@@ -50,6 +50,20 @@
       cpu_baseline     SURVEY 8(d)(ii): the oracle's restatement of Reader::search, queries
                        one at a time, one thread per chunk, suffix arrays in RAM and -- like
                        the reference -- probed on disk with lseek + read(8 KiB)
+
+Plain run and --full
+    A plain run sets up, warms up, times the steps, checks the suffix array of the last timed step
+    (`verified`) and prints the line: the headline figures and what the timed loop itself reports.
+    Everything that takes runs of its own is measured with --full only: verified_search, roofline,
+    value_cold / build_ms_first_chunk, cpu_baseline, seam1_host_pointers, secondary, adversarial,
+    real_files, the e2e and corpus15 legs of the chunk config; packed_queries_per_sec,
+    single_query_us and cpu_baseline of the corpus15 config; multi_device_handles of --inproc.
+    Without --full these fields are null or absent.
+
+--dump-outputs DIR
+    After the timed steps, what the last step handed its caller, as float64 / float32 .npy files
+    (dump_outputs below).  Inputs come from fixed seeds, so two builds run with the same arguments can
+    be compared output for output.
 """
 import pathlib
 import argparse
@@ -72,6 +86,8 @@ KINDS = {'lines': 0, 'words': 1, 'runs': 2, 'periodic': 3, 'repeat_line': 4, 'du
 ALPHA = b'abcdefghijklmnopqrstuvwxyz0123456789 .'
 METRIC = 'queries/sec (batched) + index-build GB/s on 512MB chunk, 1/2/4/8 GPU'
 MASK64 = (1 << 64) - 1
+DUMP_BYTES = 60 * 10 ** 6      # --dump-outputs: the data of all files together (64 MB at most, with the .npy headers)
+DUMP_SA_POSITIONS = 1 << 20    # ... of which the suffix array takes at most this many float64 values
 
 
 # ----------------------------------------------------------------------------- verification --
@@ -151,6 +167,46 @@ def verify_sa(d_sa, host_text: np.ndarray, kind: str, chunk_index: int, goldens,
         ref = O.sa_restatement(host_text)
         return bool(np.array_equal(d_sa.cpu().numpy(), ref)), 'oracle restatement run on the same text (libsais not built)'
     return None, 'no libsais known answer for this input (add it with tests/golden/make_golden_big.py)'
+
+
+def dump_outputs(where: str, d_sa, entries, counts):
+    """--dump-outputs: what the last timed step handed its caller, as .npy files.
+      sa.npy              the suffix array (device int32 tensor; None: the timed path builds none) in float64, which holds
+                          it exactly; longer than DUMP_SA_POSITIONS: its values at a fixed, seeded sample of positions
+      search_counts.npy   entries per query (counts None: the list API, one flat list)
+      search_lengths.npy  byte length of every entry, query by query, each query's entries sorted (the order inside one
+                          query's result is not part of the API)
+      search_bytes.npy    those entries back to back, one float32 per byte
+    The entries stop at the first query whose entries would take the files past DUMP_BYTES."""
+    os.makedirs(where, exist_ok=True)
+    left = DUMP_BYTES
+    if d_sa is not None:
+        n = d_sa.numel()
+        if n > DUMP_SA_POSITIONS:
+            import torch
+            pos = np.unique(np.random.default_rng(0).integers(0, n, DUMP_SA_POSITIONS))
+            sa = d_sa[torch.from_numpy(pos).to(d_sa.device)].cpu().numpy()
+        else:
+            sa = d_sa.cpu().numpy()
+        np.save(os.path.join(where, 'sa.npy'), sa.astype(np.float64))
+        left -= 8 * sa.size
+    if counts is None:                                  # the list API: str entries (str and its UTF-8 bytes sort alike)
+        groups = ([e.encode()] for e in sorted(entries))
+    else:
+        counts = np.asarray(counts, dtype=np.int64)
+        np.save(os.path.join(where, 'search_counts.npy'), counts.astype(np.float64))
+        left -= 8 * counts.size
+        ends = np.cumsum(counts)
+        groups = (sorted(entries[e - c:e]) for c, e in zip(counts.tolist(), ends.tolist()))
+    kept = []
+    for g in groups:
+        need = sum(8 + 4 * len(e) for e in g)
+        if need > left:
+            break
+        left -= need
+        kept.extend(g)
+    np.save(os.path.join(where, 'search_lengths.npy'), np.array([len(e) for e in kept], dtype=np.float64))
+    np.save(os.path.join(where, 'search_bytes.npy'), np.frombuffer(b''.join(kept), dtype=np.uint8).astype(np.float32))
 
 
 # ----------------------------------------------------------------------------- queries --
@@ -387,6 +443,7 @@ def run_inproc(args):
             st = _ffi.SaStats()
             k = 0
             tb = ts = 0.0
+            result = []
 
             def step():
                 nonlocal k, tb, ts
@@ -396,8 +453,10 @@ def run_inproc(args):
                 t1 = time.perf_counter()
                 _ffi.check(lib.pss_reader_set_chunk_device(h, 0, dTs[k].data_ptr(), dSA.data_ptr(), n))
                 t2 = time.perf_counter()
-                ents, _ = reader.search_batch_raw(qsets[k])
+                ents, cnts = reader.search_batch_raw(qsets[k])
                 t3 = time.perf_counter()
+                if r == 0 and args.dump_outputs:
+                    result[:] = [ents, cnts]
                 return t1 - t0, t3 - t2, len(ents)
             for _ in range(args.warmup):
                 step()
@@ -411,6 +470,8 @@ def run_inproc(args):
             torch.cuda.synchronize(dev)
             stop.wait()
             ok, how = verify_sa(dSA, hosts[k], args.corpus, ids[k], gold, want_sha=False)
+            if r == 0 and args.dump_outputs:
+                dump_outputs(args.dump_outputs, dSA, *result)
             state[r] = {'build_s': tb, 'search_s': ts, 'verified': ok, 'how': how, 'entries': entries, 'device': dev,
                         'ms_total': st.ms_total}
             reader.close()
@@ -442,44 +503,45 @@ def run_inproc(args):
 
     # the multi-device handles of the drop-in API on a small index: same bytes, same results as the one-device handles
     handles = None
-    try:
-        import shutil
-        import tempfile
-        d = tempfile.mkdtemp(prefix='pss_inproc_')
+    if args.full:
         try:
-            cn = 1 << min(args.logn, 22)
-            src = os.path.join(d, 'c.txt')
-            with open(src, 'wb') as f:
-                for c in range(2 * N + 1):
-                    buf = np.empty(cn, dtype=np.uint8)
-                    _ffi.check(lib.pss_gen_corpus(KINDS[args.corpus], buf.ctypes.data, cn, c))
-                    f.write(buf.data)
-            one, many = os.path.join(d, 'one.idx'), os.path.join(d, 'many.idx')
-            w = pysubstringsearch.Writer(one, cn, device=devs[0])
-            w.add_entries_from_file_lines(src)
-            w.close()
-            t0 = time.perf_counter()
-            w = pysubstringsearch.Writer(many, cn, devices=devs)
-            w.add_entries_from_file_lines(src)
-            w.close()
-            t_w = time.perf_counter() - t0
-            same_bytes = pathlib.Path(one).read_bytes() == pathlib.Path(many).read_bytes()
-            qs = make_queries(np.fromfile(src, dtype=np.uint8, count=cn), 3000, args.qlen)
-            with pysubstringsearch.Reader(one, device=devs[0]) as r1, pysubstringsearch.Reader(many, devices=devs) as rn:
-                e1, c1 = r1.search_batch_raw(qs)
+            import shutil
+            import tempfile
+            d = tempfile.mkdtemp(prefix='pss_inproc_')
+            try:
+                cn = 1 << min(args.logn, 22)
+                src = os.path.join(d, 'c.txt')
+                with open(src, 'wb') as f:
+                    for c in range(2 * N + 1):
+                        buf = np.empty(cn, dtype=np.uint8)
+                        _ffi.check(lib.pss_gen_corpus(KINDS[args.corpus], buf.ctypes.data, cn, c))
+                        f.write(buf.data)
+                one, many = os.path.join(d, 'one.idx'), os.path.join(d, 'many.idx')
+                w = pysubstringsearch.Writer(one, cn, device=devs[0])
+                w.add_entries_from_file_lines(src)
+                w.close()
                 t0 = time.perf_counter()
-                en, cn_ = rn.search_batch_raw(qs)
-                t_r = time.perf_counter() - t0
-                same_results = list(c1) == list(cn_) and sorted(e1) == sorted(en)
-            handles = {'devices': devs, 'chunks': 2 * N + 1, 'chunk_bytes': cn, 'writer_same_bytes_as_one_device': bool(same_bytes),
-                       'reader_same_results_as_one_device': bool(same_results), 'writer_seconds': round(t_w, 3),
-                       'reader_batch_seconds': round(t_r, 4)}
-            if not (same_bytes and same_results):
-                verified = False
-        finally:
-            shutil.rmtree(d, ignore_errors=True)
-    except Exception as e:      # noqa: BLE001
-        handles = {'error': f'{type(e).__name__}: {e}'[:300]}
+                w = pysubstringsearch.Writer(many, cn, devices=devs)
+                w.add_entries_from_file_lines(src)
+                w.close()
+                t_w = time.perf_counter() - t0
+                same_bytes = pathlib.Path(one).read_bytes() == pathlib.Path(many).read_bytes()
+                qs = make_queries(np.fromfile(src, dtype=np.uint8, count=cn), 3000, args.qlen)
+                with pysubstringsearch.Reader(one, device=devs[0]) as r1, pysubstringsearch.Reader(many, devices=devs) as rn:
+                    e1, c1 = r1.search_batch_raw(qs)
+                    t0 = time.perf_counter()
+                    en, cn_ = rn.search_batch_raw(qs)
+                    t_r = time.perf_counter() - t0
+                    same_results = list(c1) == list(cn_) and sorted(e1) == sorted(en)
+                handles = {'devices': devs, 'chunks': 2 * N + 1, 'chunk_bytes': cn, 'writer_same_bytes_as_one_device': bool(same_bytes),
+                           'reader_same_results_as_one_device': bool(same_results), 'writer_seconds': round(t_w, 3),
+                           'reader_batch_seconds': round(t_r, 4)}
+                if not (same_bytes and same_results):
+                    verified = False
+            finally:
+                shutil.rmtree(d, ignore_errors=True)
+        except Exception as e:      # noqa: BLE001
+            handles = {'error': f'{type(e).__name__}: {e}'[:300]}
     value = None if verified is False else round(N * n * args.steps / build_s / 1e9, 4)
     out = {
         'metric': METRIC, 'value': value, 'unit': 'GB/s', 'n_gpus': N, 'steps': args.steps, 'warmup': args.warmup,
@@ -693,6 +755,8 @@ def run_chunk(args, D):
         t3 = time.perf_counter()
         last['entries'] = len(entries)
         last['search_stats'] = reader.last_stats()
+        if args.dump_outputs:
+            last['result'] = merged if world > 1 else (entries, counts)
         return t1 - t0, t3 - t2
 
     for _ in range(args.warmup):
@@ -716,12 +780,18 @@ def run_chunk(args, D):
     host_sa = dSA.cpu().numpy() if world == 1 else None
     verified, how = verify_sa(dSA, host, args.corpus, chunk_ids[cur['k']], load_big_goldens(), want_sha=(world == 1), host_sa=host_sa)
     verified = D.all_true(verified)
+    if args.dump_outputs and rank == 0:          # (before the --full legs below build into dSA again)
+        res = last.pop('result')
+        if world > 1:
+            res = (pdist.packed_to_list(res[0], res[1]), res[2])
+        dump_outputs(args.dump_outputs, dSA, *res)
+        del res
 
     # ... and are the results of the query leg the reference's?  A sample of the batch (sampled and random queries alike)
     # through the oracle's restatement of Reader::search (src/lib.rs:209-278) over the same text and the suffix array
     # just verified, compared per query as multisets (the reference's tests use assertCountEqual, tests:32-37).
     verified_search = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         from oracle import oracle as O
         pick = list(range(0, len(queries), max(1, len(queries) // 200)))
         qs = [queries[i] for i in pick]
@@ -744,15 +814,17 @@ def run_chunk(args, D):
 
     # roofline of the dominant kernel: one extra build in profile mode (HIP events
     # on the engine's own stream around every radix-pass launch), outside the timed region
-    _ffi.check(lib.pss_sa_build_device(dT.data_ptr(), dSA.data_ptr(), n, dev, 1, ctypes.byref(st)))
-    prof = st.as_dict()
+    prof = None
+    if args.full:
+        _ffi.check(lib.pss_sa_build_device(dT.data_ptr(), dSA.data_ptr(), n, dev, 1, ctypes.byref(st)))
+        prof = st.as_dict()
 
     # The timed steps rebuild chunks of one corpus, so from the second on the build goes straight to the initial sort the
     # previous chunk took (pss_sa_stats.plan_hint).  The build of a first chunk, which takes the sizing sample, beside it:
     # (flags bit 3: the build forgets what earlier builds on the device left behind -- include/pss.h)
     sized_ms = None
     cold_hint = None
-    for _ in range(3):
+    for _ in range(3 if args.full else 0):
         _ffi.check(lib.pss_sa_build_device(dT.data_ptr(), dSA.data_ptr(), n, dev, 8, ctypes.byref(st)))
         sized_ms = st.ms_total if sized_ms is None else min(sized_ms, st.ms_total)
         cold_hint = int(st.plan_hint)
@@ -762,7 +834,7 @@ def run_chunk(args, D):
     # the suffix array down (4 n bytes) around the build -- outside the timed region, rank 0, N = 1
     workspace = {'lines' if args.corpus == 'lines' else args.corpus: int(lib.pss_workspace_bytes(dev))}
     seam1 = None
-    if world == 1 and not os.environ.get('PSS_BENCH_NO_SECONDARY'):
+    if args.full and world == 1 and not os.environ.get('PSS_BENCH_NO_SECONDARY'):
         def host_build(t_ptr, sa_ptr):
             best = None
             for _ in range(3):
@@ -793,7 +865,7 @@ def run_chunk(args, D):
 
     # secondary corpus (natural-text-like LCP), outside the timed region, N = 1 only
     secondary = None
-    if world == 1 and args.corpus == 'lines' and not os.environ.get('PSS_BENCH_NO_SECONDARY'):
+    if args.full and world == 1 and args.corpus == 'lines' and not os.environ.get('PSS_BENCH_NO_SECONDARY'):
         # three distinct chunks of the corpus in turn, like the headline: chunk k+1 is cut by the splitters chunk k's sample
         # gave (pss_sa_stats.ss_planned), nothing about a chunk's own content is carried over; a first chunk beside it
         w_dTs, w_hosts = [], []
@@ -842,7 +914,7 @@ def run_chunk(args, D):
     # configs[4]: the adversarial corpora (long runs of equal bytes; period 4096), outside the timed region,
     # N = 1 only: the run-length path (rle_build.hip), and once the prefix-doubling path it replaces
     adversarial = None
-    if world == 1 and args.corpus == 'lines' and not os.environ.get('PSS_BENCH_NO_SECONDARY'):
+    if args.full and world == 1 and args.corpus == 'lines' and not os.environ.get('PSS_BENCH_NO_SECONDARY'):
         adversarial = []
         for kind in ('runs', 'periodic', 'repeat_line', 'dup_blocks', 'mixed', 'source'):
             a_host = np.empty(n, dtype=np.uint8)
@@ -896,7 +968,7 @@ def run_chunk(args, D):
     # indentation, 200-odd byte values; four suffixes in five sit inside copies, so the build goes through the sample
     # sort, a text round and the anchor round.  Checked against libsais run on the same bytes, here and now.
     real_files = None
-    if world == 1 and args.corpus == 'lines' and not os.environ.get('PSS_BENCH_NO_SECONDARY') and not args.no_real_files:
+    if args.full and world == 1 and args.corpus == 'lines' and not os.environ.get('PSS_BENCH_NO_SECONDARY') and not args.no_real_files:
         try:
             import importlib.util
             spec = importlib.util.spec_from_file_location('real_text', os.path.join(ROOT, 'tests', 'tools', 'real_text.py'))
@@ -943,21 +1015,22 @@ def run_chunk(args, D):
         # build: the passes of the initial sort are fs_scatter_kernel<KIN, KOUT> (key plane bytes in /
         # out, 4-byte values), the sorts of the rounds and of the sizing sample rs_scatter_kernel<false>
         cands = []
-        for idx in range(9):
-            if prof['fs_launches'][idx]:
-                kin, kout = (idx // 3) * 4, (idx % 3) * 4
-                bpe = (kin + 4 if kin else 1) + kout + 4          # the text pass reads 1 B / suffix
-                cands.append((prof['fs_ms'][idx], f'fs_scatter_kernel<{kin}, {kout}>', prof['fs_launches'][idx],
-                              prof['fs_elems'][idx], bpe))
-        if prof['pairs_launches']:
-            cands.append((prof['ms_pairs'], 'rs_scatter_kernel<false>', prof['pairs_launches'], prof['pairs_elems'], 24))
-        if prof['msd']:
-            # hybrid MSD initial sort (msd_sort.hip): partition from the text (1 B in, 8 B out per suffix), partition of
-            # the 8-byte elements (8 in, 8 out), LDS-resident local sort (8 in, 4 out)
-            lb = bool(prof.get('msd_lookback'))      # round 6: digits in LSD order, the second pass in one sweep (look-back)
-            cands.append((prof['msd_ms_g1'], 'msd_scatter2_kernel<true, 1024, true>' if lb else 'msd_scatter2_kernel<true, 1024>', 1, n, 9))
-            cands.append((prof['msd_ms_g2'], 'msd_scatter_lb_kernel' if lb else 'msd_scatter2_kernel<false, 1024>', 1, n, 16))
-            cands.append((prof['msd_ms_local'], 'msd_local_fast_kernel', 1, n, 12))
+        if prof is not None:             # (--full: the build in profile mode above)
+            for idx in range(9):
+                if prof['fs_launches'][idx]:
+                    kin, kout = (idx // 3) * 4, (idx % 3) * 4
+                    bpe = (kin + 4 if kin else 1) + kout + 4          # the text pass reads 1 B / suffix
+                    cands.append((prof['fs_ms'][idx], f'fs_scatter_kernel<{kin}, {kout}>', prof['fs_launches'][idx],
+                                  prof['fs_elems'][idx], bpe))
+            if prof['pairs_launches']:
+                cands.append((prof['ms_pairs'], 'rs_scatter_kernel<false>', prof['pairs_launches'], prof['pairs_elems'], 24))
+            if prof['msd']:
+                # hybrid MSD initial sort (msd_sort.hip): partition from the text (1 B in, 8 B out per suffix), partition of
+                # the 8-byte elements (8 in, 8 out), LDS-resident local sort (8 in, 4 out)
+                lb = bool(prof.get('msd_lookback'))      # round 6: digits in LSD order, the second pass in one sweep (look-back)
+                cands.append((prof['msd_ms_g1'], 'msd_scatter2_kernel<true, 1024, true>' if lb else 'msd_scatter2_kernel<true, 1024>', 1, n, 9))
+                cands.append((prof['msd_ms_g2'], 'msd_scatter_lb_kernel' if lb else 'msd_scatter2_kernel<false, 1024>', 1, n, 16))
+                cands.append((prof['msd_ms_local'], 'msd_local_fast_kernel', 1, n, 12))
         roof = None
         if cands:
             ms_sum, kname, launches, elems, bpe = max(cands)
@@ -1011,10 +1084,10 @@ def run_chunk(args, D):
                       'traffic_evidence': m_stamp,
                       'passes': sa_stats['initial_passes'], 'rounds': sa_stats['rounds'], 'sum_active': sa_stats['sum_active']}
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline_chunk(host, queries, args.cpu_sample_logn)
         value = None if verified is False else round(world * n * args.steps / build_s / 1e9, 4)
-        value_cold = None if verified is False else round(world * n / sized_ms / 1e6, 4)
+        value_cold = None if verified is False or sized_ms is None else round(world * n / sized_ms / 1e6, 4)
 
         def pick(obj, *path):
             for k in path:
@@ -1031,7 +1104,7 @@ def run_chunk(args, D):
             # filled in by the legs that run after this one)
             'summary': {
                 'index_build_gbs_warm': value, 'index_build_gbs_cold': value_cold,
-                'build_ms_warm': round(build_s / args.steps * 1e3, 3), 'build_ms_first_chunk': round(sized_ms, 3),
+                'build_ms_warm': round(build_s / args.steps * 1e3, 3), 'build_ms_first_chunk': sized_ms and round(sized_ms, 3),
                 'distinct_chunks_in_timed_loop': ROT,
                 'dominant_kernel': None if roof is None else roof['kernel'], 'roofline_frac': None if roof is None else roof['frac'],
                 'build_roofline_frac': build_roof['frac'],
@@ -1070,7 +1143,7 @@ def run_chunk(args, D):
             },
             'queries_per_sec': round(len(queries) * args.steps / search_s, 1),
             'build_ms': round(build_s / args.steps * 1e3, 3),
-            'build_ms_first_chunk': round(sized_ms, 3), 'plan_hint': int(sa_stats.get('plan_hint', 0)), 'plan_hint_first_chunk': cold_hint,
+            'build_ms_first_chunk': sized_ms and round(sized_ms, 3), 'plan_hint': int(sa_stats.get('plan_hint', 0)), 'plan_hint_first_chunk': cold_hint,
             'search_ms': round(search_s / args.steps * 1e3, 3),
             'per_rank_build_ms': per_rank_build_ms, 'per_rank_search_ms': per_rank_search_ms,
             'ranks': world, 'gather': None if world == 1 else f'{D.backend} (torch.distributed P2P, device-side merge on rank 0)',
@@ -1085,7 +1158,7 @@ def run_chunk(args, D):
                             else 'LSD passes with shrinking keys',
             'kernel_ms': ({('msd_scatter2_kernel<true, 1024, true>' if prof.get('msd_lookback') else 'msd_scatter2_kernel<true, 1024>'): round(prof['msd_ms_g1'], 3),
                            ('msd_scatter_lb_kernel' if prof.get('msd_lookback') else 'msd_scatter2_kernel<false, 1024>'): round(prof['msd_ms_g2'], 3),
-                           'msd_local_fast_kernel': round(prof['msd_ms_local'], 3)} if prof['msd'] else None),
+                           'msd_local_fast_kernel': round(prof['msd_ms_local'], 3)} if prof and prof['msd'] else None),
             'roofline': roof,
             'build_roofline': build_roof,
             'cpu_baseline': cpu,
@@ -1102,7 +1175,7 @@ def run_chunk(args, D):
 
 # ----------------------------------------------------------------------------- configs[2] / [3] --
 
-def run_corpus(args, D, steps=None, warmup=None):
+def run_corpus(args, D, steps=None, warmup=None, dump=None):
     import torch
     steps = args.steps if steps is None else steps
     warmup = args.warmup if warmup is None else warmup
@@ -1116,7 +1189,7 @@ def run_corpus(args, D, steps=None, warmup=None):
     chunks = args.chunks
     mine = [c for c in range(chunks) if pdist.chunk_owner(c, world) == rank]
     goldens = load_big_goldens()
-    keep_host = world == 1 and not args.no_cpu_baseline      # the CPU baseline needs text + SA of every chunk
+    keep_host = args.full and world == 1 and not args.no_cpu_baseline      # the CPU baseline needs text + SA of every chunk
 
     h = ctypes.c_void_p()
     _ffi.check(lib.pss_reader_create(dev, ctypes.byref(h)))
@@ -1178,19 +1251,23 @@ def run_corpus(args, D, steps=None, warmup=None):
         step()
     D.sync_all()
     total_s = time.perf_counter() - t_begin
+    if dump and keep:                    # (rank 0: the list of the last timed step)
+        dump_outputs(dump, None, keep[-1], None)
     keep.clear()
     stats = reader.last_stats()
-    D.sync_all()
-    t_p = time.perf_counter()
-    for _ in range(steps):
-        step(packed=True)
-    D.sync_all()
-    packed_s = time.perf_counter() - t_p
+    packed_s = 0.0
+    if args.full:
+        D.sync_all()
+        t_p = time.perf_counter()
+        for _ in range(steps):
+            step(packed=True)
+        D.sync_all()
+        packed_s = time.perf_counter() - t_p
     per_rank_build_ms = [round(x * 1e3, 2) for x in D.gather_floats(build_s)]
     total_s, packed_s, build_s = D.max_over_ranks([total_s, packed_s, build_s])
 
     lat = None
-    if world == 1:
+    if args.full and world == 1:
         ts = []
         for q in queries[:1000]:
             t0 = time.perf_counter()
@@ -1272,7 +1349,7 @@ def run_corpus(args, D, steps=None, warmup=None):
                              f'fullest rank: best-case speed-up {chunks / max(len([c for c in range(chunks) if c % world == r]) for r in range(world)):.2f}x',
             },
             'entries_per_batch': last.get('entries'), 'hits_per_query': round(hits_q, 2),
-            'packed_queries_per_sec': round(len(queries) * steps / packed_s, 1),
+            'packed_queries_per_sec': round(len(queries) * steps / packed_s, 1) if args.full else None,
             'single_query_us': lat,
             'index_build_gbs': round(chunks * n / build_s / 1e9, 3),
             'per_rank_build_ms': per_rank_build_ms,
@@ -1373,14 +1450,17 @@ def main():
     ap.add_argument('--cpu-sample-queries', type=int, default=5000)
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-disk-baseline', action='store_true')
-    ap.add_argument('--no-corpus15', action='store_true', help='chunk config: skip the configs[2]/[3] leg of the line')
+    ap.add_argument('--no-corpus15', action='store_true', help='--full, chunk config: skip the configs[2]/[3] leg of the line')
     ap.add_argument('--corpus15-queries', type=int, default=100000)
-    ap.add_argument('--no-real-files', action='store_true', help='chunk config: skip the build of real files found on the machine')
+    ap.add_argument('--no-real-files', action='store_true', help='--full, chunk config: skip the build of real files found on the machine')
     ap.add_argument('--real-files-logn', type=int, default=28, help='... and how many bytes of them (2^this) make the chunk')
-    ap.add_argument('--no-e2e', action='store_true', help='chunk config: skip the file-API leg (Writer -> .idx -> Reader)')
+    ap.add_argument('--no-e2e', action='store_true', help='--full, chunk config: skip the file-API leg (Writer -> .idx -> Reader)')
     ap.add_argument('--e2e-chunks', type=int, default=4)
     ap.add_argument('--inproc', action='store_true',
                     help='N GPUs inside ONE process (a host thread per device; no torch.distributed, no RCCL)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check what takes runs of its own: baselines, other corpora, legs, roofline')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step computed to DIR/*.npy')
     args = ap.parse_args()
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ and not args.inproc:
         printed = []
@@ -1463,6 +1543,10 @@ def main():
                '--warmup', str(args.warmup), '--logn', str(args.logn), '--corpus', args.corpus, '--qlen', str(args.qlen)]
         if args.queries:
             cmd += ['--queries', str(args.queries)]
+        if args.full:
+            cmd += ['--full']
+        if args.dump_outputs:
+            cmd += ['--dump-outputs', args.dump_outputs]
         code, line = 1, None
         try:
             r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1500)
@@ -1514,7 +1598,7 @@ def main():
     if chunk_done is not None:
         chunk_done.set()
     if args.config == 'chunk':
-        if D.world == 1 and not args.no_e2e and out is not None:
+        if args.full and D.world == 1 and not args.no_e2e and out is not None:
             import torch
             torch.cuda.empty_cache()
             try:
@@ -1529,7 +1613,7 @@ def main():
             if e2e.get('verified') is False:
                 out['value'] = None
                 rc = rc or 1
-        if not args.no_corpus15:
+        if args.full and not args.no_corpus15:
             # BASELINE configs[2] / [3] in the same line: the 7.5 GB corpus (chunk c on rank c mod N), one batch of 100 000
             # queries of 4..32 bytes, at most 3 timed steps; the CPU path (one thread per chunk; RAM and the reference's
             # lseek + read probes) beside it at N = 1
@@ -1628,7 +1712,7 @@ def main():
                 except Exception:
                     pass
     else:
-        rc, out = run_corpus(args, D)
+        rc, out = run_corpus(args, D, dump=args.dump_outputs)
     if out is not None:
         print(json.dumps(out), flush=True)
     D.finish()

@@ -30,7 +30,7 @@ def _last_json(out):
 
 
 def test_bench_single_gpu_contract():
-    r = subprocess.run([sys.executable, 'bench.py', '--steps', '2', '--warmup', '1', '--logn', '22', '--queries', '500',
+    r = subprocess.run([sys.executable, 'bench.py', '--full', '--steps', '2', '--warmup', '1', '--logn', '22', '--queries', '500',
                         '--cpu-sample-logn', '20', '--chunks', '5', '--corpus15-queries', '3000', '--cpu-sample-queries', '300',
                         '--real-files-logn', '24'],
                        cwd=ROOT, capture_output=True, text=True, timeout=600)
@@ -67,6 +67,32 @@ def test_bench_single_gpu_contract():
     assert ll['same_results'] is True and ll['median'] > 0 and ll['queries_served'] >= 1000 and ll['kernels_started'] >= 1
 
 
+def test_bench_plain_run_and_its_outputs(tmp_path):
+    """Without --full the line carries the timed loop and its check only; --dump-outputs writes what the last timed step
+    computed (float .npy), and a second run with the same arguments writes the same outputs."""
+    import numpy as np
+    cmd = [sys.executable, 'bench.py', '--gpus', '1', '--steps', '4', '--warmup', '1', '--logn', '22', '--queries', '500']
+    lines = []
+    for k in range(2):
+        r = subprocess.run(cmd + ['--dump-outputs', str(tmp_path / str(k))], cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(_last_json(r.stdout))
+    d = lines[0]
+    assert d['steps'] == 4 and d['ms_per_step'] > 0 and d['value'] > 0 and d['verified'] is True
+    assert d['roofline'] is None and d['cpu_baseline'] is None and d['verified_search'] is None
+    assert 'corpus15' not in d and 'e2e' not in d and d['real_files'] is None
+    files = sorted(os.listdir(tmp_path / '0'))
+    assert files == ['sa.npy', 'search_bytes.npy', 'search_counts.npy', 'search_lengths.npy']
+    out = {f: np.load(tmp_path / '0' / f) for f in files}
+    for f in files:
+        assert out[f].dtype in (np.float32, np.float64) and np.array_equal(out[f], np.load(tmp_path / '1' / f)), f
+    assert sum(os.path.getsize(tmp_path / '0' / f) for f in files) <= 64 * 10 ** 6
+    sa, counts, lengths = out['sa.npy'], out['search_counts.npy'], out['search_lengths.npy']
+    assert sa.size > 900000 and sa.min() >= 0 and sa.max() < 1 << 22 and np.unique(sa).size == sa.size
+    assert counts.size == 500 and counts.sum() == d['entries_per_batch'] == lengths.size
+    assert lengths.sum() == out['search_bytes.npy'].size
+
+
 def _check_two_ranks(d):
     assert d['n_gpus'] == 2 and d['scaling'] == 'weak' and d['value'] > 0
     assert d['cpu_baseline'] is None and d['secondary'] is None     # rank 0, N = 1 only
@@ -84,7 +110,7 @@ def test_bench_two_ranks_self_launch():
     env = dict(os.environ, PSS_BENCH_BACKEND='gloo')
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
-    cmd = [sys.executable, 'bench.py', '--gpus', '2', '--steps', '2', '--warmup', '1', '--logn', '22', '--queries', '500',
+    cmd = [sys.executable, 'bench.py', '--full', '--gpus', '2', '--steps', '2', '--warmup', '1', '--logn', '22', '--queries', '500',
            '--chunks', '5', '--corpus15-queries', '3000']
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -99,7 +125,7 @@ def test_bench_two_ranks_keep_the_headline_when_the_corpus_leg_fails():
     env = dict(os.environ, PSS_BENCH_BACKEND='gloo', PSS_BENCH_FAIL_CORPUS15='1', PSS_BENCH_CORPUS15_TIMEOUT='60')
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
-    cmd = [sys.executable, 'bench.py', '--gpus', '2', '--steps', '2', '--warmup', '1', '--logn', '22', '--queries', '500',
+    cmd = [sys.executable, 'bench.py', '--full', '--gpus', '2', '--steps', '2', '--warmup', '1', '--logn', '22', '--queries', '500',
            '--chunks', '5', '--corpus15-queries', '3000']
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     d = _last_json(r.stdout)
@@ -109,7 +135,7 @@ def test_bench_two_ranks_keep_the_headline_when_the_corpus_leg_fails():
 def test_bench_two_ranks_under_torchrun():
     env = dict(os.environ, PSS_BENCH_BACKEND='gloo', MASTER_ADDR='127.0.0.1')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
-           '--master-port', str(_free_port()), 'bench.py', '--gpus', '2', '--steps', '2', '--warmup', '1', '--logn', '22',
+           '--master-port', str(_free_port()), 'bench.py', '--full', '--gpus', '2', '--steps', '2', '--warmup', '1', '--logn', '22',
            '--queries', '500', '--chunks', '5', '--corpus15-queries', '3000']
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -128,7 +154,8 @@ def test_bench_inproc_route():
     env = dict(os.environ)
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT', 'PSS_BENCH_BACKEND'):
         env.pop(k, None)
-    cmd = [sys.executable, 'bench.py', '--gpus', '2', '--inproc', '--steps', '2', '--warmup', '1', '--logn', '22', '--queries', '500']
+    cmd = [sys.executable, 'bench.py', '--full', '--gpus', '2', '--inproc', '--steps', '2', '--warmup', '1', '--logn', '22',
+           '--queries', '500']
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _last_json(r.stdout)

@@ -1,5 +1,5 @@
 import os, sys, ctypes, time
-sys.path.insert(0,'/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np
 from pysubstringsearch_amd import _ffi
 from oracle import oracle as O

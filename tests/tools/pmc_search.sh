@@ -4,6 +4,6 @@
 out=$1
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $c --kernel-trace --output-format csv -d $out/$c -o pmc -- python3 bench.py --config corpus15 --steps 1 --warmup 0 --no-cpu-baseline > $out.$c.log 2>&1
+  rocprofv3 --pmc $c --kernel-trace --output-format csv -d $out/$c -o pmc -- python3 bench.py --full --config corpus15 --steps 1 --warmup 0 --no-cpu-baseline > $out.$c.log 2>&1
 done
 ls $out

@@ -40,7 +40,7 @@ for name, cs in vals.items():
     total_raw += f + w
     total_x2 += 2 * f + w
 res = {'source': 'tests/tools/pmc_search.sh: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate runs) around '
-                 'bench.py --config corpus15 --steps 1 (15 x 512 MiB resident, one batch of 100 000 queries of 4..32 bytes); per '
+                 'bench.py --full --config corpus15 --steps 1 (15 x 512 MiB resident, one batch of 100 000 queries of 4..32 bytes); per '
                  'kernel the launches with the largest grid',
        'note': 'FETCH_SIZE counts 64 B per read request; 128-byte requests of wide coalesced loads are tallied at half their size '
                '(guide: x 2 for streaming reads), sector gathers are not -- both totals are given; the truth lies between them',

@@ -1,7 +1,7 @@
 """Run-length path (rle_build.hip) against the oracle: forced on random texts of every shape, then the
 full-size adversarial corpora against libsais' hashes, timed with and without the path."""
 import os, sys, ctypes
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np
 from pysubstringsearch_amd import _ffi
 from oracle import oracle as O

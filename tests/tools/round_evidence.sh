@@ -13,7 +13,7 @@ tail -3 $ev/${tag}_pytest_gpu.log
 # 2. the driver's command: below, once the counter files of THIS tree exist (the line quotes them and says whether they are current)
 # 3. kernel stats under rocprofv3
 cd /tmp && export TMPDIR=/tmp; cd $root
-PSS_BENCH_NO_SECONDARY=1 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $ev/prof_bench -o t -- python3 bench.py --no-cpu-baseline --no-corpus15 --no-e2e > $ev/${tag}_bench_under_rocprof.json 2>/dev/null
+PSS_BENCH_NO_SECONDARY=1 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $ev/prof_bench -o t -- python3 bench.py --full --no-cpu-baseline --no-corpus15 --no-e2e > $ev/${tag}_bench_under_rocprof.json 2>/dev/null
 cp $ev/prof_bench/t_kernel_stats.csv $ev/${tag}_bench_kernel_stats.csv
 for spec in lines:12 words:5 dup_blocks:3 mixed:3 source:3 real:3; do
   c=${spec%%:*}; k=${spec#*:}
@@ -39,12 +39,12 @@ for spec in lines:3 words:2 dup_blocks:2 mixed:2 source:2 real:2 runs:2; do
 done
 cp $ev/json/*.json $root/profiles/ 2>/dev/null      # (on the box: the bench line below reads them)
 # 4b. configs[2] / [3] on natural-text-like chunks, and the look-back micro-benchmark behind DESIGN 4.2
-timeout 1500 python bench.py --config corpus15 --corpus words --qmin 16 --steps 2 --warmup 1 > $ev/${tag}_bench_corpus15_words.json 2> $ev/bench_corpus15_words.err
+timeout 1500 python bench.py --full --config corpus15 --corpus words --qmin 16 --steps 2 --warmup 1 > $ev/${tag}_bench_corpus15_words.json 2> $ev/bench_corpus15_words.err
 [ -x tests/tools/bin/lookback_micro ] && timeout 240 tests/tools/bin/lookback_micro > $ev/${tag}_lookback_micro_final.txt 2>&1
 mkdir -p $ev/pmc_sq; tests/tools/pmc.sh $ev/pmc_sq/p -- python3 tests/tools/sa_perf.py lines 29 3 > /dev/null 2>&1
 python tests/tools/pmc_summary.py $ev/pmc_sq/p msd_ > $ev/${tag}_pmc_sq_lines_kernels.txt 2>&1; rm -rf $ev/pmc_sq
 cp $ev/${tag}_bench_corpus15_words.json $root/profiles/ 2>/dev/null
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $ev/${tag}_bench_default.json 2> $ev/bench_default.err
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $ev/${tag}_bench_default.json 2> $ev/bench_default.err
 timeout 600 tests/tools/pmc_requests.sh $ev/pmcreq_words words 1 > /dev/null 2>&1
 python tests/tools/pmc_requests_json.py $ev/pmcreq_words $ev/json/pmc_requests_words.json 1 > $ev/pmc_requests_words.txt 2>&1
 timeout 1500 tests/tools/pmc_search.sh $ev/pmc_search > /dev/null 2>&1
