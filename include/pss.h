@@ -368,7 +368,25 @@ typedef struct pss_search_stats {
     double ms_device;       /* HIP-event time of the kernels of the batch */
     double ms_interval;     /* ... of the interval-search kernel alone */
     double ms_host;         /* wall time of the whole batch inside the library (host clock) */
+    uint32_t route;         /* PSS_ROUTE_* bits: which search routes served the batch (a multi-device reader: OR of its devices) */
+    uint32_t route_pad;
 } pss_search_stats;
+
+/* Bits of pss_search_stats.route.  A batch that one route could not finish names every route it went through: e.g.
+ * SMALL_BLOCK | SMALL_OVERFLOW | INTERVAL_WAVE | MID for a fused launch over its capacities that the mid pipeline took. */
+#define PSS_ROUTE_RESIDENT        0x0001u  /* the resident low-latency kernel answered (pss_reader_set_low_latency) */
+#define PSS_ROUTE_SMALL_BLOCK     0x0002u  /* fused path, one to 32 workgroups per (query, chunk) pair */
+#define PSS_ROUTE_SMALL_WAVE      0x0004u  /* fused path, one wavefront per pair */
+#define PSS_ROUTE_SMALL_OVERFLOW  0x0008u  /* the fused path ran over a capacity; a later route took the batch */
+#define PSS_ROUTE_INTERVAL_LANE   0x0010u  /* interval search, one lane per pair */
+#define PSS_ROUTE_INTERVAL_GROUP  0x0020u  /* interval search, 16 lanes per pair */
+#define PSS_ROUTE_INTERVAL_WAVE   0x0040u  /* interval search, one wavefront per pair */
+#define PSS_ROUTE_KEY_SAMPLES     0x0080u  /* the reader's chunks have key-sample tables (the searches start from a window) */
+#define PSS_ROUTE_MID             0x0100u  /* mid pipeline */
+#define PSS_ROUTE_MID_OVERFLOW    0x0200u  /* the mid pipeline ran over its hits or bytes; the general pipeline took the batch */
+#define PSS_ROUTE_GENERAL         0x0400u  /* general multi-kernel pipeline */
+#define PSS_ROUTE_SA_ORDER        0x0800u  /* ... with the suffix-array result order (pss_reader_set_result_order) */
+#define PSS_ROUTE_COUNTS          0x1000u  /* ... counting entries only (pss_reader_count_batch) */
 
 /*
  * Reader::search (src/lib.rs:201-287) for a whole batch in one call, i.e.

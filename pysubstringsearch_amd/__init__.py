@@ -472,6 +472,8 @@ class Reader:
         return self._search_batch(patterns, False)
 
     def last_stats(self) -> dict:
+        """Statistics of the last batch (pss_search_stats): counts, times, and ``route`` -- the PSS_ROUTE_* bits of
+        the search routes that served it (``_ffi.ROUTES`` names them)."""
         st = _ffi.SearchStats()
         _ffi.check(_lib.pss_reader_last_stats(self._handle(), ctypes.byref(st)))
         return st.as_dict()

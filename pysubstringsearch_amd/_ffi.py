@@ -121,10 +121,30 @@ class SearchStats(ctypes.Structure):
         ('ms_device', ctypes.c_double),
         ('ms_interval', ctypes.c_double),
         ('ms_host', ctypes.c_double),
+        ('route', ctypes.c_uint32),
+        ('route_pad', ctypes.c_uint32),
     ]
 
     def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != 'route_pad'}
+
+
+# Bits of SearchStats.route (PSS_ROUTE_* in include/pss.h): which search routes served a batch.
+ROUTES = {
+    'RESIDENT': 0x0001,
+    'SMALL_BLOCK': 0x0002,
+    'SMALL_WAVE': 0x0004,
+    'SMALL_OVERFLOW': 0x0008,
+    'INTERVAL_LANE': 0x0010,
+    'INTERVAL_GROUP': 0x0020,
+    'INTERVAL_WAVE': 0x0040,
+    'KEY_SAMPLES': 0x0080,
+    'MID': 0x0100,
+    'MID_OVERFLOW': 0x0200,
+    'GENERAL': 0x0400,
+    'SA_ORDER': 0x0800,
+    'COUNTS': 0x1000,
+}
 
 
 class DeviceResult(ctypes.Structure):

@@ -186,6 +186,17 @@ int reader_sample_chunk(pss_reader *r, const ChunkDesc &c)
 
 void reader_free(pss_reader *r);
 
+// PSS_ROUTE_KEY_SAMPLES of the last batch: whether the chunks have key-sample tables was decided when they were loaded
+// (reader_alloc_chunk), not by search_batch_device, which sees the chunk table only on the device.
+void reader_note_route(pss_reader *r)
+{
+    for (const ChunkDesc &c : r->chunks)
+        if (c.skeys) {
+            r->last.route |= PSS_ROUTE_KEY_SAMPLES;
+            return;
+        }
+}
+
 void part_run(pss_reader::Part *p)      // the job in p's mailbox, on p's reader
 {
     pss_reader *r = p->reader;
@@ -202,6 +213,7 @@ void part_run(pss_reader::Part *p)      // the job in p's mailbox, on p's reader
         uint64_t *hits = reader_hits_buffer(r);
         rc = search_batch_device(r->ctx, r->d_descs, (uint32_t)r->chunks.size(), p->qbytes, p->qoffsets, p->nq, &p->res, &r->last,
                                  (SearchMode)p->mode, false, hits, r->order_sa);
+        if (rc == PSS_OK) reader_note_route(r);
         if (rc == PSS_OK && hits) reader_note_batch(r);
     }
     if (rc != PSS_OK) p->err = last_error();
@@ -607,6 +619,7 @@ int multi_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, 
         st.result_bytes += ps.result_bytes;
         st.ms_device = std::max(st.ms_device, ps.ms_device);
         st.ms_interval = std::max(st.ms_interval, ps.ms_interval);
+        st.route |= ps.route;
         E += p->res.n_entries;
         B += p->res.n_bytes;
     }
@@ -1005,6 +1018,7 @@ extern "C" int pss_reader_search_batch(pss_reader *r, const uint8_t *qbytes, con
         uint64_t *hits = reader_hits_buffer(r);
         const int rc = search_batch_device(r->ctx, r->d_descs, nc, qbytes, qoffsets, nq, &res->r, &r->last, SEARCH_FULL,
                                            r->low_latency, hits, r->order_sa);
+        if (rc == PSS_OK) reader_note_route(r);
         if (rc == PSS_OK && hits) reader_note_batch(r);
         if (rc != PSS_OK) {
             pss_result_free(res);
@@ -1076,6 +1090,7 @@ extern "C" int pss_reader_count_batch(pss_reader *r, const uint8_t *qbytes, cons
         pss_result res;
         uint64_t *hits = reader_hits_buffer(r);
         const int rc = search_batch_device(r->ctx, r->d_descs, nc, qbytes, qoffsets, nq, &res.r, &r->last, SEARCH_COUNTS, false, hits);
+        if (rc == PSS_OK) reader_note_route(r);
         if (rc == PSS_OK && hits) reader_note_batch(r);
         if (rc == PSS_OK && nq) memcpy(counts, res.r.qcount, (size_t)nq * sizeof(uint64_t));
         res.r.release();
@@ -1103,6 +1118,7 @@ extern "C" int pss_reader_search_batch_device(pss_reader *r, const uint8_t *qbyt
         const int rc = search_batch_device(r->ctx, r->d_descs, nc, qbytes, qoffsets, nq, &hr, &r->last, SEARCH_DEVICE, false, nullptr,
                                            r->order_sa);
         if (rc == PSS_OK) {
+            reader_note_route(r);
             out->num_queries = nq;
             out->num_entries = hr.n_entries;
             out->num_bytes = hr.n_bytes;

@@ -1710,6 +1710,7 @@ static int resident_query(DeviceCtx *ctx, const ChunkDesc *d_chunks, u32 nc, con
             ++R.served;
             if (*h_overflow) return PSS_OK;      // too many hits for this path: the launch path and its fallbacks take it
             PSS_TRY(small_collect(ctx, h_arena, arena + 64, (u64)nc * spread, spread, nc, res, st));
+            st->route |= PSS_ROUTE_RESIDENT;
             *served = true;
             return PSS_OK;
         }
@@ -1839,6 +1840,7 @@ int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, u32 nc, const
         u32 spread = 1;
         if (block_path)
             while (spread < SM_SPREAD && nvq * spread * 2 <= (nvq <= 32 ? 64u : 256u)) spread *= 2;
+        st->route |= block_path ? PSS_ROUTE_SMALL_BLOCK : PSS_ROUTE_SMALL_WAVE;
         if (block_path)
             hipLaunchKernelGGL(search_block_kernel, dim3((u32)nvq * spread), dim3(SM_BLOCK), 0, s, d_chunks, nc, v_q, v_qoff,
                                (u32)nvq, d_hdr, v_flags, v_rec, v_ent, d_bytes, v_arena + SM_OFF_BYTES, spread);
@@ -1858,6 +1860,7 @@ int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, u32 nc, const
             return PSS_OK;
         }
         // overflow: fall through to the general path (qcount is still all zero)
+        st->route |= PSS_ROUTE_SMALL_OVERFLOW;
     }
     if (tiny) {
         // pageable H2D copies are synchronous and slow to start: tiny batches go up from the pinned staging
@@ -1881,15 +1884,19 @@ int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, u32 nc, const
     PSS_HIP(hipEventRecord(e0, s));
     const u64 lane_min = knobs.lane_search_min;   // pairs from which one lane per pair is at least as fast as 16
                                                   // (10 000 pairs: 0.039 ms either way; 30 000: 0.044 vs 0.078 ms)
-    if (nvq >= lane_min && !knobs.wave_search)
+    if (nvq >= lane_min && !knobs.wave_search) {
+        st->route |= PSS_ROUTE_INTERVAL_LANE;
         hipLaunchKernelGGL(search_interval_lane_kernel, dim3((u32)((nvq + 255) / 256)), dim3(256), 0, s, d_chunks, nc,
                            d_q, d_qoff, nvq, d_lo, d_cnt);
-    else if (nvq >= 2048 && !knobs.wave_search && !knobs.no_group_search)
+    } else if (nvq >= 2048 && !knobs.wave_search && !knobs.no_group_search) {
+        st->route |= PSS_ROUTE_INTERVAL_GROUP;
         hipLaunchKernelGGL(search_interval_group_kernel, dim3((u32)((nvq + 15) / 16)), dim3(256), 0, s, d_chunks, nc, d_q,
                            d_qoff, nvq, d_lo, d_cnt);
-    else
+    } else {
+        st->route |= PSS_ROUTE_INTERVAL_WAVE;
         hipLaunchKernelGGL(search_interval_kernel, dim3((u32)((nvq + waves_per_block - 1) / waves_per_block)), dim3(256),
                            0, s, d_chunks, nc, d_q, d_qoff, nvq, d_lo, d_cnt);
+    }
     PSS_HIP(hipEventRecord(e1, s));
     if (chunk_hits && nc <= 4096) {
         // (a reader with suffix arrays on the host tier: where did this batch's hits land?  One small kernel over the
@@ -1902,6 +1909,7 @@ int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, u32 nc, const
     }
     if (nvq <= MID_MAX && !counts_only && !knobs.no_mid_pipeline && !sa_order) {
         // ---- mid pipeline: totals stay on the device, one wait for them, one for the result ----
+        st->route |= PSS_ROUTE_MID;
         const u64 byte_cap = (u64)16 << 20;
         PSS_TRY(ctx->slot[Q_START].reserve((size_t)MID_MAX * 4));
         PSS_TRY(ctx->slot[Q_LEN].reserve((size_t)MID_MAX * 4));
@@ -1983,7 +1991,9 @@ int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, u32 nc, const
             return PSS_OK;
         }
         // more hits or bytes than the caps: the general pipeline below takes over (intervals are kept)
+        st->route |= PSS_ROUTE_MID_OVERFLOW;
     }
+    st->route |= PSS_ROUTE_GENERAL | (sa_order ? PSS_ROUTE_SA_ORDER : 0u) | (counts_only ? PSS_ROUTE_COUNTS : 0u);
     PSS_TRY(device_excl_scan(ctx, InU32{d_cnt}, nvq, d_partial, d_total, d_hitoff));
     PSS_HIP(hipMemcpyAsync(h_small, d_total, 8, hipMemcpyDeviceToHost, s));
     PSS_HIP(hipStreamSynchronize(s));
