@@ -411,6 +411,32 @@ int pss_reader_search_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t
 int pss_reader_count_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets,
                            uint32_t nq, uint64_t *counts);
 /*
+ * Entry ids (no reference counterpart: Reader::search hands out entry text only, src/lib.rs:254-286).  An entry id is
+ * (chunk index in the index file << 32) | line, line = the number of 0x0A bytes in the chunk's text before the entry's
+ * first byte; a chunk holds count(0x0A) + (1 when it is non-empty and does not end in 0x0A) entries, empty ones
+ * included.  A sharded or multi-device reader hands out the chunk's index IN THE FILE, so the ids of one file mean the
+ * same everywhere; a reader filled by pss_reader_add_chunk_device numbers its chunks as they were added.  For a
+ * whole-file reader, (entries of the chunks before c) + line is the entry's 0-based position in the order the entries
+ * were added -- the line number in the source file for an index made by one pss_writer_add_file_lines call.
+ * The ids rest on a line index per chunk (one u32 newline rank per 256 bytes of text, 1/64 of the text, in HBM) that is
+ * built by the first of these three calls on a reader -- and again for a chunk that is replaced or appended; a
+ * reader that never asks for ids allocates nothing for it.  From then on pss_reader_residency counts it in hbm_bytes.
+ *
+ * pss_reader_search_ids_batch: the ids of the entries pss_reader_search_batch would return, in the same order (the
+ * reader's result order included).  *out is a pss_result whose query_counts are the entries per query and whose bytes
+ * are num_entries little-endian u64 ids, 8-byte aligned (offsets[i] = 8 * i).  The batch takes the general pipeline as
+ * pss_reader_count_batch does -- interval search, dedupe, one scan -- and then writes one id per entry: no entry text is
+ * measured, copied or brought down.
+ */
+int pss_reader_search_ids_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq,
+                                pss_result **out);
+/* Text of the entries ids[0 .. n): a packed result of n "queries" with one entry each, in the order asked.
+ * PSS_EINVAL (message in pss_last_error, *out untouched) when an id names a chunk this reader does not hold or a
+ * line the chunk does not have.  The same id may be asked for more than once. */
+int pss_reader_entries_by_id(pss_reader *r, const uint64_t *ids, uint64_t n, pss_result **out);
+/* For the first `cap` resident chunks, in file order: index in the file and number of entries; *num = resident chunks. */
+int pss_reader_chunk_entries(pss_reader *r, uint64_t *chunk_index, uint64_t *entries, uint64_t cap, uint64_t *num);
+/*
  * The same search with the packed result LEFT ON THE DEVICE: the multi-GPU gather (RCCL send / recv of
  * device buffers to the collecting rank, pysubstringsearch_amd/dist.py) takes it from there, so a
  * contributing rank never moves an entry through its host.  Replaces, across GPUs, what

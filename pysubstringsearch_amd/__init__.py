@@ -26,7 +26,7 @@ try:   # C loop for result lists (csrc/pyglue.c); plain Python slicing if it was
 except ImportError:   # pragma: no cover
     _pssglue = None
 
-__all__ = ['Writer', 'Reader', 'PackedResult', 'DeviceResult', 'device_count', 'default_devices', 'release_workspace', 'workspace_bytes']
+__all__ = ['Writer', 'Reader', 'PackedResult', 'IdResult', 'DeviceResult', 'device_count', 'default_devices', 'release_workspace', 'workspace_bytes']
 
 
 def device_count() -> int:
@@ -200,6 +200,12 @@ class _ResultOwner:
 class PackedResult(typing.NamedTuple):
     data: typing.Any      # numpy uint8: all entries back to back
     offsets: typing.Any   # numpy uint64 [num_entries + 1]
+    counts: typing.Any    # numpy uint64 [num_queries]
+
+
+class IdResult(typing.NamedTuple):
+    """Entry ids of one batch (``Reader.search_ids_batch``): ``(chunk index in the file << 32) | line``."""
+    ids: typing.Any       # numpy uint64 [num_entries], read-only view of the result, query-major
     counts: typing.Any    # numpy uint64 [num_queries]
 
 
@@ -423,6 +429,95 @@ class Reader:
         offsets = owner.view(_lib.pss_result_offsets(res), n + 1, np.uint64)
         data = owner.view(_lib.pss_result_bytes(res), int(offsets[n]), np.uint8)
         return PackedResult(data, offsets, counts)
+
+    def search_ids_batch(self, patterns: typing.Sequence[bytes]) -> 'IdResult':
+        """Extension: WHICH entries match instead of their text -- one ``uint64`` id per entry
+        ``search_batch_packed(patterns)`` would return, in the same order (query-major; ``counts[q]`` of them belong to
+        query q; each id once per query).  An id is ``(chunk index in the index file << 32) | line``, ``line`` = the
+        entry's number inside its chunk; a shard and a multi-device reader hand out the same ids as a whole-file
+        reader.  8 bytes per entry come down whatever the entries' length; ``entries_by_id`` fetches the text of the
+        ones that are wanted, ``entry_ordinals`` turns ids into positions in the order the entries were added (line
+        numbers of the file given to ``add_entries_from_file_lines``)."""
+        import numpy as np
+        nq = len(patterns)
+        blob = b''.join(patterns)
+        offs = np.zeros(nq + 1, dtype=np.uint64)
+        if nq:
+            np.cumsum(np.fromiter(map(len, patterns), dtype=np.uint64, count=nq), out=offs[1:])
+        res = ctypes.c_void_p()
+        _ffi.check(_lib.pss_reader_search_ids_batch(self._handle(), blob, offs.ctypes.data, nq, ctypes.byref(res)))
+        owner = _ResultOwner(res)      # the arrays below are views of the C result; it lives as long as they do
+        n = _lib.pss_result_num_entries(res)
+        counts = owner.view(_lib.pss_result_query_counts(res), nq, np.uint64)
+        ids = owner.view(_lib.pss_result_bytes(res), 8 * n, np.uint8).view(np.uint64)
+        ids.flags.writeable = False     # (also the empty array of a batch without entries, which views nothing)
+        return IdResult(ids, counts)
+
+    def search_ids(self, substring: str):
+        """Extension: the ids of the entries ``search(substring)`` returns, in its order (numpy uint64)."""
+        return self.search_ids_batch([_utf8(substring, 'substring')]).ids
+
+    def entries_by_id_packed(self, ids) -> 'PackedResult':
+        """Extension: the text of the entries ``ids`` (any integer sequence or array; an id may repeat) as a packed
+        result -- entry i = ``data[offsets[i]:offsets[i+1]]``, in the order asked, ``counts`` all one.  ``ValueError``
+        when an id names a chunk this reader does not hold or a line its chunk does not have."""
+        import numpy as np
+        arr = np.ascontiguousarray(np.asarray(ids).reshape(-1) if len(ids) else np.zeros(0, dtype=np.uint64))
+        if arr.dtype != np.uint64:
+            if arr.dtype.kind not in 'iu':
+                raise TypeError('entry ids must be integers')
+            if arr.dtype.kind == 'i' and arr.size and int(arr.min()) < 0:
+                raise ValueError('entry ids are not negative')
+            arr = arr.astype(np.uint64)
+        n = int(arr.size)
+        res = ctypes.c_void_p()
+        _ffi.check(_lib.pss_reader_entries_by_id(self._handle(), arr.ctypes.data, n, ctypes.byref(res)))
+        owner = _ResultOwner(res)
+        counts = owner.view(_lib.pss_result_query_counts(res), n, np.uint64)
+        offsets = owner.view(_lib.pss_result_offsets(res), n + 1, np.uint64)
+        data = owner.view(_lib.pss_result_bytes(res), int(offsets[n]), np.uint8)
+        return PackedResult(data, offsets, counts)
+
+    def entries_by_id(self, ids) -> typing.List[bytes]:
+        """Extension: ``entries_by_id_packed`` as a list of byte strings."""
+        p = self.entries_by_id_packed(ids)
+        data = p.data.tobytes()
+        o = p.offsets.tolist()
+        return [data[o[i]:o[i + 1]] for i in range(len(o) - 1)]
+
+    @property
+    def entry_counts(self) -> typing.Dict[int, int]:
+        """Extension: entries of every chunk this reader holds, keyed by the chunk's index in the index file."""
+        num = ctypes.c_uint64()
+        _ffi.check(_lib.pss_reader_chunk_entries(self._handle(), None, None, 0, ctypes.byref(num)))
+        k = int(num.value)
+        idx = (ctypes.c_uint64 * max(k, 1))()
+        ent = (ctypes.c_uint64 * max(k, 1))()
+        _ffi.check(_lib.pss_reader_chunk_entries(self._handle(), idx, ent, k, ctypes.byref(num)))
+        return {int(idx[i]): int(ent[i]) for i in range(min(k, int(num.value)))}
+
+    def entry_ordinals(self, ids):
+        """Extension: ids -> 0-based positions of the entries in the order they were added (numpy int64): entries of
+        the chunks before the id's chunk, plus its line.  For an index made by one ``add_entries_from_file_lines``
+        call that is the line number in the source file.  ``ValueError`` when this reader does not hold every chunk
+        of the file from 0 up to the largest one named (a shard cannot know what the others hold)."""
+        import numpy as np
+        arr = np.asarray(ids, dtype=np.uint64).reshape(-1)
+        if not arr.size:
+            return np.zeros(0, dtype=np.int64)
+        chunk = (arr >> np.uint64(32)).astype(np.int64)
+        line = (arr & np.uint64(0xffffffff)).astype(np.int64)
+        counts = self.entry_counts
+        top = int(chunk.max())
+        missing = [c for c in range(top + 1) if c not in counts]
+        if missing:
+            raise ValueError(f'entry_ordinals needs every chunk from 0 to {top}; this reader does not hold chunk {missing[0]}')
+        per = np.array([counts[c] for c in range(top + 1)], dtype=np.int64)
+        if (line >= per[chunk]).any():
+            bad = int(arr[np.argmax(line >= per[chunk])])
+            raise ValueError(f'entry id {bad:#x}: chunk {bad >> 32} has {int(per[bad >> 32])} entries')
+        base = np.concatenate(([0], np.cumsum(per)[:-1]))
+        return base[chunk] + line
 
     def search_batch_device(self, patterns: typing.Sequence[bytes]) -> 'DeviceResult':
         """One batched device call whose packed result STAYS in HBM (torch tensors, no copy): what the

@@ -36,6 +36,11 @@ class PackedResult(typing.NamedTuple):
     counts: typing.Any    # numpy uint64 array [num_queries]
 
 
+class IdResult(typing.NamedTuple):
+    ids: typing.Any       # numpy uint64 array [num_entries]: (chunk index in the file << 32) | line, query-major
+    counts: typing.Any    # numpy uint64 array [num_queries]
+
+
 class DeviceResult(typing.NamedTuple):
     data: typing.Any      # torch uint8 tensor in HBM: all entries back to back
     starts: typing.Any    # torch int64 tensor [num_entries]: start of every entry
@@ -82,6 +87,19 @@ class Reader:
     def search_batch_packed(self, patterns: typing.Sequence[bytes]) -> PackedResult: ...
 
     def search_batch_device(self, patterns: typing.Sequence[bytes]) -> DeviceResult: ...
+
+    def search_ids(self, substring: str) -> typing.Any: ...     # numpy uint64 array
+
+    def search_ids_batch(self, patterns: typing.Sequence[bytes]) -> IdResult: ...
+
+    def entries_by_id(self, ids: typing.Any) -> typing.List[bytes]: ...
+
+    def entries_by_id_packed(self, ids: typing.Any) -> PackedResult: ...
+
+    @property
+    def entry_counts(self) -> typing.Dict[int, int]: ...
+
+    def entry_ordinals(self, ids: typing.Any) -> typing.Any: ...     # numpy int64 array
 
     def search_multiple_bytes_as_str(self, patterns: typing.Sequence[bytes]) -> typing.List[str]: ...
 

@@ -279,6 +279,9 @@ def _load() -> ctypes.CDLL:
         'pss_reader_search_batch': (ctypes.c_int, [vp, vp, vp, u32, pvp]),
         'pss_reader_count_batch': (ctypes.c_int, [vp, vp, vp, u32, vp]),
         'pss_reader_search_batch_device': (ctypes.c_int, [vp, vp, vp, u32, ctypes.POINTER(DeviceResult)]),
+        'pss_reader_search_ids_batch': (ctypes.c_int, [vp, vp, vp, u32, pvp]),
+        'pss_reader_entries_by_id': (ctypes.c_int, [vp, vp, u64, pvp]),
+        'pss_reader_chunk_entries': (ctypes.c_int, [vp, vp, vp, u64, ctypes.POINTER(u64)]),
         'pss_merge_packed': (ctypes.c_int, [u32, u64, vp, vp, vp, vp, vp, vp, vp, vp]),
         'pss_merge_packed_device': (ctypes.c_int, [i32, u32, u64, vp, vp, vp, vp, vp, vp, vp, vp]),
         'pss_comm_unique_id': (ctypes.c_int, [vp]),

@@ -17,8 +17,17 @@ struct pss_reader {
         void *skeys = nullptr;     // own hipMalloc when the suffix array is on the host, else inside `sa`
         bool sa_host = false;
         uint64_t hbm_bytes = 0, host_bytes = 0;
+        // Line index behind the entry ids (search.h, LineDesc): built by the first call that asks for ids, always in HBM,
+        // counted in hbm_bytes from then on, never moved by the residency manager.
+        void *lines = nullptr;
+        uint64_t lines_bytes = 0;
+        uint32_t line_shift = 0, entries = 0;
+        bool lines_built = false;
     };
     std::vector<Mem> mem;
+    std::vector<uint64_t> file_index;   // chunk i's index in the index file (a shard holds every k-th): the high word of its entry ids
+    LineDesc *d_lines = nullptr;        // device copy of the line tables' descriptors, parallel to d_descs
+    size_t d_lines_cap = 0;
     ChunkDesc *d_descs = nullptr;
     size_t d_descs_cap = 0;
     bool dirty = true;
@@ -54,7 +63,7 @@ struct pss_reader::Part {
     const uint8_t *qbytes = nullptr;
     const uint64_t *qoffsets = nullptr;
     uint32_t nq = 0;
-    int mode = 0;                        // SEARCH_FULL / SEARCH_COUNTS
+    int mode = 0;                        // SEARCH_FULL / SEARCH_COUNTS / SEARCH_IDS
     int rc = 0;
     HostResult res;
     std::string err;
@@ -67,6 +76,7 @@ struct pss_result {
 namespace {
 
 int reader_sync_descs(pss_reader *r);
+int reader_ensure_lines(pss_reader *r);
 
 // HBM the reader may still take for suffix arrays: PSS_READER_HBM_BUDGET (bytes, over all chunks of
 // this reader; tests use it to force the host tier), else whatever hipMalloc grants while
@@ -78,7 +88,18 @@ void reader_free_mem(pss_reader::Mem &m)
     if (m.text) (void)hipFree(m.text);
     if (m.sa) (void)(m.sa_host ? hipHostFree(m.sa) : hipFree(m.sa));
     if (m.skeys) (void)hipFree(m.skeys);
+    if (m.lines) (void)hipFree(m.lines);
     m = pss_reader::Mem{};
+}
+
+void reader_drop_lines(pss_reader::Mem &m)
+{
+    if (m.lines) (void)hipFree(m.lines);
+    m.hbm_bytes -= m.lines_bytes;
+    m.lines = nullptr;
+    m.lines_bytes = 0;
+    m.entries = 0;
+    m.lines_built = false;
 }
 
 // Text (zero padded) and suffix array of one chunk; the key-sample table (search.h) lives behind
@@ -209,10 +230,11 @@ void part_run(pss_reader::Part *p)      // the job in p's mailbox, on p's reader
         rc = PSS_EDEVICE;
     }
     if (rc == PSS_OK) rc = reader_sync_descs(r);
+    if (rc == PSS_OK && p->mode == SEARCH_IDS) rc = reader_ensure_lines(r);
     if (rc == PSS_OK) {
         uint64_t *hits = reader_hits_buffer(r);
         rc = search_batch_device(r->ctx, r->d_descs, (uint32_t)r->chunks.size(), p->qbytes, p->qoffsets, p->nq, &p->res, &r->last,
-                                 (SearchMode)p->mode, false, hits, r->order_sa);
+                                 (SearchMode)p->mode, false, hits, r->order_sa, r->d_lines);
         if (rc == PSS_OK) reader_note_route(r);
         if (rc == PSS_OK && hits) reader_note_batch(r);
     }
@@ -256,6 +278,7 @@ void reader_free(pss_reader *r)
     }
     for (auto &m : r->mem) reader_free_mem(m);
     if (r->d_descs) (void)hipFree(r->d_descs);
+    if (r->d_lines) (void)hipFree(r->d_lines);
     delete r;
 }
 
@@ -360,6 +383,66 @@ int reader_sync_descs(pss_reader *r)
     }
     PSS_HIP(hipMemcpy(r->d_descs, r->chunks.data(), sizeof(ChunkDesc) * nc, hipMemcpyHostToDevice));
     r->dirty = false;
+    return PSS_OK;
+}
+
+// The line index of every resident chunk that has none yet -- all of them on the first call that asks for ids, later the
+// chunks pss_reader_add_chunk_device appended or pss_reader_set_chunk_device replaced -- and the device copy of the
+// descriptors.  A reader that never asks for ids never gets here.  (The caller holds the context and has made the
+// device current.)
+int reader_ensure_lines(pss_reader *r)
+{
+    const size_t nc = r->chunks.size();
+    uint32_t shift = kLineShift;
+    if (const char *ev = knob("PSS_LINE_BLOCK_SHIFT")) {
+        const int v = atoi(ev);
+        if (v >= (int)kLineShiftMin && v <= (int)kLineShiftMax) shift = (uint32_t)v;
+    }
+    std::vector<size_t> fresh;
+    for (size_t c = 0; c < nc; ++c) {
+        pss_reader::Mem &m = r->mem[c];
+        const ChunkDesc &cd = r->chunks[c];
+        if (m.lines_built || cd.n == 0) continue;
+        if (!m.lines) {
+            const size_t bytes = line_table_bytes(cd.n, shift);
+            const hipError_t e = hipMalloc(&m.lines, bytes);
+            if (e != hipSuccess) {
+                (void)hipGetLastError();
+                m.lines = nullptr;
+                set_error("hipMalloc of the line index of a %u-byte chunk failed: %s", cd.n, hipGetErrorString(e));
+                return PSS_ENOMEM;
+            }
+            m.lines_bytes = bytes;
+            m.hbm_bytes += bytes;
+            m.line_shift = shift;
+        }
+        PSS_TRY(build_line_index(r->ctx, cd.text, cd.n, m.line_shift, static_cast<uint32_t *>(m.lines)));
+        fresh.push_back(c);
+    }
+    if (fresh.empty() && r->d_lines) return PSS_OK;
+    PSS_HIP(hipStreamSynchronize(r->ctx->stream));
+    for (size_t c : fresh) {
+        pss_reader::Mem &m = r->mem[c];
+        const uint32_t *rank = static_cast<const uint32_t *>(m.lines);
+        PSS_HIP(hipMemcpy(&m.entries, rank + line_blocks(r->chunks[c].n, m.line_shift) + 1, 4, hipMemcpyDeviceToHost));
+        m.lines_built = true;
+    }
+    if (nc == 0) return PSS_OK;
+    if (r->d_lines_cap < nc) {
+        if (r->d_lines) (void)hipFree(r->d_lines);
+        r->d_lines = nullptr;
+        r->d_lines_cap = 0;
+        const size_t cap = nc < 16 ? 16 : nc * 2;
+        PSS_HIP(hipMalloc(reinterpret_cast<void **>(&r->d_lines), sizeof(LineDesc) * cap));
+        r->d_lines_cap = cap;
+    }
+    std::vector<LineDesc> ld(nc);
+    for (size_t c = 0; c < nc; ++c) {
+        const pss_reader::Mem &m = r->mem[c];
+        ld[c] = LineDesc{static_cast<const uint32_t *>(m.lines), m.lines_built ? (uint32_t)line_blocks(r->chunks[c].n, m.line_shift) : 0u,
+                         m.line_shift, m.entries, (uint32_t)r->file_index[c]};
+    }
+    PSS_HIP(hipMemcpy(r->d_lines, ld.data(), sizeof(LineDesc) * nc, hipMemcpyHostToDevice));
     return PSS_OK;
 }
 }  // namespace
@@ -482,6 +565,7 @@ extern "C" int pss_reader_open(const char *path, int32_t device, int32_t shard_i
                 if (rc) break;
                 r->chunks.push_back(cd);
                 r->mem.push_back(cm);
+                r->file_index.push_back((uint64_t)index);
                 rc = upload_from_file(r, fp, const_cast<uint8_t *>(cd.text), dlen);
                 if (rc) break;
             } else if (fseeko(fp, dlen, SEEK_CUR) != 0) { rc = io_error(path); break; }
@@ -721,6 +805,7 @@ extern "C" int pss_reader_add_chunk_device(pss_reader *r, const void *d_text, co
         PSS_TRY(reader_alloc_chunk(r, n, &cd, &cm));
         r->chunks.push_back(cd);
         r->mem.push_back(cm);
+        r->file_index.push_back(r->file_index.empty() ? 0 : r->file_index.back() + 1);      // (a reader made by pss_reader_create: the resident index)
         PSS_HIP(hipMemcpyAsync(cm.text, d_text, n, hipMemcpyDeviceToDevice, r->ctx->stream));
         PSS_HIP(hipMemcpyAsync(cm.sa, d_sa, (size_t)n * 4, cm.sa_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
                                r->ctx->stream));
@@ -753,6 +838,7 @@ extern "C" int pss_reader_set_chunk_device(pss_reader *r, uint64_t index, const 
             r->mem[index] = fm;
             r->dirty = true;
         }
+        reader_drop_lines(r->mem[index]);              // the next call that asks for ids indexes the new text
         const pss_reader::Mem &cm = r->mem[index];
         PSS_HIP(hipMemcpyAsync(cm.text, d_text, n, hipMemcpyDeviceToDevice, r->ctx->stream));
         PSS_HIP(hipMemcpyAsync(cm.sa, d_sa, (size_t)n * 4, cm.sa_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
@@ -1129,6 +1215,175 @@ extern "C" int pss_reader_search_batch_device(pss_reader *r, const uint8_t *qbyt
         }
         hr.release();
         return rc;
+    });
+}
+
+// ---- entry ids ---------------------------------------------------------------------------------------------------
+
+extern "C" int pss_reader_search_ids_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq,
+                                           pss_result **out)
+{
+    return guarded([&]() -> int {
+        if (!r || !out || (nq && !qoffsets)) {
+            set_error("pss_reader_search_ids_batch: bad arguments");
+            return PSS_EINVAL;
+        }
+        pss_result *res = new pss_result();
+        int rc = PSS_OK;
+        if (!r->parts.empty()) {
+            // (the parts' ids travel as the bytes of ordinary packed results, 8 per entry: the merge is the one of the entries)
+            rc = multi_batch(r, qbytes, qoffsets, nq, SEARCH_IDS, &res->r);
+        } else {
+            std::lock_guard<std::recursive_mutex> lk(r->ctx->mu);
+            PSS_HIP(hipSetDevice(r->device));
+            rc = reader_sync_descs(r);
+            if (rc == PSS_OK) rc = reader_ensure_lines(r);
+            if (rc == PSS_OK) {
+                uint64_t *hits = reader_hits_buffer(r);
+                rc = search_batch_device(r->ctx, r->d_descs, (uint32_t)r->chunks.size(), qbytes, qoffsets, nq, &res->r, &r->last,
+                                         SEARCH_IDS, false, hits, r->order_sa, r->d_lines);
+                if (rc == PSS_OK) reader_note_route(r);
+                if (rc == PSS_OK && hits) reader_note_batch(r);
+            }
+        }
+        if (rc != PSS_OK) {
+            pss_result_free(res);
+            return rc;
+        }
+        *out = res;
+        return PSS_OK;
+    });
+}
+
+namespace {
+
+// ids[0 .. n) of ONE single-device reader: validation on the host (the reader knows every chunk's entry count once the
+// line tables exist), select + copy on the device.
+int reader_entries_single(pss_reader *x, const uint64_t *ids, uint64_t n, HostResult *res)
+{
+    std::lock_guard<std::recursive_mutex> lk(x->ctx->mu);
+    PSS_HIP(hipSetDevice(x->device));
+    PSS_TRY(reader_sync_descs(x));
+    PSS_TRY(reader_ensure_lines(x));
+    std::vector<uint32_t> chunk_of(n), line_of(n);
+    size_t at = 0;                                   // (consecutive ids mostly name the same chunk)
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t c = ids[i] >> 32;
+        const uint32_t line = (uint32_t)ids[i];
+        if (at >= x->file_index.size() || x->file_index[at] != c) {
+            for (at = 0; at < x->file_index.size() && x->file_index[at] != c; ++at) {}
+        }
+        if (at == x->file_index.size()) {
+            set_error("entry id %#llx: this reader does not hold chunk %llu", (unsigned long long)ids[i], (unsigned long long)c);
+            return PSS_EINVAL;
+        }
+        if (line >= x->mem[at].entries) {
+            set_error("entry id %#llx: chunk %llu has %u entries", (unsigned long long)ids[i], (unsigned long long)c, x->mem[at].entries);
+            return PSS_EINVAL;
+        }
+        chunk_of[i] = (uint32_t)at;
+        line_of[i] = line;
+    }
+    return entries_by_id_device(x->ctx, x->d_descs, x->d_lines, chunk_of.data(), line_of.data(), n, res);
+}
+
+}  // namespace
+
+extern "C" int pss_reader_entries_by_id(pss_reader *r, const uint64_t *ids, uint64_t n, pss_result **out)
+{
+    return guarded([&]() -> int {
+        if (!r || !out || (n && !ids)) {
+            set_error("pss_reader_entries_by_id: bad arguments");
+            return PSS_EINVAL;
+        }
+        pss_result *res = new pss_result();
+        struct Drop {
+            pss_result *p;
+            ~Drop() { if (p) pss_result_free(p); }
+        } drop{res};
+        if (r->parts.empty()) {
+            PSS_TRY(reader_entries_single(r, ids, n, &res->r));
+        } else {
+            // every part fetches the entries of its chunks (one part after the other: a fetch is two small kernels and a
+            // copy), then the texts are put back in the order asked
+            std::lock_guard<std::mutex> batch(r->multi_mu);
+            const size_t G = r->parts.size();
+            std::vector<std::vector<uint64_t>> sub(G);
+            std::vector<uint32_t> part_of(n);
+            for (uint64_t i = 0; i < n; ++i) {
+                const uint64_t c = ids[i] >> 32;
+                size_t g = 0;
+                for (; g < G; ++g) {
+                    const std::vector<uint64_t> &fi = r->parts[g]->reader->file_index;
+                    if (std::find(fi.begin(), fi.end(), c) != fi.end()) break;
+                }
+                if (g == G) {
+                    set_error("entry id %#llx: this reader does not hold chunk %llu", (unsigned long long)ids[i], (unsigned long long)c);
+                    return PSS_EINVAL;
+                }
+                part_of[i] = (uint32_t)g;
+                sub[g].push_back(ids[i]);
+            }
+            std::vector<HostResult> pr(G);
+            struct Release {
+                std::vector<HostResult> &v;
+                ~Release() { for (auto &x : v) x.release(); }
+            } release{pr};
+            uint64_t B = 0;
+            for (size_t g = 0; g < G; ++g) {
+                if (sub[g].empty()) continue;
+                PSS_TRY(reader_entries_single(r->parts[g]->reader, sub[g].data(), sub[g].size(), &pr[g]));
+                B += pr[g].n_bytes;
+            }
+            HostResult &o = res->r;
+            o.nq = n;
+            o.qcount = static_cast<uint64_t *>(malloc((n ? n : 1) * sizeof(uint64_t)));
+            if (!o.qcount) return PSS_ENOMEM;
+            PSS_TRY(alloc_host_result(&o, n, B, !search_knobs().no_pinned_results));
+            std::vector<uint64_t> cursor(G, 0);
+            uint64_t b = 0;
+            for (uint64_t i = 0; i < n; ++i) {
+                const HostResult &p = pr[part_of[i]];
+                const uint64_t e = cursor[part_of[i]]++;
+                const uint64_t len = p.offsets[e + 1] - p.offsets[e];
+                o.qcount[i] = 1;
+                o.offsets[i] = b;
+                if (len) memcpy(o.bytes + b, p.bytes + p.offsets[e], (size_t)len);
+                b += len;
+            }
+            o.offsets[n] = b;
+            o.n_entries = n;
+            o.n_bytes = b;
+        }
+        drop.p = nullptr;
+        *out = res;
+        return PSS_OK;
+    });
+}
+
+extern "C" int pss_reader_chunk_entries(pss_reader *r, uint64_t *chunk_index, uint64_t *entries, uint64_t cap, uint64_t *num)
+{
+    return guarded([&]() -> int {
+        if (!r) return PSS_EINVAL;
+        std::vector<std::pair<uint64_t, uint64_t>> all;
+        auto add = [&](pss_reader *x) -> int {
+            if (!x->ctx) return PSS_OK;
+            std::lock_guard<std::recursive_mutex> lk(x->ctx->mu);
+            PSS_HIP(hipSetDevice(x->device));
+            PSS_TRY(reader_sync_descs(x));
+            PSS_TRY(reader_ensure_lines(x));
+            for (size_t c = 0; c < x->chunks.size(); ++c) all.emplace_back(x->file_index[c], (uint64_t)x->mem[c].entries);
+            return PSS_OK;
+        };
+        if (r->parts.empty()) PSS_TRY(add(r));
+        for (pss_reader::Part *p : r->parts) PSS_TRY(add(p->reader));
+        std::sort(all.begin(), all.end());
+        for (size_t i = 0; i < all.size() && i < cap; ++i) {
+            if (chunk_index) chunk_index[i] = all[i].first;
+            if (entries) entries[i] = all[i].second;
+        }
+        if (num) *num = all.size();
+        return PSS_OK;
     });
 }
 

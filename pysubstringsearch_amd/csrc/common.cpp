@@ -455,6 +455,7 @@ const KnobDef kKnobs[] = {
     {"PSS_READER_AUTO_RESIDENCY", "1", "", "Reader: 0 = the residency manager never moves a suffix array by itself"},
     {"PSS_NO_KEY_SAMPLES", "unset", "", "Reader: no key-sample table"},
     {"PSS_SAMPLE_SHIFT", "11", "", "Reader: one key sample per 2^shift suffixes"},
+    {"PSS_LINE_BLOCK_SHIFT", "8", "6|7|9|10", "Reader: the line index behind entry ids keeps one newline rank per 2^shift bytes of text (6 .. 10)"},
     {"PSS_NO_SMALL_PATH", "unset", "1", "search: no fused single-query kernels"},
     {"PSS_NO_BLOCK_PATH", "unset", "1", "search: small batches one wave per pair instead of one workgroup"},
     {"PSS_NO_SEARCH_STAGE", "unset", "1", "search: no pinned staging of queries and results"},

@@ -25,6 +25,24 @@ static inline uint64_t sample_count(uint32_t n, uint32_t shift) { return ((uint6
 int build_key_samples(DeviceCtx *ctx, const uint8_t *d_text, const uint32_t *d_sa, uint32_t n, uint32_t shift,
                       uint64_t *d_skeys);
 
+// Line index of one resident chunk (line_index_impl.h): what turns the start of an entry into its number inside the chunk
+// and back.  rank[j] = newlines in text[0, j << shift), j = 0 .. nblocks; rank[nblocks + 1] = entries.  Kept beside
+// ChunkDesc, in a parallel array indexed by chunk, because every search kernel copies ChunkDesc by value and only the
+// two id kernels need this.  file_index = the chunk's index in the index file: the high word of its entry ids.
+struct LineDesc {
+    const uint32_t *rank;
+    uint32_t nblocks;
+    uint32_t shift;
+    uint32_t entries;
+    uint32_t file_index;
+};
+constexpr uint32_t kLineShift = 8;      // blocks of 256 bytes: the table is 1/64 of the text ("Entry ids")
+constexpr uint32_t kLineShiftMin = 6, kLineShiftMax = 10;     // one group of 4 .. 64 lanes counts a block
+static inline uint64_t line_blocks(uint32_t n, uint32_t shift) { return ((uint64_t)n + (1u << shift) - 1) >> shift; }
+static inline size_t line_table_bytes(uint32_t n, uint32_t shift) { return (size_t)(line_blocks(n, shift) + 2) * 4; }
+// Fills d_rank (line_table_bytes) for the n-byte text (stream-ordered on ctx->stream).
+int build_line_index(DeviceCtx *ctx, const uint8_t *d_text, uint32_t n, uint32_t shift, uint32_t *d_rank);
+
 // Host-side packed result of one batch (owned by pss_result).  Small results are malloc'ed; large
 // ones (offsets + bytes) share ONE pinned block from the pool in common.h, so the D2H copy runs at
 // link speed.  In SEARCH_DEVICE mode nothing but the totals comes down: d_* point into the device
@@ -52,6 +70,8 @@ enum SearchMode {
     SEARCH_FULL = 0,     // packed result on the host
     SEARCH_COUNTS = 1,   // res->qcount only (entries each query would return); no entry is materialised
     SEARCH_DEVICE = 2,   // packed result left on the device (multi-GPU gather over RCCL takes it from there)
+    SEARCH_IDS = 3,      // packed result on the host whose "bytes" are one u64 entry id per entry (offsets[i] = 8 i): the general
+                         // pipeline up to the kept-hit scan, then one id per kept hit -- no byte scan, no text copy.  Needs d_lines.
 };
 
 // chunk_hits (optional, nc entries): how much of the batch's work landed on every chunk -- suffix-array hits per chunk on
@@ -60,11 +80,16 @@ enum SearchMode {
 int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, uint32_t nc, const uint8_t *qbytes,
                         const uint64_t *qoffsets, uint32_t nq, HostResult *res, pss_search_stats *st,
                         SearchMode mode = SEARCH_FULL, bool low_latency = false, uint64_t *chunk_hits = nullptr,
-                        bool sa_order = false);
+                        bool sa_order = false, const LineDesc *d_lines = nullptr);
 // sa_order: the entries of one (query, chunk) pair come out in the reference's order -- suffix-array order of the FIRST hit
 // inside each entry (src/lib.rs:262-276: the hits are walked in suffix-array order and an entry is pushed when its line
 // start is first seen) -- instead of the order of each entry's leftmost match.  Opt-in (pss_reader_set_result_order): it
 // takes the general pipeline and one extra sort of the hits.
+
+// Text of n entries named by (resident chunk, line) pairs the caller has validated (line < entries of that chunk): a
+// packed result of n "queries" with one entry each, in the order asked.
+int entries_by_id_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, const LineDesc *d_lines, const uint32_t *chunk_of,
+                         const uint32_t *line_of, uint64_t n, HostResult *res);
 
 // Merge of `world` packed results of the same nq queries, all resident on ctx's device, into one (query-major,
 // rank-major inside a query -- pss_merge_packed's order) on the same device.  starts[r] = entry starts (no closing

@@ -20,6 +20,8 @@
 //                        reference's.
 //   scan x2              kept flags -> entry index, entry lengths -> byte offset
 //   K3 emit              copies entry bytes into the packed result
+//   K3' emit_ids         ids mode: one u64 entry id per kept hit instead of the copy
+//                        (rank over the chunk's line index, line_index_impl.h)
 //
 // Output order: query-major, inside a query chunk-major, inside a chunk
 // suffix-array order of the kept hit (the reference's inter-chunk order is
@@ -1519,7 +1521,7 @@ constexpr size_t SM_ARENA_BYTES = SM_ARENA_RHDR + 64;
 #error "search.hip is written for gfx950 (MI355X): the fused search kernels keep ~72 KiB of LDS per workgroup (160 KiB per CU there; gfx90a / gfx942 stop at 64 KiB)"
 #endif
 
-enum SSlot { Q_ORD_K0 = 50, Q_ORD_K1, Q_ORD_V0, Q_ORD_V1, Q_ORD_WORK, Q_BYTES = 10, Q_OFF, Q_LO, Q_CNT, Q_HITOFF, Q_START, Q_LEN, Q_EIDX, Q_BOFF, Q_ENTOFF, Q_OUT, Q_SMALL, Q_QCOUNT, Q_ARENA = 28, Q_HEAT = 46 };
+enum SSlot { Q_ORD_K0 = 50, Q_ORD_K1, Q_ORD_V0, Q_ORD_V1, Q_ORD_WORK, Q_BYTES = 10, Q_OFF, Q_LO, Q_CNT, Q_HITOFF, Q_START, Q_LEN, Q_EIDX, Q_BOFF, Q_ENTOFF, Q_OUT, Q_SMALL, Q_QCOUNT, Q_ARENA = 28, Q_HEAT = 46, Q_LINE_TMP = 47 };
 
 void HostResult::release()
 {
@@ -1720,6 +1722,8 @@ static int resident_query(DeviceCtx *ctx, const ChunkDesc *d_chunks, u32 nc, con
     return PSS_OK;
 }
 
+#include "line_index_impl.h"
+
 // Suffix-array hits of the batch per chunk (pair p = query p / nc on chunk p % nc): one workgroup per chunk.
 __global__ __launch_bounds__(256) void chunk_hits_kernel(const u32 *cnt, u64 nq, u32 nc, u64 *out)
 {
@@ -1736,12 +1740,17 @@ __global__ __launch_bounds__(256) void chunk_hits_kernel(const u32 *cnt, u64 nq,
 
 int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, u32 nc, const uint8_t *qbytes,
                         const uint64_t *qoffsets, uint32_t nq, HostResult *res, pss_search_stats *st, SearchMode mode, bool low_latency,
-                        uint64_t *chunk_hits, bool sa_order)
+                        uint64_t *chunk_hits, bool sa_order, const LineDesc *d_lines)
 {
     if (chunk_hits)
         for (u32 c = 0; c < nc; ++c) chunk_hits[c] = 0;
     const bool counts_only = mode == SEARCH_COUNTS;
     const bool device_only = mode == SEARCH_DEVICE;
+    const bool ids_only = mode == SEARCH_IDS;
+    if (ids_only && nc && !d_lines) {
+        set_error("search: the ids mode needs the chunks' line tables");
+        return PSS_EINVAL;
+    }
     const SearchKnobs &knobs = search_knobs();
     hipStream_t s = ctx->stream;
     memset(st, 0, sizeof *st);
@@ -1796,7 +1805,7 @@ int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, u32 nc, const
         memcpy(stg + 8192, qoffsets, off_bytes);
     }
     if (counts_only) sa_order = false;          // (counts do not depend on the order)
-    bool small = tiny && nvq <= SM_MAX_VQ && !counts_only && !device_only && !knobs.no_small_path && !sa_order;
+    bool small = tiny && nvq <= SM_MAX_VQ && !counts_only && !device_only && !ids_only && !knobs.no_small_path && !sa_order;
     for (u32 i = 0; small && i < nq; ++i) small = qoffsets[i + 1] - qoffsets[i] <= SM_MAX_PLEN;
     const u64 waves_per_block = 256 / kWave;
     if (small) {
@@ -1907,7 +1916,7 @@ int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, u32 nc, const
         PSS_HIP(hipMemcpyAsync(chunk_hits, d_heat, (size_t)nc * 8, hipMemcpyDeviceToHost, s));
         PSS_HIP(hipStreamSynchronize(s));
     }
-    if (nvq <= MID_MAX && !counts_only && !knobs.no_mid_pipeline && !sa_order) {
+    if (nvq <= MID_MAX && !counts_only && !ids_only && !knobs.no_mid_pipeline && !sa_order) {
         // ---- mid pipeline: totals stay on the device, one wait for them, one for the result ----
         st->route |= PSS_ROUTE_MID;
         const u64 byte_cap = (u64)16 << 20;
@@ -2054,17 +2063,28 @@ int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, u32 nc, const
             st->ms_host = host_ms();
             return PSS_OK;
         }
-        PSS_TRY(device_excl_scan(ctx, InLen{d_len}, H, d_partial, d_total, d_boff));
-        PSS_HIP(hipMemcpyAsync(h_small + 1, d_total, 8, hipMemcpyDeviceToHost, s));
-        PSS_HIP(hipStreamSynchronize(s));
-        E = h_small[0];
-        B = h_small[1];
+        if (ids_only) {
+            // one id per kept hit, 8 bytes each: no byte scan, the entry count alone sizes the result
+            PSS_HIP(hipStreamSynchronize(s));
+            E = h_small[0];
+            B = E * 8;
+        } else {
+            PSS_TRY(device_excl_scan(ctx, InLen{d_len}, H, d_partial, d_total, d_boff));
+            PSS_HIP(hipMemcpyAsync(h_small + 1, d_total, 8, hipMemcpyDeviceToHost, s));
+            PSS_HIP(hipStreamSynchronize(s));
+            E = h_small[0];
+            B = h_small[1];
+        }
         PSS_TRY(ctx->slot[Q_ENTOFF].reserve((E + 1) * 8));
         PSS_TRY(ctx->slot[Q_OUT].reserve(B + 16));
         u64 *d_entoff = ctx->slot[Q_ENTOFF].as<u64>();
         u8 *d_out = ctx->slot[Q_OUT].as<u8>();
-        hipLaunchKernelGGL(emit_kernel, dim3(grid), dim3(256), 0, s, d_chunks, nc, nvq, d_hitoff, H,
-                           (const MidState *)nullptr, d_start, d_len, d_eidx, d_boff, d_entoff, d_out);
+        if (ids_only)
+            hipLaunchKernelGGL(emit_ids_kernel, dim3(grid), dim3(256), 0, s, d_chunks, d_lines, nc, nvq, d_hitoff, H, d_start, d_len,
+                               d_eidx, d_entoff, reinterpret_cast<u64 *>(d_out));
+        else
+            hipLaunchKernelGGL(emit_kernel, dim3(grid), dim3(256), 0, s, d_chunks, nc, nvq, d_hitoff, H,
+                               (const MidState *)nullptr, d_start, d_len, d_eidx, d_boff, d_entoff, d_out);
         hipLaunchKernelGGL(query_counts_kernel, dim3((nq + 255) / 256), dim3(256), 0, s, nc, nq, d_hitoff, d_eidx,
                            d_qcount, (const MidState *)nullptr);
         PSS_HIP(hipEventRecord(e2, s));
