@@ -192,6 +192,23 @@ def test_every_environment_switch_is_in_the_one_registry():
     assert set(names) - read == {'PSS_DEVICE'}, f'registered but never read: {sorted(set(names) - read)}'
 
 
+def test_every_fuzzable_switch_is_set_by_some_test():
+    """A switch the fuzzer may draw (non-empty `fuzz` column of the registry) chooses a route that must give the same
+    result: every one of them is named -- set -- in at least one test module, so no route is left to tests/tools/fuzz.py,
+    which the suite does not run."""
+    import re
+    from pysubstringsearch_amd import _ffi
+    tests_dir = os.path.join(ROOT, 'tests')
+    named = set()
+    for f in sorted(os.listdir(tests_dir)):
+        if f.startswith('test_') and f.endswith('.py'):
+            named |= set(re.findall(r'PSS_[A-Z0-9_]+', pathlib.Path(os.path.join(tests_dir, f)).read_text(encoding='utf-8')))
+    drawn = [k['name'] for k in _ffi.knobs() if k['fuzz']]
+    assert len(drawn) >= 40
+    missing = [name for name in drawn if name not in named]
+    assert missing == [], f'switches no test sets: {missing}'
+
+
 # ---- corpus generators: C++ (libpss) vs an independent Python restatement of SURVEY 8(d) ----
 
 M64 = (1 << 64) - 1
@@ -433,6 +450,10 @@ def test_io_pool_is_done_with_a_batch_before_its_waiter_returns(tmp_path):
     env = dict(os.environ, LD_LIBRARY_PATH='/opt/rocm/lib:' + os.environ.get('LD_LIBRARY_PATH', ''))
     r = subprocess.run([exe, '40000'], capture_output=True, text=True, env=env, timeout=180)
     assert r.returncode == 0, r.stdout[-1000:] + r.stderr[-1000:]
+    # the pool's size is read once per process (PSS_IO_THREADS): the same pattern with fewer threads than pieces of a batch
+    for threads in ('2', '5'):
+        r = subprocess.run([exe, '4000'], capture_output=True, text=True, env=dict(env, PSS_IO_THREADS=threads), timeout=180)
+        assert r.returncode == 0, threads + ': ' + r.stdout[-1000:] + r.stderr[-1000:]
 
 
 def test_host_logic_under_sanitizers(tmp_path):
