@@ -387,6 +387,7 @@ typedef struct pss_search_stats {
 #define PSS_ROUTE_GENERAL         0x0400u  /* general multi-kernel pipeline */
 #define PSS_ROUTE_SA_ORDER        0x0800u  /* ... with the suffix-array result order (pss_reader_set_result_order) */
 #define PSS_ROUTE_COUNTS          0x1000u  /* ... counting entries only (pss_reader_count_batch) */
+#define PSS_ROUTE_ANCHORED        0x2000u  /* ... of an anchored batch (pss_reader_search_anchored_batch) */
 
 /*
  * Reader::search (src/lib.rs:201-287) for a whole batch in one call, i.e.
@@ -434,6 +435,45 @@ int pss_reader_search_ids_batch(pss_reader *r, const uint8_t *qbytes, const uint
  * PSS_EINVAL (message in pss_last_error, *out untouched) when an id names a chunk this reader does not hold or a
  * line the chunk does not have.  The same id may be asked for more than once. */
 int pss_reader_entries_by_id(pss_reader *r, const uint64_t *ids, uint64_t n, pss_result **out);
+/*
+ * Anchored search (no reference counterpart: Reader::search answers "contains" only).  Which entries START WITH the
+ * pattern, END WITH it, or EQUAL it -- exact bytes, as everywhere.  anchors[q] is PSS_ANCHOR_START, PSS_ANCHOR_END or
+ * both, one value per query, so one batch may mix the three kinds.  With s the start of an entry and e the position of
+ * its closing 0x0A (or the length n of the chunk's text when none follows; the entries are those of "Entry ids" above),
+ * a pattern of m bytes matches the entry when
+ *   PSS_ANCHOR_START                   text[s, s + m) == pattern and s + m <= e,
+ *   PSS_ANCHOR_END                     text[e - m, e) == pattern and e - m >= s,
+ *   PSS_ANCHOR_START | PSS_ANCHOR_END  e - s == m and text[s, e) == pattern.
+ * Every entry matches at most once.  The empty pattern matches every entry under START and under END, and the empty
+ * entries under both.  A pattern that holds 0x0A matches nothing.  The text handed out for a matching entry is what
+ * pss_reader_search_batch hands out for a hit in it (an unterminated last entry loses its last byte); the ids are
+ * those of pss_reader_search_ids_batch.
+ * The search is the interval search of pss_reader_search_batch on "\n" + pattern, pattern + "\n" or
+ * "\n" + pattern + "\n" -- an interval of exactly one hit per matching entry -- plus at most two hits per chunk that no
+ * newline delimits: its first entry and an unterminated last one.  The work follows the answer, not the number of
+ * occurrences of the pattern, and nothing is deduplicated.
+ * Order: query-major, chunk-major inside a query; inside one (query, chunk) pair deterministic and the same for the
+ * text and the id variant, otherwise unspecified -- pss_reader_set_result_order has no effect (one hit per entry).
+ * An anchors[q] of 0 or above 3 is PSS_EINVAL (message in pss_last_error, *out untouched); anchor 0 is what
+ * pss_reader_search_batch is for.  Whole-file, sharded and multi-device readers, and suffix arrays on the host tier,
+ * are served alike.  pss_reader_last_stats: hits = interval hits + chunk-edge hits; route = GENERAL | ANCHORED | the
+ * interval bits (| COUNTS for the count call).  The id variant builds the line tables on first use, the other two
+ * allocate nothing for them.
+ * Out of scope: the fused small-batch path and the resident low-latency kernel (an anchored batch always takes the
+ * general pipeline, as an id batch does), a device-resident result (pss_reader_search_batch_device), and the multi-process
+ * gather over RCCL (dist.ShardedReader).
+ */
+#define PSS_ANCHOR_START 1u
+#define PSS_ANCHOR_END   2u
+/* packed entry text, as pss_reader_search_batch */
+int pss_reader_search_anchored_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq,
+                                     const uint8_t *anchors, pss_result **out);
+/* u64 entry ids, packed as pss_reader_search_ids_batch packs them */
+int pss_reader_search_anchored_ids_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq,
+                                         const uint8_t *anchors, pss_result **out);
+/* counts[q] = entries query q matches; nothing but nq counters comes down */
+int pss_reader_count_anchored_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq,
+                                    const uint8_t *anchors, uint64_t *counts);
 /* For the first `cap` resident chunks, in file order: index in the file and number of entries; *num = resident chunks. */
 int pss_reader_chunk_entries(pss_reader *r, uint64_t *chunk_index, uint64_t *entries, uint64_t cap, uint64_t *num);
 /*

@@ -485,6 +485,96 @@ class Reader:
         o = p.offsets.tolist()
         return [data[o[i]:o[i + 1]] for i in range(len(o) - 1)]
 
+    @staticmethod
+    def _anchored_args(patterns: typing.Sequence[bytes], anchors):
+        """(blob, offsets, anchor bytes) of one anchored batch; ``ValueError`` for an anchor that is none of
+        ``'start' | 'end' | 'entry'`` or a sequence of another length than ``patterns``."""
+        import numpy as np
+        nq = len(patterns)
+        if isinstance(anchors, str):
+            kinds = [anchors] * nq
+            if anchors not in _ffi.ANCHORS:
+                raise ValueError(f"anchors must be 'start', 'end' or 'entry' (or one of them per pattern), not {anchors!r}")
+        else:
+            try:
+                kinds = list(anchors)
+            except TypeError:
+                raise ValueError(f"anchors must be 'start', 'end' or 'entry' (or one of them per pattern), not {anchors!r}") from None
+        if len(kinds) != nq:
+            raise ValueError(f'{len(kinds)} anchors for {nq} patterns')
+        for k in kinds:
+            if not isinstance(k, str) or k not in _ffi.ANCHORS:
+                raise ValueError(f"an anchor is 'start', 'end' or 'entry', not {k!r}")
+        offs = np.zeros(nq + 1, dtype=np.uint64)
+        if nq:
+            np.cumsum(np.fromiter(map(len, patterns), dtype=np.uint64, count=nq), out=offs[1:])
+        return b''.join(patterns), offs, np.array([_ffi.ANCHORS[k] for k in kinds], dtype=np.uint8)
+
+    def search_anchored_batch_packed(self, patterns: typing.Sequence[bytes], anchors) -> 'PackedResult':
+        """Extension: the entries that START WITH (``'start'``), END WITH (``'end'``) or EQUAL (``'entry'``) each
+        pattern, as a packed result like ``search_batch_packed``'s.  ``anchors`` is one of the three words for the whole
+        batch or a sequence of them, one per pattern.  Exact bytes; every entry at most once per query; the empty
+        pattern matches every entry under 'start' and 'end' and the empty entries under 'entry'; a pattern holding a
+        newline matches nothing.  The suffix array holds the answer as one interval -- of ``"\\n" + pattern`` and the
+        like -- so the work follows the number of matching entries, not of occurrences (include/pss.h)."""
+        import numpy as np
+        nq = len(patterns)
+        blob, offs, anc = self._anchored_args(patterns, anchors)
+        res = ctypes.c_void_p()
+        _ffi.check(_lib.pss_reader_search_anchored_batch(self._handle(), blob, offs.ctypes.data, nq, anc.ctypes.data, ctypes.byref(res)))
+        owner = _ResultOwner(res)      # the arrays below are views of the C result; it lives as long as they do
+        n = _lib.pss_result_num_entries(res)
+        counts = owner.view(_lib.pss_result_query_counts(res), nq, np.uint64)
+        offsets = owner.view(_lib.pss_result_offsets(res), n + 1, np.uint64)
+        data = owner.view(_lib.pss_result_bytes(res), int(offsets[n]), np.uint8)
+        return PackedResult(data, offsets, counts)
+
+    def search_anchored_ids_batch(self, patterns: typing.Sequence[bytes], anchors) -> 'IdResult':
+        """Extension: the ids (``search_ids_batch``) of the entries ``search_anchored_batch_packed`` returns, in the
+        same order."""
+        import numpy as np
+        nq = len(patterns)
+        blob, offs, anc = self._anchored_args(patterns, anchors)
+        res = ctypes.c_void_p()
+        _ffi.check(_lib.pss_reader_search_anchored_ids_batch(self._handle(), blob, offs.ctypes.data, nq, anc.ctypes.data, ctypes.byref(res)))
+        owner = _ResultOwner(res)
+        n = _lib.pss_result_num_entries(res)
+        counts = owner.view(_lib.pss_result_query_counts(res), nq, np.uint64)
+        ids = owner.view(_lib.pss_result_bytes(res), 8 * n, np.uint8).view(np.uint64)
+        ids.flags.writeable = False
+        return IdResult(ids, counts)
+
+    def count_anchored_bytes(self, patterns: typing.Sequence[bytes], anchors) -> typing.List[int]:
+        """Extension: how many entries each pattern matches under its anchor; only the counters come back."""
+        import numpy as np
+        nq = len(patterns)
+        blob, offs, anc = self._anchored_args(patterns, anchors)
+        counts = np.zeros(max(nq, 1), dtype=np.uint64)
+        _ffi.check(_lib.pss_reader_count_anchored_batch(self._handle(), blob, offs.ctypes.data, nq, anc.ctypes.data, counts.ctypes.data))
+        return [int(c) for c in counts[:nq]]
+
+    def _search_anchored_str(self, s: str, anchor: str) -> typing.List[str]:
+        p = self.search_anchored_batch_packed([_utf8(s, 'substring')], anchor)
+        data = p.data.tobytes()
+        o = p.offsets.tolist()
+        return [data[o[i]:o[i + 1]].decode('utf-8') for i in range(len(o) - 1)]
+
+    def search_prefix(self, s: str) -> typing.List[str]:
+        """Extension: the entries that start with ``s``."""
+        return self._search_anchored_str(s, 'start')
+
+    def search_suffix(self, s: str) -> typing.List[str]:
+        """Extension: the entries that end with ``s``."""
+        return self._search_anchored_str(s, 'end')
+
+    def search_exact(self, s: str) -> typing.List[str]:
+        """Extension: the entries equal to ``s`` (one per copy in the index)."""
+        return self._search_anchored_str(s, 'entry')
+
+    def has_entries(self, texts: typing.List[str]) -> typing.List[bool]:
+        """Extension: for every text, whether the index holds an entry equal to it."""
+        return [c > 0 for c in self.count_anchored_bytes([_utf8(t, 'text') for t in texts], 'entry')]
+
     @property
     def entry_counts(self) -> typing.Dict[int, int]:
         """Extension: entries of every chunk this reader holds, keyed by the chunk's index in the index file."""

@@ -92,6 +92,23 @@ class Reader:
 
     def search_ids_batch(self, patterns: typing.Sequence[bytes]) -> IdResult: ...
 
+    def search_anchored_batch_packed(self, patterns: typing.Sequence[bytes],
+                                     anchors: typing.Union[str, typing.Sequence[str]]) -> PackedResult: ...
+
+    def search_anchored_ids_batch(self, patterns: typing.Sequence[bytes],
+                                  anchors: typing.Union[str, typing.Sequence[str]]) -> IdResult: ...
+
+    def count_anchored_bytes(self, patterns: typing.Sequence[bytes],
+                             anchors: typing.Union[str, typing.Sequence[str]]) -> typing.List[int]: ...
+
+    def search_prefix(self, s: str) -> typing.List[str]: ...
+
+    def search_suffix(self, s: str) -> typing.List[str]: ...
+
+    def search_exact(self, s: str) -> typing.List[str]: ...
+
+    def has_entries(self, texts: typing.List[str]) -> typing.List[bool]: ...
+
     def entries_by_id(self, ids: typing.Any) -> typing.List[bytes]: ...
 
     def entries_by_id_packed(self, ids: typing.Any) -> PackedResult: ...

@@ -144,7 +144,11 @@ ROUTES = {
     'GENERAL': 0x0400,
     'SA_ORDER': 0x0800,
     'COUNTS': 0x1000,
+    'ANCHORED': 0x2000,
 }
+
+# Anchors of the anchored search (PSS_ANCHOR_* in include/pss.h): where in the entry the pattern must sit.
+ANCHORS = {'start': 1, 'end': 2, 'entry': 3}
 
 
 class DeviceResult(ctypes.Structure):
@@ -281,6 +285,9 @@ def _load() -> ctypes.CDLL:
         'pss_reader_search_batch_device': (ctypes.c_int, [vp, vp, vp, u32, ctypes.POINTER(DeviceResult)]),
         'pss_reader_search_ids_batch': (ctypes.c_int, [vp, vp, vp, u32, pvp]),
         'pss_reader_entries_by_id': (ctypes.c_int, [vp, vp, u64, pvp]),
+        'pss_reader_search_anchored_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, pvp]),
+        'pss_reader_search_anchored_ids_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, pvp]),
+        'pss_reader_count_anchored_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, vp]),
         'pss_reader_chunk_entries': (ctypes.c_int, [vp, vp, vp, u64, ctypes.POINTER(u64)]),
         'pss_merge_packed': (ctypes.c_int, [u32, u64, vp, vp, vp, vp, vp, vp, vp, vp]),
         'pss_merge_packed_device': (ctypes.c_int, [i32, u32, u64, vp, vp, vp, vp, vp, vp, vp, vp]),

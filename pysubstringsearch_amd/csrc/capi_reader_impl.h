@@ -63,6 +63,7 @@ struct pss_reader::Part {
     const uint8_t *qbytes = nullptr;
     const uint64_t *qoffsets = nullptr;
     uint32_t nq = 0;
+    const uint8_t *anchors = nullptr;    // anchored batch: one PSS_ANCHOR_* value per query
     int mode = 0;                        // SEARCH_FULL / SEARCH_COUNTS / SEARCH_IDS
     int rc = 0;
     HostResult res;
@@ -234,7 +235,7 @@ void part_run(pss_reader::Part *p)      // the job in p's mailbox, on p's reader
     if (rc == PSS_OK) {
         uint64_t *hits = reader_hits_buffer(r);
         rc = search_batch_device(r->ctx, r->d_descs, (uint32_t)r->chunks.size(), p->qbytes, p->qoffsets, p->nq, &p->res, &r->last,
-                                 (SearchMode)p->mode, false, hits, r->order_sa, r->d_lines);
+                                 (SearchMode)p->mode, false, hits, r->order_sa, r->d_lines, p->anchors);
         if (rc == PSS_OK) reader_note_route(r);
         if (rc == PSS_OK && hits) reader_note_batch(r);
     }
@@ -662,7 +663,8 @@ namespace {
 
 // One batch over the parts of a multi-device reader: every worker answers for its chunks, the caller for part 0;
 // then the per-part results are merged query-major, part-major inside a query (pss_merge_packed's order).
-int multi_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, int mode, HostResult *out)
+int multi_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, int mode, HostResult *out,
+                const uint8_t *anchors = nullptr)
 {
     std::lock_guard<std::mutex> batch(r->multi_mu);
     const auto t0 = std::chrono::steady_clock::now();
@@ -673,6 +675,7 @@ int multi_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, 
         p->qbytes = qbytes;
         p->qoffsets = qoffsets;
         p->nq = nq;
+        p->anchors = anchors;
         p->mode = mode;
         if (k) p->pending = true;
     }
@@ -1252,6 +1255,88 @@ extern "C" int pss_reader_search_ids_batch(pss_reader *r, const uint8_t *qbytes,
         }
         *out = res;
         return PSS_OK;
+    });
+}
+
+// ---- anchored search (anchored_impl.h) ---------------------------------------------------------------------------
+
+namespace {
+
+// One anchored batch in `mode` (SEARCH_FULL / SEARCH_IDS / SEARCH_COUNTS) into *res, on whatever kind of reader r is.
+int reader_anchored(pss_reader *r, const char *who, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, const uint8_t *anchors,
+                    int mode, HostResult *res)
+{
+    if (!r || (nq && (!qoffsets || !anchors))) {
+        set_error("%s: bad arguments", who);
+        return PSS_EINVAL;
+    }
+    for (uint32_t q = 0; q < nq; ++q)
+        if (anchors[q] == 0 || anchors[q] > (PSS_ANCHOR_START | PSS_ANCHOR_END)) {
+            set_error("%s: anchors[%u] = %u (PSS_ANCHOR_START = 1, PSS_ANCHOR_END = 2 or both; an unanchored batch is pss_reader_search_batch's)",
+                      who, q, (unsigned)anchors[q]);
+            return PSS_EINVAL;
+        }
+    if (!r->parts.empty()) return multi_batch(r, qbytes, qoffsets, nq, mode, res, anchors);
+    std::lock_guard<std::recursive_mutex> lk(r->ctx->mu);
+    PSS_HIP(hipSetDevice(r->device));
+    PSS_TRY(reader_sync_descs(r));
+    if (mode == SEARCH_IDS) PSS_TRY(reader_ensure_lines(r));
+    uint64_t *hits = reader_hits_buffer(r);
+    PSS_TRY(search_batch_device(r->ctx, r->d_descs, (uint32_t)r->chunks.size(), qbytes, qoffsets, nq, res, &r->last, (SearchMode)mode, false,
+                                hits, false, mode == SEARCH_IDS ? r->d_lines : nullptr, anchors));
+    reader_note_route(r);
+    if (hits) reader_note_batch(r);
+    return PSS_OK;
+}
+
+int reader_anchored_result(pss_reader *r, const char *who, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq,
+                           const uint8_t *anchors, int mode, pss_result **out)
+{
+    if (!out) {
+        set_error("%s: bad arguments", who);
+        return PSS_EINVAL;
+    }
+    pss_result *res = new pss_result();
+    const int rc = reader_anchored(r, who, qbytes, qoffsets, nq, anchors, mode, &res->r);
+    if (rc != PSS_OK) {
+        pss_result_free(res);
+        return rc;
+    }
+    *out = res;
+    return PSS_OK;
+}
+
+}  // namespace
+
+extern "C" int pss_reader_search_anchored_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq,
+                                                const uint8_t *anchors, pss_result **out)
+{
+    return guarded([&]() -> int {
+        return reader_anchored_result(r, "pss_reader_search_anchored_batch", qbytes, qoffsets, nq, anchors, SEARCH_FULL, out);
+    });
+}
+
+extern "C" int pss_reader_search_anchored_ids_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq,
+                                                    const uint8_t *anchors, pss_result **out)
+{
+    return guarded([&]() -> int {
+        return reader_anchored_result(r, "pss_reader_search_anchored_ids_batch", qbytes, qoffsets, nq, anchors, SEARCH_IDS, out);
+    });
+}
+
+extern "C" int pss_reader_count_anchored_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq,
+                                               const uint8_t *anchors, uint64_t *counts)
+{
+    return guarded([&]() -> int {
+        if (nq && !counts) {
+            set_error("pss_reader_count_anchored_batch: bad arguments");
+            return PSS_EINVAL;
+        }
+        pss_result res;
+        const int rc = reader_anchored(r, "pss_reader_count_anchored_batch", qbytes, qoffsets, nq, anchors, SEARCH_COUNTS, &res.r);
+        if (rc == PSS_OK && nq) memcpy(counts, res.r.qcount, (size_t)nq * sizeof(uint64_t));
+        res.r.release();
+        return rc;
     });
 }
 

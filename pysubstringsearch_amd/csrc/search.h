@@ -80,11 +80,15 @@ enum SearchMode {
 int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, uint32_t nc, const uint8_t *qbytes,
                         const uint64_t *qoffsets, uint32_t nq, HostResult *res, pss_search_stats *st,
                         SearchMode mode = SEARCH_FULL, bool low_latency = false, uint64_t *chunk_hits = nullptr,
-                        bool sa_order = false, const LineDesc *d_lines = nullptr);
+                        bool sa_order = false, const LineDesc *d_lines = nullptr, const uint8_t *anchors = nullptr);
 // sa_order: the entries of one (query, chunk) pair come out in the reference's order -- suffix-array order of the FIRST hit
 // inside each entry (src/lib.rs:262-276: the hits are walked in suffix-array order and an entry is pushed when its line
 // start is first seen) -- instead of the order of each entry's leftmost match.  Opt-in (pss_reader_set_result_order): it
 // takes the general pipeline and one extra sort of the hits.
+
+// anchors (nq values, PSS_ANCHOR_START | PSS_ANCHOR_END, validated by the caller): the anchored search of anchored_impl.h --
+// entries that start with, end with or equal the pattern instead of entries that contain it.  Modes FULL, COUNTS and IDS;
+// always the general pipeline, one hit per entry, so sa_order has nothing to order.
 
 // Text of n entries named by (resident chunk, line) pairs the caller has validated (line < entries of that chunk): a
 // packed result of n "queries" with one entry each, in the order asked.

@@ -1521,7 +1521,7 @@ constexpr size_t SM_ARENA_BYTES = SM_ARENA_RHDR + 64;
 #error "search.hip is written for gfx950 (MI355X): the fused search kernels keep ~72 KiB of LDS per workgroup (160 KiB per CU there; gfx90a / gfx942 stop at 64 KiB)"
 #endif
 
-enum SSlot { Q_ORD_K0 = 50, Q_ORD_K1, Q_ORD_V0, Q_ORD_V1, Q_ORD_WORK, Q_BYTES = 10, Q_OFF, Q_LO, Q_CNT, Q_HITOFF, Q_START, Q_LEN, Q_EIDX, Q_BOFF, Q_ENTOFF, Q_OUT, Q_SMALL, Q_QCOUNT, Q_ARENA = 28, Q_HEAT = 46, Q_LINE_TMP = 47 };
+enum SSlot { Q_ORD_K0 = 50, Q_ORD_K1, Q_ORD_V0, Q_ORD_V1, Q_ORD_WORK, Q_BYTES = 10, Q_OFF, Q_LO, Q_CNT, Q_HITOFF, Q_START, Q_LEN, Q_EIDX, Q_BOFF, Q_ENTOFF, Q_OUT, Q_SMALL, Q_QCOUNT, Q_ANCHOR, Q_ARENA = 28, Q_HEAT = 46, Q_LINE_TMP = 47 };
 
 void HostResult::release()
 {
@@ -1723,6 +1723,7 @@ static int resident_query(DeviceCtx *ctx, const ChunkDesc *d_chunks, u32 nc, con
 }
 
 #include "line_index_impl.h"
+#include "anchored_impl.h"
 
 // Suffix-array hits of the batch per chunk (pair p = query p / nc on chunk p % nc): one workgroup per chunk.
 __global__ __launch_bounds__(256) void chunk_hits_kernel(const u32 *cnt, u64 nq, u32 nc, u64 *out)
@@ -1740,7 +1741,7 @@ __global__ __launch_bounds__(256) void chunk_hits_kernel(const u32 *cnt, u64 nq,
 
 int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, u32 nc, const uint8_t *qbytes,
                         const uint64_t *qoffsets, uint32_t nq, HostResult *res, pss_search_stats *st, SearchMode mode, bool low_latency,
-                        uint64_t *chunk_hits, bool sa_order, const LineDesc *d_lines)
+                        uint64_t *chunk_hits, bool sa_order, const LineDesc *d_lines, const uint8_t *anchors)
 {
     if (chunk_hits)
         for (u32 c = 0; c < nc; ++c) chunk_hits[c] = 0;
@@ -1749,6 +1750,10 @@ int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, u32 nc, const
     const bool ids_only = mode == SEARCH_IDS;
     if (ids_only && nc && !d_lines) {
         set_error("search: the ids mode needs the chunks' line tables");
+        return PSS_EINVAL;
+    }
+    if (anchors && (device_only || low_latency)) {
+        set_error("search: an anchored batch takes the general pipeline to a host result");
         return PSS_EINVAL;
     }
     const SearchKnobs &knobs = search_knobs();
@@ -1774,7 +1779,8 @@ int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, u32 nc, const
         res->offsets = (u64 *)calloc(1, sizeof(u64));
         return res->offsets ? PSS_OK : PSS_ENOMEM;
     }
-    const u64 qtotal = qoffsets[nq];
+    // (an anchored batch searches its rewritten queries: a newline in front of and / or behind every pattern)
+    const u64 qtotal = anchors ? anchored_query_bytes(qoffsets, nq, anchors) : qoffsets[nq];
     const u64 nvq = (u64)nq * nc;
     PSS_TRY(ctx->slot[Q_BYTES].reserve(qtotal + 32));
     PSS_TRY(ctx->slot[Q_OFF].reserve(((size_t)nq + 1) * 8));
@@ -1797,14 +1803,14 @@ int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, u32 nc, const
     const auto t_begin = std::chrono::steady_clock::now();
     auto host_ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(); };
     const size_t off_bytes = ((size_t)nq + 1) * 8;
-    const bool tiny = qtotal + 32 <= 8192 && off_bytes <= 8192;
+    const bool tiny = !anchors && qtotal + 32 <= 8192 && off_bytes <= 8192;
     u8 *stg = static_cast<u8 *>(ctx->pinned) + SM_OFF_QUERY;          // 16 KiB of the pinned scratch
     if (tiny) {
         memcpy(stg, qbytes, qtotal);
         memset(stg + qtotal, 0, 32);
         memcpy(stg + 8192, qoffsets, off_bytes);
     }
-    if (counts_only) sa_order = false;          // (counts do not depend on the order)
+    if (counts_only || anchors) sa_order = false;          // (counts do not depend on the order; one hit per entry has one order)
     bool small = tiny && nvq <= SM_MAX_VQ && !counts_only && !device_only && !ids_only && !knobs.no_small_path && !sa_order;
     for (u32 i = 0; small && i < nq; ++i) small = qoffsets[i + 1] - qoffsets[i] <= SM_MAX_PLEN;
     const u64 waves_per_block = 256 / kWave;
@@ -1871,7 +1877,33 @@ int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, u32 nc, const
         // overflow: fall through to the general path (qcount is still all zero)
         st->route |= PSS_ROUTE_SMALL_OVERFLOW;
     }
-    if (tiny) {
+    u8 *d_aflags = nullptr, *d_edge = nullptr;      // anchored batch: flags per query, chunk-edge hits per pair
+    std::vector<u8> anc_bytes;                      // ... and its rewritten queries when they do not fit the staging
+    std::vector<u64> anc_off;
+    if (anchors) {
+        PSS_TRY(ctx->slot[Q_ANCHOR].reserve(round_up((size_t)nq, 64) + nvq));
+        d_aflags = ctx->slot[Q_ANCHOR].as<u8>();
+        d_edge = d_aflags + round_up((size_t)nq, 64);
+        const size_t q_room = round_up(qtotal + 32, 64), o_room = round_up(off_bytes, 64);
+        u8 *hq, *hf;
+        u64 *ho;
+        if (q_room + o_room + nq <= DeviceCtx::kStageQ && !knobs.no_search_stage) {
+            PSS_TRY(ctx->ensure_search_stage());
+            hq = static_cast<u8 *>(ctx->search_stage);
+            ho = reinterpret_cast<u64 *>(hq + q_room);
+            hf = hq + q_room + o_room;
+        } else {
+            anc_bytes.resize(q_room + nq);
+            anc_off.resize((size_t)nq + 1);
+            hq = anc_bytes.data();
+            ho = anc_off.data();
+            hf = hq + q_room;
+        }
+        anchored_rewrite(qbytes, qoffsets, nq, anchors, hq, ho, hf);
+        PSS_HIP(hipMemcpyAsync(d_q, hq, qtotal + 32, hipMemcpyHostToDevice, s));
+        PSS_HIP(hipMemcpyAsync(d_qoff, ho, off_bytes, hipMemcpyHostToDevice, s));
+        PSS_HIP(hipMemcpyAsync(d_aflags, hf, nq, hipMemcpyHostToDevice, s));
+    } else if (tiny) {
         // pageable H2D copies are synchronous and slow to start: tiny batches go up from the pinned staging
         PSS_HIP(hipMemcpyAsync(d_q, stg, qtotal + 32, hipMemcpyHostToDevice, s));
         PSS_HIP(hipMemcpyAsync(d_qoff, stg + 8192, off_bytes, hipMemcpyHostToDevice, s));
@@ -1907,6 +1939,9 @@ int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, u32 nc, const
                            0, s, d_chunks, nc, d_q, d_qoff, nvq, d_lo, d_cnt);
     }
     PSS_HIP(hipEventRecord(e1, s));
+    if (anchors)        // the matches at the two ends of every chunk join the pair's hits before anything is sized
+        hipLaunchKernelGGL(anchor_edges_kernel, dim3((u32)((nvq + 255) / 256)), dim3(256), 0, s, d_chunks, nc, d_q, d_qoff, d_aflags, nvq,
+                           d_cnt, d_edge);
     if (chunk_hits && nc <= 4096) {
         // (a reader with suffix arrays on the host tier: where did this batch's hits land?  One small kernel over the
         // pair counts and a wait -- next to probes over PCIe, nothing)
@@ -1916,7 +1951,7 @@ int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, u32 nc, const
         PSS_HIP(hipMemcpyAsync(chunk_hits, d_heat, (size_t)nc * 8, hipMemcpyDeviceToHost, s));
         PSS_HIP(hipStreamSynchronize(s));
     }
-    if (nvq <= MID_MAX && !counts_only && !ids_only && !knobs.no_mid_pipeline && !sa_order) {
+    if (nvq <= MID_MAX && !counts_only && !ids_only && !knobs.no_mid_pipeline && !sa_order && !anchors) {
         // ---- mid pipeline: totals stay on the device, one wait for them, one for the result ----
         st->route |= PSS_ROUTE_MID;
         const u64 byte_cap = (u64)16 << 20;
@@ -2002,7 +2037,8 @@ int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, u32 nc, const
         // more hits or bytes than the caps: the general pipeline below takes over (intervals are kept)
         st->route |= PSS_ROUTE_MID_OVERFLOW;
     }
-    st->route |= PSS_ROUTE_GENERAL | (sa_order ? PSS_ROUTE_SA_ORDER : 0u) | (counts_only ? PSS_ROUTE_COUNTS : 0u);
+    st->route |= PSS_ROUTE_GENERAL | (sa_order ? PSS_ROUTE_SA_ORDER : 0u) | (counts_only ? PSS_ROUTE_COUNTS : 0u) |
+                 (anchors ? PSS_ROUTE_ANCHORED : 0u);
     PSS_TRY(device_excl_scan(ctx, InU32{d_cnt}, nvq, d_partial, d_total, d_hitoff));
     PSS_HIP(hipMemcpyAsync(h_small, d_total, 8, hipMemcpyDeviceToHost, s));
     PSS_HIP(hipStreamSynchronize(s));
@@ -2040,7 +2076,10 @@ int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, u32 nc, const
             SortStats oss;
             PSS_TRY(radix_sort_pairs(ctx, OK, OV, (u32)H, 31 + pair_bits, 0xffffffffu, nullptr, 0, ctx->slot[Q_ORD_WORK].p, &od, false, &oss));
             hipLaunchKernelGGL(mark_later_hits_kernel, dim3(grid), dim3(256), 0, s, OK[od], OV[od], H, d_len);
-        } else
+        } else if (anchors)
+            hipLaunchKernelGGL(anchored_hits_kernel, dim3(grid), dim3(256), 0, s, d_chunks, nc, d_aflags, nvq, d_lo, d_edge, d_hitoff, H,
+                               d_start, d_len);
+        else
         hipLaunchKernelGGL(hit_lines_kernel, dim3(grid), dim3(256), 0, s, d_chunks, nc, d_q, d_qoff, nvq, d_lo,
                            d_hitoff, H, (const MidState *)nullptr, d_start, d_len);
         PSS_TRY(device_excl_scan(ctx, InKept{d_len}, H, d_partial, d_total, d_eidx));
