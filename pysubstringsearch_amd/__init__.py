@@ -74,6 +74,16 @@ def _path(value, name: str) -> bytes:
     return os.fsencode(value)
 
 
+def _pack_queries(patterns: typing.Sequence[bytes]):
+    """(blob, offsets) of one batch as the C calls take it: the patterns back to back and their nq + 1 offsets (numpy uint64)."""
+    import numpy as np
+    nq = len(patterns)
+    offs = np.zeros(nq + 1, dtype=np.uint64)
+    if nq:
+        np.cumsum(np.fromiter(map(len, patterns), dtype=np.uint64, count=nq), out=offs[1:])
+    return b''.join(patterns), offs
+
+
 class Writer:
     """Reference: pysubstringsearch/__init__.py:6-41, src/lib.rs:42-144."""
 
@@ -417,10 +427,7 @@ class Reader:
         the search itself (~50 ns per entry); this is the bulk alternative."""
         import numpy as np
         nq = len(patterns)
-        blob = b''.join(patterns)
-        offs = np.zeros(nq + 1, dtype=np.uint64)
-        if nq:
-            np.cumsum(np.fromiter(map(len, patterns), dtype=np.uint64, count=nq), out=offs[1:])
+        blob, offs = _pack_queries(patterns)
         res = ctypes.c_void_p()
         _ffi.check(_lib.pss_reader_search_batch(self._handle(), blob, offs.ctypes.data, nq, ctypes.byref(res)))
         owner = _ResultOwner(res)      # the arrays below are views of the C result; it lives as long as they do
@@ -440,10 +447,7 @@ class Reader:
         numbers of the file given to ``add_entries_from_file_lines``)."""
         import numpy as np
         nq = len(patterns)
-        blob = b''.join(patterns)
-        offs = np.zeros(nq + 1, dtype=np.uint64)
-        if nq:
-            np.cumsum(np.fromiter(map(len, patterns), dtype=np.uint64, count=nq), out=offs[1:])
+        blob, offs = _pack_queries(patterns)
         res = ctypes.c_void_p()
         _ffi.check(_lib.pss_reader_search_ids_batch(self._handle(), blob, offs.ctypes.data, nq, ctypes.byref(res)))
         owner = _ResultOwner(res)      # the arrays below are views of the C result; it lives as long as they do
@@ -505,10 +509,8 @@ class Reader:
         for k in kinds:
             if not isinstance(k, str) or k not in _ffi.ANCHORS:
                 raise ValueError(f"an anchor is 'start', 'end' or 'entry', not {k!r}")
-        offs = np.zeros(nq + 1, dtype=np.uint64)
-        if nq:
-            np.cumsum(np.fromiter(map(len, patterns), dtype=np.uint64, count=nq), out=offs[1:])
-        return b''.join(patterns), offs, np.array([_ffi.ANCHORS[k] for k in kinds], dtype=np.uint8)
+        blob, offs = _pack_queries(patterns)
+        return blob, offs, np.array([_ffi.ANCHORS[k] for k in kinds], dtype=np.uint8)
 
     def search_anchored_batch_packed(self, patterns: typing.Sequence[bytes], anchors) -> 'PackedResult':
         """Extension: the entries that START WITH (``'start'``), END WITH (``'end'``) or EQUAL (``'entry'``) each
@@ -615,10 +617,7 @@ class Reader:
         import numpy as np
         import torch
         nq = len(patterns)
-        blob = b''.join(patterns)
-        offs = np.zeros(nq + 1, dtype=np.uint64)
-        if nq:
-            np.cumsum(np.fromiter(map(len, patterns), dtype=np.uint64, count=nq), out=offs[1:])
+        blob, offs = _pack_queries(patterns)
         dr = _ffi.DeviceResult()
         _ffi.check(_lib.pss_reader_search_batch_device(self._handle(), blob, offs.ctypes.data, nq, ctypes.byref(dr)))
         dev = torch.device('cuda', dr.device)
@@ -644,11 +643,9 @@ class Reader:
         """``count_multiple`` for queries that are already bytes."""
         import numpy as np
         nq = len(patterns)
-        offs = np.zeros(nq + 1, dtype=np.uint64)
-        if nq:
-            np.cumsum(np.fromiter(map(len, patterns), dtype=np.uint64, count=nq), out=offs[1:])
+        blob, offs = _pack_queries(patterns)
         counts = np.zeros(max(nq, 1), dtype=np.uint64)
-        _ffi.check(_lib.pss_reader_count_batch(self._handle(), b''.join(patterns), offs.ctypes.data, nq, counts.ctypes.data))
+        _ffi.check(_lib.pss_reader_count_batch(self._handle(), blob, offs.ctypes.data, nq, counts.ctypes.data))
         return [int(c) for c in counts[:nq]]
 
     def search_batch_raw(self, patterns: typing.Sequence[bytes]):

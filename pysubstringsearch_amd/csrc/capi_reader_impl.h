@@ -60,11 +60,7 @@ struct pss_reader::Part {
     std::condition_variable cv;
     // mailbox: the caller fills the job and raises `pending`; the worker clears it when `rc` / `res` / `err` are set
     bool pending = false, quit = false;
-    const uint8_t *qbytes = nullptr;
-    const uint64_t *qoffsets = nullptr;
-    uint32_t nq = 0;
-    const uint8_t *anchors = nullptr;    // anchored batch: one PSS_ANCHOR_* value per query
-    int mode = 0;                        // SEARCH_FULL / SEARCH_COUNTS / SEARCH_IDS
+    SearchRequest rq;                    // SEARCH_FULL / SEARCH_COUNTS / SEARCH_IDS, anchored or not
     int rc = 0;
     HostResult res;
     std::string err;
@@ -219,28 +215,32 @@ void reader_note_route(pss_reader *r)
         }
 }
 
+int multi_batch(pss_reader *r, const SearchRequest &rq, HostResult *out);
+
+// One batch on whatever kind of reader r is: the one way from every entry point below to search_batch_device.  The caller
+// states queries, mode and anchors; the reader's settings supply the rest.
+int reader_batch(pss_reader *r, SearchRequest rq, HostResult *res)
+{
+    if (!r->parts.empty()) return multi_batch(r, rq, res);
+    std::lock_guard<std::recursive_mutex> lk(r->ctx->mu);
+    PSS_HIP(hipSetDevice(r->device));
+    PSS_TRY(reader_sync_descs(r));
+    if (rq.mode == SEARCH_IDS) PSS_TRY(reader_ensure_lines(r));
+    rq.sa_order = r->order_sa;
+    rq.low_latency = r->low_latency && rq.mode == SEARCH_FULL && !rq.anchors;
+    rq.chunk_hits = rq.mode == SEARCH_DEVICE ? nullptr : reader_hits_buffer(r);     // (device results have never fed the residency manager)
+    PSS_TRY(search_batch_device(r->ctx, r->d_descs, r->d_lines, (uint32_t)r->chunks.size(), rq, res, &r->last));
+    reader_note_route(r);
+    if (rq.chunk_hits) reader_note_batch(r);
+    return PSS_OK;
+}
+
 void part_run(pss_reader::Part *p)      // the job in p's mailbox, on p's reader
 {
-    pss_reader *r = p->reader;
-    std::lock_guard<std::recursive_mutex> lk(r->ctx->mu);
     p->res.release();
     p->err.clear();
-    int rc = PSS_OK;
-    if (hipSetDevice(r->device) != hipSuccess) {
-        set_error("hipSetDevice(%d) failed", r->device);
-        rc = PSS_EDEVICE;
-    }
-    if (rc == PSS_OK) rc = reader_sync_descs(r);
-    if (rc == PSS_OK && p->mode == SEARCH_IDS) rc = reader_ensure_lines(r);
-    if (rc == PSS_OK) {
-        uint64_t *hits = reader_hits_buffer(r);
-        rc = search_batch_device(r->ctx, r->d_descs, (uint32_t)r->chunks.size(), p->qbytes, p->qoffsets, p->nq, &p->res, &r->last,
-                                 (SearchMode)p->mode, false, hits, r->order_sa, r->d_lines, p->anchors);
-        if (rc == PSS_OK) reader_note_route(r);
-        if (rc == PSS_OK && hits) reader_note_batch(r);
-    }
-    if (rc != PSS_OK) p->err = last_error();
-    p->rc = rc;
+    p->rc = reader_batch(p->reader, p->rq, &p->res);
+    if (p->rc != PSS_OK) p->err = last_error();
 }
 
 void part_worker(pss_reader::Part *p)
@@ -663,20 +663,16 @@ namespace {
 
 // One batch over the parts of a multi-device reader: every worker answers for its chunks, the caller for part 0;
 // then the per-part results are merged query-major, part-major inside a query (pss_merge_packed's order).
-int multi_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, int mode, HostResult *out,
-                const uint8_t *anchors = nullptr)
+int multi_batch(pss_reader *r, const SearchRequest &rq, HostResult *out)
 {
+    const uint32_t nq = rq.nq;
     std::lock_guard<std::mutex> batch(r->multi_mu);
     const auto t0 = std::chrono::steady_clock::now();
     const size_t G = r->parts.size();
     for (size_t k = 0; k < G; ++k) {
         pss_reader::Part *p = r->parts[k];
         std::lock_guard<std::mutex> lk(p->mu);
-        p->qbytes = qbytes;
-        p->qoffsets = qoffsets;
-        p->nq = nq;
-        p->anchors = anchors;
-        p->mode = mode;
+        p->rq = rq;
         if (k) p->pending = true;
     }
     for (size_t k = 1; k < G; ++k) r->parts[k]->cv.notify_all();
@@ -713,7 +709,7 @@ int multi_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, 
     out->nq = nq;
     out->qcount = static_cast<uint64_t *>(calloc(nq ? nq : 1, sizeof(uint64_t)));
     if (!out->qcount) return PSS_ENOMEM;
-    if (mode == SEARCH_COUNTS) {
+    if (rq.mode == SEARCH_COUNTS) {
         for (pss_reader::Part *p : r->parts)
             for (uint32_t q = 0; q < nq; ++q) out->qcount[q] += p->res.qcount[q];
     } else {
@@ -789,6 +785,30 @@ int multi_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, 
     st.ms_host = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     r->last = st;
     return PSS_OK;
+}
+
+// A batch into a fresh pss_result that *out hands to the caller (or that is freed again when the batch fails).
+int reader_batch_result(pss_reader *r, const SearchRequest &rq, pss_result **out)
+{
+    pss_result *res = new pss_result();
+    const int rc = reader_batch(r, rq, &res->r);
+    if (rc != PSS_OK) {
+        pss_result_free(res);
+        return rc;
+    }
+    *out = res;
+    return PSS_OK;
+}
+
+// The counts of a batch (rq.mode is set here) into the caller's nq counters.
+int reader_batch_counts(pss_reader *r, SearchRequest rq, uint64_t *counts)
+{
+    rq.mode = SEARCH_COUNTS;
+    HostResult res;
+    const int rc = reader_batch(r, rq, &res);
+    if (rc == PSS_OK && rq.nq) memcpy(counts, res.qcount, (size_t)rq.nq * sizeof(uint64_t));
+    res.release();
+    return rc;
 }
 
 }  // namespace
@@ -1089,32 +1109,7 @@ extern "C" int pss_reader_search_batch(pss_reader *r, const uint8_t *qbytes, con
             set_error("pss_reader_search_batch: bad arguments");
             return PSS_EINVAL;
         }
-        if (!r->parts.empty()) {
-            pss_result *res = new pss_result();
-            const int rc = multi_batch(r, qbytes, qoffsets, nq, SEARCH_FULL, &res->r);
-            if (rc != PSS_OK) {
-                pss_result_free(res);
-                return rc;
-            }
-            *out = res;
-            return PSS_OK;
-        }
-        std::lock_guard<std::recursive_mutex> lk(r->ctx->mu);
-        PSS_HIP(hipSetDevice(r->device));
-        const uint32_t nc = (uint32_t)r->chunks.size();
-        PSS_TRY(reader_sync_descs(r));
-        pss_result *res = new pss_result();
-        uint64_t *hits = reader_hits_buffer(r);
-        const int rc = search_batch_device(r->ctx, r->d_descs, nc, qbytes, qoffsets, nq, &res->r, &r->last, SEARCH_FULL,
-                                           r->low_latency, hits, r->order_sa);
-        if (rc == PSS_OK) reader_note_route(r);
-        if (rc == PSS_OK && hits) reader_note_batch(r);
-        if (rc != PSS_OK) {
-            pss_result_free(res);
-            return rc;
-        }
-        *out = res;
-        return PSS_OK;
+        return reader_batch_result(r, SearchRequest{qbytes, qoffsets, nq}, out);
     });
 }
 
@@ -1165,25 +1160,7 @@ extern "C" int pss_reader_count_batch(pss_reader *r, const uint8_t *qbytes, cons
             set_error("pss_reader_count_batch: bad arguments");
             return PSS_EINVAL;
         }
-        if (!r->parts.empty()) {
-            pss_result res;
-            const int rc = multi_batch(r, qbytes, qoffsets, nq, SEARCH_COUNTS, &res.r);
-            if (rc == PSS_OK && nq) memcpy(counts, res.r.qcount, (size_t)nq * sizeof(uint64_t));
-            res.r.release();
-            return rc;
-        }
-        std::lock_guard<std::recursive_mutex> lk(r->ctx->mu);
-        PSS_HIP(hipSetDevice(r->device));
-        const uint32_t nc = (uint32_t)r->chunks.size();
-        PSS_TRY(reader_sync_descs(r));
-        pss_result res;
-        uint64_t *hits = reader_hits_buffer(r);
-        const int rc = search_batch_device(r->ctx, r->d_descs, nc, qbytes, qoffsets, nq, &res.r, &r->last, SEARCH_COUNTS, false, hits);
-        if (rc == PSS_OK) reader_note_route(r);
-        if (rc == PSS_OK && hits) reader_note_batch(r);
-        if (rc == PSS_OK && nq) memcpy(counts, res.r.qcount, (size_t)nq * sizeof(uint64_t));
-        res.r.release();
-        return rc;
+        return reader_batch_counts(r, SearchRequest{qbytes, qoffsets, nq}, counts);
     });
 }
 
@@ -1199,15 +1176,9 @@ extern "C" int pss_reader_search_batch_device(pss_reader *r, const uint8_t *qbyt
             set_error("pss_reader_search_batch_device: a multi-device reader has no single device to leave the result on");
             return PSS_EINVAL;
         }
-        std::lock_guard<std::recursive_mutex> lk(r->ctx->mu);
-        PSS_HIP(hipSetDevice(r->device));
-        const uint32_t nc = (uint32_t)r->chunks.size();
-        PSS_TRY(reader_sync_descs(r));
         HostResult hr;
-        const int rc = search_batch_device(r->ctx, r->d_descs, nc, qbytes, qoffsets, nq, &hr, &r->last, SEARCH_DEVICE, false, nullptr,
-                                           r->order_sa);
+        const int rc = reader_batch(r, SearchRequest{qbytes, qoffsets, nq, SEARCH_DEVICE}, &hr);
         if (rc == PSS_OK) {
-            reader_note_route(r);
             out->num_queries = nq;
             out->num_entries = hr.n_entries;
             out->num_bytes = hr.n_bytes;
@@ -1231,30 +1202,9 @@ extern "C" int pss_reader_search_ids_batch(pss_reader *r, const uint8_t *qbytes,
             set_error("pss_reader_search_ids_batch: bad arguments");
             return PSS_EINVAL;
         }
-        pss_result *res = new pss_result();
-        int rc = PSS_OK;
-        if (!r->parts.empty()) {
-            // (the parts' ids travel as the bytes of ordinary packed results, 8 per entry: the merge is the one of the entries)
-            rc = multi_batch(r, qbytes, qoffsets, nq, SEARCH_IDS, &res->r);
-        } else {
-            std::lock_guard<std::recursive_mutex> lk(r->ctx->mu);
-            PSS_HIP(hipSetDevice(r->device));
-            rc = reader_sync_descs(r);
-            if (rc == PSS_OK) rc = reader_ensure_lines(r);
-            if (rc == PSS_OK) {
-                uint64_t *hits = reader_hits_buffer(r);
-                rc = search_batch_device(r->ctx, r->d_descs, (uint32_t)r->chunks.size(), qbytes, qoffsets, nq, &res->r, &r->last,
-                                         SEARCH_IDS, false, hits, r->order_sa, r->d_lines);
-                if (rc == PSS_OK) reader_note_route(r);
-                if (rc == PSS_OK && hits) reader_note_batch(r);
-            }
-        }
-        if (rc != PSS_OK) {
-            pss_result_free(res);
-            return rc;
-        }
-        *out = res;
-        return PSS_OK;
+        // (on a multi-device reader the parts' ids travel as the bytes of ordinary packed results, 8 per entry: the merge is the
+        // one of the entries)
+        return reader_batch_result(r, SearchRequest{qbytes, qoffsets, nq, SEARCH_IDS}, out);
     });
 }
 
@@ -1262,11 +1212,10 @@ extern "C" int pss_reader_search_ids_batch(pss_reader *r, const uint8_t *qbytes,
 
 namespace {
 
-// One anchored batch in `mode` (SEARCH_FULL / SEARCH_IDS / SEARCH_COUNTS) into *res, on whatever kind of reader r is.
-int reader_anchored(pss_reader *r, const char *who, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, const uint8_t *anchors,
-                    int mode, HostResult *res)
+// The argument checks of the three anchored calls (out_ok: the call's own output argument is usable).
+int anchored_args(const pss_reader *r, const char *who, const uint64_t *qoffsets, uint32_t nq, const uint8_t *anchors, bool out_ok)
 {
-    if (!r || (nq && (!qoffsets || !anchors))) {
+    if (!r || !out_ok || (nq && (!qoffsets || !anchors))) {
         set_error("%s: bad arguments", who);
         return PSS_EINVAL;
     }
@@ -1276,33 +1225,6 @@ int reader_anchored(pss_reader *r, const char *who, const uint8_t *qbytes, const
                       who, q, (unsigned)anchors[q]);
             return PSS_EINVAL;
         }
-    if (!r->parts.empty()) return multi_batch(r, qbytes, qoffsets, nq, mode, res, anchors);
-    std::lock_guard<std::recursive_mutex> lk(r->ctx->mu);
-    PSS_HIP(hipSetDevice(r->device));
-    PSS_TRY(reader_sync_descs(r));
-    if (mode == SEARCH_IDS) PSS_TRY(reader_ensure_lines(r));
-    uint64_t *hits = reader_hits_buffer(r);
-    PSS_TRY(search_batch_device(r->ctx, r->d_descs, (uint32_t)r->chunks.size(), qbytes, qoffsets, nq, res, &r->last, (SearchMode)mode, false,
-                                hits, false, mode == SEARCH_IDS ? r->d_lines : nullptr, anchors));
-    reader_note_route(r);
-    if (hits) reader_note_batch(r);
-    return PSS_OK;
-}
-
-int reader_anchored_result(pss_reader *r, const char *who, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq,
-                           const uint8_t *anchors, int mode, pss_result **out)
-{
-    if (!out) {
-        set_error("%s: bad arguments", who);
-        return PSS_EINVAL;
-    }
-    pss_result *res = new pss_result();
-    const int rc = reader_anchored(r, who, qbytes, qoffsets, nq, anchors, mode, &res->r);
-    if (rc != PSS_OK) {
-        pss_result_free(res);
-        return rc;
-    }
-    *out = res;
     return PSS_OK;
 }
 
@@ -1312,7 +1234,8 @@ extern "C" int pss_reader_search_anchored_batch(pss_reader *r, const uint8_t *qb
                                                 const uint8_t *anchors, pss_result **out)
 {
     return guarded([&]() -> int {
-        return reader_anchored_result(r, "pss_reader_search_anchored_batch", qbytes, qoffsets, nq, anchors, SEARCH_FULL, out);
+        PSS_TRY(anchored_args(r, "pss_reader_search_anchored_batch", qoffsets, nq, anchors, out != nullptr));
+        return reader_batch_result(r, SearchRequest{qbytes, qoffsets, nq, SEARCH_FULL, anchors}, out);
     });
 }
 
@@ -1320,7 +1243,8 @@ extern "C" int pss_reader_search_anchored_ids_batch(pss_reader *r, const uint8_t
                                                     const uint8_t *anchors, pss_result **out)
 {
     return guarded([&]() -> int {
-        return reader_anchored_result(r, "pss_reader_search_anchored_ids_batch", qbytes, qoffsets, nq, anchors, SEARCH_IDS, out);
+        PSS_TRY(anchored_args(r, "pss_reader_search_anchored_ids_batch", qoffsets, nq, anchors, out != nullptr));
+        return reader_batch_result(r, SearchRequest{qbytes, qoffsets, nq, SEARCH_IDS, anchors}, out);
     });
 }
 
@@ -1328,15 +1252,8 @@ extern "C" int pss_reader_count_anchored_batch(pss_reader *r, const uint8_t *qby
                                                const uint8_t *anchors, uint64_t *counts)
 {
     return guarded([&]() -> int {
-        if (nq && !counts) {
-            set_error("pss_reader_count_anchored_batch: bad arguments");
-            return PSS_EINVAL;
-        }
-        pss_result res;
-        const int rc = reader_anchored(r, "pss_reader_count_anchored_batch", qbytes, qoffsets, nq, anchors, SEARCH_COUNTS, &res.r);
-        if (rc == PSS_OK && nq) memcpy(counts, res.r.qcount, (size_t)nq * sizeof(uint64_t));
-        res.r.release();
-        return rc;
+        PSS_TRY(anchored_args(r, "pss_reader_count_anchored_batch", qoffsets, nq, anchors, !nq || counts));
+        return reader_batch_counts(r, SearchRequest{qbytes, qoffsets, nq, SEARCH_COUNTS, anchors}, counts);
     });
 }
 

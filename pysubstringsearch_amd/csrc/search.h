@@ -74,21 +74,30 @@ enum SearchMode {
                          // pipeline up to the kept-hit scan, then one id per kept hit -- no byte scan, no text copy.  Needs d_lines.
 };
 
-// chunk_hits (optional, nc entries): how much of the batch's work landed on every chunk -- suffix-array hits per chunk on
-// the multi-kernel paths, entries per chunk on the fused small-batch path.  The reader's residency manager feeds on it
-// (capi.cpp); it costs one small kernel and a stream synchronisation, so readers whose chunks all live in HBM pass nullptr.
-int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, uint32_t nc, const uint8_t *qbytes,
-                        const uint64_t *qoffsets, uint32_t nq, HostResult *res, pss_search_stats *st,
-                        SearchMode mode = SEARCH_FULL, bool low_latency = false, uint64_t *chunk_hits = nullptr,
-                        bool sa_order = false, const LineDesc *d_lines = nullptr, const uint8_t *anchors = nullptr);
-// sa_order: the entries of one (query, chunk) pair come out in the reference's order -- suffix-array order of the FIRST hit
-// inside each entry (src/lib.rs:262-276: the hits are walked in suffix-array order and an entry is pushed when its line
-// start is first seen) -- instead of the order of each entry's leftmost match.  Opt-in (pss_reader_set_result_order): it
-// takes the general pipeline and one extra sort of the hits.
+// One batch as its caller states it.  search_batch_device normalises it once into the few booleans its stages read.
+struct SearchRequest {
+    const uint8_t *qbytes = nullptr; const uint64_t *qoffsets = nullptr; uint32_t nq = 0;   // nq patterns back to back, nq + 1 offsets
+    SearchMode mode = SEARCH_FULL;
+    // anchors (nq values, PSS_ANCHOR_START | PSS_ANCHOR_END, validated by the caller): the anchored search of anchored_impl.h --
+    // entries that start with, end with or equal the pattern instead of entries that contain it.  Modes FULL, COUNTS and IDS;
+    // always the general pipeline, one hit per entry, so sa_order has nothing to order.
+    const uint8_t *anchors = nullptr;
+    bool low_latency = false;            // one query through the resident kernel when it fits (an unanchored SEARCH_FULL batch only)
+    // sa_order: the entries of one (query, chunk) pair come out in the reference's order -- suffix-array order of the FIRST hit
+    // inside each entry (src/lib.rs:262-276: the hits are walked in suffix-array order and an entry is pushed when its line
+    // start is first seen) -- instead of the order of each entry's leftmost match.  Opt-in (pss_reader_set_result_order): it
+    // takes the general pipeline and one extra sort of the hits.
+    bool sa_order = false;
+    // chunk_hits (optional, nc entries): how much of the batch's work landed on every chunk -- suffix-array hits per chunk on
+    // the multi-kernel paths, entries per chunk on the fused small-batch path.  The reader's residency manager feeds on it
+    // (capi.cpp); it costs one small kernel and a stream synchronisation, so readers whose chunks all live in HBM pass nullptr.
+    uint64_t *chunk_hits = nullptr;
+};
 
-// anchors (nq values, PSS_ANCHOR_START | PSS_ANCHOR_END, validated by the caller): the anchored search of anchored_impl.h --
-// entries that start with, end with or equal the pattern instead of entries that contain it.  Modes FULL, COUNTS and IDS;
-// always the general pipeline, one hit per entry, so sa_order has nothing to order.
+// The batch over the nc resident chunks of d_chunks (d_lines: their line tables, parallel to d_chunks; read by SEARCH_IDS
+// alone, nullptr where none were built).
+int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, const LineDesc *d_lines, uint32_t nc, const SearchRequest &rq,
+                        HostResult *res, pss_search_stats *st);
 
 // Text of n entries named by (resident chunk, line) pairs the caller has validated (line < entries of that chunk): a
 // packed result of n "queries" with one entry each, in the order asked.

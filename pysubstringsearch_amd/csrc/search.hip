@@ -1739,192 +1739,232 @@ __global__ __launch_bounds__(256) void chunk_hits_kernel(const u32 *cnt, u64 nq,
     if (threadIdx.x == 0) out[c] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
 }
 
-int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, u32 nc, const uint8_t *qbytes,
-                        const uint64_t *qoffsets, uint32_t nq, HostResult *res, pss_search_stats *st, SearchMode mode, bool low_latency,
-                        uint64_t *chunk_hits, bool sa_order, const LineDesc *d_lines, const uint8_t *anchors)
-{
-    if (chunk_hits)
-        for (u32 c = 0; c < nc; ++c) chunk_hits[c] = 0;
-    const bool counts_only = mode == SEARCH_COUNTS;
-    const bool device_only = mode == SEARCH_DEVICE;
-    const bool ids_only = mode == SEARCH_IDS;
-    if (ids_only && nc && !d_lines) {
-        set_error("search: the ids mode needs the chunks' line tables");
-        return PSS_EINVAL;
-    }
-    if (anchors && (device_only || low_latency)) {
-        set_error("search: an anchored batch takes the general pipeline to a host result");
-        return PSS_EINVAL;
-    }
-    const SearchKnobs &knobs = search_knobs();
-    hipStream_t s = ctx->stream;
-    memset(st, 0, sizeof *st);
-    st->queries = nq;
-    res->nq = nq;
-    res->qcount = (u64 *)calloc(nq ? nq : 1, sizeof(u64));
-    res->offsets = nullptr;
-    res->bytes = nullptr;
-    res->n_entries = 0;
-    if (!res->qcount) return PSS_ENOMEM;
-    if (nq == 0 || nc == 0) {
-        if (device_only) {        // a rank that owns no chunk still answers: nq zero counters, no entries
-            if (nq) {
-                PSS_TRY(ctx->slot[Q_QCOUNT].reserve((size_t)nq * 8));
-                PSS_HIP(hipMemsetAsync(ctx->slot[Q_QCOUNT].p, 0, (size_t)nq * 8, s));
-                PSS_HIP(hipStreamSynchronize(s));
-                res->d_qcount = ctx->slot[Q_QCOUNT].as<u64>();
-            }
-            return PSS_OK;
-        }
-        res->offsets = (u64 *)calloc(1, sizeof(u64));
-        return res->offsets ? PSS_OK : PSS_ENOMEM;
-    }
-    // (an anchored batch searches its rewritten queries: a newline in front of and / or behind every pattern)
-    const u64 qtotal = anchors ? anchored_query_bytes(qoffsets, nq, anchors) : qoffsets[nq];
-    const u64 nvq = (u64)nq * nc;
-    PSS_TRY(ctx->slot[Q_BYTES].reserve(qtotal + 32));
-    PSS_TRY(ctx->slot[Q_OFF].reserve(((size_t)nq + 1) * 8));
-    PSS_TRY(ctx->slot[Q_LO].reserve(nvq * 4));
-    PSS_TRY(ctx->slot[Q_CNT].reserve(nvq * 4));
-    PSS_TRY(ctx->slot[Q_HITOFF].reserve((nvq + 1) * 8));
-    PSS_TRY(ctx->slot[Q_SMALL].reserve(SC_MAX_BLOCKS * 8 + 256));      // scan partials, totals, MidState
-    PSS_TRY(ctx->slot[Q_QCOUNT].reserve((size_t)nq * 8));
-    u8 *d_q = ctx->slot[Q_BYTES].as<u8>();
-    u64 *d_qoff = ctx->slot[Q_OFF].as<u64>();
-    u32 *d_lo = ctx->slot[Q_LO].as<u32>();
-    u32 *d_cnt = ctx->slot[Q_CNT].as<u32>();
-    u64 *d_hitoff = ctx->slot[Q_HITOFF].as<u64>();
-    u64 *d_partial = ctx->slot[Q_SMALL].as<u64>();
-    u64 *d_total = d_partial + SC_MAX_BLOCKS;
-    u64 *d_qcount = ctx->slot[Q_QCOUNT].as<u64>();
-    u64 *h_small = static_cast<u64 *>(ctx->pinned);
+// ---- host driver of one batch -------------------------------------------------------------------------------------
+// search_batch_device reads top to bottom: empty batch -> stage_queries -> run_fused? -> launch_interval -> run_mid? ->
+// run_general -> finish.  The stages share one Batch: the request normalised into the few booleans they read, the
+// workspace every route needs, the timing events and the two outputs.
+namespace {
 
-    const hipEvent_t e0 = ctx->search_ev[0], e1 = ctx->search_ev[1], e2 = ctx->search_ev[2];
-    const auto t_begin = std::chrono::steady_clock::now();
-    auto host_ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(); };
-    const size_t off_bytes = ((size_t)nq + 1) * 8;
-    const bool tiny = !anchors && qtotal + 32 <= 8192 && off_bytes <= 8192;
-    u8 *stg = static_cast<u8 *>(ctx->pinned) + SM_OFF_QUERY;          // 16 KiB of the pinned scratch
-    if (tiny) {
-        memcpy(stg, qbytes, qtotal);
-        memset(stg + qtotal, 0, 32);
-        memcpy(stg + 8192, qoffsets, off_bytes);
+struct Batch {
+    DeviceCtx *ctx;
+    hipStream_t s;
+    const ChunkDesc *d_chunks;
+    const LineDesc *d_lines;
+    const SearchRequest &rq;
+    HostResult *res;
+    pss_search_stats *st;
+    const SearchKnobs &knobs;
+    const u32 nq, nc;
+    const u64 nvq;                      // (query, chunk) pairs
+    u64 qtotal;                         // bytes of the queries as they are searched (an anchored batch: rewritten)
+    size_t off_bytes;
+    // the request, normalised once: nothing below asks for a mode again
+    bool counts, device, ids, anchored, sa_order;
+    bool tiny;                          // queries and offsets fit the 16 KiB of the pinned scratch
+    bool fused_ok, resident_ok, mid_ok; // routes this batch may take (each may still overflow into the next)
+    // host copy of queries, offsets and anchor flags (stage_queries)
+    const u8 *h_q = nullptr, *h_flags = nullptr;
+    const u64 *h_off = nullptr;
+    bool h_padded = false;              // 32 zero bytes follow the queries
+    std::vector<u8> own_q;              // an anchored batch too large for the staging
+    std::vector<u64> own_off;
+    // workspace of every route
+    u8 *d_q = nullptr, *d_aflags = nullptr, *d_edge = nullptr;
+    u64 *d_qoff = nullptr, *d_hitoff = nullptr, *d_partial = nullptr, *d_total = nullptr, *d_qcount = nullptr, *h_small = nullptr;
+    u32 *d_lo = nullptr, *d_cnt = nullptr;
+    // ... and of the mid and the general pipeline, sized by each: entry bounds per hit, the scans over them, the result
+    u32 *d_start = nullptr, *d_len = nullptr;
+    u64 *d_eidx = nullptr, *d_boff = nullptr, *d_entoff = nullptr;
+    u8 *d_out = nullptr;
+    hipEvent_t e0, e1, e2;              // e0 .. e1: the interval search, e0 .. e2: the route
+    bool timed_route = true, timed_interval = true;     // which of them finish() reads
+    std::chrono::steady_clock::time_point t_begin;
+
+    Batch(DeviceCtx *c, const ChunkDesc *chunks, const LineDesc *lines, u32 nchunks, const SearchRequest &r, HostResult *out,
+          pss_search_stats *stats)
+        : ctx(c), s(c->stream), d_chunks(chunks), d_lines(lines), rq(r), res(out), st(stats), knobs(search_knobs()), nq(r.nq),
+          nc(nchunks), nvq((u64)r.nq * nchunks), e0(c->search_ev[0]), e1(c->search_ev[1]), e2(c->search_ev[2])
+    {
+        counts = rq.mode == SEARCH_COUNTS;
+        device = rq.mode == SEARCH_DEVICE;
+        ids = rq.mode == SEARCH_IDS;
+        anchored = rq.anchors != nullptr;
+        sa_order = rq.sa_order && !counts && !anchored;     // (counts do not depend on the order; one hit per entry has one order)
+        // (an anchored batch searches its rewritten queries: a newline in front of and / or behind every pattern)
+        qtotal = anchored ? anchored_query_bytes(rq.qoffsets, nq, rq.anchors) : rq.qoffsets[nq];
+        off_bytes = ((size_t)nq + 1) * 8;
+        tiny = !anchored && qtotal + 32 <= 8192 && off_bytes <= 8192;
+        const bool plain = !anchored && !sa_order;          // entries that contain the pattern, in text order
+        fused_ok = plain && rq.mode == SEARCH_FULL && tiny && nvq <= SM_MAX_VQ && !knobs.no_small_path;
+        for (u32 i = 0; fused_ok && i < nq; ++i) fused_ok = rq.qoffsets[i + 1] - rq.qoffsets[i] <= SM_MAX_PLEN;
+        resident_ok = fused_ok && rq.low_latency && nq == 1 && nvq <= SM_BLOCK_MAX_VQ && !knobs.no_block_path;
+        mid_ok = plain && (rq.mode == SEARCH_FULL || device) && nvq <= MID_MAX && !knobs.no_mid_pipeline;
     }
-    if (counts_only || anchors) sa_order = false;          // (counts do not depend on the order; one hit per entry has one order)
-    bool small = tiny && nvq <= SM_MAX_VQ && !counts_only && !device_only && !ids_only && !knobs.no_small_path && !sa_order;
-    for (u32 i = 0; small && i < nq; ++i) small = qoffsets[i + 1] - qoffsets[i] <= SM_MAX_PLEN;
-    const u64 waves_per_block = 256 / kWave;
-    if (small) {
-        // ---- fused small-batch path: one kernel, queries and results through pinned host memory ----
-        if (low_latency && nq == 1 && nvq <= SM_BLOCK_MAX_VQ && !knobs.no_block_path) {
-            // a reader in low-latency mode: the resident kernel answers without a launch (or declines)
-            bool served = false;
-            PSS_TRY(resident_query(ctx, d_chunks, nc, qbytes + qoffsets[0], (u32)(qoffsets[1] - qoffsets[0]), res, st, &served));
-            if (served) {
-                st->ms_host = host_ms();
-                return PSS_OK;
-            }
-            for (u32 i = 0; i < nq; ++i) res->qcount[i] = 0;
-        }
-        PSS_TRY(ctx->slot[Q_ARENA].reserve(SM_ARENA_BYTES));
-        u8 *arena = ctx->slot[Q_ARENA].as<u8>();
-        SmallHeader *d_hdr = reinterpret_cast<SmallHeader *>(arena);
-        u8 *d_bytes = arena + 64;
-        if (ctx->small_hdr_ready != arena) {
-            PSS_HIP(hipMemsetAsync(d_hdr, 0, 64, s));
-            ctx->small_hdr_ready = arena;
-        }
-        u8 *h_arena = static_cast<u8 *>(ctx->pinned);
-        u8 *v_arena = static_cast<u8 *>(ctx->pinned_dev);               // the same bytes, device view
-        volatile u32 *h_overflow = reinterpret_cast<volatile u32 *>(h_arena + SM_OFF_FLAGS);
-        *h_overflow = 0;
-        // (the events bracket the kernel for last_stats().ms_device; two records cost the single-query path a couple of
-        // microseconds of host time and two marker packets, so it only takes them when asked: PSS_SEARCH_EVENTS=1)
-        const bool timed = knobs.small_path_events;
-        if (timed) PSS_HIP(hipEventRecord(e0, s));
-        const u8 *v_q = v_arena + SM_OFF_QUERY;
-        const u64 *v_qoff = reinterpret_cast<const u64 *>(v_arena + SM_OFF_QUERY + 8192);
-        u32 *v_flags = reinterpret_cast<u32 *>(v_arena + SM_OFF_FLAGS);
-        SmallRecord *v_rec = reinterpret_cast<SmallRecord *>(v_arena + SM_OFF_REC);
-        SmallEntry *v_ent = reinterpret_cast<SmallEntry *>(v_arena + SM_OFF_ENT);
-        const bool block_path = nvq <= SM_BLOCK_MAX_VQ && !knobs.no_block_path;
-        // workgroups per pair: as many as keep the launch at <= 64 workgroups (every one of them searches the
-        // interval first; on 15 chunks 32 per pair cost a miss 7 us, 4 per pair nothing measurable)
-        // (33 .. 64 pairs -- one query over that many chunks -- get up to 4 per pair, 256 workgroups at most: a pair of
-        // 1025 .. 4096 hits stays on this path instead of throwing the launch away for the general pipeline)
-        u32 spread = 1;
-        if (block_path)
-            while (spread < SM_SPREAD && nvq * spread * 2 <= (nvq <= 32 ? 64u : 256u)) spread *= 2;
-        st->route |= block_path ? PSS_ROUTE_SMALL_BLOCK : PSS_ROUTE_SMALL_WAVE;
-        if (block_path)
-            hipLaunchKernelGGL(search_block_kernel, dim3((u32)nvq * spread), dim3(SM_BLOCK), 0, s, d_chunks, nc, v_q, v_qoff,
-                               (u32)nvq, d_hdr, v_flags, v_rec, v_ent, d_bytes, v_arena + SM_OFF_BYTES, spread);
-        else
-            hipLaunchKernelGGL(search_small_kernel, dim3((u32)((nvq + waves_per_block - 1) / waves_per_block)), dim3(256),
-                               0, s, d_chunks, nc, v_q, v_qoff, (u32)nvq, d_hdr, v_flags, v_rec, v_ent, d_bytes,
-                               v_arena + SM_OFF_BYTES);
-        if (timed) PSS_HIP(hipEventRecord(e2, s));
-        PSS_HIP(hipStreamSynchronize(s));
-        if (!*h_overflow) {
-            PSS_TRY(small_collect(ctx, h_arena, d_bytes, nvq * spread, spread, nc, res, st, chunk_hits));
-            float ms = 0.f;
-            if (timed) PSS_HIP(hipEventElapsedTime(&ms, e0, e2));
-            st->ms_device = ms;
-            st->ms_interval = ms;
-            st->ms_host = host_ms();
+    template <typename T>
+    int take(SSlot which, size_t bytes, T *&p)          // room in one slot of the device's grow-only workspace
+    {
+        PSS_TRY(ctx->slot[which].reserve(bytes));
+        p = ctx->slot[which].as<T>();
+        return PSS_OK;
+    }
+    int stage_queries(), run_fused(bool *served), launch_interval(), run_mid(bool *done), run_general(), finish();
+    int sa_order_hits(u32 grid, u64 H);
+    int download_result(u64 E, u64 B, const u64 *d_starts, const u8 *d_bytes, bool via_stage);
+    void leave_on_device(const u64 *d_starts, const u8 *d_bytes), set_totals(u64 hits, u64 kept, u64 E, u64 B);
+};
+
+int empty_offsets(HostResult *res)       // the offsets of a host result without entries: the closing 0
+{
+    res->offsets = (u64 *)calloc(1, sizeof(u64));
+    return res->offsets ? PSS_OK : PSS_ENOMEM;
+}
+
+// No query or no chunk: nothing is searched.
+int empty_batch(DeviceCtx *ctx, const SearchRequest &rq, HostResult *res)
+{
+    if (rq.mode != SEARCH_DEVICE) return empty_offsets(res);
+    if (rq.nq) {                  // a rank that owns no chunk still answers: nq zero counters, no entries
+        PSS_TRY(ctx->slot[Q_QCOUNT].reserve((size_t)rq.nq * 8));
+        PSS_HIP(hipMemsetAsync(ctx->slot[Q_QCOUNT].p, 0, (size_t)rq.nq * 8, ctx->stream));
+        PSS_HIP(hipStreamSynchronize(ctx->stream));
+        res->d_qcount = ctx->slot[Q_QCOUNT].as<u64>();
+    }
+    return PSS_OK;
+}
+
+// Where the host copy of queries, offsets and anchor flags sits, and that copy itself.  Pageable H2D copies are
+// synchronous and slow to start, so whatever fits goes up from pinned memory: a tiny batch from the 16 KiB of the pinned
+// scratch (filled before the fused path, which reads it through the device view), a mid-size one from the 2 MiB
+// staging; the rest from the caller's memory.  An anchored batch is rewritten into the staging or, too large for it,
+// into vectors of the batch.
+int Batch::stage_queries()
+{
+    PSS_TRY(take(Q_BYTES, qtotal + 32, d_q));
+    PSS_TRY(take(Q_OFF, off_bytes, d_qoff));
+    PSS_TRY(take(Q_LO, nvq * 4, d_lo));
+    PSS_TRY(take(Q_CNT, nvq * 4, d_cnt));
+    PSS_TRY(take(Q_HITOFF, (nvq + 1) * 8, d_hitoff));
+    PSS_TRY(take(Q_SMALL, SC_MAX_BLOCKS * 8 + 256, d_partial));          // scan partials, totals, MidState
+    PSS_TRY(take(Q_QCOUNT, (size_t)nq * 8, d_qcount));
+    d_total = d_partial + SC_MAX_BLOCKS;
+    h_small = static_cast<u64 *>(ctx->pinned);
+    t_begin = std::chrono::steady_clock::now();
+    const size_t q_room = round_up(qtotal + 32, 64), o_room = round_up(off_bytes, 64);
+    const size_t staged = anchored ? q_room + o_room + nq : qtotal + 32 + off_bytes + 64;
+    u8 *hq = nullptr, *hf = nullptr;
+    u64 *ho = nullptr;
+    if (tiny) {
+        hq = static_cast<u8 *>(ctx->pinned) + SM_OFF_QUERY;
+        ho = reinterpret_cast<u64 *>(hq + 8192);
+    } else if (staged <= DeviceCtx::kStageQ && !knobs.no_search_stage) {
+        PSS_TRY(ctx->ensure_search_stage());
+        hq = static_cast<u8 *>(ctx->search_stage);
+        ho = reinterpret_cast<u64 *>(hq + q_room);
+        hf = hq + q_room + o_room;
+    } else if (anchored) {
+        own_q.resize(q_room + nq);
+        own_off.resize((size_t)nq + 1);
+        hq = own_q.data();
+        ho = own_off.data();
+        hf = hq + q_room;
+    }
+    if (anchored) {
+        PSS_TRY(take(Q_ANCHOR, round_up((size_t)nq, 64) + nvq, d_aflags));         // flags per query, chunk-edge hits per pair
+        d_edge = d_aflags + round_up((size_t)nq, 64);
+        anchored_rewrite(rq.qbytes, rq.qoffsets, nq, rq.anchors, hq, ho, hf);
+    } else if (hq) {
+        memcpy(hq, rq.qbytes, qtotal);
+        memset(hq + qtotal, 0, 32);
+        memcpy(ho, rq.qoffsets, off_bytes);
+    }
+    h_q = hq ? hq : rq.qbytes;
+    h_off = hq ? ho : rq.qoffsets;
+    h_flags = hf;
+    h_padded = hq != nullptr;
+    return PSS_OK;
+}
+
+// Fused small-batch path: one kernel, queries and results through pinned host memory -- or, for a reader in low-latency
+// mode, the resident kernel, which answers without a launch (or declines).  *served = false: more hits than the path
+// holds; the pipelines below take the batch (qcount is still all zero).
+int Batch::run_fused(bool *served)
+{
+    *served = false;
+    if (resident_ok) {
+        PSS_TRY(resident_query(ctx, d_chunks, nc, rq.qbytes + rq.qoffsets[0], (u32)(rq.qoffsets[1] - rq.qoffsets[0]), res, st, served));
+        if (*served) {
+            timed_route = timed_interval = false;   // (no HIP events on that path: resident_query took the times)
             return PSS_OK;
         }
-        // overflow: fall through to the general path (qcount is still all zero)
-        st->route |= PSS_ROUTE_SMALL_OVERFLOW;
+        for (u32 i = 0; i < nq; ++i) res->qcount[i] = 0;
     }
-    u8 *d_aflags = nullptr, *d_edge = nullptr;      // anchored batch: flags per query, chunk-edge hits per pair
-    std::vector<u8> anc_bytes;                      // ... and its rewritten queries when they do not fit the staging
-    std::vector<u64> anc_off;
-    if (anchors) {
-        PSS_TRY(ctx->slot[Q_ANCHOR].reserve(round_up((size_t)nq, 64) + nvq));
-        d_aflags = ctx->slot[Q_ANCHOR].as<u8>();
-        d_edge = d_aflags + round_up((size_t)nq, 64);
-        const size_t q_room = round_up(qtotal + 32, 64), o_room = round_up(off_bytes, 64);
-        u8 *hq, *hf;
-        u64 *ho;
-        if (q_room + o_room + nq <= DeviceCtx::kStageQ && !knobs.no_search_stage) {
-            PSS_TRY(ctx->ensure_search_stage());
-            hq = static_cast<u8 *>(ctx->search_stage);
-            ho = reinterpret_cast<u64 *>(hq + q_room);
-            hf = hq + q_room + o_room;
-        } else {
-            anc_bytes.resize(q_room + nq);
-            anc_off.resize((size_t)nq + 1);
-            hq = anc_bytes.data();
-            ho = anc_off.data();
-            hf = hq + q_room;
-        }
-        anchored_rewrite(qbytes, qoffsets, nq, anchors, hq, ho, hf);
-        PSS_HIP(hipMemcpyAsync(d_q, hq, qtotal + 32, hipMemcpyHostToDevice, s));
-        PSS_HIP(hipMemcpyAsync(d_qoff, ho, off_bytes, hipMemcpyHostToDevice, s));
-        PSS_HIP(hipMemcpyAsync(d_aflags, hf, nq, hipMemcpyHostToDevice, s));
-    } else if (tiny) {
-        // pageable H2D copies are synchronous and slow to start: tiny batches go up from the pinned staging
-        PSS_HIP(hipMemcpyAsync(d_q, stg, qtotal + 32, hipMemcpyHostToDevice, s));
-        PSS_HIP(hipMemcpyAsync(d_qoff, stg + 8192, off_bytes, hipMemcpyHostToDevice, s));
-    } else if (qtotal + 32 + off_bytes + 64 <= DeviceCtx::kStageQ && !knobs.no_search_stage) {
-        // mid-size batch: the same through the larger pinned staging
-        PSS_TRY(ctx->ensure_search_stage());
-        u8 *sq = static_cast<u8 *>(ctx->search_stage);
-        u8 *so = sq + round_up(qtotal + 32, 64);
-        memcpy(sq, qbytes, qtotal);
-        memset(sq + qtotal, 0, 32);
-        memcpy(so, qoffsets, off_bytes);
-        PSS_HIP(hipMemcpyAsync(d_q, sq, qtotal + 32, hipMemcpyHostToDevice, s));
-        PSS_HIP(hipMemcpyAsync(d_qoff, so, off_bytes, hipMemcpyHostToDevice, s));
+    u8 *arena;
+    PSS_TRY(take(Q_ARENA, SM_ARENA_BYTES, arena));
+    SmallHeader *d_hdr = reinterpret_cast<SmallHeader *>(arena);
+    u8 *d_bytes = arena + 64;
+    if (ctx->small_hdr_ready != arena) {
+        PSS_HIP(hipMemsetAsync(d_hdr, 0, 64, s));
+        ctx->small_hdr_ready = arena;
+    }
+    u8 *h_arena = static_cast<u8 *>(ctx->pinned);
+    u8 *v_arena = static_cast<u8 *>(ctx->pinned_dev);               // the same bytes, device view
+    volatile u32 *h_overflow = reinterpret_cast<volatile u32 *>(h_arena + SM_OFF_FLAGS);
+    *h_overflow = 0;
+    // (the events bracket the kernel for last_stats().ms_device; two records cost the single-query path a couple of
+    // microseconds of host time and two marker packets, so it only takes them when asked: PSS_SEARCH_EVENTS=1)
+    const bool timed = knobs.small_path_events;
+    if (timed) PSS_HIP(hipEventRecord(e0, s));
+    const u8 *v_q = v_arena + SM_OFF_QUERY;
+    const u64 *v_qoff = reinterpret_cast<const u64 *>(v_arena + SM_OFF_QUERY + 8192);
+    u32 *v_flags = reinterpret_cast<u32 *>(v_arena + SM_OFF_FLAGS);
+    SmallRecord *v_rec = reinterpret_cast<SmallRecord *>(v_arena + SM_OFF_REC);
+    SmallEntry *v_ent = reinterpret_cast<SmallEntry *>(v_arena + SM_OFF_ENT);
+    const bool block_path = nvq <= SM_BLOCK_MAX_VQ && !knobs.no_block_path;
+    // workgroups per pair: as many as keep the launch at <= 64 workgroups (every one of them searches the
+    // interval first; on 15 chunks 32 per pair cost a miss 7 us, 4 per pair nothing measurable)
+    // (33 .. 64 pairs -- one query over that many chunks -- get up to 4 per pair, 256 workgroups at most: a pair of
+    // 1025 .. 4096 hits stays on this path instead of throwing the launch away for the general pipeline)
+    u32 spread = 1;
+    if (block_path)
+        while (spread < SM_SPREAD && nvq * spread * 2 <= (nvq <= 32 ? 64u : 256u)) spread *= 2;
+    st->route |= block_path ? PSS_ROUTE_SMALL_BLOCK : PSS_ROUTE_SMALL_WAVE;
+    const u64 waves_per_block = 256 / kWave;
+    if (block_path)
+        hipLaunchKernelGGL(search_block_kernel, dim3((u32)nvq * spread), dim3(SM_BLOCK), 0, s, d_chunks, nc, v_q, v_qoff,
+                           (u32)nvq, d_hdr, v_flags, v_rec, v_ent, d_bytes, v_arena + SM_OFF_BYTES, spread);
+    else
+        hipLaunchKernelGGL(search_small_kernel, dim3((u32)((nvq + waves_per_block - 1) / waves_per_block)), dim3(256),
+                           0, s, d_chunks, nc, v_q, v_qoff, (u32)nvq, d_hdr, v_flags, v_rec, v_ent, d_bytes,
+                           v_arena + SM_OFF_BYTES);
+    if (timed) PSS_HIP(hipEventRecord(e2, s));
+    PSS_HIP(hipStreamSynchronize(s));
+    if (*h_overflow) {
+        st->route |= PSS_ROUTE_SMALL_OVERFLOW;
+        return PSS_OK;
+    }
+    PSS_TRY(small_collect(ctx, h_arena, d_bytes, nvq * spread, spread, nc, res, st, rq.chunk_hits));
+    timed_route = timed;
+    timed_interval = false;
+    *served = true;
+    return PSS_OK;
+}
+
+// The staged queries up in one sequence; the interval search of every (query, chunk) pair into d_lo / d_cnt, bracketed
+// by e0 / e1; then what reads the pair counts before anything is sized.
+int Batch::launch_interval()
+{
+    if (h_padded) {
+        PSS_HIP(hipMemcpyAsync(d_q, h_q, qtotal + 32, hipMemcpyHostToDevice, s));
     } else {
         PSS_HIP(hipMemsetAsync(d_q + qtotal, 0, 32, s));
-        if (qtotal) PSS_HIP(hipMemcpyAsync(d_q, qbytes, qtotal, hipMemcpyHostToDevice, s));
-        PSS_HIP(hipMemcpyAsync(d_qoff, qoffsets, off_bytes, hipMemcpyHostToDevice, s));
+        if (qtotal) PSS_HIP(hipMemcpyAsync(d_q, h_q, qtotal, hipMemcpyHostToDevice, s));
     }
+    PSS_HIP(hipMemcpyAsync(d_qoff, h_off, off_bytes, hipMemcpyHostToDevice, s));
+    if (anchored) PSS_HIP(hipMemcpyAsync(d_aflags, h_flags, nq, hipMemcpyHostToDevice, s));
     PSS_HIP(hipEventRecord(e0, s));
-    const u64 lane_min = knobs.lane_search_min;   // pairs from which one lane per pair is at least as fast as 16
+    const u64 lane_min = knobs.lane_search_min; // pairs from which one lane per pair is at least as fast as 16
                                                   // (10 000 pairs: 0.039 ms either way; 30 000: 0.044 vs 0.078 ms)
+    const u64 waves_per_block = 256 / kWave;
     if (nvq >= lane_min && !knobs.wave_search) {
         st->route |= PSS_ROUTE_INTERVAL_LANE;
         hipLaunchKernelGGL(search_interval_lane_kernel, dim3((u32)((nvq + 255) / 256)), dim3(256), 0, s, d_chunks, nc,
@@ -1939,231 +1979,266 @@ int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, u32 nc, const
                            0, s, d_chunks, nc, d_q, d_qoff, nvq, d_lo, d_cnt);
     }
     PSS_HIP(hipEventRecord(e1, s));
-    if (anchors)        // the matches at the two ends of every chunk join the pair's hits before anything is sized
-        hipLaunchKernelGGL(anchor_edges_kernel, dim3((u32)((nvq + 255) / 256)), dim3(256), 0, s, d_chunks, nc, d_q, d_qoff, d_aflags, nvq,
-                           d_cnt, d_edge);
-    if (chunk_hits && nc <= 4096) {
+    if (anchored)     // the matches at the two ends of every chunk join the pair's hits before anything is sized
+        hipLaunchKernelGGL(anchor_edges_kernel, dim3((u32)((nvq + 255) / 256)), dim3(256), 0, s, d_chunks, nc, d_q, d_qoff,
+                           d_aflags, nvq, d_cnt, d_edge);
+    if (rq.chunk_hits && nc <= 4096) {
         // (a reader with suffix arrays on the host tier: where did this batch's hits land?  One small kernel over the
         // pair counts and a wait -- next to probes over PCIe, nothing)
         PSS_TRY(ctx->slot[Q_HEAT].reserve((size_t)nc * 8));
         u64 *d_heat = ctx->slot[Q_HEAT].as<u64>();
         hipLaunchKernelGGL(chunk_hits_kernel, dim3(nc), dim3(256), 0, s, d_cnt, (u64)nq, nc, d_heat);
-        PSS_HIP(hipMemcpyAsync(chunk_hits, d_heat, (size_t)nc * 8, hipMemcpyDeviceToHost, s));
+        PSS_HIP(hipMemcpyAsync(rq.chunk_hits, d_heat, (size_t)nc * 8, hipMemcpyDeviceToHost, s));
         PSS_HIP(hipStreamSynchronize(s));
     }
-    if (nvq <= MID_MAX && !counts_only && !ids_only && !knobs.no_mid_pipeline && !sa_order && !anchors) {
-        // ---- mid pipeline: totals stay on the device, one wait for them, one for the result ----
-        st->route |= PSS_ROUTE_MID;
-        const u64 byte_cap = (u64)16 << 20;
-        PSS_TRY(ctx->slot[Q_START].reserve((size_t)MID_MAX * 4));
-        PSS_TRY(ctx->slot[Q_LEN].reserve((size_t)MID_MAX * 4));
-        PSS_TRY(ctx->slot[Q_EIDX].reserve(((size_t)MID_MAX + 1) * 8));
-        PSS_TRY(ctx->slot[Q_BOFF].reserve(((size_t)MID_MAX + 1) * 8));
-        PSS_TRY(ctx->slot[Q_ENTOFF].reserve(((size_t)MID_MAX + 1) * 8));
-        PSS_TRY(ctx->slot[Q_OUT].reserve(byte_cap + 16));
-        u32 *d_start = ctx->slot[Q_START].as<u32>();
-        u32 *d_len = ctx->slot[Q_LEN].as<u32>();
-        u64 *d_eidx = ctx->slot[Q_EIDX].as<u64>();
-        u64 *d_boff = ctx->slot[Q_BOFF].as<u64>();
-        u64 *d_entoff = ctx->slot[Q_ENTOFF].as<u64>();
-        u8 *d_out = ctx->slot[Q_OUT].as<u8>();
-        MidState *d_ms = reinterpret_cast<MidState *>(d_total + 8);         // behind the scan partials
-        const u32 grid = (u32)ctx->num_cus * 4;
-        hipLaunchKernelGGL(mid_hitoff_kernel, dim3(1), dim3(MID_BLOCK), 0, s, d_cnt, (u32)nvq, d_hitoff, d_ms);
-        hipLaunchKernelGGL(hit_lines_kernel, dim3(grid), dim3(256), 0, s, d_chunks, nc, d_q, d_qoff, nvq, d_lo, d_hitoff,
-                           (u64)0, d_ms, d_start, d_len);
-        hipLaunchKernelGGL(mid_hit_scans_kernel, dim3(1), dim3(MID_BLOCK), 0, s, d_len, d_ms, byte_cap, d_eidx, d_boff);
-        hipLaunchKernelGGL(emit_kernel, dim3(grid), dim3(256), 0, s, d_chunks, nc, nvq, d_hitoff, (u64)0, d_ms, d_start,
-                           d_len, d_eidx, d_boff, d_entoff, d_out);
-        hipLaunchKernelGGL(query_counts_kernel, dim3((nq + 255) / 256), dim3(256), 0, s, nc, nq, d_hitoff, d_eidx, d_qcount,
-                           (const MidState *)d_ms);
-        PSS_HIP(hipEventRecord(e2, s));
-        MidState *h_ms = reinterpret_cast<MidState *>(h_small);
-        PSS_HIP(hipMemcpyAsync(h_ms, d_ms, sizeof(MidState), hipMemcpyDeviceToHost, s));
-        PSS_HIP(hipStreamSynchronize(s));
-        if (!h_ms->flag) {
-            const u64 H = h_ms->hits, E = h_ms->entries, B = h_ms->bytes;
-            if (device_only) {
-                res->d_qcount = d_qcount;
-                res->d_offsets = d_entoff;
-                res->d_bytes = d_out;
-                res->n_entries = E;
-                res->n_bytes = B;
-                st->hits = H;
-                st->entries = E;
-                st->result_bytes = B;
-                float msd = 0.f;
-                PSS_HIP(hipEventElapsedTime(&msd, e0, e2));
-                st->ms_device = msd;
-                PSS_HIP(hipEventElapsedTime(&msd, e0, e1));
-                st->ms_interval = msd;
-                st->ms_host = host_ms();
-                return PSS_OK;
-            }
-            PSS_TRY(alloc_host_result(res, E, B, false));
-            const size_t need = round_up(E * 8, 64) + round_up(B, 64) + (size_t)nq * 8;
-            if (need <= DeviceCtx::kStageR && !knobs.no_search_stage) {
-                // down through pinned staging (three DMA copies, one wait), then plain memcpy
-                PSS_TRY(ctx->ensure_search_stage());
-                u8 *r0 = static_cast<u8 *>(ctx->search_stage) + DeviceCtx::kStageQ;
-                u8 *r1 = r0 + round_up(E * 8, 64), *r2 = r1 + round_up(B, 64);
-                if (E) PSS_HIP(hipMemcpyAsync(r0, d_entoff, E * 8, hipMemcpyDeviceToHost, s));
-                if (B) PSS_HIP(hipMemcpyAsync(r1, d_out, B, hipMemcpyDeviceToHost, s));
-                PSS_HIP(hipMemcpyAsync(r2, d_qcount, (size_t)nq * 8, hipMemcpyDeviceToHost, s));
-                PSS_HIP(hipStreamSynchronize(s));
-                if (E) memcpy(res->offsets, r0, E * 8);
-                if (B) memcpy(res->bytes, r1, B);
-                memcpy(res->qcount, r2, (size_t)nq * 8);
-            } else {
-                if (E) PSS_HIP(hipMemcpyAsync(res->offsets, d_entoff, E * 8, hipMemcpyDeviceToHost, s));
-                if (B) PSS_HIP(hipMemcpyAsync(res->bytes, d_out, B, hipMemcpyDeviceToHost, s));
-                PSS_HIP(hipMemcpyAsync(res->qcount, d_qcount, (size_t)nq * 8, hipMemcpyDeviceToHost, s));
-                PSS_HIP(hipStreamSynchronize(s));
-            }
-            res->offsets[E] = B;
-            res->n_entries = E;
-            res->n_bytes = B;
-            st->hits = H;
-            st->entries = E;
-            st->result_bytes = B;
-            float ms = 0.f;
-            PSS_HIP(hipEventElapsedTime(&ms, e0, e2));
-            st->ms_device = ms;
-            PSS_HIP(hipEventElapsedTime(&ms, e0, e1));
-            st->ms_interval = ms;
-            st->ms_host = host_ms();
-            return PSS_OK;
-        }
-        // more hits or bytes than the caps: the general pipeline below takes over (intervals are kept)
+    return PSS_OK;
+}
+
+// SEARCH_DEVICE: the packed result stays in the workspace; nothing but the totals comes down.
+void Batch::leave_on_device(const u64 *d_starts, const u8 *d_bytes)
+{
+    res->d_qcount = d_qcount;
+    res->d_offsets = d_starts;
+    res->d_bytes = d_bytes;
+}
+
+// E entry starts, B bytes and the nq counts down into a fresh host result, with one wait.  via_stage: through the pinned
+// staging when they fit (three DMA copies, then plain memcpy); else straight into the result, which is itself a block
+// of the pinned pool when it is large.
+int Batch::download_result(u64 E, u64 B, const u64 *d_starts, const u8 *d_bytes, bool via_stage)
+{
+    const size_t cnt_bytes = (size_t)nq * 8;
+    PSS_TRY(alloc_host_result(res, E, B, !via_stage && !knobs.no_pinned_results));
+    u8 *to_off = reinterpret_cast<u8 *>(res->offsets), *to_bytes = res->bytes, *to_cnt = reinterpret_cast<u8 *>(res->qcount);
+    const bool staged = via_stage && round_up(E * 8, 64) + round_up(B, 64) + cnt_bytes <= DeviceCtx::kStageR && !knobs.no_search_stage;
+    if (staged) {
+        PSS_TRY(ctx->ensure_search_stage());
+        to_off = static_cast<u8 *>(ctx->search_stage) + DeviceCtx::kStageQ;
+        to_bytes = to_off + round_up(E * 8, 64);
+        to_cnt = to_bytes + round_up(B, 64);
+    }
+    if (E) PSS_HIP(hipMemcpyAsync(to_off, d_starts, E * 8, hipMemcpyDeviceToHost, s));
+    if (B) PSS_HIP(hipMemcpyAsync(to_bytes, d_bytes, B, hipMemcpyDeviceToHost, s));
+    PSS_HIP(hipMemcpyAsync(to_cnt, d_qcount, cnt_bytes, hipMemcpyDeviceToHost, s));
+    PSS_HIP(hipStreamSynchronize(s));
+    if (staged) {
+        if (E) memcpy(res->offsets, to_off, E * 8);
+        if (B) memcpy(res->bytes, to_bytes, B);
+        memcpy(res->qcount, to_cnt, cnt_bytes);
+    }
+    res->offsets[E] = B;
+    return PSS_OK;
+}
+
+void Batch::set_totals(u64 hits, u64 kept, u64 E, u64 B)
+{
+    res->n_entries = E;
+    res->n_bytes = B;
+    st->hits = hits;
+    st->entries = kept;
+    st->result_bytes = B;
+}
+
+// Mid pipeline: totals stay on the device, one wait for them, one for the result.  *done = false: more hits or bytes
+// than its caps; the general pipeline takes over (the intervals are kept).
+int Batch::run_mid(bool *done)
+{
+    *done = false;
+    st->route |= PSS_ROUTE_MID;
+    const u64 byte_cap = (u64)16 << 20;
+    PSS_TRY(take(Q_START, (size_t)MID_MAX * 4, d_start));
+    PSS_TRY(take(Q_LEN, (size_t)MID_MAX * 4, d_len));
+    PSS_TRY(take(Q_EIDX, ((size_t)MID_MAX + 1) * 8, d_eidx));
+    PSS_TRY(take(Q_BOFF, ((size_t)MID_MAX + 1) * 8, d_boff));
+    PSS_TRY(take(Q_ENTOFF, ((size_t)MID_MAX + 1) * 8, d_entoff));
+    PSS_TRY(take(Q_OUT, byte_cap + 16, d_out));
+    MidState *d_ms = reinterpret_cast<MidState *>(d_total + 8);       // behind the scan partials
+    const u32 grid = (u32)ctx->num_cus * 4;
+    hipLaunchKernelGGL(mid_hitoff_kernel, dim3(1), dim3(MID_BLOCK), 0, s, d_cnt, (u32)nvq, d_hitoff, d_ms);
+    hipLaunchKernelGGL(hit_lines_kernel, dim3(grid), dim3(256), 0, s, d_chunks, nc, d_q, d_qoff, nvq, d_lo, d_hitoff,
+                       (u64)0, d_ms, d_start, d_len);
+    hipLaunchKernelGGL(mid_hit_scans_kernel, dim3(1), dim3(MID_BLOCK), 0, s, d_len, d_ms, byte_cap, d_eidx, d_boff);
+    hipLaunchKernelGGL(emit_kernel, dim3(grid), dim3(256), 0, s, d_chunks, nc, nvq, d_hitoff, (u64)0, d_ms, d_start,
+                       d_len, d_eidx, d_boff, d_entoff, d_out);
+    hipLaunchKernelGGL(query_counts_kernel, dim3((nq + 255) / 256), dim3(256), 0, s, nc, nq, d_hitoff, d_eidx, d_qcount,
+                       (const MidState *)d_ms);
+    PSS_HIP(hipEventRecord(e2, s));
+    MidState *h_ms = reinterpret_cast<MidState *>(h_small);
+    PSS_HIP(hipMemcpyAsync(h_ms, d_ms, sizeof(MidState), hipMemcpyDeviceToHost, s));
+    PSS_HIP(hipStreamSynchronize(s));
+    if (h_ms->flag) {
         st->route |= PSS_ROUTE_MID_OVERFLOW;
+        return PSS_OK;
     }
-    st->route |= PSS_ROUTE_GENERAL | (sa_order ? PSS_ROUTE_SA_ORDER : 0u) | (counts_only ? PSS_ROUTE_COUNTS : 0u) |
-                 (anchors ? PSS_ROUTE_ANCHORED : 0u);
+    const u64 H = h_ms->hits, E = h_ms->entries, B = h_ms->bytes;
+    if (device)
+        leave_on_device(d_entoff, d_out);
+    else
+        PSS_TRY(download_result(E, B, d_entoff, d_out, true));
+    set_totals(H, E, E, B);
+    *done = true;
+    return PSS_OK;
+}
+
+// sa_order: every hit reports its entry, a stable sort by (pair, line start) brings the hits of one entry together in
+// suffix-array order, and all but the first of each run are dropped (hit_bounds_kernel).
+int Batch::sa_order_hits(u32 grid, u64 H)
+{
+    if (H >= (1ull << 32) || nvq >= (1ull << 33)) {
+        set_error("search: %llu hits of %llu (query, chunk) pairs are more than the suffix-array result order takes in one batch",
+                  (unsigned long long)H, (unsigned long long)nvq);
+        return PSS_EINVAL;
+    }
+    u64 *OK[2];
+    u32 *OV[2];
+    PSS_TRY(take(Q_ORD_K0, H * 8, OK[0]));
+    PSS_TRY(take(Q_ORD_K1, H * 8, OK[1]));
+    PSS_TRY(take(Q_ORD_V0, H * 4, OV[0]));
+    PSS_TRY(take(Q_ORD_V1, H * 4, OV[1]));
+    PSS_TRY(ctx->slot[Q_ORD_WORK].reserve(radix_sort_workspace_bytes()));
+    hipLaunchKernelGGL(hit_bounds_kernel, dim3(grid), dim3(256), 0, s, d_chunks, nc, nvq, d_lo, d_hitoff, H, d_start, d_len,
+                       OK[0], OV[0]);
+    int pair_bits = 1;
+    while ((1ull << pair_bits) < nvq) ++pair_bits;
+    int od = 0;
+    SortStats oss;
+    PSS_TRY(radix_sort_pairs(ctx, OK, OV, (u32)H, 31 + pair_bits, 0xffffffffu, nullptr, 0, ctx->slot[Q_ORD_WORK].p, &od, false, &oss));
+    hipLaunchKernelGGL(mark_later_hits_kernel, dim3(grid), dim3(256), 0, s, OK[od], OV[od], H, d_len);
+    return PSS_OK;
+}
+
+// General pipeline: every size comes down to the host before what it sizes is reserved -- hits, then kept hits (entries),
+// then bytes.
+int Batch::run_general()
+{
+    st->route |= PSS_ROUTE_GENERAL | (sa_order ? PSS_ROUTE_SA_ORDER : 0u) | (counts ? PSS_ROUTE_COUNTS : 0u) |
+                   (anchored ? PSS_ROUTE_ANCHORED : 0u);
     PSS_TRY(device_excl_scan(ctx, InU32{d_cnt}, nvq, d_partial, d_total, d_hitoff));
     PSS_HIP(hipMemcpyAsync(h_small, d_total, 8, hipMemcpyDeviceToHost, s));
     PSS_HIP(hipStreamSynchronize(s));
     const u64 H = h_small[0];
-    st->hits = H;
-    u64 E = 0, B = 0;
-    if (H) {
-        PSS_TRY(ctx->slot[Q_START].reserve(H * 4));
-        PSS_TRY(ctx->slot[Q_LEN].reserve(H * 4));
-        PSS_TRY(ctx->slot[Q_EIDX].reserve((H + 1) * 8));
-        PSS_TRY(ctx->slot[Q_BOFF].reserve((H + 1) * 8));
-        u32 *d_start = ctx->slot[Q_START].as<u32>();
-        u32 *d_len = ctx->slot[Q_LEN].as<u32>();
-        u64 *d_eidx = ctx->slot[Q_EIDX].as<u64>();
-        u64 *d_boff = ctx->slot[Q_BOFF].as<u64>();
-        const u32 grid = (u32)std::min<u64>((u64)ctx->num_cus * 16, (H + 255) / 256);
-        if (sa_order) {
-            if (H >= (1ull << 32) || nvq >= (1ull << 33)) {
-                set_error("search: %llu hits of %llu (query, chunk) pairs are more than the suffix-array result order takes in one batch",
-                          (unsigned long long)H, (unsigned long long)nvq);
-                return PSS_EINVAL;
-            }
-            PSS_TRY(ctx->slot[Q_ORD_K0].reserve(H * 8));
-            PSS_TRY(ctx->slot[Q_ORD_K1].reserve(H * 8));
-            PSS_TRY(ctx->slot[Q_ORD_V0].reserve(H * 4));
-            PSS_TRY(ctx->slot[Q_ORD_V1].reserve(H * 4));
-            PSS_TRY(ctx->slot[Q_ORD_WORK].reserve(radix_sort_workspace_bytes()));
-            u64 *OK[2] = {ctx->slot[Q_ORD_K0].as<u64>(), ctx->slot[Q_ORD_K1].as<u64>()};
-            u32 *OV[2] = {ctx->slot[Q_ORD_V0].as<u32>(), ctx->slot[Q_ORD_V1].as<u32>()};
-            hipLaunchKernelGGL(hit_bounds_kernel, dim3(grid), dim3(256), 0, s, d_chunks, nc, nvq, d_lo, d_hitoff, H, d_start, d_len,
-                               OK[0], OV[0]);
-            int pair_bits = 1;
-            while ((1ull << pair_bits) < nvq) ++pair_bits;
-            int od = 0;
-            SortStats oss;
-            PSS_TRY(radix_sort_pairs(ctx, OK, OV, (u32)H, 31 + pair_bits, 0xffffffffu, nullptr, 0, ctx->slot[Q_ORD_WORK].p, &od, false, &oss));
-            hipLaunchKernelGGL(mark_later_hits_kernel, dim3(grid), dim3(256), 0, s, OK[od], OV[od], H, d_len);
-        } else if (anchors)
-            hipLaunchKernelGGL(anchored_hits_kernel, dim3(grid), dim3(256), 0, s, d_chunks, nc, d_aflags, nvq, d_lo, d_edge, d_hitoff, H,
-                               d_start, d_len);
-        else
+    if (H == 0) {
+        PSS_HIP(hipEventRecord(e2, s));
+        if (device) {
+            PSS_HIP(hipMemsetAsync(d_qcount, 0, (size_t)nq * 8, s));
+            leave_on_device(nullptr, nullptr);
+        }
+        PSS_HIP(hipStreamSynchronize(s));
+        if (!device) PSS_TRY(empty_offsets(res));
+        set_totals(0, 0, 0, 0);
+        return PSS_OK;
+    }
+    PSS_TRY(take(Q_START, H * 4, d_start));
+    PSS_TRY(take(Q_LEN, H * 4, d_len));
+    PSS_TRY(take(Q_EIDX, (H + 1) * 8, d_eidx));
+    PSS_TRY(take(Q_BOFF, (H + 1) * 8, d_boff));
+    const u32 grid = (u32)std::min<u64>((u64)ctx->num_cus * 16, (H + 255) / 256);
+    // the entry of every hit; a hit whose entry another hit of the pair stands for is marked in d_len and dropped by the scans
+    if (sa_order)
+        PSS_TRY(sa_order_hits(grid, H));
+    else if (anchored)
+        hipLaunchKernelGGL(anchored_hits_kernel, dim3(grid), dim3(256), 0, s, d_chunks, nc, d_aflags, nvq, d_lo, d_edge,
+                           d_hitoff, H, d_start, d_len);
+    else
         hipLaunchKernelGGL(hit_lines_kernel, dim3(grid), dim3(256), 0, s, d_chunks, nc, d_q, d_qoff, nvq, d_lo,
                            d_hitoff, H, (const MidState *)nullptr, d_start, d_len);
-        PSS_TRY(device_excl_scan(ctx, InKept{d_len}, H, d_partial, d_total, d_eidx));
-        PSS_HIP(hipMemcpyAsync(h_small, d_total, 8, hipMemcpyDeviceToHost, s));
-        if (counts_only) {
-            // entries per query without materialising one: interval search, dedupe flags, two scans
-            hipLaunchKernelGGL(query_counts_kernel, dim3((nq + 255) / 256), dim3(256), 0, s, nc, nq, d_hitoff, d_eidx,
-                               d_qcount, (const MidState *)nullptr);
-            PSS_HIP(hipEventRecord(e2, s));
-            PSS_HIP(hipMemcpyAsync(res->qcount, d_qcount, (size_t)nq * 8, hipMemcpyDeviceToHost, s));
-            PSS_HIP(hipStreamSynchronize(s));
-            res->offsets = (u64 *)calloc(1, sizeof(u64));
-            if (!res->offsets) return PSS_ENOMEM;
-            st->entries = h_small[0];
-            float msc = 0.f;
-            PSS_HIP(hipEventElapsedTime(&msc, e0, e2));
-            st->ms_device = msc;
-            PSS_HIP(hipEventElapsedTime(&msc, e0, e1));
-            st->ms_interval = msc;
-            st->ms_host = host_ms();
-            return PSS_OK;
-        }
-        if (ids_only) {
-            // one id per kept hit, 8 bytes each: no byte scan, the entry count alone sizes the result
-            PSS_HIP(hipStreamSynchronize(s));
-            E = h_small[0];
-            B = E * 8;
-        } else {
-            PSS_TRY(device_excl_scan(ctx, InLen{d_len}, H, d_partial, d_total, d_boff));
-            PSS_HIP(hipMemcpyAsync(h_small + 1, d_total, 8, hipMemcpyDeviceToHost, s));
-            PSS_HIP(hipStreamSynchronize(s));
-            E = h_small[0];
-            B = h_small[1];
-        }
-        PSS_TRY(ctx->slot[Q_ENTOFF].reserve((E + 1) * 8));
-        PSS_TRY(ctx->slot[Q_OUT].reserve(B + 16));
-        u64 *d_entoff = ctx->slot[Q_ENTOFF].as<u64>();
-        u8 *d_out = ctx->slot[Q_OUT].as<u8>();
-        if (ids_only)
-            hipLaunchKernelGGL(emit_ids_kernel, dim3(grid), dim3(256), 0, s, d_chunks, d_lines, nc, nvq, d_hitoff, H, d_start, d_len,
-                               d_eidx, d_entoff, reinterpret_cast<u64 *>(d_out));
-        else
-            hipLaunchKernelGGL(emit_kernel, dim3(grid), dim3(256), 0, s, d_chunks, nc, nvq, d_hitoff, H,
-                               (const MidState *)nullptr, d_start, d_len, d_eidx, d_boff, d_entoff, d_out);
+    PSS_TRY(device_excl_scan(ctx, InKept{d_len}, H, d_partial, d_total, d_eidx));
+    PSS_HIP(hipMemcpyAsync(h_small, d_total, 8, hipMemcpyDeviceToHost, s));
+    if (counts) {
+        // entries per query without materialising one: interval search, dedupe flags, two scans
         hipLaunchKernelGGL(query_counts_kernel, dim3((nq + 255) / 256), dim3(256), 0, s, nc, nq, d_hitoff, d_eidx,
                            d_qcount, (const MidState *)nullptr);
         PSS_HIP(hipEventRecord(e2, s));
-        if (device_only) {
-            res->d_qcount = d_qcount;
-            res->d_offsets = d_entoff;
-            res->d_bytes = d_out;
-            PSS_HIP(hipStreamSynchronize(s));
-        } else {
-            PSS_TRY(alloc_host_result(res, E, B, !knobs.no_pinned_results));
-            if (E) PSS_HIP(hipMemcpyAsync(res->offsets, d_entoff, E * 8, hipMemcpyDeviceToHost, s));
-            if (B) PSS_HIP(hipMemcpyAsync(res->bytes, d_out, B, hipMemcpyDeviceToHost, s));
-            PSS_HIP(hipMemcpyAsync(res->qcount, d_qcount, (size_t)nq * 8, hipMemcpyDeviceToHost, s));
-            PSS_HIP(hipStreamSynchronize(s));
-            res->offsets[E] = B;
-        }
-    } else {
-        PSS_HIP(hipEventRecord(e2, s));
-        if (device_only) {
-            PSS_HIP(hipMemsetAsync(d_qcount, 0, (size_t)nq * 8, s));
-            res->d_qcount = d_qcount;
-        }
+        PSS_HIP(hipMemcpyAsync(res->qcount, d_qcount, (size_t)nq * 8, hipMemcpyDeviceToHost, s));
         PSS_HIP(hipStreamSynchronize(s));
-        if (!device_only) {
-            res->offsets = (u64 *)calloc(1, sizeof(u64));
-            if (!res->offsets) return PSS_ENOMEM;
-        }
+        PSS_TRY(empty_offsets(res));
+        set_totals(H, h_small[0], 0, 0);
+        return PSS_OK;
     }
-    PSS_HIP(hipGetLastError());
-    res->n_entries = E;
-    res->n_bytes = B;
-    st->entries = E;
-    st->result_bytes = B;
-    float ms = 0.f;
-    PSS_HIP(hipEventElapsedTime(&ms, e0, e2));
-    st->ms_device = ms;
-    PSS_HIP(hipEventElapsedTime(&ms, e0, e1));
-    st->ms_interval = ms;
-    st->ms_host = host_ms();
+    if (!ids) {         // (ids: one per kept hit, 8 bytes each -- no byte scan, the entry count alone sizes the result)
+        PSS_TRY(device_excl_scan(ctx, InLen{d_len}, H, d_partial, d_total, d_boff));
+        PSS_HIP(hipMemcpyAsync(h_small + 1, d_total, 8, hipMemcpyDeviceToHost, s));
+    }
+    PSS_HIP(hipStreamSynchronize(s));
+    const u64 E = h_small[0], B = ids ? E * 8 : h_small[1];
+    PSS_TRY(take(Q_ENTOFF, (E + 1) * 8, d_entoff));
+    PSS_TRY(take(Q_OUT, B + 16, d_out));
+    if (ids)
+        hipLaunchKernelGGL(emit_ids_kernel, dim3(grid), dim3(256), 0, s, d_chunks, d_lines, nc, nvq, d_hitoff, H, d_start, d_len,
+                           d_eidx, d_entoff, reinterpret_cast<u64 *>(d_out));
+    else
+        hipLaunchKernelGGL(emit_kernel, dim3(grid), dim3(256), 0, s, d_chunks, nc, nvq, d_hitoff, H,
+                           (const MidState *)nullptr, d_start, d_len, d_eidx, d_boff, d_entoff, d_out);
+    hipLaunchKernelGGL(query_counts_kernel, dim3((nq + 255) / 256), dim3(256), 0, s, nc, nq, d_hitoff, d_eidx,
+                       d_qcount, (const MidState *)nullptr);
+    PSS_HIP(hipEventRecord(e2, s));
+    if (device) {
+        leave_on_device(d_entoff, d_out);
+        PSS_HIP(hipStreamSynchronize(s));
+    } else {
+        PSS_TRY(download_result(E, B, d_entoff, d_out, false));
+    }
+    set_totals(H, E, E, B);
     return PSS_OK;
+}
+
+// The common end of every route: a launch that failed, the device times of the route, the host time of the call.
+int Batch::finish()
+{
+    PSS_HIP(hipGetLastError());
+    float ms = 0.f;
+    if (timed_route) {
+        PSS_HIP(hipEventElapsedTime(&ms, e0, e2));
+        st->ms_device = st->ms_interval = ms;       // (the fused path: one kernel, both times)
+    }
+    if (timed_interval) {
+        PSS_HIP(hipEventElapsedTime(&ms, e0, e1));
+        st->ms_interval = ms;
+    }
+    st->ms_host = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    return PSS_OK;
+}
+
+}  // namespace
+
+int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, const LineDesc *d_lines, uint32_t nc, const SearchRequest &rq,
+                        HostResult *res, pss_search_stats *st)
+{
+    if (rq.chunk_hits)
+        for (u32 c = 0; c < nc; ++c) rq.chunk_hits[c] = 0;
+    if (rq.mode == SEARCH_IDS && nc && !d_lines) {
+        set_error("search: the ids mode needs the chunks' line tables");
+        return PSS_EINVAL;
+    }
+    if (rq.anchors && (rq.mode == SEARCH_DEVICE || rq.low_latency)) {
+        set_error("search: an anchored batch takes the general pipeline to a host result");
+        return PSS_EINVAL;
+    }
+    memset(st, 0, sizeof *st);
+    st->queries = rq.nq;
+    res->nq = rq.nq;
+    res->qcount = (u64 *)calloc(rq.nq ? rq.nq : 1, sizeof(u64));
+    res->offsets = nullptr;
+    res->bytes = nullptr;
+    res->n_entries = 0;
+    if (!res->qcount) return PSS_ENOMEM;
+    if (rq.nq == 0 || nc == 0) return empty_batch(ctx, rq, res);
+
+    Batch b(ctx, d_chunks, d_lines, nc, rq, res, st);       // the request, normalised
+    PSS_TRY(b.stage_queries());
+    if (b.fused_ok) {
+        bool served = false;
+        PSS_TRY(b.run_fused(&served));
+        if (served) return b.finish();
+    }
+    PSS_TRY(b.launch_interval());
+    if (b.mid_ok) {
+        bool done = false;
+        PSS_TRY(b.run_mid(&done));
+        if (done) return b.finish();
+    }
+    PSS_TRY(b.run_general());
+    return b.finish();
 }
 
 // ---- device-side merge of per-rank packed results (multi-GPU gather) ---------------------------------------------
