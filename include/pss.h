@@ -474,6 +474,48 @@ int pss_reader_search_anchored_ids_batch(pss_reader *r, const uint8_t *qbytes, c
 /* counts[q] = entries query q matches; nothing but nq counters comes down */
 int pss_reader_count_anchored_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq,
                                     const uint8_t *anchors, uint64_t *counts);
+/*
+ * All-terms search (no reference counterpart): which entries contain ALL of some terms and NONE of some others, e.g.
+ * "error" and "timeout" but not "retry".  The batch holds ngroups GROUPS.  Group g is the terms group_offsets[g] ..
+ * group_offsets[g + 1] of the nterms terms packed in tbytes / toffsets (as queries are everywhere); exclude[t] = 0 makes
+ * term t an INCLUDE term, 1 an EXCLUDE term.  An entry of a chunk matches a group when every include term occurs in it
+ * and no exclude term does, where "occurs in" is what pss_reader_search_batch means: the entry is among the entries that
+ * call returns for the term alone (exact bytes, the whole entry, the last byte of an unterminated last entry included).
+ * The answer for a group is therefore the intersection of its include terms' pss_reader_search_ids_batch results minus
+ * the union of its exclude terms'.  A term may be repeated; a term both included and excluded gives an empty answer.  An
+ * include term that holds 0x0A makes its group match nothing; an exclude term that holds 0x0A excludes nothing.
+ * *out has one row ("query") per GROUP: query_counts[g] entries, packed as pss_reader_search_batch (text; an unterminated
+ * last entry loses its last byte) or pss_reader_search_ids_batch (ids) pack them; counts[g] likewise.
+ * PSS_EINVAL (message in pss_last_error, *out untouched): a group without an include term ("everything except" is not a
+ * search), an empty term, an exclude[t] other than 0 or 1, group offsets that do not start at 0, decrease or do not end
+ * at nterms, a null group_offsets / out, a null tbytes / toffsets / exclude with nterms > 0, a null reader.  The batch
+ * is checked before the reader: a malformed batch is reported as such even when r is null, a null r after that.
+ * The search: the interval search of pss_reader_search_batch over all (term, chunk) pairs gives every term's
+ * occurrences per chunk; per (group, chunk) pair the include term with the fewest (the lowest index on a tie) DRIVES
+ * the general pipeline as a plain query would, and each candidate entry it yields is scanned once for the group's other
+ * terms.  The work follows the rarest include term, and a chunk in which any include term is absent contributes nothing
+ * without a hit being looked at.
+ * Order: group-major, chunk-major inside a group; inside one (group, chunk) pair the plain search's default order for
+ * the driver term, the same for the text and the id variant -- pss_reader_set_result_order has no effect.  A group of one
+ * include term and no exclude term returns exactly what pss_reader_search_ids_batch returns for that term under the
+ * default order.
+ * Whole-file, sharded and multi-device readers, and suffix arrays on the host tier, are served alike.
+ * pss_reader_last_stats: queries = groups, hits = the sum of the drivers' interval hits, entries = what is returned;
+ * route = GENERAL | the interval bits (| COUNTS for the count call) -- there is no bit of its own.  The id variant builds
+ * the line tables on first use, the other two allocate nothing for them.
+ * Out of scope: the fused small-batch path and the resident low-latency kernel, the mid pipeline (an all-terms batch
+ * always takes the general pipeline), a device-resident result (pss_reader_search_batch_device), and the multi-process
+ * gather over RCCL (dist.ShardedReader).
+ */
+/* packed entry text, one row per group */
+int pss_reader_search_terms_batch(pss_reader *r, const uint8_t *tbytes, const uint64_t *toffsets, uint32_t nterms,
+                                  const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *exclude, pss_result **out);
+/* u64 entry ids, packed as pss_reader_search_ids_batch packs them */
+int pss_reader_search_terms_ids_batch(pss_reader *r, const uint8_t *tbytes, const uint64_t *toffsets, uint32_t nterms,
+                                      const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *exclude, pss_result **out);
+/* counts[g] = entries group g matches; nothing but ngroups counters comes down */
+int pss_reader_count_terms_batch(pss_reader *r, const uint8_t *tbytes, const uint64_t *toffsets, uint32_t nterms,
+                                 const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *exclude, uint64_t *counts);
 /* For the first `cap` resident chunks, in file order: index in the file and number of entries; *num = resident chunks. */
 int pss_reader_chunk_entries(pss_reader *r, uint64_t *chunk_index, uint64_t *entries, uint64_t cap, uint64_t *num);
 /*

@@ -577,6 +577,101 @@ class Reader:
         """Extension: for every text, whether the index holds an entry equal to it."""
         return [c > 0 for c in self.count_anchored_bytes([_utf8(t, 'text') for t in texts], 'entry')]
 
+    @staticmethod
+    def _terms_args(groups):
+        """(blob, term offsets, group offsets, exclude flags) of one all-terms batch.  A group is an ``(include,
+        exclude)`` pair of byte-string sequences, or a bare sequence of byte strings (no exclusions).  ``ValueError`` for
+        a group without an include term and for an empty term."""
+        import numpy as np
+        terms: typing.List[bytes] = []
+        flags: typing.List[int] = []
+        goff = [0]
+        for g, group in enumerate(groups):
+            if isinstance(group, (bytes, bytearray, str)):
+                raise TypeError(f'group {g} must be a sequence of byte strings or an (include, exclude) pair of them')
+            group = list(group)
+            if len(group) == 2 and not isinstance(group[0], (bytes, bytearray)) and not isinstance(group[1], (bytes, bytearray)):
+                include, exclude = list(group[0]), list(group[1])
+            else:
+                include, exclude = group, []
+            for t in include + exclude:
+                if not isinstance(t, (bytes, bytearray)):
+                    raise TypeError(f'group {g}: a term must be bytes, not {type(t).__name__}')
+                if len(t) == 0:
+                    raise ValueError(f'group {g}: an empty term (every entry contains it: leave it out)')
+            if not include:
+                raise ValueError(f'group {g} has no include term ("everything except" is not a search)')
+            terms += [bytes(t) for t in include + exclude]
+            flags += [0] * len(include) + [1] * len(exclude)
+            goff.append(len(terms))
+        blob, offs = _pack_queries(terms)
+        return blob, offs, np.array(goff, dtype=np.uint64), np.array(flags if flags else [0], dtype=np.uint8)
+
+    def search_all_batch_packed(self, groups) -> 'PackedResult':
+        """Extension: per group, the entries that contain EVERY include term and NO exclude term, as a packed result
+        like ``search_batch_packed``'s with one row per group.  ``groups`` is a sequence of ``(include, exclude)``
+        pairs of byte-string sequences; a bare sequence of byte strings means no exclusions.  "Contains" is what
+        ``search`` means, so the answer is the intersection of the include terms' ``search_ids_batch`` results minus the
+        union of the exclude terms'.  On the device the rarest include term of every (group, chunk) pair drives the
+        search and its candidate entries are checked against the other terms, so the work follows the rarest term
+        (include/pss.h).  ``set_result_order`` has no effect."""
+        import numpy as np
+        blob, offs, goff, excl = self._terms_args(groups)
+        ng = len(goff) - 1
+        res = ctypes.c_void_p()
+        _ffi.check(_lib.pss_reader_search_terms_batch(self._handle(), blob, offs.ctypes.data, len(offs) - 1, goff.ctypes.data, ng,
+                                                      excl.ctypes.data, ctypes.byref(res)))
+        owner = _ResultOwner(res)      # the arrays below are views of the C result; it lives as long as they do
+        n = _lib.pss_result_num_entries(res)
+        counts = owner.view(_lib.pss_result_query_counts(res), ng, np.uint64)
+        offsets = owner.view(_lib.pss_result_offsets(res), n + 1, np.uint64)
+        data = owner.view(_lib.pss_result_bytes(res), int(offsets[n]), np.uint8)
+        return PackedResult(data, offsets, counts)
+
+    def search_all_ids_batch(self, groups) -> 'IdResult':
+        """Extension: the ids (``search_ids_batch``) of the entries ``search_all_batch_packed`` returns, in the same
+        order; ``counts[g]`` of them belong to group g."""
+        import numpy as np
+        blob, offs, goff, excl = self._terms_args(groups)
+        ng = len(goff) - 1
+        res = ctypes.c_void_p()
+        _ffi.check(_lib.pss_reader_search_terms_ids_batch(self._handle(), blob, offs.ctypes.data, len(offs) - 1, goff.ctypes.data, ng,
+                                                          excl.ctypes.data, ctypes.byref(res)))
+        owner = _ResultOwner(res)
+        n = _lib.pss_result_num_entries(res)
+        counts = owner.view(_lib.pss_result_query_counts(res), ng, np.uint64)
+        ids = owner.view(_lib.pss_result_bytes(res), 8 * n, np.uint8).view(np.uint64)
+        ids.flags.writeable = False
+        return IdResult(ids, counts)
+
+    def count_all_bytes(self, groups) -> typing.List[int]:
+        """Extension: how many entries each group matches; only the counters come back."""
+        import numpy as np
+        blob, offs, goff, excl = self._terms_args(groups)
+        ng = len(goff) - 1
+        counts = np.zeros(max(ng, 1), dtype=np.uint64)
+        _ffi.check(_lib.pss_reader_count_terms_batch(self._handle(), blob, offs.ctypes.data, len(offs) - 1, goff.ctypes.data, ng,
+                                                     excl.ctypes.data, counts.ctypes.data))
+        return [int(c) for c in counts[:ng]]
+
+    @staticmethod
+    def _str_terms(terms, exclude):
+        if isinstance(terms, (str, bytes, bytearray)) or isinstance(exclude, (str, bytes, bytearray)):
+            bad = terms if isinstance(terms, (str, bytes, bytearray)) else exclude
+            raise TypeError(f"argument 'terms': '{type(bad).__name__}' object cannot be converted to a sequence of 'PyString'")
+        return [([_utf8(t, 'terms') for t in terms], [_utf8(t, 'exclude') for t in exclude])]
+
+    def search_all(self, terms: typing.Sequence[str], exclude: typing.Sequence[str] = ()) -> typing.List[str]:
+        """Extension: the entries that contain every one of ``terms`` and none of ``exclude``."""
+        p = self.search_all_batch_packed(self._str_terms(terms, exclude))
+        data = p.data.tobytes()
+        o = p.offsets.tolist()
+        return [data[o[i]:o[i + 1]].decode('utf-8') for i in range(len(o) - 1)]
+
+    def count_all(self, terms: typing.Sequence[str], exclude: typing.Sequence[str] = ()) -> int:
+        """Extension: how many entries contain every one of ``terms`` and none of ``exclude``."""
+        return self.count_all_bytes(self._str_terms(terms, exclude))[0]
+
     @property
     def entry_counts(self) -> typing.Dict[int, int]:
         """Extension: entries of every chunk this reader holds, keyed by the chunk's index in the index file."""

@@ -288,6 +288,9 @@ def _load() -> ctypes.CDLL:
         'pss_reader_search_anchored_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, pvp]),
         'pss_reader_search_anchored_ids_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, pvp]),
         'pss_reader_count_anchored_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, vp]),
+        'pss_reader_search_terms_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, u32, vp, pvp]),
+        'pss_reader_search_terms_ids_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, u32, vp, pvp]),
+        'pss_reader_count_terms_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, u32, vp, vp]),
         'pss_reader_chunk_entries': (ctypes.c_int, [vp, vp, vp, u64, ctypes.POINTER(u64)]),
         'pss_merge_packed': (ctypes.c_int, [u32, u64, vp, vp, vp, vp, vp, vp, vp, vp]),
         'pss_merge_packed_device': (ctypes.c_int, [i32, u32, u64, vp, vp, vp, vp, vp, vp, vp, vp]),

@@ -60,7 +60,7 @@ struct pss_reader::Part {
     std::condition_variable cv;
     // mailbox: the caller fills the job and raises `pending`; the worker clears it when `rc` / `res` / `err` are set
     bool pending = false, quit = false;
-    SearchRequest rq;                    // SEARCH_FULL / SEARCH_COUNTS / SEARCH_IDS, anchored or not
+    SearchRequest rq;                    // SEARCH_FULL / SEARCH_COUNTS / SEARCH_IDS; plain, anchored or all-terms
     int rc = 0;
     HostResult res;
     std::string err;
@@ -227,7 +227,7 @@ int reader_batch(pss_reader *r, SearchRequest rq, HostResult *res)
     PSS_TRY(reader_sync_descs(r));
     if (rq.mode == SEARCH_IDS) PSS_TRY(reader_ensure_lines(r));
     rq.sa_order = r->order_sa;
-    rq.low_latency = r->low_latency && rq.mode == SEARCH_FULL && !rq.anchors;
+    rq.low_latency = r->low_latency && rq.mode == SEARCH_FULL && !rq.anchors && !rq.group_offsets;
     rq.chunk_hits = rq.mode == SEARCH_DEVICE ? nullptr : reader_hits_buffer(r);     // (device results have never fed the residency manager)
     PSS_TRY(search_batch_device(r->ctx, r->d_descs, r->d_lines, (uint32_t)r->chunks.size(), rq, res, &r->last));
     reader_note_route(r);
@@ -662,10 +662,11 @@ extern "C" int pss_reader_open_multi(const char *path, const int32_t *devices, i
 namespace {
 
 // One batch over the parts of a multi-device reader: every worker answers for its chunks, the caller for part 0;
-// then the per-part results are merged query-major, part-major inside a query (pss_merge_packed's order).
+// then the per-part results are merged query-major, part-major inside a query (pss_merge_packed's order).  The "queries"
+// of the merge are the rows of the results: the groups of an all-terms batch.
 int multi_batch(pss_reader *r, const SearchRequest &rq, HostResult *out)
 {
-    const uint32_t nq = rq.nq;
+    const uint32_t nq = rq.rows();
     std::lock_guard<std::mutex> batch(r->multi_mu);
     const auto t0 = std::chrono::steady_clock::now();
     const size_t G = r->parts.size();
@@ -800,13 +801,13 @@ int reader_batch_result(pss_reader *r, const SearchRequest &rq, pss_result **out
     return PSS_OK;
 }
 
-// The counts of a batch (rq.mode is set here) into the caller's nq counters.
+// The counts of a batch (rq.mode is set here) into the caller's counters, one per row of the result.
 int reader_batch_counts(pss_reader *r, SearchRequest rq, uint64_t *counts)
 {
     rq.mode = SEARCH_COUNTS;
     HostResult res;
     const int rc = reader_batch(r, rq, &res);
-    if (rc == PSS_OK && rq.nq) memcpy(counts, res.qcount, (size_t)rq.nq * sizeof(uint64_t));
+    if (rc == PSS_OK && rq.rows()) memcpy(counts, res.qcount, (size_t)rq.rows() * sizeof(uint64_t));
     res.release();
     return rc;
 }
@@ -1254,6 +1255,87 @@ extern "C" int pss_reader_count_anchored_batch(pss_reader *r, const uint8_t *qby
     return guarded([&]() -> int {
         PSS_TRY(anchored_args(r, "pss_reader_count_anchored_batch", qoffsets, nq, anchors, !nq || counts));
         return reader_batch_counts(r, SearchRequest{qbytes, qoffsets, nq, SEARCH_COUNTS, anchors}, counts);
+    });
+}
+
+// ---- all-terms search (all_terms_impl.h) -------------------------------------------------------------------------
+
+namespace {
+
+// The argument checks of the three all-terms calls (out_ok: the call's own output argument is usable).
+int terms_args(const pss_reader *r, const char *who, const uint8_t *tbytes, const uint64_t *toffsets, uint32_t nterms,
+               const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *exclude, bool out_ok)
+{
+    if (!out_ok || !group_offsets || (nterms && (!tbytes || !toffsets || !exclude))) {
+        set_error("%s: bad arguments", who);
+        return PSS_EINVAL;
+    }
+    for (uint32_t t = 0; t < nterms; ++t) {
+        if (toffsets[t + 1] <= toffsets[t]) {
+            set_error("%s: term %u is empty (every entry contains the empty term: leave it out)", who, t);
+            return PSS_EINVAL;
+        }
+        if (exclude[t] > 1) {
+            set_error("%s: exclude[%u] = %u (0 = the entry must contain the term, 1 = it must not)", who, t, (unsigned)exclude[t]);
+            return PSS_EINVAL;
+        }
+    }
+    if (group_offsets[0] != 0 || group_offsets[ngroups] != nterms) {
+        set_error("%s: the group offsets run from %llu to %llu, not from 0 to the %u terms", who, (unsigned long long)group_offsets[0],
+                  (unsigned long long)group_offsets[ngroups], nterms);
+        return PSS_EINVAL;
+    }
+    for (uint32_t g = 0; g < ngroups; ++g) {
+        if (group_offsets[g + 1] < group_offsets[g] || group_offsets[g + 1] > nterms) {
+            set_error("%s: the group offsets decrease or pass the %u terms at group %u", who, nterms, g);
+            return PSS_EINVAL;
+        }
+        bool include = false;
+        for (uint64_t t = group_offsets[g]; t < group_offsets[g + 1] && !include; ++t) include = exclude[t] == 0;
+        if (!include) {
+            set_error("%s: group %u has no include term (\"everything except\" is not a search)", who, g);
+            return PSS_EINVAL;
+        }
+    }
+    if (!r) {                   // (last, as pss.h says: a malformed batch is reported as such with or without a reader)
+        set_error("%s: bad arguments (no reader)", who);
+        return PSS_EINVAL;
+    }
+    return PSS_OK;
+}
+
+SearchRequest terms_request(const uint8_t *tbytes, const uint64_t *toffsets, uint32_t nterms, const uint64_t *group_offsets,
+                            uint32_t ngroups, const uint8_t *exclude, SearchMode mode)
+{
+    return SearchRequest{tbytes, toffsets, nterms, mode, nullptr, group_offsets, ngroups, exclude};
+}
+
+}  // namespace
+
+extern "C" int pss_reader_search_terms_batch(pss_reader *r, const uint8_t *tbytes, const uint64_t *toffsets, uint32_t nterms,
+                                             const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *exclude, pss_result **out)
+{
+    return guarded([&]() -> int {
+        PSS_TRY(terms_args(r, "pss_reader_search_terms_batch", tbytes, toffsets, nterms, group_offsets, ngroups, exclude, out != nullptr));
+        return reader_batch_result(r, terms_request(tbytes, toffsets, nterms, group_offsets, ngroups, exclude, SEARCH_FULL), out);
+    });
+}
+
+extern "C" int pss_reader_search_terms_ids_batch(pss_reader *r, const uint8_t *tbytes, const uint64_t *toffsets, uint32_t nterms,
+                                                 const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *exclude, pss_result **out)
+{
+    return guarded([&]() -> int {
+        PSS_TRY(terms_args(r, "pss_reader_search_terms_ids_batch", tbytes, toffsets, nterms, group_offsets, ngroups, exclude, out != nullptr));
+        return reader_batch_result(r, terms_request(tbytes, toffsets, nterms, group_offsets, ngroups, exclude, SEARCH_IDS), out);
+    });
+}
+
+extern "C" int pss_reader_count_terms_batch(pss_reader *r, const uint8_t *tbytes, const uint64_t *toffsets, uint32_t nterms,
+                                            const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *exclude, uint64_t *counts)
+{
+    return guarded([&]() -> int {
+        PSS_TRY(terms_args(r, "pss_reader_count_terms_batch", tbytes, toffsets, nterms, group_offsets, ngroups, exclude, !ngroups || counts));
+        return reader_batch_counts(r, terms_request(tbytes, toffsets, nterms, group_offsets, ngroups, exclude, SEARCH_COUNTS), counts);
     });
 }
 

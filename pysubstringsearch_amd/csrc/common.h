@@ -126,7 +126,7 @@ struct DeviceCtx {
     int device = -1;
     hipStream_t stream = nullptr;
     int num_cus = 256;
-    static constexpr int kSlots = 56;
+    static constexpr int kSlots = 57;
     DevBuf slot[kSlots];
     static constexpr size_t kPinnedBytes = (size_t)640 << 10;   // 64 KiB of counters / small tables / query staging, 64 KiB of
                                                                 // result bytes, 512 KiB of entry records (search.hip, SM_OFF_*)
@@ -248,7 +248,7 @@ int get_ctx(int device, DeviceCtx **out);
 // The context of the BUILDER side of the same device (pss_sa_build*, the Writer's builder threads): its own lock, stream,
 // pinned scratch and workspace slots (round 5).  With one context per device a Reader waited for a whole build (9 .. 131 ms)
 // whenever a Writer shared its GPU, and a gather over RCCL held up every build; the two sides never touch each other's
-// slots (sa_build.hip 0-9, 26-49; search.hip 10-23, 28, 46, 47, 50-54; the Writer 24, 25), so they need not share a lock.
+// slots (sa_build.hip 0-9, 26-49; search.hip 10-23, 28, 46, 47, 50-54, 56; the Writer 24, 25), so they need not share a lock.
 int get_build_ctx(int device, DeviceCtx **out);
 // Frees every workspace slot of every context (memory pressure relief).
 void trim_all();

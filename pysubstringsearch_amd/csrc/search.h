@@ -82,6 +82,12 @@ struct SearchRequest {
     // entries that start with, end with or equal the pattern instead of entries that contain it.  Modes FULL, COUNTS and IDS;
     // always the general pipeline, one hit per entry, so sa_order has nothing to order.
     const uint8_t *anchors = nullptr;
+    // group_offsets (ngroups + 1 entries into the nq patterns, which are then TERMS) and exclude (nq flags, 0 or 1, validated by
+    // the caller like the offsets): the all-terms search of all_terms_impl.h -- per group the entries that contain every include
+    // term and no exclude term.  The result's rows are the groups.  Modes FULL, COUNTS and IDS; not with anchors; always the
+    // general pipeline, in the plain search's order for each pair's driver term, so sa_order has no say.
+    const uint64_t *group_offsets = nullptr; uint32_t ngroups = 0; const uint8_t *exclude = nullptr;
+    uint32_t rows() const { return group_offsets ? ngroups : nq; }     // rows of the result: queries, or groups of terms
     bool low_latency = false;            // one query through the resident kernel when it fits (an unanchored SEARCH_FULL batch only)
     // sa_order: the entries of one (query, chunk) pair come out in the reference's order -- suffix-array order of the FIRST hit
     // inside each entry (src/lib.rs:262-276: the hits are walked in suffix-array order and an entry is pushed when its line

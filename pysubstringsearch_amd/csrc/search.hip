@@ -1521,7 +1521,7 @@ constexpr size_t SM_ARENA_BYTES = SM_ARENA_RHDR + 64;
 #error "search.hip is written for gfx950 (MI355X): the fused search kernels keep ~72 KiB of LDS per workgroup (160 KiB per CU there; gfx90a / gfx942 stop at 64 KiB)"
 #endif
 
-enum SSlot { Q_ORD_K0 = 50, Q_ORD_K1, Q_ORD_V0, Q_ORD_V1, Q_ORD_WORK, Q_BYTES = 10, Q_OFF, Q_LO, Q_CNT, Q_HITOFF, Q_START, Q_LEN, Q_EIDX, Q_BOFF, Q_ENTOFF, Q_OUT, Q_SMALL, Q_QCOUNT, Q_ANCHOR, Q_ARENA = 28, Q_HEAT = 46, Q_LINE_TMP = 47 };
+enum SSlot { Q_ORD_K0 = 50, Q_ORD_K1, Q_ORD_V0, Q_ORD_V1, Q_ORD_WORK, Q_BYTES = 10, Q_OFF, Q_LO, Q_CNT, Q_HITOFF, Q_START, Q_LEN, Q_EIDX, Q_BOFF, Q_ENTOFF, Q_OUT, Q_SMALL, Q_QCOUNT, Q_ANCHOR, Q_ARENA = 28, Q_HEAT = 46, Q_LINE_TMP = 47, Q_TERMS = 56 };
 
 void HostResult::release()
 {
@@ -1724,6 +1724,7 @@ static int resident_query(DeviceCtx *ctx, const ChunkDesc *d_chunks, u32 nc, con
 
 #include "line_index_impl.h"
 #include "anchored_impl.h"
+#include "all_terms_impl.h"
 
 // Suffix-array hits of the batch per chunk (pair p = query p / nc on chunk p % nc): one workgroup per chunk.
 __global__ __launch_bounds__(256) void chunk_hits_kernel(const u32 *cnt, u64 nq, u32 nc, u64 *out)
@@ -1741,7 +1742,8 @@ __global__ __launch_bounds__(256) void chunk_hits_kernel(const u32 *cnt, u64 nq,
 
 // ---- host driver of one batch -------------------------------------------------------------------------------------
 // search_batch_device reads top to bottom: empty batch -> stage_queries -> run_fused? -> launch_interval -> run_mid? ->
-// run_general -> finish.  The stages share one Batch: the request normalised into the few booleans they read, the
+// pick_drivers (an all-terms batch) -> run_general -> finish.
+// The stages share one Batch: the request normalised into the few booleans they read, the
 // workspace every route needs, the timing events and the two outputs.
 namespace {
 
@@ -1755,11 +1757,15 @@ struct Batch {
     pss_search_stats *st;
     const SearchKnobs &knobs;
     const u32 nq, nc;
-    const u64 nvq;                      // (query, chunk) pairs
+    const u64 nvq;                      // (query, chunk) pairs: what the interval search runs over
+    // An all-terms batch (all_terms_impl.h) has a second pair space: its nq queries are terms, its result rows are the ng
+    // groups, and everything from the first scan on runs over (group, chunk) pairs.  For every other batch the two agree.
+    const u32 nrow;                     // rows of the result: groups of an all-terms batch, else queries
+    const u64 nrp;                      // (row, chunk) pairs: what the scans, the hit kernels and the emit kernels run over
     u64 qtotal;                         // bytes of the queries as they are searched (an anchored batch: rewritten)
     size_t off_bytes;
     // the request, normalised once: nothing below asks for a mode again
-    bool counts, device, ids, anchored, sa_order;
+    bool counts, device, ids, anchored, terms, sa_order;
     bool tiny;                          // queries and offsets fit the 16 KiB of the pinned scratch
     bool fused_ok, resident_ok, mid_ok; // routes this batch may take (each may still overflow into the next)
     // host copy of queries, offsets and anchor flags (stage_queries)
@@ -1768,10 +1774,15 @@ struct Batch {
     bool h_padded = false;              // 32 zero bytes follow the queries
     std::vector<u8> own_q;              // an anchored batch too large for the staging
     std::vector<u64> own_off;
+    std::vector<u8> own_tflags;         // per-term flags of an all-terms batch
     // workspace of every route
     u8 *d_q = nullptr, *d_aflags = nullptr, *d_edge = nullptr;
     u64 *d_qoff = nullptr, *d_hitoff = nullptr, *d_partial = nullptr, *d_total = nullptr, *d_qcount = nullptr, *h_small = nullptr;
     u32 *d_lo = nullptr, *d_cnt = nullptr;
+    u32 *p_lo = nullptr, *p_cnt = nullptr;          // interval and hits per (row, chunk) pair: d_lo / d_cnt, or the drivers'
+    u64 *d_goff = nullptr;                          // all-terms batch: group offsets, term flags, driver term per group pair
+    u8 *d_tflags = nullptr;
+    u32 *d_gdrv = nullptr;
     // ... and of the mid and the general pipeline, sized by each: entry bounds per hit, the scans over them, the result
     u32 *d_start = nullptr, *d_len = nullptr;
     u64 *d_eidx = nullptr, *d_boff = nullptr, *d_entoff = nullptr;
@@ -1783,18 +1794,20 @@ struct Batch {
     Batch(DeviceCtx *c, const ChunkDesc *chunks, const LineDesc *lines, u32 nchunks, const SearchRequest &r, HostResult *out,
           pss_search_stats *stats)
         : ctx(c), s(c->stream), d_chunks(chunks), d_lines(lines), rq(r), res(out), st(stats), knobs(search_knobs()), nq(r.nq),
-          nc(nchunks), nvq((u64)r.nq * nchunks), e0(c->search_ev[0]), e1(c->search_ev[1]), e2(c->search_ev[2])
+          nc(nchunks), nvq((u64)r.nq * nchunks), nrow(r.rows()), nrp((u64)r.rows() * nchunks), e0(c->search_ev[0]), e1(c->search_ev[1]), e2(c->search_ev[2])
     {
         counts = rq.mode == SEARCH_COUNTS;
         device = rq.mode == SEARCH_DEVICE;
         ids = rq.mode == SEARCH_IDS;
         anchored = rq.anchors != nullptr;
-        sa_order = rq.sa_order && !counts && !anchored;     // (counts do not depend on the order; one hit per entry has one order)
+        terms = rq.group_offsets != nullptr;
+        // (counts do not depend on the order; one hit per entry has one order; an all-terms batch keeps its driver's text order)
+        sa_order = rq.sa_order && !counts && !anchored && !terms;
         // (an anchored batch searches its rewritten queries: a newline in front of and / or behind every pattern)
         qtotal = anchored ? anchored_query_bytes(rq.qoffsets, nq, rq.anchors) : rq.qoffsets[nq];
         off_bytes = ((size_t)nq + 1) * 8;
         tiny = !anchored && qtotal + 32 <= 8192 && off_bytes <= 8192;
-        const bool plain = !anchored && !sa_order;          // entries that contain the pattern, in text order
+        const bool plain = !anchored && !terms && !sa_order;    // entries that contain the pattern, in text order
         fused_ok = plain && rq.mode == SEARCH_FULL && tiny && nvq <= SM_MAX_VQ && !knobs.no_small_path;
         for (u32 i = 0; fused_ok && i < nq; ++i) fused_ok = rq.qoffsets[i + 1] - rq.qoffsets[i] <= SM_MAX_PLEN;
         resident_ok = fused_ok && rq.low_latency && nq == 1 && nvq <= SM_BLOCK_MAX_VQ && !knobs.no_block_path;
@@ -1807,7 +1820,7 @@ struct Batch {
         p = ctx->slot[which].as<T>();
         return PSS_OK;
     }
-    int stage_queries(), run_fused(bool *served), launch_interval(), run_mid(bool *done), run_general(), finish();
+    int stage_queries(), run_fused(bool *served), launch_interval(), run_mid(bool *done), pick_drivers(), run_general(), finish();
     int sa_order_hits(u32 grid, u64 H);
     int download_result(u64 E, u64 B, const u64 *d_starts, const u8 *d_bytes, bool via_stage);
     void leave_on_device(const u64 *d_starts, const u8 *d_bytes), set_totals(u64 hits, u64 kept, u64 E, u64 B);
@@ -1843,10 +1856,12 @@ int Batch::stage_queries()
     PSS_TRY(take(Q_OFF, off_bytes, d_qoff));
     PSS_TRY(take(Q_LO, nvq * 4, d_lo));
     PSS_TRY(take(Q_CNT, nvq * 4, d_cnt));
-    PSS_TRY(take(Q_HITOFF, (nvq + 1) * 8, d_hitoff));
+    PSS_TRY(take(Q_HITOFF, (std::max(nvq, nrp) + 1) * 8, d_hitoff));
     PSS_TRY(take(Q_SMALL, SC_MAX_BLOCKS * 8 + 256, d_partial));          // scan partials, totals, MidState
-    PSS_TRY(take(Q_QCOUNT, (size_t)nq * 8, d_qcount));
+    PSS_TRY(take(Q_QCOUNT, (size_t)std::max(nq, nrow) * 8, d_qcount));
     d_total = d_partial + SC_MAX_BLOCKS;
+    p_lo = d_lo;
+    p_cnt = d_cnt;
     h_small = static_cast<u64 *>(ctx->pinned);
     t_begin = std::chrono::steady_clock::now();
     const size_t q_room = round_up(qtotal + 32, 64), o_room = round_up(off_bytes, 64);
@@ -1881,6 +1896,10 @@ int Batch::stage_queries()
     h_off = hq ? ho : rq.qoffsets;
     h_flags = hf;
     h_padded = hq != nullptr;
+    if (terms) {
+        own_tflags.resize(nq);
+        terms_flags(rq.qbytes, rq.qoffsets, nq, rq.exclude, own_tflags.data());
+    }
     return PSS_OK;
 }
 
@@ -2007,7 +2026,7 @@ void Batch::leave_on_device(const u64 *d_starts, const u8 *d_bytes)
 // of the pinned pool when it is large.
 int Batch::download_result(u64 E, u64 B, const u64 *d_starts, const u8 *d_bytes, bool via_stage)
 {
-    const size_t cnt_bytes = (size_t)nq * 8;
+    const size_t cnt_bytes = (size_t)nrow * 8;
     PSS_TRY(alloc_host_result(res, E, B, !via_stage && !knobs.no_pinned_results));
     u8 *to_off = reinterpret_cast<u8 *>(res->offsets), *to_bytes = res->bytes, *to_cnt = reinterpret_cast<u8 *>(res->qcount);
     const bool staged = via_stage && round_up(E * 8, 64) + round_up(B, 64) + cnt_bytes <= DeviceCtx::kStageR && !knobs.no_search_stage;
@@ -2107,20 +2126,37 @@ int Batch::sa_order_hits(u32 grid, u64 H)
     return PSS_OK;
 }
 
+// All-terms batch: from the term pairs to the group pairs.  Group offsets and term flags go up, and one lane per (group,
+// chunk) pair picks the pair's driver term; from here on the pipeline runs over the drivers' intervals.
+int Batch::pick_drivers()
+{
+    const size_t goff_room = round_up(((size_t)nrow + 1) * 8, 64), flag_room = round_up((size_t)nq, 64);
+    PSS_TRY(take(Q_TERMS, goff_room + flag_room + nrp * 12, d_goff));
+    d_tflags = reinterpret_cast<u8 *>(d_goff) + goff_room;
+    d_gdrv = reinterpret_cast<u32 *>(d_tflags + flag_room);
+    p_lo = d_gdrv + nrp;
+    p_cnt = p_lo + nrp;
+    PSS_HIP(hipMemcpyAsync(d_goff, rq.group_offsets, ((size_t)nrow + 1) * 8, hipMemcpyHostToDevice, s));
+    PSS_HIP(hipMemcpyAsync(d_tflags, own_tflags.data(), nq, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(terms_driver_kernel, dim3((u32)((nrp + 255) / 256)), dim3(256), 0, s, nc, d_goff, d_tflags, d_lo, d_cnt, nrp,
+                       d_gdrv, p_lo, p_cnt);
+    return PSS_OK;
+}
+
 // General pipeline: every size comes down to the host before what it sizes is reserved -- hits, then kept hits (entries),
 // then bytes.
 int Batch::run_general()
 {
     st->route |= PSS_ROUTE_GENERAL | (sa_order ? PSS_ROUTE_SA_ORDER : 0u) | (counts ? PSS_ROUTE_COUNTS : 0u) |
                    (anchored ? PSS_ROUTE_ANCHORED : 0u);
-    PSS_TRY(device_excl_scan(ctx, InU32{d_cnt}, nvq, d_partial, d_total, d_hitoff));
+    PSS_TRY(device_excl_scan(ctx, InU32{p_cnt}, nrp, d_partial, d_total, d_hitoff));
     PSS_HIP(hipMemcpyAsync(h_small, d_total, 8, hipMemcpyDeviceToHost, s));
     PSS_HIP(hipStreamSynchronize(s));
     const u64 H = h_small[0];
     if (H == 0) {
         PSS_HIP(hipEventRecord(e2, s));
         if (device) {
-            PSS_HIP(hipMemsetAsync(d_qcount, 0, (size_t)nq * 8, s));
+            PSS_HIP(hipMemsetAsync(d_qcount, 0, (size_t)nrow * 8, s));
             leave_on_device(nullptr, nullptr);
         }
         PSS_HIP(hipStreamSynchronize(s));
@@ -2137,19 +2173,26 @@ int Batch::run_general()
     if (sa_order)
         PSS_TRY(sa_order_hits(grid, H));
     else if (anchored)
-        hipLaunchKernelGGL(anchored_hits_kernel, dim3(grid), dim3(256), 0, s, d_chunks, nc, d_aflags, nvq, d_lo, d_edge,
+        hipLaunchKernelGGL(anchored_hits_kernel, dim3(grid), dim3(256), 0, s, d_chunks, nc, d_aflags, nrp, p_lo, d_edge,
                            d_hitoff, H, d_start, d_len);
-    else
-        hipLaunchKernelGGL(hit_lines_kernel, dim3(grid), dim3(256), 0, s, d_chunks, nc, d_q, d_qoff, nvq, d_lo,
+    else if (terms) {
+        // candidates: the entries that hold the pair's driver term; then every candidate against the group's other terms
+        hipLaunchKernelGGL(terms_hits_kernel, dim3(grid), dim3(256), 0, s, d_chunks, nc, d_q, d_qoff, d_gdrv, nrp, p_lo, d_hitoff, H,
+                           d_start, d_len);
+        const u32 vgrid = (u32)std::min<u64>((u64)ctx->num_cus * 16, (H * TG + 255) / 256);
+        hipLaunchKernelGGL(terms_verify_kernel, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, d_q, d_qoff, d_goff, d_tflags, d_cnt,
+                           d_gdrv, nrp, d_hitoff, H, d_start, d_len);
+    } else
+        hipLaunchKernelGGL(hit_lines_kernel, dim3(grid), dim3(256), 0, s, d_chunks, nc, d_q, d_qoff, nrp, p_lo,
                            d_hitoff, H, (const MidState *)nullptr, d_start, d_len);
     PSS_TRY(device_excl_scan(ctx, InKept{d_len}, H, d_partial, d_total, d_eidx));
     PSS_HIP(hipMemcpyAsync(h_small, d_total, 8, hipMemcpyDeviceToHost, s));
     if (counts) {
         // entries per query without materialising one: interval search, dedupe flags, two scans
-        hipLaunchKernelGGL(query_counts_kernel, dim3((nq + 255) / 256), dim3(256), 0, s, nc, nq, d_hitoff, d_eidx,
+        hipLaunchKernelGGL(query_counts_kernel, dim3((nrow + 255) / 256), dim3(256), 0, s, nc, nrow, d_hitoff, d_eidx,
                            d_qcount, (const MidState *)nullptr);
         PSS_HIP(hipEventRecord(e2, s));
-        PSS_HIP(hipMemcpyAsync(res->qcount, d_qcount, (size_t)nq * 8, hipMemcpyDeviceToHost, s));
+        PSS_HIP(hipMemcpyAsync(res->qcount, d_qcount, (size_t)nrow * 8, hipMemcpyDeviceToHost, s));
         PSS_HIP(hipStreamSynchronize(s));
         PSS_TRY(empty_offsets(res));
         set_totals(H, h_small[0], 0, 0);
@@ -2164,12 +2207,12 @@ int Batch::run_general()
     PSS_TRY(take(Q_ENTOFF, (E + 1) * 8, d_entoff));
     PSS_TRY(take(Q_OUT, B + 16, d_out));
     if (ids)
-        hipLaunchKernelGGL(emit_ids_kernel, dim3(grid), dim3(256), 0, s, d_chunks, d_lines, nc, nvq, d_hitoff, H, d_start, d_len,
+        hipLaunchKernelGGL(emit_ids_kernel, dim3(grid), dim3(256), 0, s, d_chunks, d_lines, nc, nrp, d_hitoff, H, d_start, d_len,
                            d_eidx, d_entoff, reinterpret_cast<u64 *>(d_out));
     else
-        hipLaunchKernelGGL(emit_kernel, dim3(grid), dim3(256), 0, s, d_chunks, nc, nvq, d_hitoff, H,
+        hipLaunchKernelGGL(emit_kernel, dim3(grid), dim3(256), 0, s, d_chunks, nc, nrp, d_hitoff, H,
                            (const MidState *)nullptr, d_start, d_len, d_eidx, d_boff, d_entoff, d_out);
-    hipLaunchKernelGGL(query_counts_kernel, dim3((nq + 255) / 256), dim3(256), 0, s, nc, nq, d_hitoff, d_eidx,
+    hipLaunchKernelGGL(query_counts_kernel, dim3((nrow + 255) / 256), dim3(256), 0, s, nc, nrow, d_hitoff, d_eidx,
                        d_qcount, (const MidState *)nullptr);
     PSS_HIP(hipEventRecord(e2, s));
     if (device) {
@@ -2214,15 +2257,20 @@ int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, const LineDes
         set_error("search: an anchored batch takes the general pipeline to a host result");
         return PSS_EINVAL;
     }
+    if (rq.group_offsets && (rq.anchors || (rq.nq && !rq.exclude) || rq.mode == SEARCH_DEVICE || rq.low_latency)) {
+        set_error("search: an all-terms batch takes the general pipeline to a host result, and its terms are not anchored");
+        return PSS_EINVAL;
+    }
+    const u32 rows = rq.rows();
     memset(st, 0, sizeof *st);
-    st->queries = rq.nq;
-    res->nq = rq.nq;
-    res->qcount = (u64 *)calloc(rq.nq ? rq.nq : 1, sizeof(u64));
+    st->queries = rows;
+    res->nq = rows;
+    res->qcount = (u64 *)calloc(rows ? rows : 1, sizeof(u64));
     res->offsets = nullptr;
     res->bytes = nullptr;
     res->n_entries = 0;
     if (!res->qcount) return PSS_ENOMEM;
-    if (rq.nq == 0 || nc == 0) return empty_batch(ctx, rq, res);
+    if (rows == 0 || rq.nq == 0 || nc == 0) return empty_batch(ctx, rq, res);
 
     Batch b(ctx, d_chunks, d_lines, nc, rq, res, st);       // the request, normalised
     PSS_TRY(b.stage_queries());
@@ -2236,6 +2284,9 @@ int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, const LineDes
         bool done = false;
         PSS_TRY(b.run_mid(&done));
         if (done) return b.finish();
+    }
+    if (b.terms) {
+        PSS_TRY(b.pick_drivers());
     }
     PSS_TRY(b.run_general());
     return b.finish();
