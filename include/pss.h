@@ -516,6 +516,51 @@ int pss_reader_search_terms_ids_batch(pss_reader *r, const uint8_t *tbytes, cons
 /* counts[g] = entries group g matches; nothing but ngroups counters comes down */
 int pss_reader_count_terms_batch(pss_reader *r, const uint8_t *tbytes, const uint64_t *toffsets, uint32_t nterms,
                                  const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *exclude, uint64_t *counts);
+/*
+ * Wildcard search (no reference counterpart): which entries hold these pieces IN THIS ORDER -- SQL's LIKE 'GET %/admin% 500',
+ * a shell glob whose only wildcard is `*`.  The batch holds ngroups SEQUENCE GROUPS.  Group g is the ordered list of the
+ * k >= 1 non-empty SEGMENTS group_offsets[g] .. group_offsets[g + 1] of the nsegs segments packed in sbytes / soffsets (as
+ * queries are everywhere), s_0 .. s_{k-1}, and the anchor byte anchors[g]: 0, PSS_ANCHOR_START, PSS_ANCHOR_END or both.
+ * An entry is the bytes [start, end) of a chunk's text, end = its closing 0x0A or the length n of the text when none
+ * follows; the last byte of an unterminated last entry TAKES PART in the match, exactly as in the all-terms search,
+ * although the text handed out loses it.  The entry matches the group when positions p_0 < p_1 < .. < p_{k-1} exist with
+ *   entry[p_j, p_j + |s_j|) == s_j                for every j,
+ *   p_{j+1} >= p_j + |s_j|                        in order, no overlap,
+ *   p_0 == start                                  when PSS_ANCHOR_START is set,
+ *   p_{k-1} + |s_{k-1}| == end                    when PSS_ANCHOR_END is set.
+ * As a glob:  0: *s0*s1*..*   START: s0*s1*..*   END: *s0*..*sk-1   START | END: s0*..*sk-1.  With k = 1 and both anchors
+ * the entry equals s_0; with k = 1 and no anchor this is pss_reader_search_batch's "contains".  `a*a` does not match the
+ * entry `a`.  A segment that holds 0x0A makes its group match nothing.  Every entry appears at most once per group.
+ * *out has one row ("query") per GROUP, packed as the all-terms calls pack theirs (text or ids); counts[g] likewise.
+ * PSS_EINVAL (message in pss_last_error, *out / counts untouched): a group without a segment, an empty segment, an
+ * anchor byte with bits other than START | END, group offsets that do not start at 0, decrease or do not end at nsegs, a
+ * null group_offsets / anchors / out, a null sbytes / soffsets with nsegs > 0, a null reader (judged last, as for the
+ * all-terms calls).
+ * The search: the all-terms search up to its verify step -- the interval search over all (segment, chunk) pairs, per
+ * (group, chunk) pair the segment with the fewest occurrences (the lowest index on a tie) DRIVES, one candidate per entry
+ * that holds it -- then every candidate entry is walked once, left to right: the anchored segments are pinned to the
+ * entry's ends and each remaining segment takes its leftmost occurrence behind the one before it.  Leftmost-greedy is
+ * complete when `*` is the only wildcard.  A chunk that lacks any segment contributes nothing without a hit being looked at.
+ * Order: group-major, chunk-major inside a group; inside one (group, chunk) pair the plain search's default order for the
+ * driver segment, the same for the text and the id variant -- pss_reader_set_result_order has no effect.  A group of one
+ * segment and no anchor returns exactly what pss_reader_search_ids_batch returns for it under the default order.
+ * Whole-file, sharded and multi-device readers, and suffix arrays on the host tier, are served alike.
+ * pss_reader_last_stats: queries = groups, hits = the sum of the drivers' interval hits, entries = what is returned;
+ * route = GENERAL | the interval bits (| COUNTS for the count call) -- there is no bit of its own.  The id variant builds
+ * the line tables on first use, the other two allocate nothing for them.
+ * Out of scope: `?` and character classes; exclusions inside a group; driving an anchored first or last segment through
+ * the anchored search's "\n" + s rewrite (`a*` follows the occurrences of `a`, not the entries that start with it); the
+ * fused, resident and mid paths; a device-resident result; the multi-process gather over RCCL (dist.ShardedReader).
+ */
+/* packed entry text, one row per group */
+int pss_reader_search_seq_batch(pss_reader *r, const uint8_t *sbytes, const uint64_t *soffsets, uint32_t nsegs,
+                                const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *anchors, pss_result **out);
+/* u64 entry ids, packed as pss_reader_search_ids_batch packs them */
+int pss_reader_search_seq_ids_batch(pss_reader *r, const uint8_t *sbytes, const uint64_t *soffsets, uint32_t nsegs,
+                                    const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *anchors, pss_result **out);
+/* counts[g] = entries group g matches; nothing but ngroups counters comes down */
+int pss_reader_count_seq_batch(pss_reader *r, const uint8_t *sbytes, const uint64_t *soffsets, uint32_t nsegs,
+                               const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *anchors, uint64_t *counts);
 /* For the first `cap` resident chunks, in file order: index in the file and number of entries; *num = resident chunks. */
 int pss_reader_chunk_entries(pss_reader *r, uint64_t *chunk_index, uint64_t *entries, uint64_t cap, uint64_t *num);
 /*

@@ -26,7 +26,8 @@ try:   # C loop for result lists (csrc/pyglue.c); plain Python slicing if it was
 except ImportError:   # pragma: no cover
     _pssglue = None
 
-__all__ = ['Writer', 'Reader', 'PackedResult', 'IdResult', 'DeviceResult', 'device_count', 'default_devices', 'release_workspace', 'workspace_bytes']
+__all__ = ['Writer', 'Reader', 'PackedResult', 'IdResult', 'DeviceResult', 'device_count', 'default_devices', 'release_workspace', 'workspace_bytes',
+           'glob_parse', 'glob_escape']
 
 
 def device_count() -> int:
@@ -82,6 +83,53 @@ def _pack_queries(patterns: typing.Sequence[bytes]):
     if nq:
         np.cumsum(np.fromiter(map(len, patterns), dtype=np.uint64, count=nq), out=offs[1:])
     return b''.join(patterns), offs
+
+
+def glob_parse(pattern: bytes) -> typing.Tuple[typing.List[bytes], int]:
+    """``(segments, anchors)`` of a glob pattern as ``Reader.search_glob_ids_batch`` searches it (include/pss.h,
+    pss_reader_search_seq_batch).  ``*`` stands for any run of bytes, also none; ``\\`` takes the next byte literally
+    (``\\*``, ``\\\\``); adjacent ``*`` are one.  The anchors follow from the pattern's ends: no unescaped ``*`` in front sets
+    ``PSS_ANCHOR_START`` (1), none behind sets ``PSS_ANCHOR_END`` (2).  ``ValueError`` for a lone ``\\`` at the end and for a
+    pattern without a literal byte.  Pure Python: no device is touched."""
+    if not isinstance(pattern, (bytes, bytearray)):
+        raise TypeError(f'a glob pattern must be bytes, not {type(pattern).__name__}')
+    pattern = bytes(pattern)
+    segments: typing.List[bytes] = []
+    cur = bytearray()
+    first_star = last_star = False
+    i, n = 0, len(pattern)
+    while i < n:
+        c = pattern[i]
+        if c == 0x2A:                               # '*': closes the segment before it
+            if cur:
+                segments.append(bytes(cur))
+                cur = bytearray()
+            elif not segments:
+                first_star = True
+            last_star = True
+            i += 1
+            continue
+        if c == 0x5C:                               # '\\': the next byte as it is
+            if i + 1 >= n:
+                raise ValueError(f'glob pattern {pattern!r} ends in a lone backslash (write it as two)')
+            i += 1
+            c = pattern[i]
+        cur.append(c)
+        last_star = False
+        i += 1
+    if cur:
+        segments.append(bytes(cur))
+    if not segments:
+        raise ValueError(f"glob pattern {pattern!r} has no literal byte: '*' alone matches every entry (entry_counts counts "
+                         "them), the empty pattern the empty entries (search_exact(''))")
+    return segments, (0 if first_star else _ffi.ANCHOR_START) | (0 if last_star else _ffi.ANCHOR_END)
+
+
+def glob_escape(text: bytes) -> bytes:
+    """``text`` with every ``*`` and ``\\`` escaped: ``glob_parse(glob_escape(x)) == ([x], 3)`` for a non-empty ``x``."""
+    if not isinstance(text, (bytes, bytearray)):
+        raise TypeError(f'glob_escape takes bytes, not {type(text).__name__}')
+    return bytes(text).replace(b'\\', b'\\\\').replace(b'*', b'\\*')
 
 
 class Writer:
@@ -671,6 +719,82 @@ class Reader:
     def count_all(self, terms: typing.Sequence[str], exclude: typing.Sequence[str] = ()) -> int:
         """Extension: how many entries contain every one of ``terms`` and none of ``exclude``."""
         return self.count_all_bytes(self._str_terms(terms, exclude))[0]
+
+    @staticmethod
+    def _glob_args(patterns):
+        """(blob, segment offsets, group offsets, anchor bytes) of one batch of glob patterns (``glob_parse`` of each)."""
+        import numpy as np
+        if isinstance(patterns, (bytes, bytearray, str)):
+            raise TypeError(f"argument 'patterns': '{type(patterns).__name__}' object cannot be converted to a sequence of glob patterns")
+        segs: typing.List[bytes] = []
+        goff = [0]
+        anch: typing.List[int] = []
+        for g, pat in enumerate(patterns):
+            if not isinstance(pat, (bytes, bytearray)):
+                raise TypeError(f'pattern {g}: a glob pattern must be bytes, not {type(pat).__name__}')
+            parts, a = glob_parse(pat)
+            segs += parts
+            goff.append(len(segs))
+            anch.append(a)
+        blob, offs = _pack_queries(segs)
+        return blob, offs, np.array(goff, dtype=np.uint64), np.array(anch if anch else [0], dtype=np.uint8)
+
+    def search_glob_batch_packed(self, patterns: typing.Sequence[bytes]) -> 'PackedResult':
+        """Extension: per glob pattern (``glob_parse``: literal pieces and ``*``), the entries that hold the pieces IN
+        ORDER and without overlap -- the first at the entry's start unless the pattern begins with ``*``, the last at its
+        end unless it ends with one -- as a packed result like ``search_batch_packed``'s with one row per pattern.  Exact
+        bytes; every entry at most once per pattern; a piece holding a newline matches nothing.  On the device the rarest
+        piece of every (pattern, chunk) pair drives the search and each candidate entry is walked once, left to right
+        (include/pss.h, pss_reader_search_seq_batch).  ``set_result_order`` has no effect."""
+        import numpy as np
+        blob, offs, goff, anch = self._glob_args(patterns)
+        ng = len(goff) - 1
+        res = ctypes.c_void_p()
+        _ffi.check(_lib.pss_reader_search_seq_batch(self._handle(), blob, offs.ctypes.data, len(offs) - 1, goff.ctypes.data, ng,
+                                                    anch.ctypes.data, ctypes.byref(res)))
+        owner = _ResultOwner(res)      # the arrays below are views of the C result; it lives as long as they do
+        n = _lib.pss_result_num_entries(res)
+        counts = owner.view(_lib.pss_result_query_counts(res), ng, np.uint64)
+        offsets = owner.view(_lib.pss_result_offsets(res), n + 1, np.uint64)
+        data = owner.view(_lib.pss_result_bytes(res), int(offsets[n]), np.uint8)
+        return PackedResult(data, offsets, counts)
+
+    def search_glob_ids_batch(self, patterns: typing.Sequence[bytes]) -> 'IdResult':
+        """Extension: the ids (``search_ids_batch``) of the entries ``search_glob_batch_packed`` returns, in the same
+        order; ``counts[g]`` of them belong to pattern g."""
+        import numpy as np
+        blob, offs, goff, anch = self._glob_args(patterns)
+        ng = len(goff) - 1
+        res = ctypes.c_void_p()
+        _ffi.check(_lib.pss_reader_search_seq_ids_batch(self._handle(), blob, offs.ctypes.data, len(offs) - 1, goff.ctypes.data, ng,
+                                                        anch.ctypes.data, ctypes.byref(res)))
+        owner = _ResultOwner(res)
+        n = _lib.pss_result_num_entries(res)
+        counts = owner.view(_lib.pss_result_query_counts(res), ng, np.uint64)
+        ids = owner.view(_lib.pss_result_bytes(res), 8 * n, np.uint8).view(np.uint64)
+        ids.flags.writeable = False
+        return IdResult(ids, counts)
+
+    def count_glob_bytes(self, patterns: typing.Sequence[bytes]) -> typing.List[int]:
+        """Extension: how many entries each glob pattern matches; only the counters come back."""
+        import numpy as np
+        blob, offs, goff, anch = self._glob_args(patterns)
+        ng = len(goff) - 1
+        counts = np.zeros(max(ng, 1), dtype=np.uint64)
+        _ffi.check(_lib.pss_reader_count_seq_batch(self._handle(), blob, offs.ctypes.data, len(offs) - 1, goff.ctypes.data, ng,
+                                                   anch.ctypes.data, counts.ctypes.data))
+        return [int(c) for c in counts[:ng]]
+
+    def search_glob(self, s: str) -> typing.List[str]:
+        """Extension: the entries that match the glob pattern ``s`` (``*`` = any run of bytes, ``\\`` escapes)."""
+        p = self.search_glob_batch_packed([_utf8(s, 'pattern')])
+        data = p.data.tobytes()
+        o = p.offsets.tolist()
+        return [data[o[i]:o[i + 1]].decode('utf-8') for i in range(len(o) - 1)]
+
+    def count_glob(self, s: str) -> int:
+        """Extension: how many entries match the glob pattern ``s``."""
+        return self.count_glob_bytes([_utf8(s, 'pattern')])[0]
 
     @property
     def entry_counts(self) -> typing.Dict[int, int]:

@@ -149,6 +149,7 @@ ROUTES = {
 
 # Anchors of the anchored search (PSS_ANCHOR_* in include/pss.h): where in the entry the pattern must sit.
 ANCHORS = {'start': 1, 'end': 2, 'entry': 3}
+ANCHOR_START, ANCHOR_END = 1, 2
 
 
 class DeviceResult(ctypes.Structure):
@@ -291,6 +292,9 @@ def _load() -> ctypes.CDLL:
         'pss_reader_search_terms_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, u32, vp, pvp]),
         'pss_reader_search_terms_ids_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, u32, vp, pvp]),
         'pss_reader_count_terms_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, u32, vp, vp]),
+        'pss_reader_search_seq_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, u32, vp, pvp]),
+        'pss_reader_search_seq_ids_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, u32, vp, pvp]),
+        'pss_reader_count_seq_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, u32, vp, vp]),
         'pss_reader_chunk_entries': (ctypes.c_int, [vp, vp, vp, u64, ctypes.POINTER(u64)]),
         'pss_merge_packed': (ctypes.c_int, [u32, u64, vp, vp, vp, vp, vp, vp, vp, vp]),
         'pss_merge_packed_device': (ctypes.c_int, [i32, u32, u64, vp, vp, vp, vp, vp, vp, vp, vp]),

@@ -1339,6 +1339,84 @@ extern "C" int pss_reader_count_terms_batch(pss_reader *r, const uint8_t *tbytes
     });
 }
 
+// ---- wildcard search: segments in order (sequence_impl.h) --------------------------------------------------------
+
+namespace {
+
+// The argument checks of the three sequence calls (out_ok: the call's own output argument is usable).
+int seq_args(const pss_reader *r, const char *who, const uint8_t *sbytes, const uint64_t *soffsets, uint32_t nsegs,
+             const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *anchors, bool out_ok)
+{
+    if (!out_ok || !group_offsets || !anchors || (nsegs && (!sbytes || !soffsets))) {
+        set_error("%s: bad arguments", who);
+        return PSS_EINVAL;
+    }
+    for (uint32_t t = 0; t < nsegs; ++t)
+        if (soffsets[t + 1] <= soffsets[t]) {
+            set_error("%s: segment %u is empty (two wildcards in a row are one: leave it out)", who, t);
+            return PSS_EINVAL;
+        }
+    if (group_offsets[0] != 0 || group_offsets[ngroups] != nsegs) {
+        set_error("%s: the group offsets run from %llu to %llu, not from 0 to the %u segments", who, (unsigned long long)group_offsets[0],
+                  (unsigned long long)group_offsets[ngroups], nsegs);
+        return PSS_EINVAL;
+    }
+    for (uint32_t g = 0; g < ngroups; ++g) {
+        if (group_offsets[g + 1] < group_offsets[g] || group_offsets[g + 1] > nsegs) {
+            set_error("%s: the group offsets decrease or pass the %u segments at group %u", who, nsegs, g);
+            return PSS_EINVAL;
+        }
+        if (group_offsets[g + 1] == group_offsets[g]) {
+            set_error("%s: group %u has no segment (a pattern of wildcards alone is not a search)", who, g);
+            return PSS_EINVAL;
+        }
+        if (anchors[g] > (PSS_ANCHOR_START | PSS_ANCHOR_END)) {
+            set_error("%s: anchors[%u] = %u (0, PSS_ANCHOR_START = 1, PSS_ANCHOR_END = 2 or both)", who, g, (unsigned)anchors[g]);
+            return PSS_EINVAL;
+        }
+    }
+    if (!r) {                   // (last, as for the all-terms calls: a malformed batch is reported as such with or without a reader)
+        set_error("%s: bad arguments (no reader)", who);
+        return PSS_EINVAL;
+    }
+    return PSS_OK;
+}
+
+SearchRequest seq_request(const uint8_t *sbytes, const uint64_t *soffsets, uint32_t nsegs, const uint64_t *group_offsets,
+                          uint32_t ngroups, const uint8_t *anchors, SearchMode mode)
+{
+    return SearchRequest{sbytes, soffsets, nsegs, mode, nullptr, group_offsets, ngroups, nullptr, anchors};
+}
+
+}  // namespace
+
+extern "C" int pss_reader_search_seq_batch(pss_reader *r, const uint8_t *sbytes, const uint64_t *soffsets, uint32_t nsegs,
+                                           const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *anchors, pss_result **out)
+{
+    return guarded([&]() -> int {
+        PSS_TRY(seq_args(r, "pss_reader_search_seq_batch", sbytes, soffsets, nsegs, group_offsets, ngroups, anchors, out != nullptr));
+        return reader_batch_result(r, seq_request(sbytes, soffsets, nsegs, group_offsets, ngroups, anchors, SEARCH_FULL), out);
+    });
+}
+
+extern "C" int pss_reader_search_seq_ids_batch(pss_reader *r, const uint8_t *sbytes, const uint64_t *soffsets, uint32_t nsegs,
+                                               const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *anchors, pss_result **out)
+{
+    return guarded([&]() -> int {
+        PSS_TRY(seq_args(r, "pss_reader_search_seq_ids_batch", sbytes, soffsets, nsegs, group_offsets, ngroups, anchors, out != nullptr));
+        return reader_batch_result(r, seq_request(sbytes, soffsets, nsegs, group_offsets, ngroups, anchors, SEARCH_IDS), out);
+    });
+}
+
+extern "C" int pss_reader_count_seq_batch(pss_reader *r, const uint8_t *sbytes, const uint64_t *soffsets, uint32_t nsegs,
+                                          const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *anchors, uint64_t *counts)
+{
+    return guarded([&]() -> int {
+        PSS_TRY(seq_args(r, "pss_reader_count_seq_batch", sbytes, soffsets, nsegs, group_offsets, ngroups, anchors, !ngroups || counts));
+        return reader_batch_counts(r, seq_request(sbytes, soffsets, nsegs, group_offsets, ngroups, anchors, SEARCH_COUNTS), counts);
+    });
+}
+
 namespace {
 
 // ids[0 .. n) of ONE single-device reader: validation on the host (the reader knows every chunk's entry count once the

@@ -87,6 +87,11 @@ struct SearchRequest {
     // term and no exclude term.  The result's rows are the groups.  Modes FULL, COUNTS and IDS; not with anchors; always the
     // general pipeline, in the plain search's order for each pair's driver term, so sa_order has no say.
     const uint64_t *group_offsets = nullptr; uint32_t ngroups = 0; const uint8_t *exclude = nullptr;
+    // seq_anchors (ngroups values, PSS_ANCHOR_START | PSS_ANCHOR_END or 0, validated by the caller), together with group_offsets:
+    // the groups are ORDERED SEQUENCES of segments -- the wildcard search of sequence_impl.h: per group the entries that hold
+    // its segments left to right without overlap, the first at the entry's start and / or the last at its end when anchored.
+    // exclude is then unused and may be null.  Everything else as for an all-terms batch.
+    const uint8_t *seq_anchors = nullptr;
     uint32_t rows() const { return group_offsets ? ngroups : nq; }     // rows of the result: queries, or groups of terms
     bool low_latency = false;            // one query through the resident kernel when it fits (an unanchored SEARCH_FULL batch only)
     // sa_order: the entries of one (query, chunk) pair come out in the reference's order -- suffix-array order of the FIRST hit

@@ -1725,6 +1725,7 @@ static int resident_query(DeviceCtx *ctx, const ChunkDesc *d_chunks, u32 nc, con
 #include "line_index_impl.h"
 #include "anchored_impl.h"
 #include "all_terms_impl.h"
+#include "sequence_impl.h"
 
 // Suffix-array hits of the batch per chunk (pair p = query p / nc on chunk p % nc): one workgroup per chunk.
 __global__ __launch_bounds__(256) void chunk_hits_kernel(const u32 *cnt, u64 nq, u32 nc, u64 *out)
@@ -1742,7 +1743,7 @@ __global__ __launch_bounds__(256) void chunk_hits_kernel(const u32 *cnt, u64 nq,
 
 // ---- host driver of one batch -------------------------------------------------------------------------------------
 // search_batch_device reads top to bottom: empty batch -> stage_queries -> run_fused? -> launch_interval -> run_mid? ->
-// pick_drivers (an all-terms batch) -> run_general -> finish.
+// pick_drivers (an all-terms or a sequence batch) -> run_general -> finish.
 // The stages share one Batch: the request normalised into the few booleans they read, the
 // workspace every route needs, the timing events and the two outputs.
 namespace {
@@ -1766,6 +1767,7 @@ struct Batch {
     size_t off_bytes;
     // the request, normalised once: nothing below asks for a mode again
     bool counts, device, ids, anchored, terms, sa_order;
+    bool seq;                           // terms, and the groups are ordered sequences (sequence_impl.h)
     bool tiny;                          // queries and offsets fit the 16 KiB of the pinned scratch
     bool fused_ok, resident_ok, mid_ok; // routes this batch may take (each may still overflow into the next)
     // host copy of queries, offsets and anchor flags (stage_queries)
@@ -1781,7 +1783,7 @@ struct Batch {
     u32 *d_lo = nullptr, *d_cnt = nullptr;
     u32 *p_lo = nullptr, *p_cnt = nullptr;          // interval and hits per (row, chunk) pair: d_lo / d_cnt, or the drivers'
     u64 *d_goff = nullptr;                          // all-terms batch: group offsets, term flags, driver term per group pair
-    u8 *d_tflags = nullptr;
+    u8 *d_tflags = nullptr, *d_sanch = nullptr;       // (d_sanch: a sequence batch's anchor byte per group)
     u32 *d_gdrv = nullptr;
     // ... and of the mid and the general pipeline, sized by each: entry bounds per hit, the scans over them, the result
     u32 *d_start = nullptr, *d_len = nullptr;
@@ -1801,6 +1803,7 @@ struct Batch {
         ids = rq.mode == SEARCH_IDS;
         anchored = rq.anchors != nullptr;
         terms = rq.group_offsets != nullptr;
+        seq = terms && rq.seq_anchors != nullptr;
         // (counts do not depend on the order; one hit per entry has one order; an all-terms batch keeps its driver's text order)
         sa_order = rq.sa_order && !counts && !anchored && !terms;
         // (an anchored batch searches its rewritten queries: a newline in front of and / or behind every pattern)
@@ -1898,7 +1901,10 @@ int Batch::stage_queries()
     h_padded = hq != nullptr;
     if (terms) {
         own_tflags.resize(nq);
-        terms_flags(rq.qbytes, rq.qoffsets, nq, rq.exclude, own_tflags.data());
+        if (seq)
+            seq_flags(rq.qbytes, rq.qoffsets, nq, own_tflags.data());
+        else
+            terms_flags(rq.qbytes, rq.qoffsets, nq, rq.exclude, own_tflags.data());
     }
     return PSS_OK;
 }
@@ -2131,13 +2137,16 @@ int Batch::sa_order_hits(u32 grid, u64 H)
 int Batch::pick_drivers()
 {
     const size_t goff_room = round_up(((size_t)nrow + 1) * 8, 64), flag_room = round_up((size_t)nq, 64);
-    PSS_TRY(take(Q_TERMS, goff_room + flag_room + nrp * 12, d_goff));
+    const size_t anch_room = seq ? round_up((size_t)nrow, 64) : 0;        // (a sequence batch: one anchor byte per group)
+    PSS_TRY(take(Q_TERMS, goff_room + flag_room + anch_room + nrp * 12, d_goff));
     d_tflags = reinterpret_cast<u8 *>(d_goff) + goff_room;
-    d_gdrv = reinterpret_cast<u32 *>(d_tflags + flag_room);
+    d_sanch = d_tflags + flag_room;
+    d_gdrv = reinterpret_cast<u32 *>(d_sanch + anch_room);
     p_lo = d_gdrv + nrp;
     p_cnt = p_lo + nrp;
     PSS_HIP(hipMemcpyAsync(d_goff, rq.group_offsets, ((size_t)nrow + 1) * 8, hipMemcpyHostToDevice, s));
     PSS_HIP(hipMemcpyAsync(d_tflags, own_tflags.data(), nq, hipMemcpyHostToDevice, s));
+    if (seq) PSS_HIP(hipMemcpyAsync(d_sanch, rq.seq_anchors, nrow, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(terms_driver_kernel, dim3((u32)((nrp + 255) / 256)), dim3(256), 0, s, nc, d_goff, d_tflags, d_lo, d_cnt, nrp,
                        d_gdrv, p_lo, p_cnt);
     return PSS_OK;
@@ -2180,8 +2189,12 @@ int Batch::run_general()
         hipLaunchKernelGGL(terms_hits_kernel, dim3(grid), dim3(256), 0, s, d_chunks, nc, d_q, d_qoff, d_gdrv, nrp, p_lo, d_hitoff, H,
                            d_start, d_len);
         const u32 vgrid = (u32)std::min<u64>((u64)ctx->num_cus * 16, (H * TG + 255) / 256);
-        hipLaunchKernelGGL(terms_verify_kernel, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, d_q, d_qoff, d_goff, d_tflags, d_cnt,
-                           d_gdrv, nrp, d_hitoff, H, d_start, d_len);
+        if (seq)    // (a sequence batch: every candidate against the group's segments in order, the driver among them)
+            hipLaunchKernelGGL(seq_verify_kernel, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, d_q, d_qoff, d_goff, d_sanch, nrp,
+                               d_hitoff, H, d_start, d_len);
+        else
+            hipLaunchKernelGGL(terms_verify_kernel, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, d_q, d_qoff, d_goff, d_tflags, d_cnt,
+                               d_gdrv, nrp, d_hitoff, H, d_start, d_len);
     } else
         hipLaunchKernelGGL(hit_lines_kernel, dim3(grid), dim3(256), 0, s, d_chunks, nc, d_q, d_qoff, nrp, p_lo,
                            d_hitoff, H, (const MidState *)nullptr, d_start, d_len);
@@ -2257,7 +2270,7 @@ int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, const LineDes
         set_error("search: an anchored batch takes the general pipeline to a host result");
         return PSS_EINVAL;
     }
-    if (rq.group_offsets && (rq.anchors || (rq.nq && !rq.exclude) || rq.mode == SEARCH_DEVICE || rq.low_latency)) {
+    if (rq.group_offsets && (rq.anchors || (rq.nq && !rq.exclude && !rq.seq_anchors) || rq.mode == SEARCH_DEVICE || rq.low_latency)) {
         set_error("search: an all-terms batch takes the general pipeline to a host result, and its terms are not anchored");
         return PSS_EINVAL;
     }
