@@ -561,6 +561,56 @@ int pss_reader_search_seq_ids_batch(pss_reader *r, const uint8_t *sbytes, const 
 /* counts[g] = entries group g matches; nothing but ngroups counters comes down */
 int pss_reader_count_seq_batch(pss_reader *r, const uint8_t *sbytes, const uint64_t *soffsets, uint32_t nsegs,
                                const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *anchors, uint64_t *counts);
+/*
+ * Case-insensitive search (no reference counterpart): `grep -i` over the entries.  ASCII only: the bytes 0x41 .. 0x5A (A .. Z)
+ * are equivalent to 0x61 .. 0x7A (a .. z), and every other byte -- 0x80 .. 0xFF included, so no letter outside ASCII -- equals
+ * only itself; fold(b) maps A .. Z to a .. z.  An entry is the bytes [start, end) of a chunk's text, end = its closing 0x0A or
+ * the length n of the text when none follows; the last byte of an unterminated last entry TAKES PART in the match, exactly as
+ * in the all-terms and the wildcard search, although the text handed out loses it.  The entry matches pattern p when some m
+ * in start .. end - |p| has fold(text[m + i]) == fold(p[i]) for all i.  One row ("query") per pattern, packed as
+ * pss_reader_search_batch (text) and pss_reader_search_ids_batch (ids) pack theirs; every entry appears at most once per
+ * pattern.  A pattern that holds 0x0A matches nothing: a count of 0, not an error.
+ * PSS_EINVAL (message in pss_last_error, *out / counts untouched): an empty pattern (as an empty term is), offsets that do not
+ * start at 0 or that decrease, a null qbytes / qoffsets with nq > 0, a null out / counts, patterns whose expansion (below)
+ * holds more than the 2^32 - 1 terms an all-terms batch takes, a pattern of more than 2^32 - 1 bytes (a chunk has fewer), a
+ * null reader (judged last, as for the all-terms calls).
+ * The search: the suffix arrays are exact-byte, so the host expands.  The SEED of a pattern is its longest window that holds
+ * at most F = PSS_ICASE_SEED_LETTERS ASCII letters (1 .. 6, default 5), the leftmost on a tie; bytes that are no letters cost
+ * nothing (`user_id=12345678` seeds with `ser_id=12345678`).  The 2^f spellings of the seed (f <= F its letter count), in
+ * ASCENDING byte order -- upper case before lower, the first letter most significant -- are the terms of one group of an
+ * all-terms-shaped batch; the interval search answers every (spelling, chunk) pair, and the hits of a (pattern, chunk) pair
+ * are its spellings' intervals one behind the other: disjoint and ascending, so still in suffix-array order.  Every hit is
+ * verified on the device: the whole pattern around the seed occurrence under fold, then the entry in front of the match for
+ * an earlier folded occurrence -- the hit of an entry's LEFTMOST folded match stands for the entry, whatever mix of spellings
+ * the entry holds.  The answer is exact for every pattern length.  pss_icase_variants shows the expansion.
+ * Order: pattern-major, chunk-major inside a pattern; inside one (pattern, chunk) pair the suffix-array order of the seed's
+ * occurrence inside each entry's leftmost folded match, the same for the text and the id variant -- pss_reader_set_result_order
+ * has no effect.  A pattern without an ASCII letter returns exactly what pss_reader_search_ids_batch returns for it under the
+ * default order, order included.
+ * Whole-file, sharded and multi-device readers, and suffix arrays on the host tier, are served alike.
+ * pss_reader_last_stats: queries = patterns, hits = the sum of the spellings' interval hits -- the candidates --, entries =
+ * what is returned; route = GENERAL | the interval bits (| COUNTS for the count call) -- there is no bit of its own.  The id
+ * variant builds the line tables on first use, the other two allocate nothing for them.
+ * The limit: the candidates follow the occurrences of the folded SEED, not of the pattern -- a long pattern whose seed is a
+ * common word looks at every occurrence of that word.
+ * Out of scope: folding outside ASCII; case-insensitive anchors, all-terms and wildcard search; the fused, resident and mid
+ * paths (a case-insensitive batch always takes the general pipeline); a device-resident result; the multi-process gather over
+ * RCCL (dist.ShardedReader); walking only the spellings that are PRESENT, on the device (the blind enumeration probes up to
+ * 2^F mostly empty intervals per pattern and chunk: the price of reusing the interval kernels as they are); picking the rarer
+ * of two seeds per chunk.
+ */
+/* packed entry text, one row per pattern */
+int pss_reader_search_icase_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, pss_result **out);
+/* u64 entry ids, packed as pss_reader_search_ids_batch packs them */
+int pss_reader_search_icase_ids_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, pss_result **out);
+/* counts[q] = entries pattern q matches; nothing but nq counters comes down */
+int pss_reader_count_icase_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, uint64_t *counts);
+/* The expansion of ONE pattern, on the host: no reader, no GPU.  letters = the letters of the seed at most, 1 .. 6; <= 0 means
+ * the configured value (PSS_ICASE_SEED_LETTERS).  *seed_off / *seed_len = the seed's window inside the pattern, *count = its
+ * 2^f spellings; out (cap bytes, or NULL for the sizes alone) receives them back to back, *seed_len bytes each, ascending.
+ * PSS_EINVAL: an empty pattern, letters > 6, a null seed_off / seed_len / count, cap < *count * *seed_len. */
+int pss_icase_variants(const uint8_t *pat, uint64_t len, int32_t letters, uint8_t *out, uint64_t cap, uint32_t *seed_off,
+                       uint32_t *seed_len, uint32_t *count);
 /* For the first `cap` resident chunks, in file order: index in the file and number of entries; *num = resident chunks. */
 int pss_reader_chunk_entries(pss_reader *r, uint64_t *chunk_index, uint64_t *entries, uint64_t cap, uint64_t *num);
 /*

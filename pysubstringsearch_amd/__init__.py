@@ -27,7 +27,7 @@ except ImportError:   # pragma: no cover
     _pssglue = None
 
 __all__ = ['Writer', 'Reader', 'PackedResult', 'IdResult', 'DeviceResult', 'device_count', 'default_devices', 'release_workspace', 'workspace_bytes',
-           'glob_parse', 'glob_escape']
+           'glob_parse', 'glob_escape', 'icase_variants']
 
 
 def device_count() -> int:
@@ -130,6 +130,28 @@ def glob_escape(text: bytes) -> bytes:
     if not isinstance(text, (bytes, bytearray)):
         raise TypeError(f'glob_escape takes bytes, not {type(text).__name__}')
     return bytes(text).replace(b'\\', b'\\\\').replace(b'*', b'\\*')
+
+
+def icase_variants(pattern: bytes, letters: typing.Optional[int] = None) -> typing.Tuple[int, typing.List[bytes]]:
+    """``(seed_off, variants)`` of a pattern as ``Reader.search_icase_ids_batch`` searches it (include/pss.h,
+    pss_icase_variants): the SEED is the pattern's longest window with at most ``letters`` ASCII letters (1 .. 6; ``None`` =
+    the configured ``PSS_ICASE_SEED_LETTERS``, default 5), the leftmost on a tie, ``seed_off`` its offset in the pattern, and
+    ``variants`` its ``2**f`` spellings in ascending byte order.  Only the ASCII letters ``A-Z`` / ``a-z`` fold; every other
+    byte, ``0x80 .. 0xFF`` included, stands for itself.  ``ValueError`` for an empty pattern and for ``letters`` outside
+    1 .. 6.  Host only: no device is touched."""
+    if not isinstance(pattern, (bytes, bytearray)):
+        raise TypeError(f'a pattern must be bytes, not {type(pattern).__name__}')
+    if letters is not None and not 1 <= int(letters) <= 6:
+        raise ValueError(f'letters = {letters!r}: 1 .. 6, or None for PSS_ICASE_SEED_LETTERS')
+    pattern = bytes(pattern)
+    want = 0 if letters is None else int(letters)
+    off, ln, cnt = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+    _ffi.check(_lib.pss_icase_variants(pattern, len(pattern), want, None, 0, ctypes.byref(off), ctypes.byref(ln), ctypes.byref(cnt)))
+    buf = ctypes.create_string_buffer(max(1, ln.value * cnt.value))
+    _ffi.check(_lib.pss_icase_variants(pattern, len(pattern), want, buf, ln.value * cnt.value, ctypes.byref(off), ctypes.byref(ln),
+                                       ctypes.byref(cnt)))
+    raw = buf.raw
+    return int(off.value), [raw[i * ln.value:(i + 1) * ln.value] for i in range(cnt.value)]
 
 
 class Writer:
@@ -795,6 +817,78 @@ class Reader:
     def count_glob(self, s: str) -> int:
         """Extension: how many entries match the glob pattern ``s``."""
         return self.count_glob_bytes([_utf8(s, 'pattern')])[0]
+
+    @staticmethod
+    def _icase_args(patterns):
+        """(blob, offsets) of one batch of case-insensitive patterns; ``ValueError`` for an empty pattern."""
+        if isinstance(patterns, (bytes, bytearray, str)):
+            raise TypeError(f"argument 'patterns': '{type(patterns).__name__}' object cannot be converted to a sequence of patterns")
+        patterns = list(patterns)
+        for q, pat in enumerate(patterns):
+            if not isinstance(pat, (bytes, bytearray)):
+                raise TypeError(f'pattern {q}: a pattern must be bytes, not {type(pat).__name__}')
+            if len(pat) == 0:
+                raise ValueError(f'pattern {q} is empty (every entry contains the empty pattern)')
+        return _pack_queries([bytes(p) for p in patterns])
+
+    def search_icase_batch_packed(self, patterns: typing.Sequence[bytes]) -> 'PackedResult':
+        """Extension: per pattern, the entries that contain it whatever the case of its ASCII letters (``grep -i``), as a
+        packed result like ``search_batch_packed``'s.  Only the ASCII letters ``A-Z`` / ``a-z`` fold: every other byte,
+        ``0x80 .. 0xFF`` included (so every letter outside ASCII), matches only itself.  Every entry at most once per
+        pattern; a pattern holding a newline matches nothing; an empty pattern is a ``ValueError``.  The suffix arrays are
+        exact-byte: the spellings of a SEED of the pattern (``icase_variants``) are looked up and every hit is verified
+        against the whole pattern on the device, so the work follows the occurrences of the folded seed
+        (include/pss.h, pss_reader_search_icase_batch).  ``set_result_order`` has no effect."""
+        import numpy as np
+        blob, offs = self._icase_args(patterns)
+        nq = len(offs) - 1
+        res = ctypes.c_void_p()
+        _ffi.check(_lib.pss_reader_search_icase_batch(self._handle(), blob, offs.ctypes.data, nq, ctypes.byref(res)))
+        owner = _ResultOwner(res)      # the arrays below are views of the C result; it lives as long as they do
+        n = _lib.pss_result_num_entries(res)
+        counts = owner.view(_lib.pss_result_query_counts(res), nq, np.uint64)
+        offsets = owner.view(_lib.pss_result_offsets(res), n + 1, np.uint64)
+        data = owner.view(_lib.pss_result_bytes(res), int(offsets[n]), np.uint8)
+        return PackedResult(data, offsets, counts)
+
+    def search_icase_ids_batch(self, patterns: typing.Sequence[bytes]) -> 'IdResult':
+        """Extension: the ids (``search_ids_batch``) of the entries ``search_icase_batch_packed`` returns, in the same
+        order; ``counts[q]`` of them belong to pattern q.  Only ASCII letters fold.  A pattern without an ASCII letter
+        returns exactly what ``search_ids_batch`` returns for it."""
+        import numpy as np
+        blob, offs = self._icase_args(patterns)
+        nq = len(offs) - 1
+        res = ctypes.c_void_p()
+        _ffi.check(_lib.pss_reader_search_icase_ids_batch(self._handle(), blob, offs.ctypes.data, nq, ctypes.byref(res)))
+        owner = _ResultOwner(res)
+        n = _lib.pss_result_num_entries(res)
+        counts = owner.view(_lib.pss_result_query_counts(res), nq, np.uint64)
+        ids = owner.view(_lib.pss_result_bytes(res), 8 * n, np.uint8).view(np.uint64)
+        ids.flags.writeable = False
+        return IdResult(ids, counts)
+
+    def count_icase_bytes(self, patterns: typing.Sequence[bytes]) -> typing.List[int]:
+        """Extension: how many entries contain each pattern whatever the case of its ASCII letters (only they fold); only
+        the counters come back."""
+        import numpy as np
+        blob, offs = self._icase_args(patterns)
+        nq = len(offs) - 1
+        counts = np.zeros(max(nq, 1), dtype=np.uint64)
+        _ffi.check(_lib.pss_reader_count_icase_batch(self._handle(), blob, offs.ctypes.data, nq, counts.ctypes.data))
+        return [int(c) for c in counts[:nq]]
+
+    def search_icase(self, s: str) -> typing.List[str]:
+        """Extension: the entries that contain ``s`` (UTF-8 encoded) whatever the case of its ASCII letters.  Only
+        ``A-Z`` / ``a-z`` fold: ``'é'`` does not match ``'É'``."""
+        p = self.search_icase_batch_packed([_utf8(s, 'substring')])
+        data = p.data.tobytes()
+        o = p.offsets.tolist()
+        return [data[o[i]:o[i + 1]].decode('utf-8') for i in range(len(o) - 1)]
+
+    def count_icase(self, s: str) -> int:
+        """Extension: how many entries contain ``s`` (UTF-8 encoded) whatever the case of its ASCII letters (only they
+        fold)."""
+        return self.count_icase_bytes([_utf8(s, 'substring')])[0]
 
     @property
     def entry_counts(self) -> typing.Dict[int, int]:

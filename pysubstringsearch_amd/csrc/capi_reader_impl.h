@@ -1417,6 +1417,164 @@ extern "C" int pss_reader_count_seq_batch(pss_reader *r, const uint8_t *sbytes, 
     });
 }
 
+// ---- case-insensitive search: the spellings of a seed (fold_impl.h) -----------------------------------------------
+
+namespace {
+
+uint32_t icase_letters(int32_t letters) { return letters <= 0 ? search_knobs().icase_seed_letters : (uint32_t)letters; }
+
+// A batch of patterns as the interval search takes it: the spellings of every pattern's seed as the terms of one group
+// per pattern, and beside them the patterns folded to lower case with their seeds' offsets.
+struct IcaseBatch {
+    std::vector<uint8_t> vbytes, fbytes;
+    std::vector<uint64_t> voff, goff;
+    std::vector<uint32_t> seed;
+    SearchRequest request(const uint64_t *qoffsets, uint32_t nq, SearchMode mode) const
+    {
+        SearchRequest rq{vbytes.data(), voff.data(), (uint32_t)(voff.size() - 1), mode, nullptr, goff.data(), nq};
+        rq.fold_seed = seed.data();
+        rq.fold_bytes = fbytes.data();
+        rq.fold_offsets = qoffsets ? qoffsets : goff.data();     // (no pattern: one closing 0)
+        return rq;
+    }
+};
+
+// The argument checks of the three case-insensitive calls (out_ok: the call's own output argument is usable), and the
+// expansion.
+int icase_args(const pss_reader *r, const char *who, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, bool out_ok,
+               IcaseBatch *b)
+{
+    if (!out_ok || (nq && (!qbytes || !qoffsets))) {
+        set_error("%s: bad arguments", who);
+        return PSS_EINVAL;
+    }
+    if (nq && qoffsets[0] != 0) {
+        set_error("%s: the pattern offsets start at %llu, not at 0", who, (unsigned long long)qoffsets[0]);
+        return PSS_EINVAL;
+    }
+    for (uint32_t q = 0; q < nq; ++q) {
+        if (qoffsets[q + 1] < qoffsets[q]) {
+            set_error("%s: the pattern offsets decrease at pattern %u", who, q);
+            return PSS_EINVAL;
+        }
+        if (qoffsets[q + 1] == qoffsets[q]) {
+            set_error("%s: pattern %u is empty (every entry contains the empty pattern)", who, q);
+            return PSS_EINVAL;
+        }
+        if (qoffsets[q + 1] - qoffsets[q] > 0xffffffffull) {
+            set_error("%s: pattern %u has more than 2^32 - 1 bytes (a chunk has fewer)", who, q);
+            return PSS_EINVAL;
+        }
+    }
+    // What the expansion holds is judged before anything is allocated for it.  At most 64 spellings per pattern: only a
+    // batch of more than 2^26 patterns can pass the limit, and only such a batch pays for a counting pass of its own.
+    const uint32_t letters = icase_letters(0);
+    const uint64_t total = nq ? qoffsets[nq] : 0;
+    if (((uint64_t)nq << letters) > 0xffffffffull) {
+        uint64_t count = 0;
+        for (uint32_t q = 0; q < nq; ++q) {
+            uint64_t so = 0, sl = 0;
+            count += 1ull << fold_seed(qbytes + qoffsets[q], qoffsets[q + 1] - qoffsets[q], letters, &so, &sl);
+            if (count > 0xffffffffull) {
+                set_error("%s: the patterns expand to more than the 2^32 - 1 terms an all-terms batch takes (at pattern %u)", who, q);
+                return PSS_EINVAL;
+            }
+        }
+    }
+    b->seed.resize(nq);
+    std::vector<uint64_t> slen(nq);
+    std::vector<uint8_t> nletters(nq);
+    uint64_t nterms = 0, vtotal = 0;
+    for (uint32_t q = 0; q < nq; ++q) {
+        uint64_t so = 0;
+        nletters[q] = (uint8_t)fold_seed(qbytes + qoffsets[q], qoffsets[q + 1] - qoffsets[q], letters, &so, &slen[q]);
+        nterms += 1ull << nletters[q];
+        vtotal += slen[q] << nletters[q];
+        b->seed[q] = (uint32_t)so;          // (inside a pattern of less than 2^32 bytes)
+    }
+    b->fbytes.resize(total + 1);
+    for (uint64_t i = 0; i < total; ++i) b->fbytes[i] = (uint8_t)((uint8_t)(qbytes[i] - 'A') < 26 ? qbytes[i] | 0x20 : qbytes[i]);
+    b->vbytes.resize(vtotal);
+    b->voff.reserve(nterms + 1);
+    b->goff.reserve((size_t)nq + 1);
+    b->voff.assign(1, 0);
+    b->goff.assign(1, 0);
+    for (uint32_t q = 0; q < nq; ++q) {
+        const uint32_t f = nletters[q];
+        fold_spellings(qbytes + qoffsets[q] + b->seed[q], slen[q], f, b->vbytes.data() + b->voff.back());
+        for (uint32_t v = 0; v < (1u << f); ++v) b->voff.push_back(b->voff.back() + slen[q]);
+        b->goff.push_back(b->goff.back() + (1ull << f));
+    }
+    b->vbytes.push_back(0);     // (data() of an empty vector may be null)
+    if (!r) {                   // (last, as for the all-terms calls: a malformed batch is reported as such with or without a reader)
+        set_error("%s: bad arguments (no reader)", who);
+        return PSS_EINVAL;
+    }
+    return PSS_OK;
+}
+
+}  // namespace
+
+extern "C" int pss_icase_variants(const uint8_t *pat, uint64_t len, int32_t letters, uint8_t *out, uint64_t cap, uint32_t *seed_off,
+                                  uint32_t *seed_len, uint32_t *count)
+{
+    return guarded([&]() -> int {
+        if (!pat || !len) {
+            set_error("pss_icase_variants: the pattern is empty (every entry contains the empty pattern)");
+            return PSS_EINVAL;
+        }
+        if (letters > 6 || !seed_off || !seed_len || !count) {
+            set_error("pss_icase_variants: bad arguments (letters = %d: 1 .. 6, or <= 0 for PSS_ICASE_SEED_LETTERS)", (int)letters);
+            return PSS_EINVAL;
+        }
+        uint64_t so = 0, sl = 0;
+        const uint32_t f = fold_seed(pat, len, icase_letters(letters), &so, &sl);
+        if (so > 0xffffffffull || sl > 0xffffffffull) {
+            set_error("pss_icase_variants: a pattern of %llu bytes", (unsigned long long)len);
+            return PSS_EINVAL;
+        }
+        *seed_off = (uint32_t)so;
+        *seed_len = (uint32_t)sl;
+        *count = 1u << f;
+        if (!out) return PSS_OK;            // (the sizes alone)
+        if (cap < (sl << f)) {
+            set_error("pss_icase_variants: %u variants of %llu bytes need more than the %llu bytes of out", 1u << f, (unsigned long long)sl,
+                      (unsigned long long)cap);
+            return PSS_EINVAL;
+        }
+        fold_spellings(pat + so, sl, f, out);
+        return PSS_OK;
+    });
+}
+
+extern "C" int pss_reader_search_icase_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, pss_result **out)
+{
+    return guarded([&]() -> int {
+        IcaseBatch b;
+        PSS_TRY(icase_args(r, "pss_reader_search_icase_batch", qbytes, qoffsets, nq, out != nullptr, &b));
+        return reader_batch_result(r, b.request(qoffsets, nq, SEARCH_FULL), out);
+    });
+}
+
+extern "C" int pss_reader_search_icase_ids_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq,
+                                                 pss_result **out)
+{
+    return guarded([&]() -> int {
+        IcaseBatch b;
+        PSS_TRY(icase_args(r, "pss_reader_search_icase_ids_batch", qbytes, qoffsets, nq, out != nullptr, &b));
+        return reader_batch_result(r, b.request(qoffsets, nq, SEARCH_IDS), out);
+    });
+}
+
+extern "C" int pss_reader_count_icase_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, uint64_t *counts)
+{
+    return guarded([&]() -> int {
+        IcaseBatch b;
+        PSS_TRY(icase_args(r, "pss_reader_count_icase_batch", qbytes, qoffsets, nq, !nq || counts, &b));
+        return reader_batch_counts(r, b.request(qoffsets, nq, SEARCH_COUNTS), counts);
+    });
+}
+
 namespace {
 
 // ids[0 .. n) of ONE single-device reader: validation on the host (the reader knows every chunk's entry count once the

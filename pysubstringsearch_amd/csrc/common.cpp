@@ -206,6 +206,7 @@ void SearchKnobs::load()
     no_pinned_results = knob("PSS_NO_PINNED_RESULTS") != nullptr;
     small_path_events = knob("PSS_SEARCH_EVENTS") != nullptr;
     if (const char *e = knob("PSS_LANE_SEARCH_MIN")) lane_search_min = strtoull(e, nullptr, 0);
+    if (const char *e = knob("PSS_ICASE_SEED_LETTERS")) icase_seed_letters = (uint32_t)std::min(6ul, std::max(1ul, strtoul(e, nullptr, 0)));
     if (const char *e = knob("PSS_RESIDENT_IDLE_US")) resident_idle_us = (uint32_t)strtoul(e, nullptr, 0);
     if (const char *e = knob("PSS_RESIDENT_LIFE_US")) resident_life_us = (uint32_t)strtoul(e, nullptr, 0);
 }
@@ -465,6 +466,7 @@ const KnobDef kKnobs[] = {
     {"PSS_PINNED_POOL_BYTES", "40 GiB", "", "search: pinned host memory the result pool keeps between batches"},
     {"PSS_NO_PINNED_RESULTS", "unset", "1", "search: large results into pageable memory"},
     {"PSS_LANE_SEARCH_MIN", "8192", "1|100000", "search: pairs from which one lane per pair searches"},
+    {"PSS_ICASE_SEED_LETTERS", "5", "1|2|3|4|5|6", "case-insensitive search: ASCII letters of a pattern's seed at most (2^letters spellings probed per pattern and chunk)"},
     {"PSS_SEARCH_EVENTS", "unset", "", "single-query path: HIP events around the fused kernel (fills ms_device; ~4 us per query)"},
     {"PSS_RESIDENT_IDLE_US", "1000", "", "low-latency mode: the resident kernel leaves after this long without a query"},
     {"PSS_RESIDENT_LIFE_US", "50000", "", "low-latency mode: ... and after this long in any case"},

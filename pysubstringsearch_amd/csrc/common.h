@@ -63,6 +63,7 @@ struct SearchKnobs {
     bool no_pinned_results = false; // PSS_NO_PINNED_RESULTS large results into pageable memory
     bool small_path_events = false; // PSS_SEARCH_EVENTS     HIP events around the fused single-query kernel (fills ms_device there)
     uint64_t lane_search_min = 8192;   // PSS_LANE_SEARCH_MIN  pairs from which one lane per pair searches
+    uint32_t icase_seed_letters = 5;   // PSS_ICASE_SEED_LETTERS  case-insensitive search: ASCII letters of a pattern's seed at most (1 .. 6)
     uint32_t resident_idle_us = 1000;  // PSS_RESIDENT_IDLE_US  resident search kernel: leaves after this long without a query ...
     uint32_t resident_life_us = 50000; // PSS_RESIDENT_LIFE_US  ... and after this long in any case (the next query starts another)
     void load();

@@ -1,0 +1,192 @@
+// fold_impl.h -- entries that contain a pattern under ASCII case folding (include/pss.h, pss_reader_search_icase_batch;
+// DESIGN.md 4.13).
+// Part of search.hip: included there behind sequence_impl.h, whose group geometry (TG lanes per surviving hit) and pair
+// spaces it shares; not a header for anybody else.
+//
+// The suffix arrays are exact-byte, so the host turns every pattern into its SEED -- the longest window with at most F
+// ASCII letters -- and the seed into its 2^f concrete spellings, in ascending byte order (fold_seed and fold_spellings below: what
+// pss_icase_variants shows).  The spellings of pattern g are the consecutive terms goff[g] .. goff[g + 1] of an
+// all-terms-shaped batch: the interval kernels answer every (spelling, chunk) pair unchanged.  Strings of one length in
+// ascending byte order have disjoint, ascending suffix-array intervals, so fold_union_kernel only adds the counts up, and
+// hit k of a (pattern, chunk) pair is found by walking the pair's at most 64 counts.  fold_hits_kernel verifies the
+// whole pattern around each seed hit under fold and takes the entry's bounds; fold_dedupe_kernel keeps the hit of an
+// entry's LEFTMOST folded match: hit_entry's dedupe, under fold.  Every match alignment holds exactly one seed
+// occurrence, in exactly one spelling, so an entry keeps exactly one hit whatever mix of spellings it holds.
+// A pattern that holds a 0x0A occurs in no entry and is flagged void: its pairs count no hit.
+
+// The seed of pat[0, len): the longest window with at most `letters` ASCII letters, the leftmost on a tie.  Returns its
+// letter count.  (Host code, declared in search.h: the C ABI expands the patterns before it states the request.)
+u32 fold_seed(const u8 *pat, u64 len, u32 letters, u64 *seed_off, u64 *seed_len)
+{
+    auto is_letter = [](u8 b) { return (u8)((b | 0x20u) - 'a') < 26u; };
+    u64 best_off = 0, best_len = 0, i = 0;
+    u32 in_window = 0, best_letters = 0;
+    for (u64 j = 0; j < len; ++j) {              // [i, j]: the longest window that ends at j
+        in_window += is_letter(pat[j]) ? 1u : 0u;
+        while (in_window > letters) in_window -= is_letter(pat[i++]) ? 1u : 0u;
+        if (j + 1 - i > best_len) {
+            best_len = j + 1 - i;
+            best_off = i;
+            best_letters = in_window;
+        }
+    }
+    *seed_off = best_off;
+    *seed_len = best_len;
+    return best_letters;
+}
+
+// The 2^f spellings of seed[0, len) (f letters) back to back into out, ascending bytewise: upper case sorts before lower,
+// and the first letter is the most significant.
+void fold_spellings(const u8 *seed, u64 len, u32 f, u8 *out)
+{
+    for (u32 v = 0; v < (1u << f); ++v) {
+        u32 bit = f;
+        for (u64 i = 0; i < len; ++i) {
+            u8 b = seed[i];
+            if ((u8)((b | 0x20u) - 'a') < 26u) b = (v >> --bit) & 1u ? (u8)(b | 0x20u) : (u8)(b & ~0x20u);
+            out[(u64)v * len + i] = b;
+        }
+    }
+}
+
+// Bytes of an 8-byte word under fold: 0x20 is set on the bytes in 'A' .. 'Z' and on no other.  Exact per byte, without
+// carries between bytes: the low seven bits of a byte plus 0x3f (0x25) set its high bit iff they are >= 0x41 (>= 0x5b),
+// and the sums stay below 0x100; a byte >= 0x80 is taken out by its own high bit.
+__device__ __forceinline__ u64 fold8(u64 w)
+{
+    const u64 H = 0x8080808080808080ull;
+    const u64 l = w & ~H;
+    const u64 ge_a = l + 0x3f3f3f3f3f3f3f3full, gt_z = l + 0x2525252525252525ull;
+    return w | ((ge_a & ~gt_z & ~w & H) >> 2);
+}
+
+// Is pat (folded, plen bytes) what text[s, s + plen) folds to?  The caller knows s + plen <= n.  Loads reach 15 bytes past
+// the last compared byte of the text and 10 past the pattern's end (load_u64_unaligned at the pattern's last byte takes
+// three aligned dwords).
+__device__ __forceinline__ bool fold_equal(const u8 *text, u32 s, const u8 *pat, u32 plen)
+{
+    for (u32 i = 0; i < plen; i += 8) {
+        u64 a = fold8(load_text8(text + s + i)), b = load_u64_unaligned(pat + i);
+        const u32 rem = plen - i;
+        if (rem < 8) {
+            const u64 mask = (1ull << (8 * rem)) - 1ull;
+            a &= mask;
+            b &= mask;
+        }
+        if (a != b) return false;
+    }
+    return true;
+}
+
+// One lane per (pattern, chunk) pair: the hits of the pair are the hits of its spellings, one interval behind the other.
+// (Disjoint intervals of one suffix array: the sum is at most n and fits u32.)
+__global__ __launch_bounds__(256) void fold_union_kernel(u32 nc, const u64 *goff, const u8 *fvoid, const u32 *cnt, u64 ngq, u32 *p_cnt)
+{
+    const u64 gq = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gq >= ngq) return;
+    const u32 g = (u32)(gq / nc), c = (u32)(gq % nc);
+    u32 sum = 0;
+    if (!fvoid[g])
+        for (u32 v = (u32)goff[g], v1 = (u32)goff[g + 1]; v < v1; ++v) sum += cnt[(u64)v * nc + c];
+    p_cnt[gq] = sum;
+}
+
+// One lane per hit: hit k of a pair is suffix sa[lo[v, c] + k'] of the spelling v its walk over the pair's counts ends
+// in.  With di that text offset the match would start at m = di - seed_off: out of the chunk -> rejected before anything
+// is read.  Else the whole pattern at m under fold (the bytes outside the seed are what is unknown; the pattern holds no
+// 0x0A, so a match cannot leave its entry), and the entry's bounds.  A surviving hit leaves start, len and m.
+__global__ __launch_bounds__(256) void fold_hits_kernel(const ChunkDesc *chunks, u32 nc, const u8 *fbytes, const u64 *foff,
+                                                          const u32 *fseed, const u64 *goff, const u32 *lo, const u32 *cnt, u64 ngq,
+                                                          const u64 *hit_off, u64 H, u32 *start_out, u32 *len_out, u32 *m_out)
+{
+    for (u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x; t < H; t += (u64)gridDim.x * blockDim.x) {
+        u64 a = 0, b = ngq;
+        while (b - a > 1) {
+            const u64 mid = a + (b - a) / 2;
+            if (hit_off[mid] <= t) a = mid; else b = mid;
+        }
+        const u32 g = (u32)(a / nc), c = (u32)(a % nc);
+        const ChunkDesc ch = chunks[c];
+        u32 k = (u32)(t - hit_off[a]);
+        u32 v = (u32)goff[g];
+        const u32 v1 = (u32)goff[g + 1];
+        for (; v + 1 < v1; ++v) {                                // (k < the pair's sum: the walk ends inside [goff[g], v1))
+            const u32 n_v = cnt[(u64)v * nc + c];
+            if (k < n_v) break;
+            k -= n_v;
+        }
+        const u32 di = ch.sa[lo[(u64)v * nc + c] + k];
+        const u32 so = fseed[g], plen = (u32)(foff[g + 1] - foff[g]);
+        u32 ls = 0, ll = kSkip, m = 0;
+        if (di >= so && (u64)(di - so) + plen <= ch.n) {
+            m = di - so;
+            if (fold_equal(ch.text, m, fbytes + foff[g], plen)) entry_bounds(ch, di, ls, ll);
+        }
+        start_out[t] = ls;
+        len_out[t] = ll;
+        m_out[t] = m;
+    }
+}
+
+// Does a folded occurrence of pat START in text[s, m)?  It may reach past m.  Called by the TG lanes of one group together
+// (gl = lane inside the group, gbase = the group's first lane); every lane returns the group's answer.  entry_holds with
+// folding: the text word and the one behind it are folded in registers, the bytes equal to the pattern's first folded
+// byte are the candidates, and a candidate is checked against the pattern's first min(8, plen) bytes in registers; only
+// a longer pattern whose first 8 match goes back to memory.  The caller's match at m lies inside the chunk, so every
+// start position p < m has p + plen < n; loads reach at most 23 bytes past a start position and 15 past p + plen (the
+// text is readable 128 bytes past n, a pattern 16 past its end).
+__device__ __forceinline__ bool fold_starts_before(const ChunkDesc &ch, u32 s, u32 m, const u8 *pat, u32 plen, u32 gl, u32 gbase)
+{
+    if (m <= s) return false;
+    const u32 last = m - 1;                                      // the last start position
+    const u64 first = 0x0101010101010101ull * pat[0];
+    const u64 pmask = plen >= 8 ? ~0ull : (1ull << (8 * plen)) - 1ull;
+    const u64 pk = load_u64_unaligned(pat) & pmask;
+    for (u64 base = s; base <= last; base += 8 * TG) {           // (the same trips for every lane of the group)
+        const u64 p64 = base + 8 * gl;
+        bool found = false;
+        if (p64 <= last) {
+            const u32 p = (u32)p64;
+            const u64 w = fold8(load_text8(ch.text + p)), nxt = fold8(load_text8(ch.text + p + 8));
+            u64 cand = zero_bytes(w ^ first);
+            const u32 nv = last - p + 1;                         // start positions of this word in front of m
+            if (nv < 8) cand &= (1ull << (8 * nv)) - 1ull;
+            while (cand && !found) {
+                const u32 k = (u32)(__builtin_ctzll(cand) >> 3);
+                cand &= cand - 1;
+                const u64 x = k ? (w >> (8 * k)) | (nxt << (64 - 8 * k)) : w;     // fold(text[p + k, p + k + 8))
+                if ((x & pmask) == pk) found = plen <= 8 || fold_equal(ch.text, p + k, pat, plen);
+            }
+        }
+        // The ballot runs while the groups of a wavefront are on different paths (other hits, other patterns, other trip
+        // counts); it counts the active lanes only, and only the group's own TG bits are read.  INVARIANT, as in
+        // entry_holds: the TG lanes of a group reach every ballot together -- every branch between the kernel's loop entry
+        // and this line depends on group-wide values only (t, len[t], s, m, plen, base), and the per-lane `p64 <= last`
+        // branch closes above.  A lane that took a path of its own would split the group's ballot.
+        if ((u32)(__ballot(found) >> gbase) & ((1u << TG) - 1u)) return true;
+    }
+    return false;
+}
+
+// TG lanes per hit that fold_hits_kernel left standing: the hit is kept iff no folded occurrence of the pattern starts
+// in [start, m) -- the leftmost match of the entry stands for it, whichever spelling's interval it came from.  The same
+// shape as terms_verify_kernel, for the same reasons: 64 bytes of entry per step, 32 hits per 256-thread workgroup,
+// grid-stride.  Every loop is bounded by m - start, an entry's length.
+__global__ __launch_bounds__(256) void fold_dedupe_kernel(const ChunkDesc *chunks, u32 nc, const u8 *fbytes, const u64 *foff, u64 ngq,
+                                                            const u64 *hit_off, u64 H, const u32 *start, const u32 *mpos, u32 *len)
+{
+    const u32 lane = lane_id(), gl = lane & (TG - 1), gbase = lane & ~(TG - 1);
+    const u64 step = (u64)gridDim.x * blockDim.x / TG;
+    for (u64 t = ((u64)blockIdx.x * blockDim.x + threadIdx.x) / TG; t < H; t += step) {
+        if (len[t] == kSkip) continue;
+        u64 a = 0, b = ngq;
+        while (b - a > 1) {
+            const u64 mid = a + (b - a) / 2;
+            if (hit_off[mid] <= t) a = mid; else b = mid;
+        }
+        const u32 g = (u32)(a / nc);
+        const ChunkDesc ch = chunks[(u32)(a % nc)];
+        const bool dup = fold_starts_before(ch, start[t], mpos[t], fbytes + foff[g], (u32)(foff[g + 1] - foff[g]), gl, gbase);
+        if (dup && gl == 0) len[t] = kSkip;
+    }
+}

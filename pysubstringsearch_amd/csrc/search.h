@@ -92,6 +92,11 @@ struct SearchRequest {
     // its segments left to right without overlap, the first at the entry's start and / or the last at its end when anchored.
     // exclude is then unused and may be null.  Everything else as for an all-terms batch.
     const uint8_t *seq_anchors = nullptr;
+    // fold_seed (ngroups values), fold_bytes and fold_offsets (ngroups + 1), together with group_offsets: the case-insensitive
+    // search of fold_impl.h.  The rows are PATTERNS -- fold_bytes holds them folded to lower case, back to back -- and the nq
+    // terms of group g are the spellings of pattern g's seed, in ascending byte order; fold_seed[g] is the seed's offset inside
+    // the pattern.  Modes FULL, COUNTS and IDS; not with anchors, exclude or seq_anchors; always the general pipeline.
+    const uint32_t *fold_seed = nullptr; const uint8_t *fold_bytes = nullptr; const uint64_t *fold_offsets = nullptr;
     uint32_t rows() const { return group_offsets ? ngroups : nq; }     // rows of the result: queries, or groups of terms
     bool low_latency = false;            // one query through the resident kernel when it fits (an unanchored SEARCH_FULL batch only)
     // sa_order: the entries of one (query, chunk) pair come out in the reference's order -- suffix-array order of the FIRST hit
@@ -104,6 +109,12 @@ struct SearchRequest {
     // (capi.cpp); it costs one small kernel and a stream synchronisation, so readers whose chunks all live in HBM pass nullptr.
     uint64_t *chunk_hits = nullptr;
 };
+
+// Host side of the case-insensitive search (fold_impl.h).  fold_seed: the seed of pat[0, len) -- its longest window with at
+// most `letters` ASCII letters, the leftmost on a tie -- into seed_off / seed_len; returns the seed's letter count f.
+// fold_spellings: the 2^f spellings of a seed of f letters back to back into out (len << f bytes), ascending bytewise.
+uint32_t fold_seed(const uint8_t *pat, uint64_t len, uint32_t letters, uint64_t *seed_off, uint64_t *seed_len);
+void fold_spellings(const uint8_t *seed, uint64_t len, uint32_t f, uint8_t *out);
 
 // The batch over the nc resident chunks of d_chunks (d_lines: their line tables, parallel to d_chunks; read by SEARCH_IDS
 // alone, nullptr where none were built).

@@ -1726,6 +1726,7 @@ static int resident_query(DeviceCtx *ctx, const ChunkDesc *d_chunks, u32 nc, con
 #include "anchored_impl.h"
 #include "all_terms_impl.h"
 #include "sequence_impl.h"
+#include "fold_impl.h"
 
 // Suffix-array hits of the batch per chunk (pair p = query p / nc on chunk p % nc): one workgroup per chunk.
 __global__ __launch_bounds__(256) void chunk_hits_kernel(const u32 *cnt, u64 nq, u32 nc, u64 *out)
@@ -1743,7 +1744,7 @@ __global__ __launch_bounds__(256) void chunk_hits_kernel(const u32 *cnt, u64 nq,
 
 // ---- host driver of one batch -------------------------------------------------------------------------------------
 // search_batch_device reads top to bottom: empty batch -> stage_queries -> run_fused? -> launch_interval -> run_mid? ->
-// pick_drivers (an all-terms or a sequence batch) -> run_general -> finish.
+// pick_drivers (an all-terms or a sequence batch) | union_spellings (a case-insensitive batch) -> run_general -> finish.
 // The stages share one Batch: the request normalised into the few booleans they read, the
 // workspace every route needs, the timing events and the two outputs.
 namespace {
@@ -1768,6 +1769,7 @@ struct Batch {
     // the request, normalised once: nothing below asks for a mode again
     bool counts, device, ids, anchored, terms, sa_order;
     bool seq;                           // terms, and the groups are ordered sequences (sequence_impl.h)
+    bool fold;                          // terms, and the groups are the spellings of one pattern's seed each (fold_impl.h)
     bool tiny;                          // queries and offsets fit the 16 KiB of the pinned scratch
     bool fused_ok, resident_ok, mid_ok; // routes this batch may take (each may still overflow into the next)
     // host copy of queries, offsets and anchor flags (stage_queries)
@@ -1785,6 +1787,9 @@ struct Batch {
     u64 *d_goff = nullptr;                          // all-terms batch: group offsets, term flags, driver term per group pair
     u8 *d_tflags = nullptr, *d_sanch = nullptr;       // (d_sanch: a sequence batch's anchor byte per group)
     u32 *d_gdrv = nullptr;
+    u8 *d_fbytes = nullptr, *d_fvoid = nullptr;     // a case-insensitive batch: the folded patterns, their offsets and seed
+    u64 *d_foff = nullptr;                          // offsets, a void flag per pattern, the match start of every hit
+    u32 *d_fseed = nullptr, *d_m = nullptr;
     // ... and of the mid and the general pipeline, sized by each: entry bounds per hit, the scans over them, the result
     u32 *d_start = nullptr, *d_len = nullptr;
     u64 *d_eidx = nullptr, *d_boff = nullptr, *d_entoff = nullptr;
@@ -1804,6 +1809,7 @@ struct Batch {
         anchored = rq.anchors != nullptr;
         terms = rq.group_offsets != nullptr;
         seq = terms && rq.seq_anchors != nullptr;
+        fold = terms && rq.fold_seed != nullptr;
         // (counts do not depend on the order; one hit per entry has one order; an all-terms batch keeps its driver's text order)
         sa_order = rq.sa_order && !counts && !anchored && !terms;
         // (an anchored batch searches its rewritten queries: a newline in front of and / or behind every pattern)
@@ -1823,7 +1829,7 @@ struct Batch {
         p = ctx->slot[which].as<T>();
         return PSS_OK;
     }
-    int stage_queries(), run_fused(bool *served), launch_interval(), run_mid(bool *done), pick_drivers(), run_general(), finish();
+    int stage_queries(), run_fused(bool *served), launch_interval(), run_mid(bool *done), pick_drivers(), union_spellings(), run_general(), finish();
     int sa_order_hits(u32 grid, u64 H);
     int download_result(u64 E, u64 B, const u64 *d_starts, const u8 *d_bytes, bool via_stage);
     void leave_on_device(const u64 *d_starts, const u8 *d_bytes), set_totals(u64 hits, u64 kept, u64 E, u64 B);
@@ -1899,7 +1905,7 @@ int Batch::stage_queries()
     h_off = hq ? ho : rq.qoffsets;
     h_flags = hf;
     h_padded = hq != nullptr;
-    if (terms) {
+    if (terms && !fold) {
         own_tflags.resize(nq);
         if (seq)
             seq_flags(rq.qbytes, rq.qoffsets, nq, own_tflags.data());
@@ -2152,6 +2158,35 @@ int Batch::pick_drivers()
     return PSS_OK;
 }
 
+// Case-insensitive batch: from the (spelling, chunk) pairs to the (pattern, chunk) pairs.  The folded patterns go up
+// beside the spellings -- bytes (32 zero bytes behind them, as behind the staged terms), offsets, seed offsets, void flags
+// -- and one lane per pair adds up the counts of its spellings; a pair has no interval of its own (p_lo is not read).
+int Batch::union_spellings()
+{
+    const u64 ftotal = rq.fold_offsets[nrow];
+    const size_t goff_room = round_up(((size_t)nrow + 1) * 8, 64), seed_room = round_up((size_t)nrow * 4, 64);
+    const size_t void_room = round_up((size_t)nrow, 64), byte_room = round_up(ftotal + 32, 64);
+    PSS_TRY(take(Q_TERMS, 2 * goff_room + seed_room + void_room + byte_room + nrp * 4, d_goff));
+    d_foff = d_goff + goff_room / 8;
+    d_fseed = reinterpret_cast<u32 *>(d_foff + goff_room / 8);
+    d_fvoid = reinterpret_cast<u8 *>(d_fseed) + seed_room;
+    d_fbytes = d_fvoid + void_room;
+    p_cnt = reinterpret_cast<u32 *>(d_fbytes + byte_room);
+    own_tflags.resize(nrow);
+    for (u32 g = 0; g < nrow; ++g) {
+        const u64 m = rq.fold_offsets[g + 1] - rq.fold_offsets[g];
+        own_tflags[g] = (m && memchr(rq.fold_bytes + rq.fold_offsets[g], '\n', m)) ? kTermVoid : 0;
+    }
+    PSS_HIP(hipMemcpyAsync(d_goff, rq.group_offsets, ((size_t)nrow + 1) * 8, hipMemcpyHostToDevice, s));
+    PSS_HIP(hipMemcpyAsync(d_foff, rq.fold_offsets, ((size_t)nrow + 1) * 8, hipMemcpyHostToDevice, s));
+    PSS_HIP(hipMemcpyAsync(d_fseed, rq.fold_seed, (size_t)nrow * 4, hipMemcpyHostToDevice, s));
+    PSS_HIP(hipMemcpyAsync(d_fvoid, own_tflags.data(), nrow, hipMemcpyHostToDevice, s));
+    PSS_HIP(hipMemsetAsync(d_fbytes + ftotal, 0, 32, s));
+    PSS_HIP(hipMemcpyAsync(d_fbytes, rq.fold_bytes, ftotal, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(fold_union_kernel, dim3((u32)((nrp + 255) / 256)), dim3(256), 0, s, nc, d_goff, d_fvoid, d_cnt, nrp, p_cnt);
+    return PSS_OK;
+}
+
 // General pipeline: every size comes down to the host before what it sizes is reserved -- hits, then kept hits (entries),
 // then bytes.
 int Batch::run_general()
@@ -2184,7 +2219,15 @@ int Batch::run_general()
     else if (anchored)
         hipLaunchKernelGGL(anchored_hits_kernel, dim3(grid), dim3(256), 0, s, d_chunks, nc, d_aflags, nrp, p_lo, d_edge,
                            d_hitoff, H, d_start, d_len);
-    else if (terms) {
+    else if (fold) {
+        // every hit of every spelling against the whole pattern under fold; then the survivors against the entry in front of them
+        PSS_TRY(take(Q_ORD_V0, H * 4, d_m));        // (the slot of the suffix-array order's values: that order is never a fold batch's)
+        hipLaunchKernelGGL(fold_hits_kernel, dim3(grid), dim3(256), 0, s, d_chunks, nc, d_fbytes, d_foff, d_fseed, d_goff, d_lo, d_cnt,
+                           nrp, d_hitoff, H, d_start, d_len, d_m);
+        const u32 vgrid = (u32)std::min<u64>((u64)ctx->num_cus * 16, (H * TG + 255) / 256);
+        hipLaunchKernelGGL(fold_dedupe_kernel, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, d_fbytes, d_foff, nrp, d_hitoff, H, d_start,
+                           d_m, d_len);
+    } else if (terms) {
         // candidates: the entries that hold the pair's driver term; then every candidate against the group's other terms
         hipLaunchKernelGGL(terms_hits_kernel, dim3(grid), dim3(256), 0, s, d_chunks, nc, d_q, d_qoff, d_gdrv, nrp, p_lo, d_hitoff, H,
                            d_start, d_len);
@@ -2270,8 +2313,12 @@ int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, const LineDes
         set_error("search: an anchored batch takes the general pipeline to a host result");
         return PSS_EINVAL;
     }
-    if (rq.group_offsets && (rq.anchors || (rq.nq && !rq.exclude && !rq.seq_anchors) || rq.mode == SEARCH_DEVICE || rq.low_latency)) {
+    if (rq.group_offsets && (rq.anchors || (rq.nq && !rq.exclude && !rq.seq_anchors && !rq.fold_seed) || rq.mode == SEARCH_DEVICE || rq.low_latency)) {
         set_error("search: an all-terms batch takes the general pipeline to a host result, and its terms are not anchored");
+        return PSS_EINVAL;
+    }
+    if (rq.fold_seed && (!rq.group_offsets || !rq.fold_bytes || !rq.fold_offsets || rq.exclude || rq.seq_anchors)) {
+        set_error("search: a case-insensitive batch is the spellings of its patterns' seeds in groups, without exclusions or anchors");
         return PSS_EINVAL;
     }
     const u32 rows = rq.rows();
@@ -2298,7 +2345,9 @@ int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, const LineDes
         PSS_TRY(b.run_mid(&done));
         if (done) return b.finish();
     }
-    if (b.terms) {
+    if (b.fold) {
+        PSS_TRY(b.union_spellings());
+    } else if (b.terms) {
         PSS_TRY(b.pick_drivers());
     }
     PSS_TRY(b.run_general());
