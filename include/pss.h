@@ -195,6 +195,8 @@ typedef struct pss_sa_stats {
                                   this text did not fit -- the build started over without it) */
     uint64_t msd_lookback;     /* 1: the MSD sort took its two digits in LSD order and partitioned the second pass in one sweep
                                   (decoupled look-back, no second histogram pass: round 6; texts below 2^30 bytes) */
+    uint64_t msd_finished;     /* suffixes of small tie groups that the MSD sort's finishing kernel placed for good with one more
+                                  64-bit text key (msd_sort.hip, msd_finish_kernel); rounds / sum_active count what was left */
 } pss_sa_stats;
 
 /*

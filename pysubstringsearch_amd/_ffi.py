@@ -92,6 +92,7 @@ class SaStats(ctypes.Structure):
         ('anchor_ms', ctypes.c_double),
         ('ms_restarts', ctypes.c_double),
         ('msd_lookback', ctypes.c_uint64),
+        ('msd_finished', ctypes.c_uint64),
     ]
 
     def as_dict(self):

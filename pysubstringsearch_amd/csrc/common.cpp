@@ -415,6 +415,7 @@ const KnobDef kKnobs[] = {
     {"PSS_MSD_KEY_CAP", "48", "", "MSD sort: largest key width tried (bits; the element format bounds it further)"},
     {"PSS_MSD_PARTIAL_SYMBOL", "unset", "1", "MSD sort: fill the element with the high bits of one more symbol than fits whole (fewer ties; measured slower on lines)"},
     {"PSS_MSD_NO_FUSE", "unset", "1", "MSD sort: ties flagged in the suffix array instead of emitted from the local sort"},
+    {"PSS_MSD_NO_FINISH", "unset", "1", "MSD sort: small tie groups go to the rounds instead of being finished by one more text key after the local sort"},
     {"PSS_MSD_SLOW_LOCAL", "unset", "1", "MSD sort: the general (ballot LSD) local-sort kernel for every tile"},
     {"PSS_MSD_SCATTER", "unset", "1", "MSD sort in MSD order: the 8192-element partition kernels of round 2"},
     {"PSS_SS", "-1 (n >= 2^24, MSD declined)", "0|1", "initial sort: never / whenever the text has the size for it the sample sort over 16-byte elements"},

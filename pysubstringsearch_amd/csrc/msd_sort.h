@@ -12,6 +12,7 @@ struct MsdStats {
     uint32_t slow_tiles = 0;   // of them, tiles the counting kernel handed to the general (ballot LSD) kernel
     uint32_t bad_symbol = 0;   // MsdFront: a byte of the text had no code in the table it was given
     uint32_t lookback = 0;     // digits in LSD order, second pass in one sweep (look-back)
+    uint32_t finished = 0;     // suffixes of small tie groups settled by msd_finish_kernel (none of them is in the active list)
     double ms_g1 = 0, ms_g2 = 0, ms_local = 0;   // profile mode: the two partition scatters and the local sort
 };
 
@@ -19,6 +20,9 @@ struct MsdStats {
 // local sort emits the active list itself -- for every suffix that is tied with a neighbour its SA slot,
 // its index and 1 + the slot of its group's head, in slot order -- which is exactly what rr_apply_tied
 // would compute from the flags with two more passes over the 4 n-byte array.
+// Groups of a few members that one more 64-bit text key separates never reach the list: msd_finish_kernel writes them to
+// their final slots of sa_out (PSS_MSD_NO_FINISH=1: every tied suffix is listed, as before).
+constexpr int MSD_FIN_MAX = 4;               // largest group the finishing kernel settles
 struct MsdActive {
     uint32_t *pos, *idx, *grp;               // the list (capacity n each)
     uint32_t *st_pos, *st_idx;               // staging of the same size (per-tile blocks before they are lined up)

@@ -980,9 +980,12 @@ __device__ __forceinline__ void msd_emit_tile(const u64 *exch, u32 count, u32 e0
     }
 }
 
+// blk_cnt[t] = records of tile t in its low half (a tile has < 8192), in the high half the records msd_finish_kernel has
+// dropped.  The scan adds both up at once -- records in the low word of its 64-bit sums, finished suffixes in the high word
+// (one counter for all tiles would be a hundred thousand atomics on one address: 1.1 ms at n = 2^29, measured).
 struct InBlkCnt {
     const u32 *c;
-    __device__ u64 operator()(u64 t) const { return c[t]; }
+    __device__ u64 operator()(u64 t) const { return (u64)(c[t] & 0xffffu) | ((u64)(c[t] >> 16) << 32); }
 };
 
 // One wavefront per tile: the tile's records (unordered) -> the active list of the first rerank in slot
@@ -998,10 +1001,10 @@ __global__ __launch_bounds__(256) void msd_gather_kernel(const MsdTile *tiles, c
     const u32 w = wave_id(), lane = lane_id();
     const u32 t = blockIdx.x * 4 + w;
     if (t >= nt) return;
-    const u32 c = blk_cnt[t];
+    const u32 c = blk_cnt[t] & 0xffffu;
     if (c == 0) return;
     const u32 e0 = tiles[t].e0;
-    const u64 d = dst_off[t];
+    const u64 d = dst_off[t] & 0xffffffffull;      // (the high word counts finished suffixes: InBlkCnt)
     u32 *occ = s_occ[w], *head = s_head[w], *pre = s_pre[w];
     for (u32 i = lane; i < GA_WORDS; i += kWave) occ[i] = head[i] = 0;
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -1037,6 +1040,142 @@ __global__ __launch_bounds__(256) void msd_gather_kernel(const MsdTile *tiles, c
         idx[d + rank] = st_idx[e0 + i] & 0x7fffffffu;
         grp[d + rank] = e0 + hq + 1;
     }
+}
+
+// ---- finishing small groups ----------------------------------------------------------------------
+
+// Nearly every tied group the local sort leaves on log-like text is a pair or a triple that differs within the next few
+// symbols.  The rounds of sa_build.hip would resolve them with their general machinery -- some twenty launches and a host
+// round trip for a few megabytes of data.  This kernel runs between the local sort and the gather instead and settles
+// such groups where they lie: one wavefront per tile block (the same unit as the gather: a tile holds a few dozen
+// records), the head of every group of g <= FIN_MAX members packs ONE more 64-bit text key per member (text_key_at from
+// symbol h0 on: the packing of the text rounds), and when the g keys are pairwise different writes the members to
+// sa_out[head slot + number of smaller keys].  Such a group's records are dropped; every other group (larger, or two
+// equal keys) keeps ALL its records, untouched.  The leftovers are compacted inside the block, blk_cnt[t] is updated (what
+// is left, and in its high half what was dropped: InBlkCnt), and the scan and msd_gather_kernel build the active list from
+// them as before.
+// FIN_MAX: the ranking is all-pairs, in registers.  The 2^29-byte `lines` chunk leaves 1 044 432 pairs and 1 396 triples
+// (random text: groups of four are expected a handful of times per chunk, of five once in hundreds of chunks), and a group
+// left behind costs the whole tail of launches again.
+constexpr int FIN_MAX = MSD_FIN_MAX;
+constexpr u32 FIN_WORDS = GA_WORDS + 2;      // the bitmap of flagged slots, read 64 bits at a time from any slot + 1 of the tile
+struct MsdFinish {
+    const u8 *codes;
+    int code_bits, key_syms, plus_one;       // key_syms = min(64 / code_bits, 16)
+    u32 h0, n;                               // whole symbols the sort key has compared
+};
+
+__global__ __launch_bounds__(256) void msd_finish_kernel(const MsdTile *tiles, u32 *blk_cnt, u32 nt, u32 *st_pos, u32 *st_idx,
+                                                           u32 *sa_out, MsdFinish f)
+{
+    __shared__ u32 s_tie[4][FIN_WORDS], s_done[4][GA_WORDS];
+    const u32 w = wave_id(), lane = lane_id();
+    const u32 t = blockIdx.x * 4 + w;
+    if (t >= nt) return;
+    // The kernel is a chain of dependent trips to memory (count and tile -> records -> the members' suffixes -> their
+    // text), a hundred thousand waves of it: the two first loads go out together, and the first 64 records of the block
+    // (a tile of `lines` has 32 on average, 77 at most) stay in registers for all three passes over them.
+    const u32 c = blk_cnt[t] & 0xffffu;
+    const u32 e0 = tiles[t].e0;
+    if (c == 0) return;
+    u32 ps0 = 0, v0 = 0;
+    if (lane < c) {
+        ps0 = st_pos[e0 + lane];
+        v0 = st_idx[e0 + lane];
+    }
+    auto record = [&](u32 i, u32 &ps, u32 &v) {
+        if (i < (u32)kWave) {
+            ps = ps0;
+            v = v0;
+        } else {
+            ps = st_pos[e0 + i];
+            v = st_idx[e0 + i];
+        }
+    };
+    u32 *tie = s_tie[w], *done = s_done[w];
+    for (u32 i = lane; i < FIN_WORDS; i += kWave) tie[i] = 0;
+    for (u32 i = lane; i < GA_WORDS; i += kWave) done[i] = 0;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    for (u32 i = lane; i < c; i += kWave) {
+        u32 ps, v;
+        record(i, ps, v);
+        const u32 q = ps - e0;
+        if (v >> 31) atomicOr(&tie[q >> 5], 1u << (q & 31u));
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    bool settled = false;
+    for (u32 i = lane; i < c; i += kWave) {
+        u32 ps, v;
+        record(i, ps, v);
+        if (v >> 31) continue;               // (a group is handled by its head: the one member without the flag)
+        const u32 q = ps - e0, a = q + 1u;
+        // members = the flagged slots that follow the head without a gap
+        const u64 win = (((u64)tie[(a >> 5) + 1u] << 32) | (u64)tie[a >> 5]) >> (a & 31u);
+        const u32 g = win == ~0ull ? 65u : 1u + (u32)__builtin_ctzll(~win);
+        if (g > (u32)FIN_MAX) continue;
+        u32 sfx[FIN_MAX], rk[FIN_MAX];
+        u64 key[FIN_MAX];
+#pragma unroll
+        for (int j = 0; j < FIN_MAX; ++j) {
+            sfx[j] = 0;
+            key[j] = 0;
+            rk[j] = 0;
+            if ((u32)j < g) {
+                sfx[j] = j == 0 ? v : sa_out[ps + j];
+                const u64 at = (u64)sfx[j] + f.h0;
+                if (at < f.n) key[j] = text_key_at(f.codes, (u32)at, f.code_bits, f.key_syms, f.plus_one, f.n);
+            }
+        }
+        bool same = false;
+#pragma unroll
+        for (int j = 0; j < FIN_MAX; ++j) {
+#pragma unroll
+            for (int l = j + 1; l < FIN_MAX; ++l) {
+                if ((u32)l < g) {
+                    same |= key[j] == key[l];
+                    rk[l] += key[j] < key[l] ? 1u : 0u;
+                    rk[j] += key[j] < key[l] ? 0u : 1u;
+                }
+            }
+        }
+        if (same) continue;
+        settled = true;
+#pragma unroll
+        for (int j = 0; j < FIN_MAX; ++j) {
+            if ((u32)j < g) {
+                sa_out[ps + rk[j]] = sfx[j];
+                atomicOr(&done[(q + j) >> 5], 1u << ((q + j) & 31u));
+            }
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    if (__ballot(settled) == 0) return;      // nothing dropped: the block stays as it is
+    // the records of the groups that stay, packed to the front of the block (a record moves down or stays: the 64 records
+    // of a trip are read before any of them is written, and what they overwrite was read in this trip or an earlier one)
+    u32 kept = 0;
+    for (u32 base = 0; base < c; base += kWave) {
+        const u32 i = base + lane;
+        u32 ps = 0, v = 0;
+        bool keep = false;
+        if (i < c) {
+            record(i, ps, v);
+            const u32 q = ps - e0;
+            keep = ((done[q >> 5] >> (q & 31u)) & 1u) == 0;
+        }
+        const u64 km = __ballot(keep);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        if (keep) {
+            const u32 o = e0 + kept + mbcnt(km);
+            st_pos[o] = ps;
+            st_idx[o] = v;
+        }
+        kept += (u32)__popcll(km);
+    }
+    if (lane == 0) blk_cnt[t] = kept | ((c - kept) << 16);      // (InBlkCnt)
 }
 
 // ---- local sort --------------------------------------------------------------------------------
@@ -1730,12 +1869,23 @@ int msd_suffix_sort(DeviceCtx *ctx, const TextKeys *text, uint32_t n, int key_bi
     if (knob("PSS_MSD_SLOW_LOCAL")) PSS_TRY(mark());
     }
     if (fused) {
+        // small groups are settled here and now (msd_finish_kernel); the list is made of what they leave.  The count of
+        // the settled suffixes comes down with the list's length, in the high word of the same sum.
+        const bool finish = knob("PSS_MSD_NO_FINISH") == nullptr;
+        if (finish) {
+            const int ks = std::min(64 / text->code_bits, 16);
+            const MsdFinish fin{text->codes, text->code_bits, ks, text->plus_one,
+                                (u32)(text->drop ? text->key_chars - 1 : text->key_chars), n};
+            hipLaunchKernelGGL(msd_finish_kernel, dim3((nt + 3) / 4), dim3(256), 0, s, (const MsdTile *)tiles_all, blk_cnt, nt,
+                               active->st_pos, active->st_idx, sa_out, fin);
+        }
         PSS_TRY(device_excl_scan(ctx, InBlkCnt{blk_cnt}, nt, partial, d_total, dst_off));
         hipLaunchKernelGGL(msd_gather_kernel, dim3((nt + 3) / 4), dim3(256), 0, s, (const MsdTile *)tiles_all, blk_cnt, dst_off, nt,
                            active->st_pos, active->st_idx, active->pos, active->idx, active->grp);
         PSS_HIP(hipMemcpyAsync(h_small, d_total, 8, hipMemcpyDeviceToHost, s));
         PSS_HIP(hipStreamSynchronize(s));
         active->count = h_small[0];
+        if (stats) stats->finished = h_small[1];
     }
     PSS_HIP(hipGetLastError());
     if (stats) {

@@ -41,6 +41,7 @@
 #include "radix_sort.h"
 #include "sa_build.h"
 #include "scan.h"
+#include "text_keys.h"
 #include "anchor_impl.h"
 
 #include <algorithm>
@@ -593,6 +594,7 @@ int sa_build_device(DeviceCtx *ctx, const void *d_T, void *d_SA, int32_t n_in, u
                 st.msd_tiles = ms.tiles;
                 st.msd_slow_tiles = ms.slow_tiles;
                 st.msd_lookback = ms.lookback;
+                st.msd_finished = ms.finished;
                 st.msd_ms_g1 = ms.ms_g1;
                 st.msd_ms_g2 = ms.ms_g2;
                 st.msd_ms_local = ms.ms_local;

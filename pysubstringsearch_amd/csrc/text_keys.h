@@ -49,4 +49,33 @@ __device__ __forceinline__ void text_keys16(const u8 *codes, u32 i0, int b, int 
     }
 }
 
+// The key of ONE suffix: the k <= 16 symbols from text position j on, b bits each, first symbol highest (the text rounds of
+// sa_build.hip, the finishing kernel of msd_sort.hip).
+__device__ __forceinline__ u64 text_key_at(const u8 *codes, u32 j, int b, int k, int plus_one, u32 n)
+{
+    // k <= 16 symbols starting at j (codes are zero padded past n).  The address is random per lane,
+    // and a scattered load costs the address unit one cycle per lane and instruction whatever its
+    // width: two aligned 16-byte loads and a funnel shift instead of six 4-byte loads
+    // (`words` 2^29: 78.4 -> 76.0 ms).
+    const uint4 *q = reinterpret_cast<const uint4 *>(codes + (j & ~15u));
+    const uint4 a = q[0], c = q[1];
+    const u64 x0 = (u64)a.x | ((u64)a.y << 32), x1 = (u64)a.z | ((u64)a.w << 32);
+    const u64 x2 = (u64)c.x | ((u64)c.y << 32), x3 = (u64)c.z | ((u64)c.w << 32);
+    const bool up = (j & 8u) != 0;
+    const u32 s8 = (j & 7u) * 8u;
+    const u64 l0 = up ? x1 : x0, l1 = up ? x2 : x1, l2 = up ? x3 : x2;
+    const u64 w0 = s8 ? (l0 >> s8) | (l1 << (64 - s8)) : l0;
+    const u64 w1 = s8 ? (l1 >> s8) | (l2 << (64 - s8)) : l1;
+    u64 key = 0;
+#pragma unroll
+    for (int c = 0; c < 16; ++c) {
+        if (c < k) {
+            u32 v = (u32)((c < 8 ? w0 : w1) >> ((c & 7) * 8)) & 0xffu;
+            if (plus_one) v = ((u64)j + c < n) ? v + 1u : 0u;
+            key = (key << b) | v;
+        }
+    }
+    return key;
+}
+
 }  // namespace pss
