@@ -58,6 +58,7 @@
 #include "msd_sort.h"
 
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 #include "prims.h"
@@ -1294,6 +1295,10 @@ constexpr u32 LS_KMAX = 64;
 #define PSS_LS_GROUP 1
 #endif
 constexpr int LS_GROUP = PSS_LS_GROUP;              // rows ranked / written out together: their LDS reads are issued back to back
+#ifndef PSS_LS_SLOT_GROUP
+#define PSS_LS_SLOT_GROUP 1
+#endif
+constexpr int LS_SLOT_GROUP = PSS_LS_SLOT_GROUP;    // rows whose slot atomics are in flight together
 constexpr int LS_WINDOW = PSS_LS_WINDOW;                        // members of its bin every element reads unconditionally (bins average 1.3)
 
 __global__ __launch_bounds__(256) void msd_tile_desc_kernel(const u32 *cstart, const u32 *tile_first, u32 nt, u32 ne, u32 n,
@@ -1327,6 +1332,31 @@ __device__ __forceinline__ void lds_barrier()
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
+// The rows of a tile (row r = positions r * 512 + tid), G at a time: every row but the last one is full, so a group
+// that ends before the last row runs f(true, g) with no lane predicate at all, under a scalar branch; the group that
+// holds the last row runs f(false, g), the one body that tests p < count.
+template <int G, class F>
+__device__ __forceinline__ void ls_rows(u32 rows, F &&f)
+{
+    static_assert(MSD_IPT % G == 0, "the groups tile the rows");
+    // (every phase compares the row count anew, a scalar compare and branch per group: shared between the phases, the
+    // sixteen outcomes are sixteen lane masks alive for the whole tile)
+    rows = (u32)__builtin_amdgcn_readfirstlane((int)rows);
+    asm volatile("" : "+s"(rows));
+#pragma unroll
+    for (int g = 0; g < MSD_IPT; g += G) {
+        // (two tests of their own, not if / else: each stays a scalar compare and branch)
+        if ((u32)(g + G) < rows) {
+            f(std::true_type{}, g);
+            asm volatile("");      // (keeps the two bodies apart: merged, every row is back under a lane mask)
+        }
+        if (rows - 1u - (u32)g < (u32)G) {
+            asm volatile("");      // (or this test is folded into the tail's lane mask, and every row computes one)
+            f(std::false_type{}, g);
+        }
+    }
+}
+
 // A tile lives ~3 us, and what it needs first -- its descriptor, then the starts of its buckets and its
 // elements -- are dependent trips to HBM of ~1 us each: one workgroup per tile leaves the CU waiting for
 // memory most of the time.  The workgroups therefore persist (two per CU) and walk over the tiles with the
@@ -1353,19 +1383,19 @@ __global__ __launch_bounds__(MSD_BLOCK, 4) void msd_local_fast_kernel(const u64 
     u32 *const hist2 = hist + LS_WORDS;
     u32 *const scr = reinterpret_cast<u32 *>(&exch[MSD_TILE - 8]);      // a tile never reaches these slots (MSD_MAX_BUCKET)
     u32 &s_fail = scr[MSD_WAVES + 2];
-    const u32 tid = threadIdx.x;
+    u32 tid = threadIdx.x;
     const u32 stride = gridDim.x;
     u32 t = blockIdx.x;
     if (t >= nt) return;
     MsdTile cur = tiles[t];
     MsdTile nxt = t + stride < nt ? tiles[t + stride] : MsdTile{0, 0, 0, 0};
-    u64 pe[MSD_IPT];          // prefetched raw elements of the tile about to be sorted
+    u64 pe[MSD_IPT];          // prefetched raw elements of the tile about to be sorted (rows beyond the tile: left as they are)
     auto prefetch = [&](const MsdTile &d) {
-#pragma unroll
-        for (int r = 0; r < MSD_IPT; ++r) {
+        const u64 *const src = in + d.e0;
+        ls_rows<1>((d.count + MSD_BLOCK - 1) / MSD_BLOCK, [&](auto full, int r) __attribute__((always_inline)) {
             const u32 p = r * MSD_BLOCK + tid;
-            pe[r] = p < d.count ? in[d.e0 + p] : 0ull;
-        }
+            if (decltype(full)::value || p < d.count) pe[r] = src[p];
+        });
     };
     prefetch(cur);
     // Six barriers per tile, not nine: the counters are zeroed for the NEXT tile while this one is permuted (they are not
@@ -1388,23 +1418,23 @@ __global__ __launch_bounds__(MSD_BLOCK, 4) void msd_local_fast_kernel(const u64 
         const u64 tag_base = (u64)cur.tag0 << (rem_bits + idx_bits);
         const int sort_bits = rem_bits + seg_bits;
         const int bin_shift = idx_bits + (sort_bits > LS_BIN_BITS ? sort_bits - LS_BIN_BITS : 0);
+        // Nothing derived from the thread number is carried from tile to tile: hoisted out of this loop, the lane masks
+        // and addresses of every phase outgrow the scalar registers and come back as lane moves in every row.
+        asm volatile("" : "+v"(tid));
+        const u32 wave_no = (u32)__builtin_amdgcn_readfirstlane((int)(tid >> 6));      // this wave's number, as a scalar
         u64 e[MSD_IPT];
-#pragma unroll
-        for (int r = 0; r < MSD_IPT; ++r) {
-            e[r] = ~0ull;
-            if ((u32)r < rows) {
-                const u32 p = r * MSD_BLOCK + tid;
-                if (p < count) {
-                    // the element carries its bucket (G2 put it there): [bucket inside the tile | remaining key bits | index]
-                    e[r] = pe[r] - tag_base;
-                    const u32 bin = (u32)(e[r] >> bin_shift);
-                    atomicAdd(&hist[bin >> 1], 1u << (16u * (bin & 1u)));    // count now; the slot is taken after the scan
-                }
+        ls_rows<1>(rows, [&](auto full, int r) __attribute__((always_inline)) {
+            if (decltype(full)::value || r * MSD_BLOCK + tid < count) {
+                // the element carries its bucket (G2 put it there): [bucket inside the tile | remaining key bits | index]
+                e[r] = pe[r] - tag_base;
+                const u32 bin = (u32)(e[r] >> bin_shift);
+                atomicAdd(&hist[bin >> 1], 1u << (16u * (bin & 1u)));    // count now; the slot is taken after the scan
             }
-        }
-        // the raw elements are consumed: their registers take the next tile while this one is sorted
+        });
+        // the raw elements are consumed: their registers take the next tile while this one is sorted (past the last
+        // tile `nxt` is empty: no rows, no loads)
         const bool more = t + stride < nt;
-        if (more) prefetch(nxt);
+        prefetch(nxt);
         lds_barrier();
         if (tid == 0) {                    // the previous tile is over for every wave: its record count, the flags for this one
             if (em && prev_ok) em->blk_cnt[prev_t] = scr[MSD_WAVES + 3];
@@ -1424,11 +1454,16 @@ __global__ __launch_bounds__(MSD_BLOCK, 4) void msd_local_fast_kernel(const u64 
                 c[2 * j + 1] = wv >> 16;
                 sum += c[2 * j] + c[2 * j + 1];
             }
-            const u32 incl = wave_incl_sum(sum);
-            if (lane_id() == kWave - 1) scr[wave_id()] = incl;
+            const u32 incl = wave_incl_sum_dpp(sum);
+            if ((tid & (kWave - 1u)) == kWave - 1u) scr[wave_no] = incl;
             lds_barrier();
+            // the totals of the waves before mine: all eight read at once, chosen by the (scalar) wave number
+            static_assert(MSD_WAVES == 8, "two 16-byte reads hold the totals of all waves");
+            const uint4 w03 = *reinterpret_cast<const uint4 *>(&scr[0]), w47 = *reinterpret_cast<const uint4 *>(&scr[4]);
+            const u32 wtot[MSD_WAVES] = {w03.x, w03.y, w03.z, w03.w, w47.x, w47.y, w47.z, w47.w};
             u32 ex = incl - sum;
-            for (int w = 0; w < wave_id(); ++w) ex += scr[w];
+#pragma unroll
+            for (u32 w = 0; w + 1 < (u32)MSD_WAVES; ++w) ex += w < wave_no ? wtot[w] : 0u;
 #pragma unroll
             for (int j = 0; j < LS_WPT; ++j) {
                 const u32 lo = ex, hi = ex + c[2 * j];
@@ -1437,18 +1472,24 @@ __global__ __launch_bounds__(MSD_BLOCK, 4) void msd_local_fast_kernel(const u64 
             }
         }
         lds_barrier();
+        // (a second returning atomic on the bin's running start hands out the slot: one more LDS atomic per
+        // element, sixteen fewer registers held across the prefetch).  LS_SLOT_GROUP rows have their atomics in flight
+        // together before the first of them is waited for.
+        ls_rows<LS_SLOT_GROUP>(rows, [&](auto full, int g) __attribute__((always_inline)) {
+            u32 slot[LS_SLOT_GROUP], sh[LS_SLOT_GROUP];
 #pragma unroll
-        for (int r = 0; r < MSD_IPT; ++r) {
-            if ((u32)r < rows) {
-                const u32 p = r * MSD_BLOCK + tid;
-                // (a second returning atomic on the bin's running start hands out the slot: one more LDS atomic per
-                // element, sixteen fewer registers held across the prefetch)
-                if (p < count) {
-                    const u32 bin = (u32)(e[r] >> bin_shift), sh = 16u * (bin & 1u);
-                    exch[(atomicAdd(&hist2[bin >> 1], 1u << sh) >> sh) & 0xffffu] = e[r];
+            for (int j = 0; j < LS_SLOT_GROUP; ++j) {
+                if (decltype(full)::value || (g + j) * MSD_BLOCK + tid < count) {
+                    const u32 bin = (u32)(e[g + j] >> bin_shift);
+                    sh[j] = 16u * (bin & 1u);
+                    slot[j] = atomicAdd(&hist2[bin >> 1], 1u << sh[j]);
                 }
             }
-        }
+#pragma unroll
+            for (int j = 0; j < LS_SLOT_GROUP; ++j) {
+                if (decltype(full)::value || (g + j) * MSD_BLOCK + tid < count) exch[(slot[j] >> sh[j]) & 0xffffu] = e[g + j];
+            }
+        });
         // sentinels behind the tile: the ranking window of the last bins reads them (count + 7 < the scalars' slots: MSD_TILE_CAP)
         if (tid < (u32)LS_WINDOW) exch[count + tid] = ~0ull;
         lds_barrier();
@@ -1459,9 +1500,11 @@ __global__ __launch_bounds__(MSD_BLOCK, 4) void msd_local_fast_kernel(const u64 
         // elements) finishes in a loop.
         const u16 *const starts16 = reinterpret_cast<const u16 *>(hist);      // starts16[bin] = first slot of the bin
         u32 rk[MSD_IPT];
+        u32 rank_rows = (u32)__builtin_amdgcn_readfirstlane((int)rows);
+        asm volatile("" : "+s"(rank_rows));      // (as in ls_rows)
 #pragma unroll
         for (int g = 0; g < MSD_IPT; g += LS_GROUP) {
-            if ((u32)g < rows) {
+            if ((u32)g < rank_rows) {
                 u64 x[LS_GROUP];
                 u32 s0[LS_GROUP], sm[LS_GROUP];
 #pragma unroll
@@ -1493,8 +1536,9 @@ __global__ __launch_bounds__(MSD_BLOCK, 4) void msd_local_fast_kernel(const u64 
                 for (int j = 0; j < LS_GROUP; ++j) {
                     // the window's last member still in my bin: the bin may go on (rare: bins average 1.3 elements) -- only then
                     // is its length looked up (the bin's end = the next bin's start)
-                    const u32 p = (g + j) * MSD_BLOCK + tid;
-                    if (p < count && ((y[j][LS_WINDOW - 1] ^ x[j]) >> bin_shift) == 0) {
+                    // (no lane predicate on the row: a lane past the tile ranks whatever its slot holds, and is asked
+                    // p < count only in here)
+                    if (((y[j][LS_WINDOW - 1] ^ x[j]) >> bin_shift) == 0 && (g + j) * MSD_BLOCK + tid < count) {
                         const u32 bin = (u32)(x[j] >> bin_shift) & (LS_BINS - 1u);
                         const u32 s1 = bin + 1u < LS_BINS ? (u32)starts16[min(bin + 1u, LS_BINS - 1u)] : count;
                         const u32 len = s1 - s0[j];
@@ -1507,9 +1551,6 @@ __global__ __launch_bounds__(MSD_BLOCK, 4) void msd_local_fast_kernel(const u64 
                     e[g + j] = x[j];
                     rk[g + j] = s0[j] + sm[j];
                 }
-            } else {
-#pragma unroll
-                for (int j = 0; j < LS_GROUP; ++j) rk[g + j] = 0;
             }
         }
         lds_barrier();
@@ -1517,56 +1558,61 @@ __global__ __launch_bounds__(MSD_BLOCK, 4) void msd_local_fast_kernel(const u64 
         if (failed) {
             if (tid == 0) fail_list[atomicAdd(fail_count, 1u)] = t;
         } else {
-#pragma unroll
-            for (int r = 0; r < MSD_IPT; ++r) {
-                if ((u32)r < rows) {
-                    const u32 p = r * MSD_BLOCK + tid;
-                    if (p < count) exch[rk[r]] = e[r];
-                }
-            }
+            ls_rows<1>(rows, [&](auto full, int r) __attribute__((always_inline)) {
+                if (decltype(full)::value || r * MSD_BLOCK + tid < count) exch[rk[r]] = e[r];
+            });
         }
         for (u32 i = tid; i < LS_WORDS; i += MSD_BLOCK) hist[i] = 0;      // (bin starts: last read in the ranking) for the next tile
         lds_barrier();
         if (!failed) {
-            // Output (msd_emit_tile with the loads of LS_GROUP rows in flight): suffix indices to sa_out[e0 ..]; a record for
-            // every element tied with a neighbour when the first rerank is fused, else bit 31 = "same key as my predecessor".
+            // Output, LS_GROUP rows with their loads in flight: suffix indices to sa_out[e0 ..], bit 31 = "same key as my
+            // predecessor" unless the first rerank is fused.  Fused, the array is written clean and a row only notes its two
+            // tie bits (bit r: row r owes a record -- it or its successor is tied --, bit 16 + r: tied with its predecessor);
+            // the records go out behind the rows.  One address per tile for the tile and one for the array: rows are a
+            // constant apart.
             const u32 imask = (u32)((1ull << idx_bits) - 1ull);
-            u32 *const s_count = &scr[MSD_WAVES + 3];
+            const u32 flag = em == nullptr ? 0x80000000u : 0u;
+            const u64 same = 1ull << idx_bits;
+            const u64 *const my = exch + tid;
+            u32 *const out = sa_out + e0 + tid;
+            u32 ties = 0;
+            ls_rows<LS_GROUP>(rows, [&](auto full, int g) __attribute__((always_inline)) {
+                u64 cur[LS_GROUP], prv[LS_GROUP], nxt[LS_GROUP];
 #pragma unroll
-            for (int g = 0; g < MSD_IPT; g += LS_GROUP) {
-                if ((u32)g < rows) {
-                    u64 cur[LS_GROUP], prv[LS_GROUP], nxt[LS_GROUP];
+                for (int j = 0; j < LS_GROUP; ++j) {
+                    const int o = (g + j) * MSD_BLOCK;
+                    cur[j] = my[o];
+                    prv[j] = o == 0 ? exch[tid - (tid != 0 ? 1u : 0u)] : my[o - 1];      // (position 0 has no predecessor: below)
+                    nxt[j] = my[o + 1];                                                 // (position 8191 + 1 is the first counter word)
+                }
 #pragma unroll
-                    for (int j = 0; j < LS_GROUP; ++j) {
-                        const u32 p = (g + j) * MSD_BLOCK + tid;
-                        cur[j] = exch[p];
-                        prv[j] = exch[p ? p - 1 : 0];
-                        nxt[j] = exch[p + 1];                                   // (position 8191 + 1 is the first counter word)
+                for (int j = 0; j < LS_GROUP; ++j) {
+                    keep_load(cur[j]);
+                    keep_load(prv[j]);
+                    keep_load(nxt[j]);
+                }
+#pragma unroll
+                for (int j = 0; j < LS_GROUP; ++j) {
+                    const int o = (g + j) * MSD_BLOCK;
+                    bool tie = (prv[j] ^ cur[j]) < same;      // equal above the index bits
+                    if (o == 0) tie = tie && tid != 0;
+                    // a full row has a successor inside the tile at every position (the last row is not empty)
+                    const bool tie_next = (nxt[j] ^ cur[j]) < same && (decltype(full)::value || o + tid + 1u < count);
+                    if (decltype(full)::value || o + tid < count) {
+                        out[o] = ((u32)cur[j] & imask) | (tie ? flag : 0u);
+                        ties |= ((tie || tie_next) ? 1u << (g + j) : 0u) | (tie ? 0x10000u << (g + j) : 0u);
                     }
-#pragma unroll
-                    for (int j = 0; j < LS_GROUP; ++j) {
-                        keep_load(cur[j]);
-                        keep_load(prv[j]);
-                        keep_load(nxt[j]);
-                    }
-#pragma unroll
-                    for (int j = 0; j < LS_GROUP; ++j) {
-                        const u32 p = (g + j) * MSD_BLOCK + tid;
-                        if (p < count) {
-                            const u64 kx = cur[j] >> idx_bits;
-                            const bool tie = p > 0 && (prv[j] >> idx_bits) == kx;
-                            const u32 sfx = (u32)cur[j] & imask;
-                            sa_out[e0 + p] = sfx | ((tie && em == nullptr) ? 0x80000000u : 0u);
-                            if (em != nullptr) {
-                                const bool tie_next = p + 1 < count && (nxt[j] >> idx_bits) == kx;
-                                if (tie || tie_next) {
-                                    const u32 slot = e0 + atomicAdd(s_count, 1u);
-                                    em->st_pos[slot] = e0 + p;
-                                    em->st_idx[slot] = sfx | (tie ? 0x80000000u : 0u);
-                                }
-                            }
-                        }
-                    }
+                }
+            });
+            if (em != nullptr) {
+                // the records of the few tied elements (0.4 % of natural text): a wave without any skips the loop
+                u32 *const s_count = &scr[MSD_WAVES + 3];
+                for (u32 m = ties & 0xffffu; m != 0; m &= m - 1u) {
+                    const u32 r = (u32)__builtin_ctz(m);
+                    const u32 p = r * MSD_BLOCK + tid;
+                    const u32 slot = e0 + atomicAdd(s_count, 1u);
+                    em->st_pos[slot] = e0 + p;
+                    em->st_idx[slot] = ((u32)exch[p] & imask) | ((ties >> (16u + r)) << 31);
                 }
             }
         }

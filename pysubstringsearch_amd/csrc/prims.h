@@ -52,6 +52,20 @@ __device__ __forceinline__ u32 wave_incl_sum(u32 v)
     }
     return v;
 }
+// The same sum by DPP adds: shifts by 1, 2, 4, 8 inside every row of 16 lanes (a lane whose source lies outside
+// its row adds the `old` operand, 0), then lane 15 of rows 0 / 2 broadcast into rows 1 / 3 and lane 31 into the upper
+// half.  Six v_add_u32 with a DPP operand: no lane-number compares (their masks are loop invariants that a kernel
+// short of scalar registers ends up spilling), no ds_bpermute.
+__device__ __forceinline__ u32 wave_incl_sum_dpp(u32 v)
+{
+    v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);      // row_shr:1
+    v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);      // row_shr:2
+    v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);      // row_shr:4
+    v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);      // row_shr:8
+    v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);      // row_bcast:15 into rows 1 and 3
+    v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);      // row_bcast:31 into rows 2 and 3
+    return v;
+}
 __device__ __forceinline__ u64 wave_incl_sum64(u64 v)
 {
     const int lane = lane_id();
