@@ -33,6 +33,7 @@ static u64 anchored_query_bytes(const u64 *qoff, u32 nq, const u8 *anchors)
 static void anchored_rewrite(const u8 *qbytes, const u64 *qoff, u32 nq, const u8 *anchors, u8 *out, u64 *out_off, u8 *flags)
 {
     u64 at = 0;
+    newline_flags(qbytes, qoff, nq, kAnchorVoid, flags);
     for (u32 q = 0; q < nq; ++q) {
         const u8 *pat = qbytes + qoff[q];
         const u64 m = qoff[q + 1] - qoff[q];
@@ -41,7 +42,7 @@ static void anchored_rewrite(const u8 *qbytes, const u64 *qoff, u32 nq, const u8
         if (m) memcpy(out + at, pat, m);
         at += m;
         if (anchors[q] & kAnchorEnd) out[at++] = '\n';
-        flags[q] = anchors[q] | ((m && memchr(pat, '\n', m)) ? kAnchorVoid : (u8)0);
+        flags[q] |= anchors[q];
     }
     out_off[nq] = at;
     memset(out + at, 0, 32);
@@ -87,11 +88,7 @@ __global__ __launch_bounds__(256) void anchored_hits_kernel(const ChunkDesc *chu
                                                               const u8 *edge, const u64 *hit_off, u64 H, u32 *start_out, u32 *len_out)
 {
     for (u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x; t < H; t += (u64)gridDim.x * blockDim.x) {
-        u64 a = 0, b = nvq;
-        while (b - a > 1) {
-            const u64 mid = a + (b - a) / 2;
-            if (hit_off[mid] <= t) a = mid; else b = mid;
-        }
+        const u64 a = pair_of_hit(hit_off, nvq, t);
         const ChunkDesc ch = chunks[(u32)(a % nc)];
         const u8 f = flags[a / nc], e = edge[a];
         const u32 k = (u32)(t - hit_off[a]);

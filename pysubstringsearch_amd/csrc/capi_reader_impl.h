@@ -1262,6 +1262,33 @@ extern "C" int pss_reader_count_anchored_batch(pss_reader *r, const uint8_t *qby
 
 namespace {
 
+// The group offsets of an all-terms or a sequence batch against its n members (`noun`: "terms" or "segments"): they run
+// from 0 to n and never decrease.  group_ok(g) is the batch's own check of group g, made once g's offsets are known good;
+// it states its own error.  The reader is looked at last, as pss.h says: a malformed batch is reported as such with or
+// without one.
+template <typename GroupOk>
+int group_args(const pss_reader *r, const char *who, const char *noun, const uint64_t *group_offsets, uint32_t ngroups, uint32_t n,
+               GroupOk group_ok)
+{
+    if (group_offsets[0] != 0 || group_offsets[ngroups] != n) {
+        set_error("%s: the group offsets run from %llu to %llu, not from 0 to the %u %s", who, (unsigned long long)group_offsets[0],
+                  (unsigned long long)group_offsets[ngroups], n, noun);
+        return PSS_EINVAL;
+    }
+    for (uint32_t g = 0; g < ngroups; ++g) {
+        if (group_offsets[g + 1] < group_offsets[g] || group_offsets[g + 1] > n) {
+            set_error("%s: the group offsets decrease or pass the %u %s at group %u", who, n, noun, g);
+            return PSS_EINVAL;
+        }
+        if (!group_ok(g)) return PSS_EINVAL;
+    }
+    if (!r) {
+        set_error("%s: bad arguments (no reader)", who);
+        return PSS_EINVAL;
+    }
+    return PSS_OK;
+}
+
 // The argument checks of the three all-terms calls (out_ok: the call's own output argument is usable).
 int terms_args(const pss_reader *r, const char *who, const uint8_t *tbytes, const uint64_t *toffsets, uint32_t nterms,
                const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *exclude, bool out_ok)
@@ -1280,28 +1307,12 @@ int terms_args(const pss_reader *r, const char *who, const uint8_t *tbytes, cons
             return PSS_EINVAL;
         }
     }
-    if (group_offsets[0] != 0 || group_offsets[ngroups] != nterms) {
-        set_error("%s: the group offsets run from %llu to %llu, not from 0 to the %u terms", who, (unsigned long long)group_offsets[0],
-                  (unsigned long long)group_offsets[ngroups], nterms);
-        return PSS_EINVAL;
-    }
-    for (uint32_t g = 0; g < ngroups; ++g) {
-        if (group_offsets[g + 1] < group_offsets[g] || group_offsets[g + 1] > nterms) {
-            set_error("%s: the group offsets decrease or pass the %u terms at group %u", who, nterms, g);
-            return PSS_EINVAL;
-        }
+    return group_args(r, who, "terms", group_offsets, ngroups, nterms, [&](uint32_t g) {
         bool include = false;
         for (uint64_t t = group_offsets[g]; t < group_offsets[g + 1] && !include; ++t) include = exclude[t] == 0;
-        if (!include) {
-            set_error("%s: group %u has no include term (\"everything except\" is not a search)", who, g);
-            return PSS_EINVAL;
-        }
-    }
-    if (!r) {                   // (last, as pss.h says: a malformed batch is reported as such with or without a reader)
-        set_error("%s: bad arguments (no reader)", who);
-        return PSS_EINVAL;
-    }
-    return PSS_OK;
+        if (!include) set_error("%s: group %u has no include term (\"everything except\" is not a search)", who, g);
+        return include;
+    });
 }
 
 SearchRequest terms_request(const uint8_t *tbytes, const uint64_t *toffsets, uint32_t nterms, const uint64_t *group_offsets,
@@ -1356,30 +1367,17 @@ int seq_args(const pss_reader *r, const char *who, const uint8_t *sbytes, const 
             set_error("%s: segment %u is empty (two wildcards in a row are one: leave it out)", who, t);
             return PSS_EINVAL;
         }
-    if (group_offsets[0] != 0 || group_offsets[ngroups] != nsegs) {
-        set_error("%s: the group offsets run from %llu to %llu, not from 0 to the %u segments", who, (unsigned long long)group_offsets[0],
-                  (unsigned long long)group_offsets[ngroups], nsegs);
-        return PSS_EINVAL;
-    }
-    for (uint32_t g = 0; g < ngroups; ++g) {
-        if (group_offsets[g + 1] < group_offsets[g] || group_offsets[g + 1] > nsegs) {
-            set_error("%s: the group offsets decrease or pass the %u segments at group %u", who, nsegs, g);
-            return PSS_EINVAL;
-        }
+    return group_args(r, who, "segments", group_offsets, ngroups, nsegs, [&](uint32_t g) {
         if (group_offsets[g + 1] == group_offsets[g]) {
             set_error("%s: group %u has no segment (a pattern of wildcards alone is not a search)", who, g);
-            return PSS_EINVAL;
+            return false;
         }
         if (anchors[g] > (PSS_ANCHOR_START | PSS_ANCHOR_END)) {
             set_error("%s: anchors[%u] = %u (0, PSS_ANCHOR_START = 1, PSS_ANCHOR_END = 2 or both)", who, g, (unsigned)anchors[g]);
-            return PSS_EINVAL;
+            return false;
         }
-    }
-    if (!r) {                   // (last, as for the all-terms calls: a malformed batch is reported as such with or without a reader)
-        set_error("%s: bad arguments (no reader)", who);
-        return PSS_EINVAL;
-    }
-    return PSS_OK;
+        return true;
+    });
 }
 
 SearchRequest seq_request(const uint8_t *sbytes, const uint64_t *soffsets, uint32_t nsegs, const uint64_t *group_offsets,

@@ -1,7 +1,7 @@
 // fold_impl.h -- entries that contain a pattern under ASCII case folding (include/pss.h, pss_reader_search_icase_batch;
 // DESIGN.md 4.13).
 // Part of search.hip: included there behind sequence_impl.h, whose group geometry (TG lanes per surviving hit) and pair
-// spaces it shares; not a header for anybody else.
+// spaces it shares, and behind entry_scan_impl.h (fold8, fold_equal, entry_scan); not a header for anybody else.
 //
 // The suffix arrays are exact-byte, so the host turns every pattern into its SEED -- the longest window with at most F
 // ASCII letters -- and the seed into its 2^f concrete spellings, in ascending byte order (fold_seed and fold_spellings below: what
@@ -10,7 +10,7 @@
 // ascending byte order have disjoint, ascending suffix-array intervals, so fold_union_kernel only adds the counts up, and
 // hit k of a (pattern, chunk) pair is found by walking the pair's at most 64 counts.  fold_hits_kernel verifies the
 // whole pattern around each seed hit under fold and takes the entry's bounds; fold_dedupe_kernel keeps the hit of an
-// entry's LEFTMOST folded match: hit_entry's dedupe, under fold.  Every match alignment holds exactly one seed
+// entry's LEFTMOST folded match: hit_entry's dedupe, under fold (entry_scan<true>).  Every match alignment holds exactly one seed
 // occurrence, in exactly one spelling, so an entry keeps exactly one hit whatever mix of spellings it holds.
 // A pattern that holds a 0x0A occurs in no entry and is flagged void: its pairs count no hit.
 
@@ -49,35 +49,6 @@ void fold_spellings(const u8 *seed, u64 len, u32 f, u8 *out)
     }
 }
 
-// Bytes of an 8-byte word under fold: 0x20 is set on the bytes in 'A' .. 'Z' and on no other.  Exact per byte, without
-// carries between bytes: the low seven bits of a byte plus 0x3f (0x25) set its high bit iff they are >= 0x41 (>= 0x5b),
-// and the sums stay below 0x100; a byte >= 0x80 is taken out by its own high bit.
-__device__ __forceinline__ u64 fold8(u64 w)
-{
-    const u64 H = 0x8080808080808080ull;
-    const u64 l = w & ~H;
-    const u64 ge_a = l + 0x3f3f3f3f3f3f3f3full, gt_z = l + 0x2525252525252525ull;
-    return w | ((ge_a & ~gt_z & ~w & H) >> 2);
-}
-
-// Is pat (folded, plen bytes) what text[s, s + plen) folds to?  The caller knows s + plen <= n.  Loads reach 15 bytes past
-// the last compared byte of the text and 10 past the pattern's end (load_u64_unaligned at the pattern's last byte takes
-// three aligned dwords).
-__device__ __forceinline__ bool fold_equal(const u8 *text, u32 s, const u8 *pat, u32 plen)
-{
-    for (u32 i = 0; i < plen; i += 8) {
-        u64 a = fold8(load_text8(text + s + i)), b = load_u64_unaligned(pat + i);
-        const u32 rem = plen - i;
-        if (rem < 8) {
-            const u64 mask = (1ull << (8 * rem)) - 1ull;
-            a &= mask;
-            b &= mask;
-        }
-        if (a != b) return false;
-    }
-    return true;
-}
-
 // One lane per (pattern, chunk) pair: the hits of the pair are the hits of its spellings, one interval behind the other.
 // (Disjoint intervals of one suffix array: the sum is at most n and fits u32.)
 __global__ __launch_bounds__(256) void fold_union_kernel(u32 nc, const u64 *goff, const u8 *fvoid, const u32 *cnt, u64 ngq, u32 *p_cnt)
@@ -100,11 +71,7 @@ __global__ __launch_bounds__(256) void fold_hits_kernel(const ChunkDesc *chunks,
                                                           const u64 *hit_off, u64 H, u32 *start_out, u32 *len_out, u32 *m_out)
 {
     for (u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x; t < H; t += (u64)gridDim.x * blockDim.x) {
-        u64 a = 0, b = ngq;
-        while (b - a > 1) {
-            const u64 mid = a + (b - a) / 2;
-            if (hit_off[mid] <= t) a = mid; else b = mid;
-        }
+        const u64 a = pair_of_hit(hit_off, ngq, t);
         const u32 g = (u32)(a / nc), c = (u32)(a % nc);
         const ChunkDesc ch = chunks[c];
         u32 k = (u32)(t - hit_off[a]);
@@ -128,44 +95,12 @@ __global__ __launch_bounds__(256) void fold_hits_kernel(const ChunkDesc *chunks,
     }
 }
 
-// Does a folded occurrence of pat START in text[s, m)?  It may reach past m.  Called by the TG lanes of one group together
-// (gl = lane inside the group, gbase = the group's first lane); every lane returns the group's answer.  entry_holds with
-// folding: the text word and the one behind it are folded in registers, the bytes equal to the pattern's first folded
-// byte are the candidates, and a candidate is checked against the pattern's first min(8, plen) bytes in registers; only
-// a longer pattern whose first 8 match goes back to memory.  The caller's match at m lies inside the chunk, so every
-// start position p < m has p + plen < n; loads reach at most 23 bytes past a start position and 15 past p + plen (the
-// text is readable 128 bytes past n, a pattern 16 past its end).
+// Does a folded occurrence of pat START in text[s, m)?  entry_scan under fold over the start positions s .. m - 1, for
+// the TG lanes of one group together.  The match may reach past m: that is safe only because the caller's own match at
+// m lies inside the chunk, so every start position p < m has p + plen < n.
 __device__ __forceinline__ bool fold_starts_before(const ChunkDesc &ch, u32 s, u32 m, const u8 *pat, u32 plen, u32 gl, u32 gbase)
 {
-    if (m <= s) return false;
-    const u32 last = m - 1;                                      // the last start position
-    const u64 first = 0x0101010101010101ull * pat[0];
-    const u64 pmask = plen >= 8 ? ~0ull : (1ull << (8 * plen)) - 1ull;
-    const u64 pk = load_u64_unaligned(pat) & pmask;
-    for (u64 base = s; base <= last; base += 8 * TG) {           // (the same trips for every lane of the group)
-        const u64 p64 = base + 8 * gl;
-        bool found = false;
-        if (p64 <= last) {
-            const u32 p = (u32)p64;
-            const u64 w = fold8(load_text8(ch.text + p)), nxt = fold8(load_text8(ch.text + p + 8));
-            u64 cand = zero_bytes(w ^ first);
-            const u32 nv = last - p + 1;                         // start positions of this word in front of m
-            if (nv < 8) cand &= (1ull << (8 * nv)) - 1ull;
-            while (cand && !found) {
-                const u32 k = (u32)(__builtin_ctzll(cand) >> 3);
-                cand &= cand - 1;
-                const u64 x = k ? (w >> (8 * k)) | (nxt << (64 - 8 * k)) : w;     // fold(text[p + k, p + k + 8))
-                if ((x & pmask) == pk) found = plen <= 8 || fold_equal(ch.text, p + k, pat, plen);
-            }
-        }
-        // The ballot runs while the groups of a wavefront are on different paths (other hits, other patterns, other trip
-        // counts); it counts the active lanes only, and only the group's own TG bits are read.  INVARIANT, as in
-        // entry_holds: the TG lanes of a group reach every ballot together -- every branch between the kernel's loop entry
-        // and this line depends on group-wide values only (t, len[t], s, m, plen, base), and the per-lane `p64 <= last`
-        // branch closes above.  A lane that took a path of its own would split the group's ballot.
-        if ((u32)(__ballot(found) >> gbase) & ((1u << TG) - 1u)) return true;
-    }
-    return false;
+    return m > s && entry_scan<true, false>(ch, s, m - 1, pat, plen, gl, gbase) != kNone;
 }
 
 // TG lanes per hit that fold_hits_kernel left standing: the hit is kept iff no folded occurrence of the pattern starts
@@ -179,11 +114,7 @@ __global__ __launch_bounds__(256) void fold_dedupe_kernel(const ChunkDesc *chunk
     const u64 step = (u64)gridDim.x * blockDim.x / TG;
     for (u64 t = ((u64)blockIdx.x * blockDim.x + threadIdx.x) / TG; t < H; t += step) {
         if (len[t] == kSkip) continue;
-        u64 a = 0, b = ngq;
-        while (b - a > 1) {
-            const u64 mid = a + (b - a) / 2;
-            if (hit_off[mid] <= t) a = mid; else b = mid;
-        }
+        const u64 a = pair_of_hit(hit_off, ngq, t);
         const u32 g = (u32)(a / nc);
         const ChunkDesc ch = chunks[(u32)(a % nc)];
         const bool dup = fold_starts_before(ch, start[t], mpos[t], fbytes + foff[g], (u32)(foff[g + 1] - foff[g]), gl, gbase);

@@ -102,12 +102,7 @@ __global__ __launch_bounds__(256) void emit_ids_kernel(const ChunkDesc *chunks, 
 {
     for (u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x; t < H; t += (u64)gridDim.x * blockDim.x) {
         if (len[t] == kSkip) continue;
-        u64 a = 0, b = nvq;
-        while (b - a > 1) {
-            const u64 mid = a + (b - a) / 2;
-            if (hit_off[mid] <= t) a = mid; else b = mid;
-        }
-        const u32 c = (u32)(a % nc);
+        const u32 c = (u32)(pair_of_hit(hit_off, nvq, t) % nc);
         const u8 *text = chunks[c].text;
         const LineDesc ld = lines[c];
         const u32 s = start[t], blk = s >> ld.shift;

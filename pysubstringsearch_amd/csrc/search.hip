@@ -478,6 +478,18 @@ __device__ __forceinline__ u64 zero_bytes(u64 x)
     return ~(((x & m) + m) | x | m);
 }
 
+// The pair that owns hit t: the last pair with hit_off[pair] <= t.  hit_off is the exclusive scan of the pairs' hit counts
+// (hit_off[0] = 0, npairs >= 1), and t lies below hit_off[npairs].
+__device__ __forceinline__ u64 pair_of_hit(const u64 *hit_off, u64 npairs, u64 t)
+{
+    u64 a = 0, b = npairs;
+    while (b - a > 1) {
+        const u64 mid = a + (b - a) / 2;
+        if (hit_off[mid] <= t) a = mid; else b = mid;
+    }
+    return a;
+}
+
 // 64 bytes starting at the (unaligned) address p as eight little-endian words, fetched as the
 // five aligned 16-byte pieces around them: scattered 4-byte loads cost the address unit one
 // cycle per lane and instruction, so the scans below move 64 bytes with 5 load instructions
@@ -771,20 +783,19 @@ __global__ __launch_bounds__(MID_BLOCK) void mid_hit_scans_kernel(const u32 *len
     }
 }
 
+// One lane per hit: hit k of a pair is suffix sa[lo + k] of the pair's interval; hit_entry gives the entry's bounds, or
+// kSkip when an earlier hit of the pair's pattern stands for the entry.  The pattern of pair vq is query vq / nc -- or,
+// Driven (an all-terms or a sequence batch, whose pairs are (group, chunk) pairs), the driver term drv[vq] of the pair.
+template <bool Driven>
 __global__ __launch_bounds__(256) void hit_lines_kernel(const ChunkDesc *chunks, u32 nc, const u8 *qbytes,
                                                           const u64 *qoff, u64 nvq, const u32 *lo, const u64 *hit_off,
-                                                          u64 H, const MidState *mid, u32 *start_out, u32 *len_out)
+                                                          u64 H, const MidState *mid, u32 *start_out, u32 *len_out,
+                                                          const u32 *drv)
 {
     if (mid) H = mid->flag ? 0 : mid->hits;      // mid pipeline: the hit count never visits the host
     for (u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x; t < H; t += (u64)gridDim.x * blockDim.x) {
-        // owning (query, chunk): last vq with hit_off[vq] <= t
-        u64 a = 0, b = nvq;
-        while (b - a > 1) {
-            const u64 mid = a + (b - a) / 2;
-            if (hit_off[mid] <= t) a = mid; else b = mid;
-        }
-        const u64 vq = a;
-        const u32 q = (u32)(vq / nc), c = (u32)(vq % nc);
+        const u64 vq = pair_of_hit(hit_off, nvq, t);
+        const u32 q = Driven ? drv[vq] : (u32)(vq / nc), c = (u32)(vq % nc);
         const ChunkDesc ch = chunks[c];
         const u8 *pat = qbytes + qoff[q];
         const u32 plen = (u32)(qoff[q + 1] - qoff[q]);
@@ -1459,11 +1470,7 @@ __global__ __launch_bounds__(256) void hit_bounds_kernel(const ChunkDesc *chunks
                                                            u64 H, u32 *start_out, u32 *len_out, u64 *key_out, u32 *val_out)
 {
     for (u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x; t < H; t += (u64)gridDim.x * blockDim.x) {
-        u64 a = 0, b = nvq;
-        while (b - a > 1) {
-            const u64 mid = a + (b - a) / 2;
-            if (hit_off[mid] <= t) a = mid; else b = mid;
-        }
+        const u64 a = pair_of_hit(hit_off, nvq, t);
         const ChunkDesc ch = chunks[(u32)(a % nc)];
         const u32 di = ch.sa[lo[a] + (u32)(t - hit_off[a])];
         u32 ls = 0, ll = 0;
@@ -1489,12 +1496,7 @@ __global__ __launch_bounds__(256) void emit_kernel(const ChunkDesc *chunks, u32 
     for (u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x; t < H; t += (u64)gridDim.x * blockDim.x) {
         const u32 l = len[t];
         if (l == kSkip) continue;
-        u64 a = 0, b = nvq;
-        while (b - a > 1) {
-            const u64 mid = a + (b - a) / 2;
-            if (hit_off[mid] <= t) a = mid; else b = mid;
-        }
-        const ChunkDesc ch = chunks[(u32)(a % nc)];
+        const ChunkDesc ch = chunks[(u32)(pair_of_hit(hit_off, nvq, t) % nc)];
         const u64 o = boff[t];
         ent_off[eidx[t]] = o;
         copy_entry(out + o, ch.text + start[t], l);
@@ -1722,8 +1724,20 @@ static int resident_query(DeviceCtx *ctx, const ChunkDesc *d_chunks, u32 nc, con
     return PSS_OK;
 }
 
+// Which of n byte strings (string i is bytes[off[i], off[i + 1])) hold a 0x0A: flags[i] = `set` for those and 0 for the
+// rest.  Such a string occurs in no entry, though its suffix-array interval need not be empty (it may match across
+// entries), so every mode that takes patterns apart flags it on the host.
+static void newline_flags(const u8 *bytes, const u64 *off, u32 n, u8 set, u8 *flags)
+{
+    for (u32 i = 0; i < n; ++i) {
+        const u64 m = off[i + 1] - off[i];
+        flags[i] = (m && memchr(bytes + off[i], '\n', m)) ? set : (u8)0;
+    }
+}
+
 #include "line_index_impl.h"
 #include "anchored_impl.h"
+#include "entry_scan_impl.h"
 #include "all_terms_impl.h"
 #include "sequence_impl.h"
 #include "fold_impl.h"
@@ -1907,10 +1921,9 @@ int Batch::stage_queries()
     h_padded = hq != nullptr;
     if (terms && !fold) {
         own_tflags.resize(nq);
-        if (seq)
-            seq_flags(rq.qbytes, rq.qoffsets, nq, own_tflags.data());
-        else
-            terms_flags(rq.qbytes, rq.qoffsets, nq, rq.exclude, own_tflags.data());
+        newline_flags(rq.qbytes, rq.qoffsets, nq, kTermVoid, own_tflags.data());
+        for (u32 t = 0; !seq && t < nq; ++t)                        // (no segment of a sequence batch excludes)
+            if (rq.exclude[t]) own_tflags[t] |= kTermExclude;
     }
     return PSS_OK;
 }
@@ -2086,8 +2099,8 @@ int Batch::run_mid(bool *done)
     MidState *d_ms = reinterpret_cast<MidState *>(d_total + 8);       // behind the scan partials
     const u32 grid = (u32)ctx->num_cus * 4;
     hipLaunchKernelGGL(mid_hitoff_kernel, dim3(1), dim3(MID_BLOCK), 0, s, d_cnt, (u32)nvq, d_hitoff, d_ms);
-    hipLaunchKernelGGL(hit_lines_kernel, dim3(grid), dim3(256), 0, s, d_chunks, nc, d_q, d_qoff, nvq, d_lo, d_hitoff,
-                       (u64)0, d_ms, d_start, d_len);
+    hipLaunchKernelGGL(hit_lines_kernel<false>, dim3(grid), dim3(256), 0, s, d_chunks, nc, d_q, d_qoff, nvq, d_lo, d_hitoff,
+                       (u64)0, d_ms, d_start, d_len, (const u32 *)nullptr);
     hipLaunchKernelGGL(mid_hit_scans_kernel, dim3(1), dim3(MID_BLOCK), 0, s, d_len, d_ms, byte_cap, d_eidx, d_boff);
     hipLaunchKernelGGL(emit_kernel, dim3(grid), dim3(256), 0, s, d_chunks, nc, nvq, d_hitoff, (u64)0, d_ms, d_start,
                        d_len, d_eidx, d_boff, d_entoff, d_out);
@@ -2173,10 +2186,7 @@ int Batch::union_spellings()
     d_fbytes = d_fvoid + void_room;
     p_cnt = reinterpret_cast<u32 *>(d_fbytes + byte_room);
     own_tflags.resize(nrow);
-    for (u32 g = 0; g < nrow; ++g) {
-        const u64 m = rq.fold_offsets[g + 1] - rq.fold_offsets[g];
-        own_tflags[g] = (m && memchr(rq.fold_bytes + rq.fold_offsets[g], '\n', m)) ? kTermVoid : 0;
-    }
+    newline_flags(rq.fold_bytes, rq.fold_offsets, nrow, kTermVoid, own_tflags.data());
     PSS_HIP(hipMemcpyAsync(d_goff, rq.group_offsets, ((size_t)nrow + 1) * 8, hipMemcpyHostToDevice, s));
     PSS_HIP(hipMemcpyAsync(d_foff, rq.fold_offsets, ((size_t)nrow + 1) * 8, hipMemcpyHostToDevice, s));
     PSS_HIP(hipMemcpyAsync(d_fseed, rq.fold_seed, (size_t)nrow * 4, hipMemcpyHostToDevice, s));
@@ -2229,8 +2239,8 @@ int Batch::run_general()
                            d_m, d_len);
     } else if (terms) {
         // candidates: the entries that hold the pair's driver term; then every candidate against the group's other terms
-        hipLaunchKernelGGL(terms_hits_kernel, dim3(grid), dim3(256), 0, s, d_chunks, nc, d_q, d_qoff, d_gdrv, nrp, p_lo, d_hitoff, H,
-                           d_start, d_len);
+        hipLaunchKernelGGL(hit_lines_kernel<true>, dim3(grid), dim3(256), 0, s, d_chunks, nc, d_q, d_qoff, nrp, p_lo, d_hitoff, H,
+                           (const MidState *)nullptr, d_start, d_len, d_gdrv);
         const u32 vgrid = (u32)std::min<u64>((u64)ctx->num_cus * 16, (H * TG + 255) / 256);
         if (seq)    // (a sequence batch: every candidate against the group's segments in order, the driver among them)
             hipLaunchKernelGGL(seq_verify_kernel, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, d_q, d_qoff, d_goff, d_sanch, nrp,
@@ -2239,8 +2249,8 @@ int Batch::run_general()
             hipLaunchKernelGGL(terms_verify_kernel, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, d_q, d_qoff, d_goff, d_tflags, d_cnt,
                                d_gdrv, nrp, d_hitoff, H, d_start, d_len);
     } else
-        hipLaunchKernelGGL(hit_lines_kernel, dim3(grid), dim3(256), 0, s, d_chunks, nc, d_q, d_qoff, nrp, p_lo,
-                           d_hitoff, H, (const MidState *)nullptr, d_start, d_len);
+        hipLaunchKernelGGL(hit_lines_kernel<false>, dim3(grid), dim3(256), 0, s, d_chunks, nc, d_q, d_qoff, nrp, p_lo,
+                           d_hitoff, H, (const MidState *)nullptr, d_start, d_len, (const u32 *)nullptr);
     PSS_TRY(device_excl_scan(ctx, InKept{d_len}, H, d_partial, d_total, d_eidx));
     PSS_HIP(hipMemcpyAsync(h_small, d_total, 8, hipMemcpyDeviceToHost, s));
     if (counts) {

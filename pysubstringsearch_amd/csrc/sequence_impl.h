@@ -5,72 +5,20 @@
 //
 // A sequence batch IS an all-terms batch up to the verify step: the interval search answers every (segment, chunk) pair,
 // terms_driver_kernel picks the rarest segment of every (group, chunk) pair (every segment is an include term), and
-// terms_hits_kernel yields one candidate per entry that holds the driver.  seq_verify_kernel then walks each candidate
-// entry once, left to right: it needs WHERE a segment sits, not whether, so it is built on entry_find -- entry_holds
-// with a position for an answer.  The driver segment is matched like any other: its position matters.
-// A segment that holds a 0x0A occurs in no entry and voids its group (kTermVoid): the pair counts no hit.
+// hit_lines_kernel over the drivers yields one candidate per entry that holds the driver.  seq_verify_kernel then walks
+// each candidate entry once, left to right: it needs WHERE a segment sits, not whether, and entry_scan
+// (entry_scan_impl.h) answers with the leftmost position.  The driver segment is matched like any other: its position
+// matters.
+// A segment that holds a 0x0A occurs in no entry and voids its group (kTermVoid, from newline_flags): the pair counts no
+// hit.
 
-constexpr u32 kNone = 0xffffffffu;               // entry_find: no occurrence
-
-// Per-segment flags of a sequence batch (nseg values): no segment excludes.
-static void seq_flags(const u8 *qbytes, const u64 *qoff, u32 nseg, u8 *flags)
-{
-    for (u32 t = 0; t < nseg; ++t) {
-        const u64 m = qoff[t + 1] - qoff[t];
-        flags[t] = (m && memchr(qbytes + qoff[t], '\n', m)) ? kTermVoid : 0;
-    }
-}
-
-// The LEFTMOST occurrence of pat that lies inside text[from, lim), or kNone.  Called by the TG lanes of one group together
-// (gl = lane inside the group, gbase = the group's first lane); every lane returns the group's answer.  A match starts at
-// from .. lim - plen and nowhere else, so it never reaches the newline at the entry's end, the next entry or the zero
-// padding behind the chunk.  The scan is entry_holds': per step the group covers 8 * TG start positions, lane gl the 8
-// that begin at its own 8-byte word; a lane stops at the LOWEST matching byte of its word (the ctz loop ascends), and
-// among the lanes that found one in a step the LOWEST LANE holds the lowest position, since lane gl's positions all lie
-// below lane gl + 1's.  Steps ascend too, so the first step with a finding holds the leftmost occurrence.  Loads reach at
-// most 23 bytes past a start position (the text is readable 128 bytes past n, a segment 16 past its end; 32 zero bytes
-// follow the staged segments).
-// A range of one start position (lim == from + plen) is the anchored test: "pat sits exactly at from".
+// The LEFTMOST occurrence of pat that lies inside text[from, lim), or kNone: entry_scan over the start positions
+// from .. lim - plen, for the TG lanes of one group together.  A range of one start position (lim == from + plen) is the
+// anchored test: "pat sits exactly at from".
 __device__ __forceinline__ u32 entry_find(const ChunkDesc &ch, u32 from, u32 lim, const u8 *pat, u32 plen, u32 gl, u32 gbase)
 {
     if (from > lim || plen > lim - from) return kNone;
-    const u32 last = lim - plen;                                 // the last start position
-    const u64 first = 0x0101010101010101ull * pat[0];
-    const u64 pmask = plen >= 8 ? ~0ull : (1ull << (8 * plen)) - 1ull;
-    const u64 pk = load_u64_unaligned(pat) & pmask;
-    for (u64 base = from; base <= last; base += 8 * TG) {        // (the same trips for every lane of the group)
-        const u64 p64 = base + 8 * gl;
-        u32 off = 8;                                             // byte of the own word where pat starts: 8 = nowhere
-        if (p64 <= last) {
-            const u32 p = (u32)p64;
-            const u64 w = load_text8(ch.text + p), nxt = load_text8(ch.text + p + 8);
-            u64 cand = zero_bytes(w ^ first);
-            const u32 nv = last - p + 1;                         // start positions of this word inside the range
-            if (nv < 8) cand &= (1ull << (8 * nv)) - 1ull;
-            while (cand && off == 8) {
-                const u32 k = (u32)(__builtin_ctzll(cand) >> 3);
-                cand &= cand - 1;
-                const u64 x = k ? (w >> (8 * k)) | (nxt << (64 - 8 * k)) : w;     // text[p + k, p + k + 8)
-                if ((x & pmask) == pk && (plen <= 8 || cmp_suffix(ch.text, ch.n, p + k, pat, plen) == 0)) off = k;
-            }
-        }
-        // The ballots run while the groups of a wavefront are on different paths (other candidates, other segments, other
-        // trip counts); a ballot counts the active lanes only, and only the group's own TG bits are read.  INVARIANT, as
-        // in entry_holds: the TG lanes of a group reach every ballot together -- every branch between the kernel's loop
-        // entry and a ballot depends on group-wide values only (t, len[t], ok, the anchors, plen, from, lim, base, and
-        // `who` below, itself a ballot read through the group's bits), and the per-lane `p64 <= last` branch closes above.
-        // The winning lane's byte offset reaches the group the same way: three more ballots over the bits of `off`, read at
-        // the winner's bit.  (No shuffle: nothing here has to argue that a source lane is active.)
-        const u32 who = (u32)(__ballot(off < 8) >> gbase) & ((1u << TG) - 1u);
-        if (who) {
-            const u32 wl = (u32)__builtin_ctz(who);              // the lowest lane that found one
-            const u32 b0 = (u32)(__ballot((off & 1u) != 0) >> (gbase + wl)) & 1u;
-            const u32 b1 = (u32)(__ballot((off & 2u) != 0) >> (gbase + wl)) & 1u;
-            const u32 b2 = (u32)(__ballot((off & 4u) != 0) >> (gbase + wl)) & 1u;
-            return (u32)base + 8 * wl + (b0 | (b1 << 1) | (b2 << 2));
-        }
-    }
-    return kNone;
+    return entry_scan<false, true>(ch, from, lim - plen, pat, plen, gl, gbase);
 }
 
 // TG lanes per hit the dedupe kept (one per candidate entry): the group's segments inside the entry [start, true end),
@@ -90,11 +38,7 @@ __global__ __launch_bounds__(256) void seq_verify_kernel(const ChunkDesc *chunks
     for (u64 t = ((u64)blockIdx.x * blockDim.x + threadIdx.x) / TG; t < H; t += step) {
         const u32 l = len[t];
         if (l == kSkip) continue;
-        u64 a = 0, b = ngq;
-        while (b - a > 1) {
-            const u64 mid = a + (b - a) / 2;
-            if (hit_off[mid] <= t) a = mid; else b = mid;
-        }
+        const u64 a = pair_of_hit(hit_off, ngq, t);
         const u32 g = (u32)(a / nc), c = (u32)(a % nc);
         const ChunkDesc ch = chunks[c];
         const u32 s = start[t], e = s + l;                       // e <= n - 1: the closing newline, or the last byte

@@ -299,7 +299,11 @@ def test_an_earlier_folded_occurrence_drops_the_hit():
     """The pattern twice in an entry, in two spellings whose intervals lie apart (the upper-case one sorts first and
     stands to the RIGHT): the entry comes once, for its leftmost match.  Beside each such entry, one whose earlier
     occurrence is a near miss -- the last byte changed, so the first bytes match in registers -- which must be kept.
-    Every geometry with the entry shifted by 0 .. 3 bytes against the 8-byte grid of the text."""
+    Every geometry with the entry shifted by 0 .. 3 bytes against the 8-byte grid of the text.
+    The last four entries and the last three patterns are the ends of the scanned range under fold: a range of ONE start
+    position whose byte is a candidate and no match (decided in registers for `aB`, by the long compare for
+    `aaaaaaaab`), and an earlier match that starts in the last, partial word of the range and is found by the long
+    compare (ten `a` in twelve `A`: the matches at 7 and 8 stand in front of the one at 9)."""
     rng = np.random.default_rng(133)
     lines = []
     for P in SCAN_PATTERNS:
@@ -313,9 +317,10 @@ def test_an_earlier_folded_occurrence_drops_the_hit():
                     e[a1:a1 + len(P)], e[a2:a2 + len(P)] = first, P.upper()
                     lines += [b'#' * lead, bytes(e)]
     lines += [b'xAaAx', b'AaA', b'aA', b'xaAaAaAaAaAaAaAaAaAaAaAaAaAaAaAaAaAaAaAaAaAaAaAaAaAaAaAaAaAaAaAaAaAaAaAaAx', b'Qq', b'qQ', b'QQQQQQQQQq', b'qqqqqqqqqqQ']
+    lines += [b'AaB', b'aAb', b'AaaaaaaaaB', b'xxxxxxxAAAAAAAAAAAA']
     r, ref, data = one_chunk(lines)
     try:
-        res = per_pattern(check(r, ref, list(SCAN_PATTERNS) + [b'aa', b'AA', b'aA', b'aaa', b'qq', b'QQ']))
+        res = per_pattern(check(r, ref, list(SCAN_PATTERNS) + [b'aa', b'AA', b'aA', b'aaa', b'qq', b'QQ', b'aB', b'aaaaaaaab', b'AAAAAaaaaa']))
         assert res[0].size == 2 * 4 * 6 and res[1].size == 2 * 4 * 4           # (the geometries each pattern's length fits)
         assert sorted(r.entries_by_id(res[3])) == sorted(r.entries_by_id(res[5])) == sorted([x for x in lines if b'aa' in x.lower()])
         assert {b'xAaAx', b'AaA', b'aA'} <= set(r.entries_by_id(res[3])) and {b'Qq', b'qQ', b'QQQQQQQQQq'} <= set(r.entries_by_id(res[7]))
