@@ -2,7 +2,9 @@
 tens of thousands of queries (fused small-batch kernel, wave-per-pair and lane-per-pair interval
 search, arena overflow, > 1024 hits per (query, chunk)), long and newline-crossing patterns,
 sharded readers, Writers and Readers over several lanes of one GPU (container formats 1, 2, striped).  Everything is
-compared with the oracle's restatement of Reader::search.
+compared with the oracle's restatement of Reader::search.  Every case then draws a case of tests/search_fuzz_cases.py from
+the same seed and runs the six batches of tests/test_search_fuzz_gpu.py on it: entry ids, anchored (twice), all-terms,
+wildcard and case-insensitive search against their brute-force references, under that case's switches and placement.
 
     python tests/tools/fuzz_search.py [seconds=120] [seed0=<time>]"""
 import pathlib
@@ -16,6 +18,35 @@ sys.path.insert(0, '.')
 import pysubstringsearch  # noqa: E402
 from oracle import oracle as O  # noqa: E402
 from pysubstringsearch_amd import Reader  # noqa: E402
+from tests import search_fuzz_cases  # noqa: E402
+from tests.test_search_fuzz_gpu import run_case  # noqa: E402
+
+KIND_SWITCHES = ('PSS_LANE_SEARCH_MIN', 'PSS_WAVE_SEARCH', 'PSS_NO_GROUP_SEARCH', 'PSS_NO_SEARCH_STAGE', 'PSS_NO_PINNED_RESULTS',
+                 'PSS_NO_MID_PIPELINE', 'PSS_SAMPLE_SHIFT', 'PSS_NO_KEY_SAMPLES', 'PSS_ICASE_SEED_LETTERS', 'PSS_NO_SMALL_PATH',
+                 'PSS_NO_BLOCK_PATH', 'PSS_READER_HBM_BUDGET', 'PSS_READER_AUTO_RESIDENCY')
+
+
+def set_switches(**kv):
+    """What the fixture search_env does in the suite: the switches into the environment, read again by the library."""
+    from pysubstringsearch_amd import _ffi
+    for k, v in kv.items():
+        if v is None:
+            os.environ.pop(k, None)
+        else:
+            os.environ[k] = str(v)
+    _ffi.lib.pss_reload_env()
+
+
+def kinds_case(seed, tmp):
+    """The entry-level search kinds on the generated case of this seed, under its own switches alone."""
+    set_switches(**{k: None for k in KIND_SWITCHES})
+    try:
+        run_case(search_fuzz_cases.make_case(seed), pathlib.Path(tmp), set_switches)
+    finally:
+        set_switches(**{k: None for k in KIND_SWITCHES})
+        for f in os.listdir(tmp):
+            if f.startswith('fuzz%d.' % seed):
+                os.remove(os.path.join(tmp, f))
 
 
 def one_case(seed, tmp):
@@ -163,6 +194,7 @@ def one_case(seed, tmp):
     assert per[:min(200, len(qb))] == oc.tolist()[:200], 'sharded counts differ'
     assert sorted(allents) == sorted(oe[:sum(oc.tolist()[:200])]), 'sharded multiset differs'
     o.close()
+    kinds_case(seed, tmp)
 
 
 def main():
@@ -182,7 +214,8 @@ def main():
                 raise
             cases += 1
             seed += 1
-    print(f'fuzz_search: {cases} cases in {time.time() - t0:.0f} s, all equal to the oracle (last seed {seed - 1})')
+    print(f'fuzz_search: {cases} cases in {time.time() - t0:.0f} s, all equal to the oracle and, for the entry-level search kinds, '
+          f'to their brute-force references (last seed {seed - 1})')
 
 
 if __name__ == '__main__':
