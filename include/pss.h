@@ -595,8 +595,9 @@ int pss_reader_count_seq_batch(pss_reader *r, const uint8_t *sbytes, const uint6
  * variant builds the line tables on first use, the other two allocate nothing for them.
  * The limit: the candidates follow the occurrences of the folded SEED, not of the pattern -- a long pattern whose seed is a
  * common word looks at every occurrence of that word.
- * Out of scope: folding outside ASCII; case-insensitive anchors, all-terms and wildcard search; the fused, resident and mid
- * paths (a case-insensitive batch always takes the general pipeline); a device-resident result; the multi-process gather over
+ * Out of scope: folding outside ASCII; a case-insensitive anchored call of its own (the all-terms and the wildcard search under
+ * fold are the calls further down; "starts with / ends with / equals" under fold is the wildcard call's `p*`, `*p`, `p`); the
+ * fused, resident and mid paths (a case-insensitive batch always takes the general pipeline); a device-resident result; the multi-process gather over
  * RCCL (dist.ShardedReader); walking only the spellings that are PRESENT, on the device (the blind enumeration probes up to
  * 2^F mostly empty intervals per pattern and chunk: the price of reusing the interval kernels as they are); picking the rarer
  * of two seeds per chunk.
@@ -613,6 +614,61 @@ int pss_reader_count_icase_batch(pss_reader *r, const uint8_t *qbytes, const uin
  * PSS_EINVAL: an empty pattern, letters > 6, a null seed_off / seed_len / count, cap < *count * *seed_len. */
 int pss_icase_variants(const uint8_t *pat, uint64_t len, int32_t letters, uint8_t *out, uint64_t cap, uint32_t *seed_off,
                        uint32_t *seed_len, uint32_t *count);
+/*
+ * Case-insensitive all-terms and wildcard search (no reference counterpart): pss_reader_search_terms_batch and
+ * pss_reader_search_seq_batch under the fold of pss_reader_search_icase_batch.  Arguments exactly as their exact-byte
+ * namesakes take them.  Fold is ASCII only: A .. Z are equivalent to a .. z, every other byte, 0x80 .. 0xFF included, equals
+ * only itself.  An entry is the bytes [start, end) of a chunk's text, end = its closing 0x0A or the length n of the text.
+ *   All-terms under fold: group (include, exclude) matches an entry iff every include term occurs in it under fold and no
+ *   exclude term does.  An include term holding 0x0A voids its group (count 0, no hit looked at); an exclude term holding 0x0A
+ *   is ignored.
+ *   Wildcard under fold: the segment / anchor semantics of pss_reader_search_seq_batch -- segments in order, without overlap,
+ *   leftmost-greedy; START / END pin the first / last segment to the entry's ends -- with every byte comparison under fold.
+ *   `a*A` does not match the entry `a`; `ab*BA` matches `abBA` and not `aBa`; one segment with both anchors is "the entry equals
+ *   it under fold".  So case-insensitive "starts with / ends with / equals" are the groups (p, START), (p, END), (p, START | END).
+ * PSS_EINVAL (message in pss_last_error naming the term or segment and the group, *out / counts untouched): whatever the
+ * exact-byte namesake refuses (an empty term or segment, a group without an include term or without a segment, bad flags,
+ * anchors or offsets, null arguments, a null reader judged last), a term of more than 2^32 - 1 bytes, and a batch whose terms
+ * expand to more than 2^32 - 1 spellings in all -- refused before anything is allocated for the expansion.
+ * The search: the host expands every term (segment) as pss_reader_search_icase_batch expands a pattern -- its SEED under
+ * PSS_ICASE_SEED_LETTERS, the seed's at most 64 spellings in ascending order, the term folded to lower case.  Three pair spaces
+ * follow: the interval search answers every (spelling, chunk) pair; the counts of a term's spellings add up to the term's SEED
+ * HITS per chunk; per (group, chunk) pair the include term (segment) with the fewest seed hits, the lowest index on a tie,
+ * DRIVES.  The driver is chosen by seed occurrences -- which is what bounds the work -- not by occurrences of the term.  Every
+ * seed hit of the driver is verified against the whole driver term under fold and deduplicated to the entry's leftmost folded
+ * match, exactly as for pss_reader_search_icase_batch; each candidate entry is then scanned once, under fold, for the group's
+ * other terms (an exclude term whose seed is absent from the chunk is not looked for), or walked once for the segments in order.
+ * A chunk in which an include term's seed is absent contributes nothing without a hit being looked at.
+ * Order: group-major, chunk-major inside a group; inside one (group, chunk) pair the suffix-array order of the driver term's
+ * seed occurrence inside each entry's leftmost folded match of the driver term; the same for the text and the id variant --
+ * pss_reader_set_result_order has no effect.  A group without an ASCII letter returns exactly what the exact-byte call
+ * returns; a group of one include term and no exclude term, and the pattern `*p*`, return exactly what
+ * pss_reader_search_icase_ids_batch returns for the term.
+ * Whole-file, sharded and multi-device readers, and suffix arrays on the host tier, are served alike.
+ * pss_reader_last_stats: queries = groups, hits = the sum over the (group, chunk) pairs of the driver term's seed hits,
+ * entries = what is returned; route = GENERAL | the interval bits (| COUNTS for the count calls) -- no bit of its own.
+ * Out of scope: folding outside ASCII; a case-insensitive route through the anchored search's "\n" + s intervals; the fused,
+ * mid, resident and device-resident paths; the multi-process gather over RCCL (dist.ShardedReader); probing only the spellings
+ * that are present; choosing the driver by anything finer than seed hits; `?` and character classes.
+ */
+/* packed entry text, one row per group */
+int pss_reader_search_terms_icase_batch(pss_reader *r, const uint8_t *tbytes, const uint64_t *toffsets, uint32_t nterms,
+                                        const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *exclude, pss_result **out);
+/* u64 entry ids, packed as pss_reader_search_ids_batch packs them */
+int pss_reader_search_terms_icase_ids_batch(pss_reader *r, const uint8_t *tbytes, const uint64_t *toffsets, uint32_t nterms,
+                                            const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *exclude, pss_result **out);
+/* counts[g] = entries group g matches; nothing but ngroups counters comes down */
+int pss_reader_count_terms_icase_batch(pss_reader *r, const uint8_t *tbytes, const uint64_t *toffsets, uint32_t nterms,
+                                       const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *exclude, uint64_t *counts);
+/* packed entry text, one row per group */
+int pss_reader_search_seq_icase_batch(pss_reader *r, const uint8_t *sbytes, const uint64_t *soffsets, uint32_t nsegs,
+                                      const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *anchors, pss_result **out);
+/* u64 entry ids, packed as pss_reader_search_ids_batch packs them */
+int pss_reader_search_seq_icase_ids_batch(pss_reader *r, const uint8_t *sbytes, const uint64_t *soffsets, uint32_t nsegs,
+                                          const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *anchors, pss_result **out);
+/* counts[g] = entries group g matches; nothing but ngroups counters comes down */
+int pss_reader_count_seq_icase_batch(pss_reader *r, const uint8_t *sbytes, const uint64_t *soffsets, uint32_t nsegs,
+                                     const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *anchors, uint64_t *counts);
 /* For the first `cap` resident chunks, in file order: index in the file and number of entries; *num = resident chunks. */
 int pss_reader_chunk_entries(pss_reader *r, uint64_t *chunk_index, uint64_t *entries, uint64_t cap, uint64_t *num);
 /*

@@ -15,6 +15,7 @@ Extras that do not change the reference signatures: ``device=`` keyword,
 ``close()`` / context-manager support, ``Reader(..., shard=(i, n))``.
 """
 import ctypes
+import functools
 import os
 import typing
 
@@ -302,6 +303,98 @@ class DeviceResult(typing.NamedTuple):
     starts: typing.Any    # torch int64 [num_entries]: start of every entry in data
     counts: typing.Any    # torch int64 [num_queries]
     num_bytes: int
+
+
+def _icase_flag(icase) -> bool:
+    """The ``icase`` keyword of the all-terms and the glob calls: a bool and nothing else (a pattern slipped into its place
+    is a mistake worth a ``TypeError``)."""
+    if not isinstance(icase, bool):
+        raise TypeError(f"argument 'icase': must be bool, not {type(icase).__name__}")
+    return icase
+
+
+def _with_icase(folded, note: str):
+    """Decorator of the ten all-terms and glob methods of ``Reader``: adds the keyword-only ``icase: bool = False``.
+    ``icase=False`` calls the decorated exact-byte method as it stands -- not one line of its path changes; ``icase=True``
+    calls ``folded`` with the same arguments.  ``functools.wraps`` keeps the method's name and appends ``note`` to its
+    docstring; like every wrapped function it also keeps the exact-byte method's ``inspect.signature`` (``__wrapped__``) --
+    the keyword itself is declared in ``__init__.pyi`` and shown by ``inspect.signature(m, follow_wrapped=False)``."""
+    def decorate(exact):
+        @functools.wraps(exact)
+        def method(self, *args, icase: bool = False, **kwargs):
+            return (folded if _icase_flag(icase) else exact)(self, *args, **kwargs)
+        method.__doc__ = (exact.__doc__ or '') + note
+        return method
+    return decorate
+
+
+def _folded_batch(kind: str, form: str):
+    """The ``icase=True`` body of one batched method: ``kind`` 'terms' (all-terms groups) or 'seq' (glob patterns), ``form``
+    'packed', 'ids' or 'counts'.  The batch is packed exactly as for the exact-byte call (``Reader._terms_args`` /
+    ``Reader._glob_args``: the same ``ValueError`` / ``TypeError``) and handed to the ``_icase`` namesake of its C entry point."""
+    pack = {'terms': '_terms_args', 'seq': '_glob_args'}[kind]
+    name = {'packed': f'pss_reader_search_{kind}_icase_batch', 'ids': f'pss_reader_search_{kind}_icase_ids_batch',
+            'counts': f'pss_reader_count_{kind}_icase_batch'}[form]
+
+    def run(self, batch):
+        import numpy as np
+        blob, offs, goff, extra = getattr(self, pack)(batch)
+        ng = len(goff) - 1
+        call = getattr(_lib, name)
+        if form == 'counts':
+            counts = np.zeros(max(ng, 1), dtype=np.uint64)
+            _ffi.check(call(self._handle(), blob, offs.ctypes.data, len(offs) - 1, goff.ctypes.data, ng, extra.ctypes.data, counts.ctypes.data))
+            return [int(c) for c in counts[:ng]]
+        res = ctypes.c_void_p()
+        _ffi.check(call(self._handle(), blob, offs.ctypes.data, len(offs) - 1, goff.ctypes.data, ng, extra.ctypes.data, ctypes.byref(res)))
+        owner = _ResultOwner(res)      # the arrays below are views of the C result; it lives as long as they do
+        n = _lib.pss_result_num_entries(res)
+        counts = owner.view(_lib.pss_result_query_counts(res), ng, np.uint64)
+        if form == 'ids':
+            ids = owner.view(_lib.pss_result_bytes(res), 8 * n, np.uint8).view(np.uint64)
+            ids.flags.writeable = False
+            return IdResult(ids, counts)
+        offsets = owner.view(_lib.pss_result_offsets(res), n + 1, np.uint64)
+        data = owner.view(_lib.pss_result_bytes(res), int(offsets[n]), np.uint8)
+        return PackedResult(data, offsets, counts)
+    return run
+
+
+def _packed_strs(p: 'PackedResult') -> typing.List[str]:
+    data = p.data.tobytes()
+    o = p.offsets.tolist()
+    return [data[o[i]:o[i + 1]].decode('utf-8') for i in range(len(o) - 1)]
+
+
+def _folded_search_all(self, terms, exclude=()):
+    return _packed_strs(_folded_batch('terms', 'packed')(self, self._str_terms(terms, exclude)))
+
+
+def _folded_count_all(self, terms, exclude=()):
+    return _folded_batch('terms', 'counts')(self, self._str_terms(terms, exclude))[0]
+
+
+def _folded_search_glob(self, s):
+    return _packed_strs(_folded_batch('seq', 'packed')(self, [_utf8(s, 'pattern')]))
+
+
+def _folded_count_glob(self, s):
+    return _folded_batch('seq', 'counts')(self, [_utf8(s, 'pattern')])[0]
+
+
+_ICASE_ALL = """
+
+        ``icase=True`` (keyword only): every term is compared under ASCII case folding (``A-Z`` = ``a-z``, every other byte
+        equals only itself), as ``search_icase_batch_packed`` compares a pattern; the driver of a (group, chunk) pair is then
+        the include term whose SEED (``icase_variants``) has the fewest hits, and the entries of a pair come in the
+        suffix-array order of that seed's occurrence inside each entry's leftmost folded match of the driver term
+        (include/pss.h, pss_reader_search_terms_icase_batch).  ``icase=False`` is the call as it always was."""
+_ICASE_GLOB = """
+
+        ``icase=True`` (keyword only): every byte is compared under ASCII case folding (``A-Z`` = ``a-z``, every other byte
+        equals only itself): ``grep -i`` for globs.  ``glob_escape(p) + b'*'``, ``b'*' + glob_escape(p)`` and
+        ``glob_escape(p)`` are then the case-insensitive "starts with", "ends with" and "equals" (include/pss.h,
+        pss_reader_search_seq_icase_batch).  ``icase=False`` is the call as it always was."""
 
 
 class Reader:
@@ -677,6 +770,7 @@ class Reader:
         blob, offs = _pack_queries(terms)
         return blob, offs, np.array(goff, dtype=np.uint64), np.array(flags if flags else [0], dtype=np.uint8)
 
+    @_with_icase(_folded_batch('terms', 'packed'), _ICASE_ALL)
     def search_all_batch_packed(self, groups) -> 'PackedResult':
         """Extension: per group, the entries that contain EVERY include term and NO exclude term, as a packed result
         like ``search_batch_packed``'s with one row per group.  ``groups`` is a sequence of ``(include, exclude)``
@@ -698,6 +792,7 @@ class Reader:
         data = owner.view(_lib.pss_result_bytes(res), int(offsets[n]), np.uint8)
         return PackedResult(data, offsets, counts)
 
+    @_with_icase(_folded_batch('terms', 'ids'), _ICASE_ALL)
     def search_all_ids_batch(self, groups) -> 'IdResult':
         """Extension: the ids (``search_ids_batch``) of the entries ``search_all_batch_packed`` returns, in the same
         order; ``counts[g]`` of them belong to group g."""
@@ -714,6 +809,7 @@ class Reader:
         ids.flags.writeable = False
         return IdResult(ids, counts)
 
+    @_with_icase(_folded_batch('terms', 'counts'), _ICASE_ALL)
     def count_all_bytes(self, groups) -> typing.List[int]:
         """Extension: how many entries each group matches; only the counters come back."""
         import numpy as np
@@ -731,6 +827,7 @@ class Reader:
             raise TypeError(f"argument 'terms': '{type(bad).__name__}' object cannot be converted to a sequence of 'PyString'")
         return [([_utf8(t, 'terms') for t in terms], [_utf8(t, 'exclude') for t in exclude])]
 
+    @_with_icase(_folded_search_all, _ICASE_ALL)
     def search_all(self, terms: typing.Sequence[str], exclude: typing.Sequence[str] = ()) -> typing.List[str]:
         """Extension: the entries that contain every one of ``terms`` and none of ``exclude``."""
         p = self.search_all_batch_packed(self._str_terms(terms, exclude))
@@ -738,6 +835,7 @@ class Reader:
         o = p.offsets.tolist()
         return [data[o[i]:o[i + 1]].decode('utf-8') for i in range(len(o) - 1)]
 
+    @_with_icase(_folded_count_all, _ICASE_ALL)
     def count_all(self, terms: typing.Sequence[str], exclude: typing.Sequence[str] = ()) -> int:
         """Extension: how many entries contain every one of ``terms`` and none of ``exclude``."""
         return self.count_all_bytes(self._str_terms(terms, exclude))[0]
@@ -761,6 +859,7 @@ class Reader:
         blob, offs = _pack_queries(segs)
         return blob, offs, np.array(goff, dtype=np.uint64), np.array(anch if anch else [0], dtype=np.uint8)
 
+    @_with_icase(_folded_batch('seq', 'packed'), _ICASE_GLOB)
     def search_glob_batch_packed(self, patterns: typing.Sequence[bytes]) -> 'PackedResult':
         """Extension: per glob pattern (``glob_parse``: literal pieces and ``*``), the entries that hold the pieces IN
         ORDER and without overlap -- the first at the entry's start unless the pattern begins with ``*``, the last at its
@@ -781,6 +880,7 @@ class Reader:
         data = owner.view(_lib.pss_result_bytes(res), int(offsets[n]), np.uint8)
         return PackedResult(data, offsets, counts)
 
+    @_with_icase(_folded_batch('seq', 'ids'), _ICASE_GLOB)
     def search_glob_ids_batch(self, patterns: typing.Sequence[bytes]) -> 'IdResult':
         """Extension: the ids (``search_ids_batch``) of the entries ``search_glob_batch_packed`` returns, in the same
         order; ``counts[g]`` of them belong to pattern g."""
@@ -797,6 +897,7 @@ class Reader:
         ids.flags.writeable = False
         return IdResult(ids, counts)
 
+    @_with_icase(_folded_batch('seq', 'counts'), _ICASE_GLOB)
     def count_glob_bytes(self, patterns: typing.Sequence[bytes]) -> typing.List[int]:
         """Extension: how many entries each glob pattern matches; only the counters come back."""
         import numpy as np
@@ -807,6 +908,7 @@ class Reader:
                                                    anch.ctypes.data, counts.ctypes.data))
         return [int(c) for c in counts[:ng]]
 
+    @_with_icase(_folded_search_glob, _ICASE_GLOB)
     def search_glob(self, s: str) -> typing.List[str]:
         """Extension: the entries that match the glob pattern ``s`` (``*`` = any run of bytes, ``\\`` escapes)."""
         p = self.search_glob_batch_packed([_utf8(s, 'pattern')])
@@ -814,6 +916,7 @@ class Reader:
         o = p.offsets.tolist()
         return [data[o[i]:o[i + 1]].decode('utf-8') for i in range(len(o) - 1)]
 
+    @_with_icase(_folded_count_glob, _ICASE_GLOB)
     def count_glob(self, s: str) -> int:
         """Extension: how many entries match the glob pattern ``s``."""
         return self.count_glob_bytes([_utf8(s, 'pattern')])[0]

@@ -299,6 +299,12 @@ def _load() -> ctypes.CDLL:
         'pss_reader_search_icase_batch': (ctypes.c_int, [vp, vp, vp, u32, pvp]),
         'pss_reader_search_icase_ids_batch': (ctypes.c_int, [vp, vp, vp, u32, pvp]),
         'pss_reader_count_icase_batch': (ctypes.c_int, [vp, vp, vp, u32, vp]),
+        'pss_reader_search_terms_icase_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, u32, vp, pvp]),
+        'pss_reader_search_terms_icase_ids_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, u32, vp, pvp]),
+        'pss_reader_count_terms_icase_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, u32, vp, vp]),
+        'pss_reader_search_seq_icase_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, u32, vp, pvp]),
+        'pss_reader_search_seq_icase_ids_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, u32, vp, pvp]),
+        'pss_reader_count_seq_icase_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, u32, vp, vp]),
         'pss_icase_variants': (ctypes.c_int, [vp, u64, i32, vp, u64, ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(u32)]),
         'pss_reader_chunk_entries': (ctypes.c_int, [vp, vp, vp, u64, ctypes.POINTER(u64)]),
         'pss_merge_packed': (ctypes.c_int, [u32, u64, vp, vp, vp, vp, vp, vp, vp, vp]),

@@ -20,6 +20,9 @@ constexpr u8 kTermExclude = 1;
 constexpr u8 kTermVoid = 0x80;                   // the term holds a newline: it occurs in no entry
 
 // One lane per (group, chunk) pair: the driver term of the pair, its interval and its hit count.
+// Lo = false: the terms have no interval of their own (the terms of a case-insensitive group batch, fold_impl.h: cnt is
+// the sum over a term's spellings), so lo is not read and g_lo not written.
+template <bool Lo>
 __global__ __launch_bounds__(256) void terms_driver_kernel(u32 nc, const u64 *goff, const u8 *flags, const u32 *lo, const u32 *cnt,
                                                              u64 ngq, u32 *g_drv, u32 *g_lo, u32 *g_cnt)
 {
@@ -44,20 +47,28 @@ __global__ __launch_bounds__(256) void terms_driver_kernel(u32 nc, const u64 *go
         }
     }
     g_drv[gq] = bt;
-    g_lo[gq] = have ? lo[(u64)bt * nc + c] : 0u;
+    if (Lo) g_lo[gq] = have ? lo[(u64)bt * nc + c] : 0u;
     g_cnt[gq] = (have && !dead) ? best : 0u;
 }
 
 // Does text[s, end) hold pat?  entry_scan (entry_scan_impl.h) over the start positions s .. end - plen, for the TG lanes
-// of one group together.
+// of one group together.  Fold: under ASCII case folding, pat folded already; end <= n, so a match at the last start
+// position end - plen ends inside the chunk, as entry_scan asks.
+template <bool Fold>
 __device__ __forceinline__ bool entry_holds(const ChunkDesc &ch, u32 s, u32 end, const u8 *pat, u32 plen, u32 gl, u32 gbase)
 {
-    return plen <= end - s && entry_scan<false, false>(ch, s, end - plen, pat, plen, gl, gbase) != kNone;
+    return plen <= end - s && entry_scan<Fold, false>(ch, s, end - plen, pat, plen, gl, gbase) != kNone;
 }
 
 // TG lanes per hit the dedupe kept (one per candidate entry): the group's other terms inside the entry [start, true
 // end).  The true end is the closing newline or n -- not start + len, which is short by one for an unterminated last
 // entry.  An exclude term without a hit in the chunk cannot be in the entry and is not looked for.
+// Fold: the terms of a case-insensitive group batch (fold_impl.h).  qbytes / qoff are then the FOLDED terms and cnt the
+// terms' seed hits per chunk (fold_union_kernel); a term whose seed is absent from the chunk is absent itself, so the
+// exclude shortcut holds as it stands.  The group-wide-branch invariant of entry_scan holds for both forms alike: every
+// branch of the loop below depends on t, on what is read at t (l, s, e, the pair and through it g, c, drv) and on the
+// group's terms (f, cnt, `found` -- entry_scan's answer, the same in every lane of the group), never on gl.
+template <bool Fold>
 __global__ __launch_bounds__(256) void terms_verify_kernel(const ChunkDesc *chunks, u32 nc, const u8 *qbytes, const u64 *qoff,
                                                              const u64 *goff, const u8 *flags, const u32 *cnt, const u32 *g_drv,
                                                              u64 ngq, const u64 *hit_off, u64 H, const u32 *start, u32 *len)
@@ -79,7 +90,7 @@ __global__ __launch_bounds__(256) void terms_verify_kernel(const ChunkDesc *chun
             const bool excl = (f & kTermExclude) != 0;
             if (j == drv || (f & kTermVoid)) continue;           // (a void include term left the pair without hits)
             if (excl && cnt[(u64)j * nc + c] == 0) continue;
-            const bool found = entry_holds(ch, s, end, qbytes + qoff[j], (u32)(qoff[j + 1] - qoff[j]), gl, gbase);
+            const bool found = entry_holds<Fold>(ch, s, end, qbytes + qoff[j], (u32)(qoff[j + 1] - qoff[j]), gl, gbase);
             ok = found != excl;
         }
         if (!ok && gl == 0) len[t] = kSkip;

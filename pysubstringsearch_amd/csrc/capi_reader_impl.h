@@ -1573,6 +1573,158 @@ extern "C" int pss_reader_count_icase_batch(pss_reader *r, const uint8_t *qbytes
     });
 }
 
+// ---- case-insensitive all-terms and wildcard search: group -> terms -> spellings -----------------------
+
+namespace {
+
+// The terms (or segments) of a group batch as the interval search takes them: the spellings of every term's seed, the
+// offsets that say which spellings are whose, and beside them the terms folded to lower case with their seeds' offsets.
+// It lives in the entry point's frame, so it outlives the batch on every part of a multi-device reader.
+struct IcaseGroups {
+    std::vector<uint8_t> vbytes, fbytes;
+    std::vector<uint64_t> voff, soff, foff;
+    std::vector<uint32_t> seed;
+    SearchRequest request(uint32_t nterms, const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *exclude, const uint8_t *anchors,
+                          SearchMode mode) const
+    {
+        SearchRequest rq{vbytes.data(), voff.data(), (uint32_t)(voff.size() - 1), mode, nullptr, group_offsets, ngroups, exclude, anchors};
+        rq.fold_seed = seed.data();
+        rq.fold_bytes = fbytes.data();
+        rq.fold_offsets = foff.data();
+        rq.spell_offsets = soff.data();
+        rq.nterms = nterms;
+        return rq;
+    }
+};
+
+// The expansion of n terms (`noun`: "term" or "segment") that terms_args / seq_args have passed: every one non-empty.
+// What it holds is judged before anything is allocated for it, as in icase_args.
+int icase_expand(const char *who, const char *noun, const uint8_t *tbytes, const uint64_t *toffsets, uint32_t n, IcaseGroups *b)
+{
+    const uint32_t letters = icase_letters(0);
+    for (uint32_t t = 0; t < n; ++t)
+        if (toffsets[t + 1] - toffsets[t] > 0xffffffffull) {
+            set_error("%s: %s %u has more than 2^32 - 1 bytes (a chunk has fewer)", who, noun, t);
+            return PSS_EINVAL;
+        }
+    if (((uint64_t)n << letters) > 0xffffffffull) {
+        uint64_t count = 0;
+        for (uint32_t t = 0; t < n; ++t) {
+            uint64_t so = 0, sl = 0;
+            count += 1ull << fold_seed(tbytes + toffsets[t], toffsets[t + 1] - toffsets[t], letters, &so, &sl);
+            if (count > 0xffffffffull) {
+                set_error("%s: the %ss expand to more than the 2^32 - 1 terms an all-terms batch takes (at %s %u)", who, noun, noun, t);
+                return PSS_EINVAL;
+            }
+        }
+    }
+    b->seed.resize((size_t)n + 1);          // (+ 1: data() of an empty vector may be null)
+    std::vector<uint64_t> slen(n);
+    std::vector<uint8_t> nletters(n);
+    uint64_t nspell = 0, vtotal = 0, ftotal = 0;
+    for (uint32_t t = 0; t < n; ++t) {
+        const uint64_t len = toffsets[t + 1] - toffsets[t];
+        uint64_t so = 0;
+        nletters[t] = (uint8_t)fold_seed(tbytes + toffsets[t], len, letters, &so, &slen[t]);
+        nspell += 1ull << nletters[t];
+        vtotal += slen[t] << nletters[t];
+        ftotal += len;
+        b->seed[t] = (uint32_t)so;          // (inside a term of less than 2^32 bytes)
+    }
+    b->fbytes.resize(ftotal + 1);
+    b->vbytes.resize(vtotal + 1);
+    b->voff.reserve(nspell + 1);
+    b->soff.reserve((size_t)n + 1);
+    b->foff.reserve((size_t)n + 1);
+    b->voff.assign(1, 0);
+    b->soff.assign(1, 0);
+    b->foff.assign(1, 0);
+    for (uint32_t t = 0; t < n; ++t) {
+        const uint8_t *src = tbytes + toffsets[t];
+        const uint64_t len = toffsets[t + 1] - toffsets[t];
+        uint8_t *dst = b->fbytes.data() + b->foff.back();
+        for (uint64_t i = 0; i < len; ++i) dst[i] = (uint8_t)((uint8_t)(src[i] - 'A') < 26 ? src[i] | 0x20 : src[i]);
+        b->foff.push_back(b->foff.back() + len);
+        const uint32_t f = nletters[t];
+        fold_spellings(src + b->seed[t], slen[t], f, b->vbytes.data() + b->voff.back());
+        for (uint32_t v = 0; v < (1u << f); ++v) b->voff.push_back(b->voff.back() + slen[t]);
+        b->soff.push_back(b->soff.back() + (1ull << f));
+    }
+    return PSS_OK;
+}
+
+}  // namespace
+
+extern "C" int pss_reader_search_terms_icase_batch(pss_reader *r, const uint8_t *tbytes, const uint64_t *toffsets, uint32_t nterms,
+                                                   const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *exclude, pss_result **out)
+{
+    return guarded([&]() -> int {
+        IcaseGroups b;
+        PSS_TRY(terms_args(r, "pss_reader_search_terms_icase_batch", tbytes, toffsets, nterms, group_offsets, ngroups, exclude, out != nullptr));
+        PSS_TRY(icase_expand("pss_reader_search_terms_icase_batch", "term", tbytes, toffsets, nterms, &b));
+        return reader_batch_result(r, b.request(nterms, group_offsets, ngroups, exclude, nullptr, SEARCH_FULL), out);
+    });
+}
+
+extern "C" int pss_reader_search_terms_icase_ids_batch(pss_reader *r, const uint8_t *tbytes, const uint64_t *toffsets, uint32_t nterms,
+                                                       const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *exclude,
+                                                       pss_result **out)
+{
+    return guarded([&]() -> int {
+        IcaseGroups b;
+        PSS_TRY(terms_args(r, "pss_reader_search_terms_icase_ids_batch", tbytes, toffsets, nterms, group_offsets, ngroups, exclude,
+                           out != nullptr));
+        PSS_TRY(icase_expand("pss_reader_search_terms_icase_ids_batch", "term", tbytes, toffsets, nterms, &b));
+        return reader_batch_result(r, b.request(nterms, group_offsets, ngroups, exclude, nullptr, SEARCH_IDS), out);
+    });
+}
+
+extern "C" int pss_reader_count_terms_icase_batch(pss_reader *r, const uint8_t *tbytes, const uint64_t *toffsets, uint32_t nterms,
+                                                  const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *exclude, uint64_t *counts)
+{
+    return guarded([&]() -> int {
+        IcaseGroups b;
+        PSS_TRY(terms_args(r, "pss_reader_count_terms_icase_batch", tbytes, toffsets, nterms, group_offsets, ngroups, exclude,
+                           !ngroups || counts));
+        PSS_TRY(icase_expand("pss_reader_count_terms_icase_batch", "term", tbytes, toffsets, nterms, &b));
+        return reader_batch_counts(r, b.request(nterms, group_offsets, ngroups, exclude, nullptr, SEARCH_COUNTS), counts);
+    });
+}
+
+extern "C" int pss_reader_search_seq_icase_batch(pss_reader *r, const uint8_t *sbytes, const uint64_t *soffsets, uint32_t nsegs,
+                                                 const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *anchors, pss_result **out)
+{
+    return guarded([&]() -> int {
+        IcaseGroups b;
+        PSS_TRY(seq_args(r, "pss_reader_search_seq_icase_batch", sbytes, soffsets, nsegs, group_offsets, ngroups, anchors, out != nullptr));
+        PSS_TRY(icase_expand("pss_reader_search_seq_icase_batch", "segment", sbytes, soffsets, nsegs, &b));
+        return reader_batch_result(r, b.request(nsegs, group_offsets, ngroups, nullptr, anchors, SEARCH_FULL), out);
+    });
+}
+
+extern "C" int pss_reader_search_seq_icase_ids_batch(pss_reader *r, const uint8_t *sbytes, const uint64_t *soffsets, uint32_t nsegs,
+                                                     const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *anchors,
+                                                     pss_result **out)
+{
+    return guarded([&]() -> int {
+        IcaseGroups b;
+        PSS_TRY(seq_args(r, "pss_reader_search_seq_icase_ids_batch", sbytes, soffsets, nsegs, group_offsets, ngroups, anchors, out != nullptr));
+        PSS_TRY(icase_expand("pss_reader_search_seq_icase_ids_batch", "segment", sbytes, soffsets, nsegs, &b));
+        return reader_batch_result(r, b.request(nsegs, group_offsets, ngroups, nullptr, anchors, SEARCH_IDS), out);
+    });
+}
+
+extern "C" int pss_reader_count_seq_icase_batch(pss_reader *r, const uint8_t *sbytes, const uint64_t *soffsets, uint32_t nsegs,
+                                                const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *anchors, uint64_t *counts)
+{
+    return guarded([&]() -> int {
+        IcaseGroups b;
+        PSS_TRY(seq_args(r, "pss_reader_count_seq_icase_batch", sbytes, soffsets, nsegs, group_offsets, ngroups, anchors, !ngroups || counts));
+        PSS_TRY(icase_expand("pss_reader_count_seq_icase_batch", "segment", sbytes, soffsets, nsegs, &b));
+        return reader_batch_counts(r, b.request(nsegs, group_offsets, ngroups, nullptr, anchors, SEARCH_COUNTS), counts);
+    });
+}
+
 namespace {
 
 // ids[0 .. n) of ONE single-device reader: validation on the host (the reader knows every chunk's entry count once the

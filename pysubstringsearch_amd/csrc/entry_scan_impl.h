@@ -44,6 +44,9 @@ __device__ __forceinline__ bool fold_equal(const u8 *text, u32 s, const u8 *pat,
 // The caller passes from <= last and knows that a match at `last` ends inside the chunk; a match starts in from .. last
 // and nowhere else, so a range that ends plen bytes before an entry's end never reaches the closing newline, the next
 // entry or the zero padding behind the chunk.
+// All four <Fold, Where> forms are compiled.  <true, true> came last, with entry_find<true> of the case-insensitive
+// wildcard search: its ranges end at lim - plen with lim <= n, so the guarantee above holds, and the
+// long compare of a candidate at p + k <= last (fold_equal) compares text[p + k, p + k + plen), which ends at or before n.
 // Per step the group covers 8 * TG start positions: lane gl takes the 8 that begin at its own 8-byte word, finds the
 // bytes equal to the pattern's first byte (zero_bytes) and checks those against the pattern's first min(8, plen) bytes in
 // registers -- its word and the one behind it, both folded under Fold; only a pattern longer than 8 bytes whose first 8

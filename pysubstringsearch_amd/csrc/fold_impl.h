@@ -13,6 +13,13 @@
 // entry's LEFTMOST folded match: hit_entry's dedupe, under fold (entry_scan<true>).  Every match alignment holds exactly one seed
 // occurrence, in exactly one spelling, so an entry keeps exactly one hit whatever mix of spellings it holds.
 // A pattern that holds a 0x0A occurs in no entry and is flagged void: its pairs count no hit.
+//
+// A case-insensitive GROUP batch (pss_reader_search_terms_icase_batch, pss_reader_search_seq_icase_batch)
+// has one level more: group -> terms -> spellings, and so three pair spaces -- (spelling, chunk), (term, chunk) and
+// (group, chunk).  fold_union_kernel runs over the (term, chunk) pairs and leaves t_cnt[term, c], the term's seed hits;
+// terms_driver_kernel<false> picks every (group, chunk) pair's driver from t_cnt; the Driven forms of the two kernels
+// below take the pair's pattern from its driver term; terms_verify_kernel<true> / seq_verify_kernel<true> check each
+// candidate entry against the group's other terms under fold.
 
 // The seed of pat[0, len): the longest window with at most `letters` ASCII letters, the leftmost on a tie.  Returns its
 // letter count.  (Host code, declared in search.h: the C ABI expands the patterns before it states the request.)
@@ -66,13 +73,16 @@ __global__ __launch_bounds__(256) void fold_union_kernel(u32 nc, const u64 *goff
 // in.  With di that text offset the match would start at m = di - seed_off: out of the chunk -> rejected before anything
 // is read.  Else the whole pattern at m under fold (the bytes outside the seed are what is unknown; the pattern holds no
 // 0x0A, so a match cannot leave its entry), and the entry's bounds.  A surviving hit leaves start, len and m.
+// Driven: the pairs are (group, chunk) pairs and the pattern of pair a is its driver term g_drv[a]; goff, fseed and foff
+// are indexed by term.  (A pair with hits has a driver that is neither void nor an exclude term: terms_driver_kernel.)
+template <bool Driven>
 __global__ __launch_bounds__(256) void fold_hits_kernel(const ChunkDesc *chunks, u32 nc, const u8 *fbytes, const u64 *foff,
                                                           const u32 *fseed, const u64 *goff, const u32 *lo, const u32 *cnt, u64 ngq,
-                                                          const u64 *hit_off, u64 H, u32 *start_out, u32 *len_out, u32 *m_out)
+                                                          const u64 *hit_off, u64 H, u32 *start_out, u32 *len_out, u32 *m_out, const u32 *g_drv)
 {
     for (u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x; t < H; t += (u64)gridDim.x * blockDim.x) {
         const u64 a = pair_of_hit(hit_off, ngq, t);
-        const u32 g = (u32)(a / nc), c = (u32)(a % nc);
+        const u32 g = Driven ? g_drv[a] : (u32)(a / nc), c = (u32)(a % nc);
         const ChunkDesc ch = chunks[c];
         u32 k = (u32)(t - hit_off[a]);
         u32 v = (u32)goff[g];
@@ -107,15 +117,19 @@ __device__ __forceinline__ bool fold_starts_before(const ChunkDesc &ch, u32 s, u
 // in [start, m) -- the leftmost match of the entry stands for it, whichever spelling's interval it came from.  The same
 // shape as terms_verify_kernel, for the same reasons: 64 bytes of entry per step, 32 hits per 256-thread workgroup,
 // grid-stride.  Every loop is bounded by m - start, an entry's length.
+// Driven: as for fold_hits_kernel, the pattern of pair a is its driver term g_drv[a] -- one value per hit, so the
+// group-wide-branch invariant of entry_scan holds as before.
+template <bool Driven>
 __global__ __launch_bounds__(256) void fold_dedupe_kernel(const ChunkDesc *chunks, u32 nc, const u8 *fbytes, const u64 *foff, u64 ngq,
-                                                            const u64 *hit_off, u64 H, const u32 *start, const u32 *mpos, u32 *len)
+                                                            const u64 *hit_off, u64 H, const u32 *start, const u32 *mpos, u32 *len,
+                                                            const u32 *g_drv)
 {
     const u32 lane = lane_id(), gl = lane & (TG - 1), gbase = lane & ~(TG - 1);
     const u64 step = (u64)gridDim.x * blockDim.x / TG;
     for (u64 t = ((u64)blockIdx.x * blockDim.x + threadIdx.x) / TG; t < H; t += step) {
         if (len[t] == kSkip) continue;
         const u64 a = pair_of_hit(hit_off, ngq, t);
-        const u32 g = (u32)(a / nc);
+        const u32 g = Driven ? g_drv[a] : (u32)(a / nc);
         const ChunkDesc ch = chunks[(u32)(a % nc)];
         const bool dup = fold_starts_before(ch, start[t], mpos[t], fbytes + foff[g], (u32)(foff[g + 1] - foff[g]), gl, gbase);
         if (dup && gl == 0) len[t] = kSkip;

@@ -95,8 +95,15 @@ struct SearchRequest {
     // fold_seed (ngroups values), fold_bytes and fold_offsets (ngroups + 1), together with group_offsets: the case-insensitive
     // search of fold_impl.h.  The rows are PATTERNS -- fold_bytes holds them folded to lower case, back to back -- and the nq
     // terms of group g are the spellings of pattern g's seed, in ascending byte order; fold_seed[g] is the seed's offset inside
-    // the pattern.  Modes FULL, COUNTS and IDS; not with anchors, exclude or seq_anchors; always the general pipeline.
+    // the pattern.  Modes FULL, COUNTS and IDS; not with anchors, and with exclude or seq_anchors only as a group batch
+    // (spell_offsets below); always the general pipeline.
     const uint32_t *fold_seed = nullptr; const uint8_t *fold_bytes = nullptr; const uint64_t *fold_offsets = nullptr;
+    // spell_offsets (nterms + 1 entries into the nq patterns), together with fold_seed and group_offsets: a case-insensitive
+    // GROUP batch -- an all-terms batch (exclude) or a sequence batch (seq_anchors) under fold.  The rows are
+    // the ngroups groups, group_offsets index the nterms TERMS, exclude has nterms flags, fold_seed / fold_bytes / fold_offsets
+    // are per term, and the nq patterns are the spellings of the terms' seeds: term t's are spell_offsets[t] ..
+    // spell_offsets[t + 1], ascending.  Null: the two-level batch above, whose groups are the patterns themselves.
+    const uint64_t *spell_offsets = nullptr; uint32_t nterms = 0;
     uint32_t rows() const { return group_offsets ? ngroups : nq; }     // rows of the result: queries, or groups of terms
     bool low_latency = false;            // one query through the resident kernel when it fits (an unanchored SEARCH_FULL batch only)
     // sa_order: the entries of one (query, chunk) pair come out in the reference's order -- suffix-array order of the FIRST hit

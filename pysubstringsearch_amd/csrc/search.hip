@@ -1758,7 +1758,8 @@ __global__ __launch_bounds__(256) void chunk_hits_kernel(const u32 *cnt, u64 nq,
 
 // ---- host driver of one batch -------------------------------------------------------------------------------------
 // search_batch_device reads top to bottom: empty batch -> stage_queries -> run_fused? -> launch_interval -> run_mid? ->
-// pick_drivers (an all-terms or a sequence batch) | union_spellings (a case-insensitive batch) -> run_general -> finish.
+// pick_drivers (an all-terms or a sequence batch) | union_spellings (a case-insensitive batch) | fold_drivers (a
+// case-insensitive group batch) -> run_general -> finish.
 // The stages share one Batch: the request normalised into the few booleans they read, the
 // workspace every route needs, the timing events and the two outputs.
 namespace {
@@ -1784,6 +1785,9 @@ struct Batch {
     bool counts, device, ids, anchored, terms, sa_order;
     bool seq;                           // terms, and the groups are ordered sequences (sequence_impl.h)
     bool fold;                          // terms, and the groups are the spellings of one pattern's seed each (fold_impl.h)
+    bool fgroups;                       // fold, and the spellings belong to TERMS of groups: three levels
+    const u32 nterm;                    // terms of such a batch (else 0) ...
+    const u64 ntp;                      // ... and its (term, chunk) pairs
     bool tiny;                          // queries and offsets fit the 16 KiB of the pinned scratch
     bool fused_ok, resident_ok, mid_ok; // routes this batch may take (each may still overflow into the next)
     // host copy of queries, offsets and anchor flags (stage_queries)
@@ -1793,6 +1797,7 @@ struct Batch {
     std::vector<u8> own_q;              // an anchored batch too large for the staging
     std::vector<u64> own_off;
     std::vector<u8> own_tflags;         // per-term flags of an all-terms batch
+    std::vector<u8> own_fvoid;          // a case-insensitive group batch: the void flags alone (what the union reads)
     // workspace of every route
     u8 *d_q = nullptr, *d_aflags = nullptr, *d_edge = nullptr;
     u64 *d_qoff = nullptr, *d_hitoff = nullptr, *d_partial = nullptr, *d_total = nullptr, *d_qcount = nullptr, *h_small = nullptr;
@@ -1804,6 +1809,8 @@ struct Batch {
     u8 *d_fbytes = nullptr, *d_fvoid = nullptr;     // a case-insensitive batch: the folded patterns, their offsets and seed
     u64 *d_foff = nullptr;                          // offsets, a void flag per pattern, the match start of every hit
     u32 *d_fseed = nullptr, *d_m = nullptr;
+    u64 *d_soff = nullptr;                          // a case-insensitive group batch: spelling offsets per term, seed hits
+    u32 *d_tcnt = nullptr;                          // per (term, chunk) pair
     // ... and of the mid and the general pipeline, sized by each: entry bounds per hit, the scans over them, the result
     u32 *d_start = nullptr, *d_len = nullptr;
     u64 *d_eidx = nullptr, *d_boff = nullptr, *d_entoff = nullptr;
@@ -1815,7 +1822,8 @@ struct Batch {
     Batch(DeviceCtx *c, const ChunkDesc *chunks, const LineDesc *lines, u32 nchunks, const SearchRequest &r, HostResult *out,
           pss_search_stats *stats)
         : ctx(c), s(c->stream), d_chunks(chunks), d_lines(lines), rq(r), res(out), st(stats), knobs(search_knobs()), nq(r.nq),
-          nc(nchunks), nvq((u64)r.nq * nchunks), nrow(r.rows()), nrp((u64)r.rows() * nchunks), e0(c->search_ev[0]), e1(c->search_ev[1]), e2(c->search_ev[2])
+          nc(nchunks), nvq((u64)r.nq * nchunks), nrow(r.rows()), nrp((u64)r.rows() * nchunks), nterm(r.spell_offsets ? r.nterms : 0u),
+          ntp((u64)(r.spell_offsets ? r.nterms : 0u) * nchunks), e0(c->search_ev[0]), e1(c->search_ev[1]), e2(c->search_ev[2])
     {
         counts = rq.mode == SEARCH_COUNTS;
         device = rq.mode == SEARCH_DEVICE;
@@ -1824,6 +1832,7 @@ struct Batch {
         terms = rq.group_offsets != nullptr;
         seq = terms && rq.seq_anchors != nullptr;
         fold = terms && rq.fold_seed != nullptr;
+        fgroups = fold && rq.spell_offsets != nullptr;
         // (counts do not depend on the order; one hit per entry has one order; an all-terms batch keeps its driver's text order)
         sa_order = rq.sa_order && !counts && !anchored && !terms;
         // (an anchored batch searches its rewritten queries: a newline in front of and / or behind every pattern)
@@ -1843,7 +1852,7 @@ struct Batch {
         p = ctx->slot[which].as<T>();
         return PSS_OK;
     }
-    int stage_queries(), run_fused(bool *served), launch_interval(), run_mid(bool *done), pick_drivers(), union_spellings(), run_general(), finish();
+    int stage_queries(), run_fused(bool *served), launch_interval(), run_mid(bool *done), pick_drivers(), union_spellings(), fold_drivers(), run_general(), finish();
     int sa_order_hits(u32 grid, u64 H);
     int download_result(u64 E, u64 B, const u64 *d_starts, const u8 *d_bytes, bool via_stage);
     void leave_on_device(const u64 *d_starts, const u8 *d_bytes), set_totals(u64 hits, u64 kept, u64 E, u64 B);
@@ -1923,6 +1932,13 @@ int Batch::stage_queries()
         own_tflags.resize(nq);
         newline_flags(rq.qbytes, rq.qoffsets, nq, kTermVoid, own_tflags.data());
         for (u32 t = 0; !seq && t < nq; ++t)                        // (no segment of a sequence batch excludes)
+            if (rq.exclude[t]) own_tflags[t] |= kTermExclude;
+    }
+    if (fgroups) {                      // (per TERM, from the folded terms: folding leaves a 0x0A alone)
+        own_fvoid.resize(nterm);
+        newline_flags(rq.fold_bytes, rq.fold_offsets, nterm, kTermVoid, own_fvoid.data());
+        own_tflags = own_fvoid;
+        for (u32 t = 0; !seq && t < nterm; ++t)                     // (no segment of a sequence batch excludes)
             if (rq.exclude[t]) own_tflags[t] |= kTermExclude;
     }
     return PSS_OK;
@@ -2166,7 +2182,7 @@ int Batch::pick_drivers()
     PSS_HIP(hipMemcpyAsync(d_goff, rq.group_offsets, ((size_t)nrow + 1) * 8, hipMemcpyHostToDevice, s));
     PSS_HIP(hipMemcpyAsync(d_tflags, own_tflags.data(), nq, hipMemcpyHostToDevice, s));
     if (seq) PSS_HIP(hipMemcpyAsync(d_sanch, rq.seq_anchors, nrow, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(terms_driver_kernel, dim3((u32)((nrp + 255) / 256)), dim3(256), 0, s, nc, d_goff, d_tflags, d_lo, d_cnt, nrp,
+    hipLaunchKernelGGL(terms_driver_kernel<true>, dim3((u32)((nrp + 255) / 256)), dim3(256), 0, s, nc, d_goff, d_tflags, d_lo, d_cnt, nrp,
                        d_gdrv, p_lo, p_cnt);
     return PSS_OK;
 }
@@ -2194,6 +2210,44 @@ int Batch::union_spellings()
     PSS_HIP(hipMemsetAsync(d_fbytes + ftotal, 0, 32, s));
     PSS_HIP(hipMemcpyAsync(d_fbytes, rq.fold_bytes, ftotal, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(fold_union_kernel, dim3((u32)((nrp + 255) / 256)), dim3(256), 0, s, nc, d_goff, d_fvoid, d_cnt, nrp, p_cnt);
+    return PSS_OK;
+}
+
+// Case-insensitive group batch: from the (spelling, chunk) pairs over the (term, chunk) pairs to the (group, chunk)
+// pairs.  What union_spellings sends up goes up per term -- spelling offsets, folded bytes (32 zero bytes behind them),
+// their offsets, seed offsets, void flags -- and with it what pick_drivers sends up: group offsets, term flags, anchor
+// bytes.  fold_union_kernel leaves every term's seed hits per chunk in d_tcnt; terms_driver_kernel picks the include term
+// with the fewest of them as the pair's driver.  Neither a term nor a pair has an interval of its own (p_lo is not read).
+int Batch::fold_drivers()
+{
+    const u64 ftotal = rq.fold_offsets[nterm];
+    const size_t goff_room = round_up(((size_t)nrow + 1) * 8, 64), toff_room = round_up(((size_t)nterm + 1) * 8, 64);
+    const size_t seed_room = round_up((size_t)nterm * 4, 64), flag_room = round_up((size_t)nterm, 64);
+    const size_t anch_room = seq ? round_up((size_t)nrow, 64) : 0, byte_room = round_up(ftotal + 32, 64);
+    const size_t tcnt_room = round_up((size_t)ntp * 4, 64);
+    PSS_TRY(take(Q_TERMS, goff_room + 2 * toff_room + seed_room + 2 * flag_room + anch_room + byte_room + tcnt_room + nrp * 8, d_goff));
+    d_soff = d_goff + goff_room / 8;
+    d_foff = d_soff + toff_room / 8;
+    d_fseed = reinterpret_cast<u32 *>(d_foff + toff_room / 8);
+    d_fvoid = reinterpret_cast<u8 *>(d_fseed) + seed_room;
+    d_tflags = d_fvoid + flag_room;
+    d_sanch = d_tflags + flag_room;
+    d_fbytes = d_sanch + anch_room;
+    d_tcnt = reinterpret_cast<u32 *>(d_fbytes + byte_room);
+    d_gdrv = reinterpret_cast<u32 *>(reinterpret_cast<u8 *>(d_tcnt) + tcnt_room);
+    p_cnt = d_gdrv + nrp;
+    PSS_HIP(hipMemcpyAsync(d_goff, rq.group_offsets, ((size_t)nrow + 1) * 8, hipMemcpyHostToDevice, s));
+    PSS_HIP(hipMemcpyAsync(d_soff, rq.spell_offsets, ((size_t)nterm + 1) * 8, hipMemcpyHostToDevice, s));
+    PSS_HIP(hipMemcpyAsync(d_foff, rq.fold_offsets, ((size_t)nterm + 1) * 8, hipMemcpyHostToDevice, s));
+    PSS_HIP(hipMemcpyAsync(d_fseed, rq.fold_seed, (size_t)nterm * 4, hipMemcpyHostToDevice, s));
+    PSS_HIP(hipMemcpyAsync(d_fvoid, own_fvoid.data(), nterm, hipMemcpyHostToDevice, s));
+    PSS_HIP(hipMemcpyAsync(d_tflags, own_tflags.data(), nterm, hipMemcpyHostToDevice, s));
+    if (seq) PSS_HIP(hipMemcpyAsync(d_sanch, rq.seq_anchors, nrow, hipMemcpyHostToDevice, s));
+    PSS_HIP(hipMemsetAsync(d_fbytes + ftotal, 0, 32, s));
+    PSS_HIP(hipMemcpyAsync(d_fbytes, rq.fold_bytes, ftotal, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(fold_union_kernel, dim3((u32)((ntp + 255) / 256)), dim3(256), 0, s, nc, d_soff, d_fvoid, d_cnt, ntp, d_tcnt);
+    hipLaunchKernelGGL(terms_driver_kernel<false>, dim3((u32)((nrp + 255) / 256)), dim3(256), 0, s, nc, d_goff, d_tflags,
+                       (const u32 *)nullptr, d_tcnt, nrp, d_gdrv, (u32 *)nullptr, p_cnt);
     return PSS_OK;
 }
 
@@ -2232,21 +2286,36 @@ int Batch::run_general()
     else if (fold) {
         // every hit of every spelling against the whole pattern under fold; then the survivors against the entry in front of them
         PSS_TRY(take(Q_ORD_V0, H * 4, d_m));        // (the slot of the suffix-array order's values: that order is never a fold batch's)
-        hipLaunchKernelGGL(fold_hits_kernel, dim3(grid), dim3(256), 0, s, d_chunks, nc, d_fbytes, d_foff, d_fseed, d_goff, d_lo, d_cnt,
-                           nrp, d_hitoff, H, d_start, d_len, d_m);
         const u32 vgrid = (u32)std::min<u64>((u64)ctx->num_cus * 16, (H * TG + 255) / 256);
-        hipLaunchKernelGGL(fold_dedupe_kernel, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, d_fbytes, d_foff, nrp, d_hitoff, H, d_start,
-                           d_m, d_len);
+        if (!fgroups) {
+            hipLaunchKernelGGL(fold_hits_kernel<false>, dim3(grid), dim3(256), 0, s, d_chunks, nc, d_fbytes, d_foff, d_fseed, d_goff, d_lo,
+                               d_cnt, nrp, d_hitoff, H, d_start, d_len, d_m, (const u32 *)nullptr);
+            hipLaunchKernelGGL(fold_dedupe_kernel<false>, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, d_fbytes, d_foff, nrp, d_hitoff, H,
+                               d_start, d_m, d_len, (const u32 *)nullptr);
+        } else {
+            // (a group batch: the same two steps for each pair's driver term -- one candidate per entry that holds it under
+            // fold -- then every candidate against the group's other terms, or its segments in order, under fold)
+            hipLaunchKernelGGL(fold_hits_kernel<true>, dim3(grid), dim3(256), 0, s, d_chunks, nc, d_fbytes, d_foff, d_fseed, d_soff, d_lo,
+                               d_cnt, nrp, d_hitoff, H, d_start, d_len, d_m, d_gdrv);
+            hipLaunchKernelGGL(fold_dedupe_kernel<true>, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, d_fbytes, d_foff, nrp, d_hitoff, H,
+                               d_start, d_m, d_len, d_gdrv);
+            if (seq)
+                hipLaunchKernelGGL(seq_verify_kernel<true>, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, d_fbytes, d_foff, d_goff, d_sanch,
+                                   nrp, d_hitoff, H, d_start, d_len);
+            else
+                hipLaunchKernelGGL(terms_verify_kernel<true>, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, d_fbytes, d_foff, d_goff,
+                                   d_tflags, d_tcnt, d_gdrv, nrp, d_hitoff, H, d_start, d_len);
+        }
     } else if (terms) {
         // candidates: the entries that hold the pair's driver term; then every candidate against the group's other terms
         hipLaunchKernelGGL(hit_lines_kernel<true>, dim3(grid), dim3(256), 0, s, d_chunks, nc, d_q, d_qoff, nrp, p_lo, d_hitoff, H,
                            (const MidState *)nullptr, d_start, d_len, d_gdrv);
         const u32 vgrid = (u32)std::min<u64>((u64)ctx->num_cus * 16, (H * TG + 255) / 256);
         if (seq)    // (a sequence batch: every candidate against the group's segments in order, the driver among them)
-            hipLaunchKernelGGL(seq_verify_kernel, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, d_q, d_qoff, d_goff, d_sanch, nrp,
+            hipLaunchKernelGGL(seq_verify_kernel<false>, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, d_q, d_qoff, d_goff, d_sanch, nrp,
                                d_hitoff, H, d_start, d_len);
         else
-            hipLaunchKernelGGL(terms_verify_kernel, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, d_q, d_qoff, d_goff, d_tflags, d_cnt,
+            hipLaunchKernelGGL(terms_verify_kernel<false>, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, d_q, d_qoff, d_goff, d_tflags, d_cnt,
                                d_gdrv, nrp, d_hitoff, H, d_start, d_len);
     } else
         hipLaunchKernelGGL(hit_lines_kernel<false>, dim3(grid), dim3(256), 0, s, d_chunks, nc, d_q, d_qoff, nrp, p_lo,
@@ -2327,8 +2396,13 @@ int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, const LineDes
         set_error("search: an all-terms batch takes the general pipeline to a host result, and its terms are not anchored");
         return PSS_EINVAL;
     }
-    if (rq.fold_seed && (!rq.group_offsets || !rq.fold_bytes || !rq.fold_offsets || rq.exclude || rq.seq_anchors)) {
-        set_error("search: a case-insensitive batch is the spellings of its patterns' seeds in groups, without exclusions or anchors");
+    if (rq.fold_seed && (!rq.group_offsets || !rq.fold_bytes || !rq.fold_offsets || ((rq.exclude || rq.seq_anchors) && !rq.spell_offsets))) {
+        set_error("search: a case-insensitive batch is the spellings of its patterns' seeds in groups; exclusions or sequence anchors "
+                  "need the spelling offsets of a group batch");
+        return PSS_EINVAL;
+    }
+    if (rq.spell_offsets && (!rq.fold_seed || (rq.nterms && !rq.exclude && !rq.seq_anchors))) {
+        set_error("search: a case-insensitive group batch states its terms' seeds and either exclude flags or sequence anchors");
         return PSS_EINVAL;
     }
     const u32 rows = rq.rows();
@@ -2355,7 +2429,9 @@ int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, const LineDes
         PSS_TRY(b.run_mid(&done));
         if (done) return b.finish();
     }
-    if (b.fold) {
+    if (b.fgroups) {
+        PSS_TRY(b.fold_drivers());
+    } else if (b.fold) {
         PSS_TRY(b.union_spellings());
     } else if (b.terms) {
         PSS_TRY(b.pick_drivers());
