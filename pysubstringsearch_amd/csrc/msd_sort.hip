@@ -131,6 +131,17 @@ struct MsdArgs {
     u32 *bad;
 };
 
+// Pins a loaded value: the load that produced it cannot be sunk into a later branch.
+__device__ __forceinline__ void keep_load(u64 &v) { asm volatile("" : "+v"(v)); }
+__device__ __forceinline__ void keep_load(uint4 &v) { asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w)); }
+
+// Workgroup barrier that waits for this wave's LDS traffic only: global loads issued before it (the
+// prefetch of the next tile) stay in flight across it.
+__device__ __forceinline__ void lds_barrier()
+{
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+}
+
 // ---- tile machinery of the two global passes -----------------------------------------------------
 
 template <bool FROM_TEXT>
@@ -524,7 +535,8 @@ __global__ __launch_bounds__(MSD_BLOCK, 4) void msd_scatter_kernel(MsdArgs a)
 // The same pass over tiles of 16384 elements (1024 threads x 16): twice as many elements per bin and tile, so the runs
 // the output loop writes are 16 x 8 = 128 bytes on average -- whole lines instead of half lines; the pass is bound by
 // the 128-byte lines it touches (docs/history 4.3).  LDS stages 8192 elements at a time: the tile goes through in two
-// pieces by destination position.
+// pieces by destination position.  (The whole tile in one piece -- 128 KiB of the CU's 160, one round of writes, two
+// barriers fewer -- was measured in both kernels and is no faster: DESIGN 4.2.)
 constexpr u32 MSD_TILE2 = 16384;
 constexpr int MSD_PIECES2 = MSD_TILE2 / MSD_TILE;    // 2
 
@@ -566,6 +578,19 @@ __global__ __launch_bounds__(BLOCK) void msd_scatter2_kernel(MsdArgs a)
     const u64 low_mask2 = (1ull << shift2) - 1ull;
     const int rest_bits = a.key_bits - MSD_D;
     const u64 rest_mask = (1ull << rest_bits) - 1ull;
+    // From the text, the code words are loaded one tile ahead: all sixteen waves of the CU's only workgroup are in the
+    // same phase, so a load issued where it is used is a trip to memory nobody hides.  The words of the next tile are
+    // asked for once the registers of the current one are free (behind the staging writes of its second piece) and land
+    // under that piece's output and the next tile's first instructions.
+    uint4 ahead[FROM_TEXT ? IPT / 16 : 1][2] = {};
+    auto load_ahead = [&](u32 b) __attribute__((always_inline)) {
+#pragma unroll
+        for (int g = 0; g < IPT / 16; ++g) {
+            const u32 i0 = b + tid * IPT + g * 16;
+            if (i0 < a.n) text_keys16_load(a.codes, i0, ahead[g][0], ahead[g][1]);
+        }
+    };
+    if (FROM_TEXT) load_ahead(e0);
     for (u32 base = e0; base < e1; base += MSD_TILE2) {
         const u32 valid = min(MSD_TILE2, e1 - base);
         u64 elem[IPT];
@@ -573,12 +598,22 @@ __global__ __launch_bounds__(BLOCK) void msd_scatter2_kernel(MsdArgs a)
         if (FROM_TEXT) {
 #pragma unroll
             for (int g = 0; g < IPT / 16; ++g) {
-                const u32 i0 = base + tid * IPT + g * 16;
+                keep_load(ahead[g][0]);      // (or the compiler sinks the loads to this place, their use)
+                keep_load(ahead[g][1]);
+            }
+            // (the thread's first position, opaque per tile: hoisted out of the loop, "first position | k" is sixteen
+            //  registers held across every phase, and the kernel spills)
+            u32 pos0 = tid * IPT;
+            asm volatile("" : "+v"(pos0));
+#pragma unroll
+            for (int g = 0; g < IPT / 16; ++g) {
+                const u32 i0 = base + pos0 + g * 16;
                 u64 key[16] = {};
-                if (i0 < a.n) text_keys16(a.codes, i0, a.code_bits, a.key_chars, a.plus_one, a.key_drop, a.n, key);
+                if (i0 < a.n)
+                    text_keys16_pack(ahead[g][0], ahead[g][1], i0, a.code_bits, a.key_chars, a.plus_one, a.key_drop, a.n, key);
 #pragma unroll
                 for (int k = 0; k < 16; ++k) {
-                    const u32 pos = tid * IPT + g * 16 + k;
+                    const u32 pos = pos0 + g * 16 + k;
                     u32 d;
                     u64 keep;                                   // the K - 10 key bits the element carries on
                     if (LSD) {                                  // the pass's digit is the SECOND ten bits; the first ten stay
@@ -614,7 +649,7 @@ __global__ __launch_bounds__(BLOCK) void msd_scatter2_kernel(MsdArgs a)
                 c[j] = hist[BPT * tid + j] & 0xffffu;
                 sum += c[j];
             }
-            u32 ex = block_excl_sum<BLOCK / kWave>(sum, scr, nullptr);
+            u32 ex = block_excl_sum_lean<BLOCK / kWave>(sum, scr);
 #pragma unroll
             for (int j = 0; j < BPT; ++j) {
                 const u32 i = BPT * tid + j;
@@ -639,7 +674,10 @@ __global__ __launch_bounds__(BLOCK) void msd_scatter2_kernel(MsdArgs a)
                 const u32 q = lp[k] - h * MSD_TILE;
                 if (q < MSD_TILE) exch[q] = elem[k];
             }
-            __syncthreads();                                // (C) the piece in bin order
+            // (a tile with a successor in its range is full: its last piece is the last one of the loop.  elem and lp are
+            //  dead from here: room for the words)
+            if (FROM_TEXT && h == MSD_PIECES2 - 1 && (u64)base + MSD_TILE2 < e1) load_ahead(base + MSD_TILE2);
+            lds_barrier();                                  // (C) the piece in bin order; the loads stay in flight
 #pragma unroll
             for (int k = 0; k < (int)(MSD_TILE / BLOCK); ++k) {
                 const u32 q = k * BLOCK + tid, p = h * MSD_TILE + q;
@@ -1320,16 +1358,6 @@ __global__ __launch_bounds__(256) void msd_tile_desc_kernel(const u32 *cstart, c
     } else {
         tiles[t] = MsdTile{e0, e1 - e0, k0 & (MSD_TAG_SPAN - 1u), k1 - k0};
     }
-}
-
-// Workgroup barrier that waits for this wave's LDS traffic only: global loads issued before it (the
-// prefetch of the next tile) stay in flight across it.
-// Pins a loaded value: the load that produced it cannot be sunk into a later branch.
-__device__ __forceinline__ void keep_load(u64 &v) { asm volatile("" : "+v"(v)); }
-
-__device__ __forceinline__ void lds_barrier()
-{
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
 // The rows of a tile (row r = positions r * 512 + tid), G at a time: every row but the last one is full, so a group

@@ -108,6 +108,26 @@ __device__ __forceinline__ u32 block_excl_sum(u32 v, u32 *scratch, u32 *total)
     return base + incl - v;
 }
 
+// The same sum for a kernel short of registers: the wave sums by DPP adds and the wave's number as the scalar it is,
+// so no lane mask is held across the caller's loop (block_excl_sum: six "lane >= o" and WAVES "w < wave" masks, two
+// scalar registers each, all loop invariants).
+template <int WAVES>
+__device__ __forceinline__ u32 block_excl_sum_lean(u32 v, u32 *scratch)
+{
+    const u32 incl = wave_incl_sum_dpp(v);
+    const u32 wid = (u32)__builtin_amdgcn_readfirstlane((int)wave_id());
+    if (lane_id() == kWave - 1) scratch[wid] = incl;
+    __syncthreads();
+    u32 base = 0;
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) {
+        const u32 s = scratch[w];
+        base += (u32)w < wid ? s : 0u;
+    }
+    __syncthreads();
+    return base + incl - v;
+}
+
 // XCD-aware work assignment.  The dispatcher is observed to place workgroup b
 // on XCD (b % 8); handing XCD x a CONTIGUOUS eighth of the ranges keeps
 // neighbouring ranges (whose scatter destinations are adjacent inside every

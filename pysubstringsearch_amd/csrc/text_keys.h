@@ -7,13 +7,20 @@ namespace pss {
 
 constexpr int TK_IPT = 16;   // suffixes per thread
 
-// Packs the keys of 16 consecutive suffixes i0 .. i0+15 (i0 % 16 == 0) from the
-// recoded text.  Sliding window: key(i+1) = ((key(i) << b) | code[i+k]) & mask.
-__device__ __forceinline__ void text_keys16(const u8 *codes, u32 i0, int b, int k, int plus_one, int drop, u32 n,
-                                            u64 (&key)[TK_IPT])
+// The 32 code bytes the keys of suffixes i0 .. i0+15 are packed from (i0 % 16 == 0; codes are zero padded past n).
+// Load and packing are separate so that a kernel can issue the load of its next tile early (msd_scatter2_kernel).
+__device__ __forceinline__ void text_keys16_load(const u8 *codes, u32 i0, uint4 &lo, uint4 &hi)
 {
     const uint4 *p = reinterpret_cast<const uint4 *>(codes + i0);
-    const uint4 lo = p[0], hi = p[1];
+    lo = p[0];
+    hi = p[1];
+}
+
+// Packs the keys of 16 consecutive suffixes i0 .. i0+15 from the words text_keys16_load brought.
+// Sliding window: key(i+1) = ((key(i) << b) | code[i+k]) & mask.
+__device__ __forceinline__ void text_keys16_pack(const uint4 &lo, const uint4 &hi, u32 i0, int b, int k, int plus_one, int drop,
+                                                 u32 n, u64 (&key)[TK_IPT])
+{
     const u64 q0 = (u64)lo.x | ((u64)lo.y << 32), q1 = (u64)lo.z | ((u64)lo.w << 32);
     const u64 q2 = (u64)hi.x | ((u64)hi.y << 32), q3 = (u64)hi.z | ((u64)hi.w << 32);
     const u64 mask = (k * b >= 64) ? ~0ull : ((1ull << (k * b)) - 1ull);
@@ -47,6 +54,14 @@ __device__ __forceinline__ void text_keys16(const u8 *codes, u32 i0, int b, int 
         win = ((win << b) | c) & mask;
         key[r] = win >> drop;
     }
+}
+
+__device__ __forceinline__ void text_keys16(const u8 *codes, u32 i0, int b, int k, int plus_one, int drop, u32 n,
+                                            u64 (&key)[TK_IPT])
+{
+    uint4 lo, hi;
+    text_keys16_load(codes, i0, lo, hi);
+    text_keys16_pack(lo, hi, i0, b, k, plus_one, drop, n, key);
 }
 
 // The key of ONE suffix: the k <= 16 symbols from text position j on, b bits each, first symbol highest (the text rounds of
