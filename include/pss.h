@@ -584,7 +584,8 @@ int pss_reader_count_seq_batch(pss_reader *r, const uint8_t *sbytes, const uint6
  * are its spellings' intervals one behind the other: disjoint and ascending, so still in suffix-array order.  Every hit is
  * verified on the device: the whole pattern around the seed occurrence under fold, then the entry in front of the match for
  * an earlier folded occurrence -- the hit of an entry's LEFTMOST folded match stands for the entry, whatever mix of spellings
- * the entry holds.  The answer is exact for every pattern length.  pss_icase_variants shows the expansion.
+ * the entry holds.  The answer is exact for every pattern length.  pss_icase_variants shows the expansion.  It is the
+ * one-term case of pss_reader_search_terms_icase_batch: every pattern a group of one include term.
  * Order: pattern-major, chunk-major inside a pattern; inside one (pattern, chunk) pair the suffix-array order of the seed's
  * occurrence inside each entry's leftmost folded match, the same for the text and the id variant -- pss_reader_set_result_order
  * has no effect.  A pattern without an ASCII letter returns exactly what pss_reader_search_ids_batch returns for it under the

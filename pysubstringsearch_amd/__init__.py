@@ -337,26 +337,7 @@ def _folded_batch(kind: str, form: str):
             'counts': f'pss_reader_count_{kind}_icase_batch'}[form]
 
     def run(self, batch):
-        import numpy as np
-        blob, offs, goff, extra = getattr(self, pack)(batch)
-        ng = len(goff) - 1
-        call = getattr(_lib, name)
-        if form == 'counts':
-            counts = np.zeros(max(ng, 1), dtype=np.uint64)
-            _ffi.check(call(self._handle(), blob, offs.ctypes.data, len(offs) - 1, goff.ctypes.data, ng, extra.ctypes.data, counts.ctypes.data))
-            return [int(c) for c in counts[:ng]]
-        res = ctypes.c_void_p()
-        _ffi.check(call(self._handle(), blob, offs.ctypes.data, len(offs) - 1, goff.ctypes.data, ng, extra.ctypes.data, ctypes.byref(res)))
-        owner = _ResultOwner(res)      # the arrays below are views of the C result; it lives as long as they do
-        n = _lib.pss_result_num_entries(res)
-        counts = owner.view(_lib.pss_result_query_counts(res), ng, np.uint64)
-        if form == 'ids':
-            ids = owner.view(_lib.pss_result_bytes(res), 8 * n, np.uint8).view(np.uint64)
-            ids.flags.writeable = False
-            return IdResult(ids, counts)
-        offsets = owner.view(_lib.pss_result_offsets(res), n + 1, np.uint64)
-        data = owner.view(_lib.pss_result_bytes(res), int(offsets[n]), np.uint8)
-        return PackedResult(data, offsets, counts)
+        return self._group_batch(name, getattr(self, pack)(batch), form)
     return run
 
 
@@ -528,6 +509,39 @@ class Reader:
         _ffi.check(_lib.pss_reader_low_latency_stats(self._handle(), ctypes.byref(launches), ctypes.byref(served)))
         return {'kernels_started': launches.value, 'queries_served': served.value}
 
+    def _batch(self, call, args, nrows: int, form: str):
+        """One batched C call ``call(handle, *args, out)`` and its result of ``nrows`` rows (queries, groups or ids) in the
+        given ``form``: 'packed' -> ``PackedResult``, 'ids' -> ``IdResult``, 'counts' -> a list of int."""
+        import numpy as np
+        if form == 'counts':
+            counts = np.zeros(max(nrows, 1), dtype=np.uint64)
+            _ffi.check(call(self._handle(), *args, counts.ctypes.data))
+            return [int(c) for c in counts[:nrows]]
+        res = ctypes.c_void_p()
+        _ffi.check(call(self._handle(), *args, ctypes.byref(res)))
+        owner = _ResultOwner(res)      # the arrays below are views of the C result; it lives as long as they do
+        n = _lib.pss_result_num_entries(res)
+        counts = owner.view(_lib.pss_result_query_counts(res), nrows, np.uint64)
+        if form == 'ids':
+            ids = owner.view(_lib.pss_result_bytes(res), 8 * n, np.uint8).view(np.uint64)
+            ids.flags.writeable = False     # (also the empty array of a batch without entries, which views nothing)
+            return IdResult(ids, counts)
+        offsets = owner.view(_lib.pss_result_offsets(res), n + 1, np.uint64)
+        data = owner.view(_lib.pss_result_bytes(res), int(offsets[n]), np.uint8)
+        return PackedResult(data, offsets, counts)
+
+    def _query_batch(self, name: str, packed, form: str, *extra):
+        """``_batch`` of the C call ``name`` over ``packed`` = (blob, offsets) of nq patterns, ``extra`` arrays behind them."""
+        blob, offs = packed
+        nq = len(offs) - 1
+        return self._batch(getattr(_lib, name), (blob, offs.ctypes.data, nq) + tuple(a.ctypes.data for a in extra), nq, form)
+
+    def _group_batch(self, name: str, packed, form: str):
+        """``_batch`` of the C call ``name`` over ``packed`` = (blob, offsets, group offsets, flags per term or group)."""
+        blob, offs, goff, extra = packed
+        ng = len(goff) - 1
+        return self._batch(getattr(_lib, name), (blob, offs.ctypes.data, len(offs) - 1, goff.ctypes.data, ng, extra.ctypes.data), ng, form)
+
     def _search_batch(self, patterns: typing.Sequence[bytes], as_str: bool):
         nq = len(patterns)
         if _pssglue is not None:
@@ -588,17 +602,7 @@ class Reader:
         them belong to query q).  For
         hit-heavy batches the Python list of ``search_multiple`` costs more than
         the search itself (~50 ns per entry); this is the bulk alternative."""
-        import numpy as np
-        nq = len(patterns)
-        blob, offs = _pack_queries(patterns)
-        res = ctypes.c_void_p()
-        _ffi.check(_lib.pss_reader_search_batch(self._handle(), blob, offs.ctypes.data, nq, ctypes.byref(res)))
-        owner = _ResultOwner(res)      # the arrays below are views of the C result; it lives as long as they do
-        n = _lib.pss_result_num_entries(res)
-        counts = owner.view(_lib.pss_result_query_counts(res), nq, np.uint64)
-        offsets = owner.view(_lib.pss_result_offsets(res), n + 1, np.uint64)
-        data = owner.view(_lib.pss_result_bytes(res), int(offsets[n]), np.uint8)
-        return PackedResult(data, offsets, counts)
+        return self._query_batch('pss_reader_search_batch', _pack_queries(patterns), 'packed')
 
     def search_ids_batch(self, patterns: typing.Sequence[bytes]) -> 'IdResult':
         """Extension: WHICH entries match instead of their text -- one ``uint64`` id per entry
@@ -608,17 +612,7 @@ class Reader:
         reader.  8 bytes per entry come down whatever the entries' length; ``entries_by_id`` fetches the text of the
         ones that are wanted, ``entry_ordinals`` turns ids into positions in the order the entries were added (line
         numbers of the file given to ``add_entries_from_file_lines``)."""
-        import numpy as np
-        nq = len(patterns)
-        blob, offs = _pack_queries(patterns)
-        res = ctypes.c_void_p()
-        _ffi.check(_lib.pss_reader_search_ids_batch(self._handle(), blob, offs.ctypes.data, nq, ctypes.byref(res)))
-        owner = _ResultOwner(res)      # the arrays below are views of the C result; it lives as long as they do
-        n = _lib.pss_result_num_entries(res)
-        counts = owner.view(_lib.pss_result_query_counts(res), nq, np.uint64)
-        ids = owner.view(_lib.pss_result_bytes(res), 8 * n, np.uint8).view(np.uint64)
-        ids.flags.writeable = False     # (also the empty array of a batch without entries, which views nothing)
-        return IdResult(ids, counts)
+        return self._query_batch('pss_reader_search_ids_batch', _pack_queries(patterns), 'ids')
 
     def search_ids(self, substring: str):
         """Extension: the ids of the entries ``search(substring)`` returns, in its order (numpy uint64)."""
@@ -637,13 +631,7 @@ class Reader:
                 raise ValueError('entry ids are not negative')
             arr = arr.astype(np.uint64)
         n = int(arr.size)
-        res = ctypes.c_void_p()
-        _ffi.check(_lib.pss_reader_entries_by_id(self._handle(), arr.ctypes.data, n, ctypes.byref(res)))
-        owner = _ResultOwner(res)
-        counts = owner.view(_lib.pss_result_query_counts(res), n, np.uint64)
-        offsets = owner.view(_lib.pss_result_offsets(res), n + 1, np.uint64)
-        data = owner.view(_lib.pss_result_bytes(res), int(offsets[n]), np.uint8)
-        return PackedResult(data, offsets, counts)
+        return self._batch(_lib.pss_reader_entries_by_id, (arr.ctypes.data, n), n, 'packed')
 
     def entries_by_id(self, ids) -> typing.List[bytes]:
         """Extension: ``entries_by_id_packed`` as a list of byte strings."""
@@ -682,47 +670,22 @@ class Reader:
         pattern matches every entry under 'start' and 'end' and the empty entries under 'entry'; a pattern holding a
         newline matches nothing.  The suffix array holds the answer as one interval -- of ``"\\n" + pattern`` and the
         like -- so the work follows the number of matching entries, not of occurrences (include/pss.h)."""
-        import numpy as np
-        nq = len(patterns)
         blob, offs, anc = self._anchored_args(patterns, anchors)
-        res = ctypes.c_void_p()
-        _ffi.check(_lib.pss_reader_search_anchored_batch(self._handle(), blob, offs.ctypes.data, nq, anc.ctypes.data, ctypes.byref(res)))
-        owner = _ResultOwner(res)      # the arrays below are views of the C result; it lives as long as they do
-        n = _lib.pss_result_num_entries(res)
-        counts = owner.view(_lib.pss_result_query_counts(res), nq, np.uint64)
-        offsets = owner.view(_lib.pss_result_offsets(res), n + 1, np.uint64)
-        data = owner.view(_lib.pss_result_bytes(res), int(offsets[n]), np.uint8)
-        return PackedResult(data, offsets, counts)
+        return self._query_batch('pss_reader_search_anchored_batch', (blob, offs), 'packed', anc)
 
     def search_anchored_ids_batch(self, patterns: typing.Sequence[bytes], anchors) -> 'IdResult':
         """Extension: the ids (``search_ids_batch``) of the entries ``search_anchored_batch_packed`` returns, in the
         same order."""
-        import numpy as np
-        nq = len(patterns)
         blob, offs, anc = self._anchored_args(patterns, anchors)
-        res = ctypes.c_void_p()
-        _ffi.check(_lib.pss_reader_search_anchored_ids_batch(self._handle(), blob, offs.ctypes.data, nq, anc.ctypes.data, ctypes.byref(res)))
-        owner = _ResultOwner(res)
-        n = _lib.pss_result_num_entries(res)
-        counts = owner.view(_lib.pss_result_query_counts(res), nq, np.uint64)
-        ids = owner.view(_lib.pss_result_bytes(res), 8 * n, np.uint8).view(np.uint64)
-        ids.flags.writeable = False
-        return IdResult(ids, counts)
+        return self._query_batch('pss_reader_search_anchored_ids_batch', (blob, offs), 'ids', anc)
 
     def count_anchored_bytes(self, patterns: typing.Sequence[bytes], anchors) -> typing.List[int]:
         """Extension: how many entries each pattern matches under its anchor; only the counters come back."""
-        import numpy as np
-        nq = len(patterns)
         blob, offs, anc = self._anchored_args(patterns, anchors)
-        counts = np.zeros(max(nq, 1), dtype=np.uint64)
-        _ffi.check(_lib.pss_reader_count_anchored_batch(self._handle(), blob, offs.ctypes.data, nq, anc.ctypes.data, counts.ctypes.data))
-        return [int(c) for c in counts[:nq]]
+        return self._query_batch('pss_reader_count_anchored_batch', (blob, offs), 'counts', anc)
 
     def _search_anchored_str(self, s: str, anchor: str) -> typing.List[str]:
-        p = self.search_anchored_batch_packed([_utf8(s, 'substring')], anchor)
-        data = p.data.tobytes()
-        o = p.offsets.tolist()
-        return [data[o[i]:o[i + 1]].decode('utf-8') for i in range(len(o) - 1)]
+        return _packed_strs(self.search_anchored_batch_packed([_utf8(s, 'substring')], anchor))
 
     def search_prefix(self, s: str) -> typing.List[str]:
         """Extension: the entries that start with ``s``."""
@@ -779,46 +742,18 @@ class Reader:
         union of the exclude terms'.  On the device the rarest include term of every (group, chunk) pair drives the
         search and its candidate entries are checked against the other terms, so the work follows the rarest term
         (include/pss.h).  ``set_result_order`` has no effect."""
-        import numpy as np
-        blob, offs, goff, excl = self._terms_args(groups)
-        ng = len(goff) - 1
-        res = ctypes.c_void_p()
-        _ffi.check(_lib.pss_reader_search_terms_batch(self._handle(), blob, offs.ctypes.data, len(offs) - 1, goff.ctypes.data, ng,
-                                                      excl.ctypes.data, ctypes.byref(res)))
-        owner = _ResultOwner(res)      # the arrays below are views of the C result; it lives as long as they do
-        n = _lib.pss_result_num_entries(res)
-        counts = owner.view(_lib.pss_result_query_counts(res), ng, np.uint64)
-        offsets = owner.view(_lib.pss_result_offsets(res), n + 1, np.uint64)
-        data = owner.view(_lib.pss_result_bytes(res), int(offsets[n]), np.uint8)
-        return PackedResult(data, offsets, counts)
+        return self._group_batch('pss_reader_search_terms_batch', self._terms_args(groups), 'packed')
 
     @_with_icase(_folded_batch('terms', 'ids'), _ICASE_ALL)
     def search_all_ids_batch(self, groups) -> 'IdResult':
         """Extension: the ids (``search_ids_batch``) of the entries ``search_all_batch_packed`` returns, in the same
         order; ``counts[g]`` of them belong to group g."""
-        import numpy as np
-        blob, offs, goff, excl = self._terms_args(groups)
-        ng = len(goff) - 1
-        res = ctypes.c_void_p()
-        _ffi.check(_lib.pss_reader_search_terms_ids_batch(self._handle(), blob, offs.ctypes.data, len(offs) - 1, goff.ctypes.data, ng,
-                                                          excl.ctypes.data, ctypes.byref(res)))
-        owner = _ResultOwner(res)
-        n = _lib.pss_result_num_entries(res)
-        counts = owner.view(_lib.pss_result_query_counts(res), ng, np.uint64)
-        ids = owner.view(_lib.pss_result_bytes(res), 8 * n, np.uint8).view(np.uint64)
-        ids.flags.writeable = False
-        return IdResult(ids, counts)
+        return self._group_batch('pss_reader_search_terms_ids_batch', self._terms_args(groups), 'ids')
 
     @_with_icase(_folded_batch('terms', 'counts'), _ICASE_ALL)
     def count_all_bytes(self, groups) -> typing.List[int]:
         """Extension: how many entries each group matches; only the counters come back."""
-        import numpy as np
-        blob, offs, goff, excl = self._terms_args(groups)
-        ng = len(goff) - 1
-        counts = np.zeros(max(ng, 1), dtype=np.uint64)
-        _ffi.check(_lib.pss_reader_count_terms_batch(self._handle(), blob, offs.ctypes.data, len(offs) - 1, goff.ctypes.data, ng,
-                                                     excl.ctypes.data, counts.ctypes.data))
-        return [int(c) for c in counts[:ng]]
+        return self._group_batch('pss_reader_count_terms_batch', self._terms_args(groups), 'counts')
 
     @staticmethod
     def _str_terms(terms, exclude):
@@ -830,10 +765,7 @@ class Reader:
     @_with_icase(_folded_search_all, _ICASE_ALL)
     def search_all(self, terms: typing.Sequence[str], exclude: typing.Sequence[str] = ()) -> typing.List[str]:
         """Extension: the entries that contain every one of ``terms`` and none of ``exclude``."""
-        p = self.search_all_batch_packed(self._str_terms(terms, exclude))
-        data = p.data.tobytes()
-        o = p.offsets.tolist()
-        return [data[o[i]:o[i + 1]].decode('utf-8') for i in range(len(o) - 1)]
+        return _packed_strs(self.search_all_batch_packed(self._str_terms(terms, exclude)))
 
     @_with_icase(_folded_count_all, _ICASE_ALL)
     def count_all(self, terms: typing.Sequence[str], exclude: typing.Sequence[str] = ()) -> int:
@@ -867,54 +799,23 @@ class Reader:
         bytes; every entry at most once per pattern; a piece holding a newline matches nothing.  On the device the rarest
         piece of every (pattern, chunk) pair drives the search and each candidate entry is walked once, left to right
         (include/pss.h, pss_reader_search_seq_batch).  ``set_result_order`` has no effect."""
-        import numpy as np
-        blob, offs, goff, anch = self._glob_args(patterns)
-        ng = len(goff) - 1
-        res = ctypes.c_void_p()
-        _ffi.check(_lib.pss_reader_search_seq_batch(self._handle(), blob, offs.ctypes.data, len(offs) - 1, goff.ctypes.data, ng,
-                                                    anch.ctypes.data, ctypes.byref(res)))
-        owner = _ResultOwner(res)      # the arrays below are views of the C result; it lives as long as they do
-        n = _lib.pss_result_num_entries(res)
-        counts = owner.view(_lib.pss_result_query_counts(res), ng, np.uint64)
-        offsets = owner.view(_lib.pss_result_offsets(res), n + 1, np.uint64)
-        data = owner.view(_lib.pss_result_bytes(res), int(offsets[n]), np.uint8)
-        return PackedResult(data, offsets, counts)
+        return self._group_batch('pss_reader_search_seq_batch', self._glob_args(patterns), 'packed')
 
     @_with_icase(_folded_batch('seq', 'ids'), _ICASE_GLOB)
     def search_glob_ids_batch(self, patterns: typing.Sequence[bytes]) -> 'IdResult':
         """Extension: the ids (``search_ids_batch``) of the entries ``search_glob_batch_packed`` returns, in the same
         order; ``counts[g]`` of them belong to pattern g."""
-        import numpy as np
-        blob, offs, goff, anch = self._glob_args(patterns)
-        ng = len(goff) - 1
-        res = ctypes.c_void_p()
-        _ffi.check(_lib.pss_reader_search_seq_ids_batch(self._handle(), blob, offs.ctypes.data, len(offs) - 1, goff.ctypes.data, ng,
-                                                        anch.ctypes.data, ctypes.byref(res)))
-        owner = _ResultOwner(res)
-        n = _lib.pss_result_num_entries(res)
-        counts = owner.view(_lib.pss_result_query_counts(res), ng, np.uint64)
-        ids = owner.view(_lib.pss_result_bytes(res), 8 * n, np.uint8).view(np.uint64)
-        ids.flags.writeable = False
-        return IdResult(ids, counts)
+        return self._group_batch('pss_reader_search_seq_ids_batch', self._glob_args(patterns), 'ids')
 
     @_with_icase(_folded_batch('seq', 'counts'), _ICASE_GLOB)
     def count_glob_bytes(self, patterns: typing.Sequence[bytes]) -> typing.List[int]:
         """Extension: how many entries each glob pattern matches; only the counters come back."""
-        import numpy as np
-        blob, offs, goff, anch = self._glob_args(patterns)
-        ng = len(goff) - 1
-        counts = np.zeros(max(ng, 1), dtype=np.uint64)
-        _ffi.check(_lib.pss_reader_count_seq_batch(self._handle(), blob, offs.ctypes.data, len(offs) - 1, goff.ctypes.data, ng,
-                                                   anch.ctypes.data, counts.ctypes.data))
-        return [int(c) for c in counts[:ng]]
+        return self._group_batch('pss_reader_count_seq_batch', self._glob_args(patterns), 'counts')
 
     @_with_icase(_folded_search_glob, _ICASE_GLOB)
     def search_glob(self, s: str) -> typing.List[str]:
         """Extension: the entries that match the glob pattern ``s`` (``*`` = any run of bytes, ``\\`` escapes)."""
-        p = self.search_glob_batch_packed([_utf8(s, 'pattern')])
-        data = p.data.tobytes()
-        o = p.offsets.tolist()
-        return [data[o[i]:o[i + 1]].decode('utf-8') for i in range(len(o) - 1)]
+        return _packed_strs(self.search_glob_batch_packed([_utf8(s, 'pattern')]))
 
     @_with_icase(_folded_count_glob, _ICASE_GLOB)
     def count_glob(self, s: str) -> int:
@@ -942,51 +843,23 @@ class Reader:
         exact-byte: the spellings of a SEED of the pattern (``icase_variants``) are looked up and every hit is verified
         against the whole pattern on the device, so the work follows the occurrences of the folded seed
         (include/pss.h, pss_reader_search_icase_batch).  ``set_result_order`` has no effect."""
-        import numpy as np
-        blob, offs = self._icase_args(patterns)
-        nq = len(offs) - 1
-        res = ctypes.c_void_p()
-        _ffi.check(_lib.pss_reader_search_icase_batch(self._handle(), blob, offs.ctypes.data, nq, ctypes.byref(res)))
-        owner = _ResultOwner(res)      # the arrays below are views of the C result; it lives as long as they do
-        n = _lib.pss_result_num_entries(res)
-        counts = owner.view(_lib.pss_result_query_counts(res), nq, np.uint64)
-        offsets = owner.view(_lib.pss_result_offsets(res), n + 1, np.uint64)
-        data = owner.view(_lib.pss_result_bytes(res), int(offsets[n]), np.uint8)
-        return PackedResult(data, offsets, counts)
+        return self._query_batch('pss_reader_search_icase_batch', self._icase_args(patterns), 'packed')
 
     def search_icase_ids_batch(self, patterns: typing.Sequence[bytes]) -> 'IdResult':
         """Extension: the ids (``search_ids_batch``) of the entries ``search_icase_batch_packed`` returns, in the same
         order; ``counts[q]`` of them belong to pattern q.  Only ASCII letters fold.  A pattern without an ASCII letter
         returns exactly what ``search_ids_batch`` returns for it."""
-        import numpy as np
-        blob, offs = self._icase_args(patterns)
-        nq = len(offs) - 1
-        res = ctypes.c_void_p()
-        _ffi.check(_lib.pss_reader_search_icase_ids_batch(self._handle(), blob, offs.ctypes.data, nq, ctypes.byref(res)))
-        owner = _ResultOwner(res)
-        n = _lib.pss_result_num_entries(res)
-        counts = owner.view(_lib.pss_result_query_counts(res), nq, np.uint64)
-        ids = owner.view(_lib.pss_result_bytes(res), 8 * n, np.uint8).view(np.uint64)
-        ids.flags.writeable = False
-        return IdResult(ids, counts)
+        return self._query_batch('pss_reader_search_icase_ids_batch', self._icase_args(patterns), 'ids')
 
     def count_icase_bytes(self, patterns: typing.Sequence[bytes]) -> typing.List[int]:
         """Extension: how many entries contain each pattern whatever the case of its ASCII letters (only they fold); only
         the counters come back."""
-        import numpy as np
-        blob, offs = self._icase_args(patterns)
-        nq = len(offs) - 1
-        counts = np.zeros(max(nq, 1), dtype=np.uint64)
-        _ffi.check(_lib.pss_reader_count_icase_batch(self._handle(), blob, offs.ctypes.data, nq, counts.ctypes.data))
-        return [int(c) for c in counts[:nq]]
+        return self._query_batch('pss_reader_count_icase_batch', self._icase_args(patterns), 'counts')
 
     def search_icase(self, s: str) -> typing.List[str]:
         """Extension: the entries that contain ``s`` (UTF-8 encoded) whatever the case of its ASCII letters.  Only
         ``A-Z`` / ``a-z`` fold: ``'é'`` does not match ``'É'``."""
-        p = self.search_icase_batch_packed([_utf8(s, 'substring')])
-        data = p.data.tobytes()
-        o = p.offsets.tolist()
-        return [data[o[i]:o[i + 1]].decode('utf-8') for i in range(len(o) - 1)]
+        return _packed_strs(self.search_icase_batch_packed([_utf8(s, 'substring')]))
 
     def count_icase(self, s: str) -> int:
         """Extension: how many entries contain ``s`` (UTF-8 encoded) whatever the case of its ASCII letters (only they
@@ -1057,12 +930,7 @@ class Reader:
 
     def count_multiple_bytes(self, patterns: typing.Sequence[bytes]) -> typing.List[int]:
         """``count_multiple`` for queries that are already bytes."""
-        import numpy as np
-        nq = len(patterns)
-        blob, offs = _pack_queries(patterns)
-        counts = np.zeros(max(nq, 1), dtype=np.uint64)
-        _ffi.check(_lib.pss_reader_count_batch(self._handle(), blob, offs.ctypes.data, nq, counts.ctypes.data))
-        return [int(c) for c in counts[:nq]]
+        return self._query_batch('pss_reader_count_batch', _pack_queries(patterns), 'counts')
 
     def search_batch_raw(self, patterns: typing.Sequence[bytes]):
         """One batched device call.  Returns (entries, per_query_counts): the

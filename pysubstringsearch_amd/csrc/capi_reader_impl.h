@@ -1415,174 +1415,19 @@ extern "C" int pss_reader_count_seq_batch(pss_reader *r, const uint8_t *sbytes, 
     });
 }
 
-// ---- case-insensitive search: the spellings of a seed (fold_impl.h) -----------------------------------------------
+// ---- case-insensitive search: group -> terms -> the spellings of a seed (fold_impl.h) --------------
 
 namespace {
 
 uint32_t icase_letters(int32_t letters) { return letters <= 0 ? search_knobs().icase_seed_letters : (uint32_t)letters; }
 
-// A batch of patterns as the interval search takes it: the spellings of every pattern's seed as the terms of one group
-// per pattern, and beside them the patterns folded to lower case with their seeds' offsets.
-struct IcaseBatch {
-    std::vector<uint8_t> vbytes, fbytes;
-    std::vector<uint64_t> voff, goff;
-    std::vector<uint32_t> seed;
-    SearchRequest request(const uint64_t *qoffsets, uint32_t nq, SearchMode mode) const
-    {
-        SearchRequest rq{vbytes.data(), voff.data(), (uint32_t)(voff.size() - 1), mode, nullptr, goff.data(), nq};
-        rq.fold_seed = seed.data();
-        rq.fold_bytes = fbytes.data();
-        rq.fold_offsets = qoffsets ? qoffsets : goff.data();     // (no pattern: one closing 0)
-        return rq;
-    }
-};
-
-// The argument checks of the three case-insensitive calls (out_ok: the call's own output argument is usable), and the
-// expansion.
-int icase_args(const pss_reader *r, const char *who, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, bool out_ok,
-               IcaseBatch *b)
-{
-    if (!out_ok || (nq && (!qbytes || !qoffsets))) {
-        set_error("%s: bad arguments", who);
-        return PSS_EINVAL;
-    }
-    if (nq && qoffsets[0] != 0) {
-        set_error("%s: the pattern offsets start at %llu, not at 0", who, (unsigned long long)qoffsets[0]);
-        return PSS_EINVAL;
-    }
-    for (uint32_t q = 0; q < nq; ++q) {
-        if (qoffsets[q + 1] < qoffsets[q]) {
-            set_error("%s: the pattern offsets decrease at pattern %u", who, q);
-            return PSS_EINVAL;
-        }
-        if (qoffsets[q + 1] == qoffsets[q]) {
-            set_error("%s: pattern %u is empty (every entry contains the empty pattern)", who, q);
-            return PSS_EINVAL;
-        }
-        if (qoffsets[q + 1] - qoffsets[q] > 0xffffffffull) {
-            set_error("%s: pattern %u has more than 2^32 - 1 bytes (a chunk has fewer)", who, q);
-            return PSS_EINVAL;
-        }
-    }
-    // What the expansion holds is judged before anything is allocated for it.  At most 64 spellings per pattern: only a
-    // batch of more than 2^26 patterns can pass the limit, and only such a batch pays for a counting pass of its own.
-    const uint32_t letters = icase_letters(0);
-    const uint64_t total = nq ? qoffsets[nq] : 0;
-    if (((uint64_t)nq << letters) > 0xffffffffull) {
-        uint64_t count = 0;
-        for (uint32_t q = 0; q < nq; ++q) {
-            uint64_t so = 0, sl = 0;
-            count += 1ull << fold_seed(qbytes + qoffsets[q], qoffsets[q + 1] - qoffsets[q], letters, &so, &sl);
-            if (count > 0xffffffffull) {
-                set_error("%s: the patterns expand to more than the 2^32 - 1 terms an all-terms batch takes (at pattern %u)", who, q);
-                return PSS_EINVAL;
-            }
-        }
-    }
-    b->seed.resize(nq);
-    std::vector<uint64_t> slen(nq);
-    std::vector<uint8_t> nletters(nq);
-    uint64_t nterms = 0, vtotal = 0;
-    for (uint32_t q = 0; q < nq; ++q) {
-        uint64_t so = 0;
-        nletters[q] = (uint8_t)fold_seed(qbytes + qoffsets[q], qoffsets[q + 1] - qoffsets[q], letters, &so, &slen[q]);
-        nterms += 1ull << nletters[q];
-        vtotal += slen[q] << nletters[q];
-        b->seed[q] = (uint32_t)so;          // (inside a pattern of less than 2^32 bytes)
-    }
-    b->fbytes.resize(total + 1);
-    for (uint64_t i = 0; i < total; ++i) b->fbytes[i] = (uint8_t)((uint8_t)(qbytes[i] - 'A') < 26 ? qbytes[i] | 0x20 : qbytes[i]);
-    b->vbytes.resize(vtotal);
-    b->voff.reserve(nterms + 1);
-    b->goff.reserve((size_t)nq + 1);
-    b->voff.assign(1, 0);
-    b->goff.assign(1, 0);
-    for (uint32_t q = 0; q < nq; ++q) {
-        const uint32_t f = nletters[q];
-        fold_spellings(qbytes + qoffsets[q] + b->seed[q], slen[q], f, b->vbytes.data() + b->voff.back());
-        for (uint32_t v = 0; v < (1u << f); ++v) b->voff.push_back(b->voff.back() + slen[q]);
-        b->goff.push_back(b->goff.back() + (1ull << f));
-    }
-    b->vbytes.push_back(0);     // (data() of an empty vector may be null)
-    if (!r) {                   // (last, as for the all-terms calls: a malformed batch is reported as such with or without a reader)
-        set_error("%s: bad arguments (no reader)", who);
-        return PSS_EINVAL;
-    }
-    return PSS_OK;
-}
-
-}  // namespace
-
-extern "C" int pss_icase_variants(const uint8_t *pat, uint64_t len, int32_t letters, uint8_t *out, uint64_t cap, uint32_t *seed_off,
-                                  uint32_t *seed_len, uint32_t *count)
-{
-    return guarded([&]() -> int {
-        if (!pat || !len) {
-            set_error("pss_icase_variants: the pattern is empty (every entry contains the empty pattern)");
-            return PSS_EINVAL;
-        }
-        if (letters > 6 || !seed_off || !seed_len || !count) {
-            set_error("pss_icase_variants: bad arguments (letters = %d: 1 .. 6, or <= 0 for PSS_ICASE_SEED_LETTERS)", (int)letters);
-            return PSS_EINVAL;
-        }
-        uint64_t so = 0, sl = 0;
-        const uint32_t f = fold_seed(pat, len, icase_letters(letters), &so, &sl);
-        if (so > 0xffffffffull || sl > 0xffffffffull) {
-            set_error("pss_icase_variants: a pattern of %llu bytes", (unsigned long long)len);
-            return PSS_EINVAL;
-        }
-        *seed_off = (uint32_t)so;
-        *seed_len = (uint32_t)sl;
-        *count = 1u << f;
-        if (!out) return PSS_OK;            // (the sizes alone)
-        if (cap < (sl << f)) {
-            set_error("pss_icase_variants: %u variants of %llu bytes need more than the %llu bytes of out", 1u << f, (unsigned long long)sl,
-                      (unsigned long long)cap);
-            return PSS_EINVAL;
-        }
-        fold_spellings(pat + so, sl, f, out);
-        return PSS_OK;
-    });
-}
-
-extern "C" int pss_reader_search_icase_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, pss_result **out)
-{
-    return guarded([&]() -> int {
-        IcaseBatch b;
-        PSS_TRY(icase_args(r, "pss_reader_search_icase_batch", qbytes, qoffsets, nq, out != nullptr, &b));
-        return reader_batch_result(r, b.request(qoffsets, nq, SEARCH_FULL), out);
-    });
-}
-
-extern "C" int pss_reader_search_icase_ids_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq,
-                                                 pss_result **out)
-{
-    return guarded([&]() -> int {
-        IcaseBatch b;
-        PSS_TRY(icase_args(r, "pss_reader_search_icase_ids_batch", qbytes, qoffsets, nq, out != nullptr, &b));
-        return reader_batch_result(r, b.request(qoffsets, nq, SEARCH_IDS), out);
-    });
-}
-
-extern "C" int pss_reader_count_icase_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, uint64_t *counts)
-{
-    return guarded([&]() -> int {
-        IcaseBatch b;
-        PSS_TRY(icase_args(r, "pss_reader_count_icase_batch", qbytes, qoffsets, nq, !nq || counts, &b));
-        return reader_batch_counts(r, b.request(qoffsets, nq, SEARCH_COUNTS), counts);
-    });
-}
-
-// ---- case-insensitive all-terms and wildcard search: group -> terms -> spellings -----------------------
-
-namespace {
-
-// The terms (or segments) of a group batch as the interval search takes them: the spellings of every term's seed, the
-// offsets that say which spellings are whose, and beside them the terms folded to lower case with their seeds' offsets.
-// It lives in the entry point's frame, so it outlives the batch on every part of a multi-device reader.
+// The terms (patterns, or segments) of a case-insensitive batch as the interval search takes them: the spellings of every
+// term's seed, the offsets that say which spellings are whose, and beside them the terms folded to lower case with their
+// seeds' offsets.  A batch of plain patterns adds its groups of one include term each: identity offsets and zero exclude
+// flags.  It lives in the entry point's frame, so it outlives the batch on every part of a multi-device reader.
 struct IcaseGroups {
-    std::vector<uint8_t> vbytes, fbytes;
-    std::vector<uint64_t> voff, soff, foff;
+    std::vector<uint8_t> vbytes, fbytes, no_exclude;
+    std::vector<uint64_t> voff, soff, foff, one_each;
     std::vector<uint32_t> seed;
     SearchRequest request(uint32_t nterms, const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *exclude, const uint8_t *anchors,
                           SearchMode mode) const
@@ -1597,8 +1442,9 @@ struct IcaseGroups {
     }
 };
 
-// The expansion of n terms (`noun`: "term" or "segment") that terms_args / seq_args have passed: every one non-empty.
-// What it holds is judged before anything is allocated for it, as in icase_args.
+// The expansion of n terms (`noun`: "pattern", "term" or "segment") that icase_plain / terms_args / seq_args have passed:
+// every one non-empty.  What it holds is judged before anything is allocated for it.  At most 64 spellings per term: only a
+// batch of more than 2^26 terms can pass the limit, and only such a batch pays for a counting pass of its own.
 int icase_expand(const char *who, const char *noun, const uint8_t *tbytes, const uint64_t *toffsets, uint32_t n, IcaseGroups *b)
 {
     const uint32_t letters = icase_letters(0);
@@ -1653,16 +1499,133 @@ int icase_expand(const char *who, const char *noun, const uint8_t *tbytes, const
     return PSS_OK;
 }
 
+// The common end of the nine case-insensitive calls: the result of the batch, or its counts.
+int icase_answer(pss_reader *r, const SearchRequest &rq, pss_result **out, uint64_t *counts)
+{
+    return rq.mode == SEARCH_COUNTS ? reader_batch_counts(r, rq, counts) : reader_batch_result(r, rq, out);
+}
+
+// Is the call's own output argument usable?  (No row: the counts may be null.)
+bool icase_out_ok(SearchMode mode, uint32_t rows, pss_result **out, const uint64_t *counts)
+{
+    return mode == SEARCH_COUNTS ? !rows || counts : out != nullptr;
+}
+
+// The three plain case-insensitive calls: their own argument checks, then every pattern as a group of one include term.
+// The reader is looked at last, as for the all-terms calls: a malformed batch is reported as such with or without one.
+int icase_plain(pss_reader *r, const char *who, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, SearchMode mode,
+                pss_result **out, uint64_t *counts)
+{
+    if (!icase_out_ok(mode, nq, out, counts) || (nq && (!qbytes || !qoffsets))) {
+        set_error("%s: bad arguments", who);
+        return PSS_EINVAL;
+    }
+    if (nq && qoffsets[0] != 0) {
+        set_error("%s: the pattern offsets start at %llu, not at 0", who, (unsigned long long)qoffsets[0]);
+        return PSS_EINVAL;
+    }
+    for (uint32_t q = 0; q < nq; ++q) {
+        if (qoffsets[q + 1] < qoffsets[q]) {
+            set_error("%s: the pattern offsets decrease at pattern %u", who, q);
+            return PSS_EINVAL;
+        }
+        if (qoffsets[q + 1] == qoffsets[q]) {
+            set_error("%s: pattern %u is empty (every entry contains the empty pattern)", who, q);
+            return PSS_EINVAL;
+        }
+        if (qoffsets[q + 1] - qoffsets[q] > 0xffffffffull) {
+            set_error("%s: pattern %u has more than 2^32 - 1 bytes (a chunk has fewer)", who, q);
+            return PSS_EINVAL;
+        }
+    }
+    IcaseGroups b;
+    PSS_TRY(icase_expand(who, "pattern", qbytes, qoffsets, nq, &b));
+    if (!r) {
+        set_error("%s: bad arguments (no reader)", who);
+        return PSS_EINVAL;
+    }
+    b.one_each.resize((size_t)nq + 1);
+    for (uint64_t g = 0; g <= nq; ++g) b.one_each[g] = g;
+    b.no_exclude.assign((size_t)nq + 1, 0);
+    return icase_answer(r, b.request(nq, b.one_each.data(), nq, b.no_exclude.data(), nullptr, mode), out, counts);
+}
+
+// The three case-insensitive all-terms calls: group -> terms -> spellings.
+int icase_terms(pss_reader *r, const char *who, const uint8_t *tbytes, const uint64_t *toffsets, uint32_t nterms,
+                const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *exclude, SearchMode mode, pss_result **out, uint64_t *counts)
+{
+    IcaseGroups b;
+    PSS_TRY(terms_args(r, who, tbytes, toffsets, nterms, group_offsets, ngroups, exclude, icase_out_ok(mode, ngroups, out, counts)));
+    PSS_TRY(icase_expand(who, "term", tbytes, toffsets, nterms, &b));
+    return icase_answer(r, b.request(nterms, group_offsets, ngroups, exclude, nullptr, mode), out, counts);
+}
+
+// ... and the three case-insensitive wildcard calls: group -> segments -> spellings.
+int icase_seq(pss_reader *r, const char *who, const uint8_t *sbytes, const uint64_t *soffsets, uint32_t nsegs, const uint64_t *group_offsets,
+              uint32_t ngroups, const uint8_t *anchors, SearchMode mode, pss_result **out, uint64_t *counts)
+{
+    IcaseGroups b;
+    PSS_TRY(seq_args(r, who, sbytes, soffsets, nsegs, group_offsets, ngroups, anchors, icase_out_ok(mode, ngroups, out, counts)));
+    PSS_TRY(icase_expand(who, "segment", sbytes, soffsets, nsegs, &b));
+    return icase_answer(r, b.request(nsegs, group_offsets, ngroups, nullptr, anchors, mode), out, counts);
+}
+
 }  // namespace
+
+extern "C" int pss_icase_variants(const uint8_t *pat, uint64_t len, int32_t letters, uint8_t *out, uint64_t cap, uint32_t *seed_off,
+                                  uint32_t *seed_len, uint32_t *count)
+{
+    return guarded([&]() -> int {
+        if (!pat || !len) {
+            set_error("pss_icase_variants: the pattern is empty (every entry contains the empty pattern)");
+            return PSS_EINVAL;
+        }
+        if (letters > 6 || !seed_off || !seed_len || !count) {
+            set_error("pss_icase_variants: bad arguments (letters = %d: 1 .. 6, or <= 0 for PSS_ICASE_SEED_LETTERS)", (int)letters);
+            return PSS_EINVAL;
+        }
+        uint64_t so = 0, sl = 0;
+        const uint32_t f = fold_seed(pat, len, icase_letters(letters), &so, &sl);
+        if (so > 0xffffffffull || sl > 0xffffffffull) {
+            set_error("pss_icase_variants: a pattern of %llu bytes", (unsigned long long)len);
+            return PSS_EINVAL;
+        }
+        *seed_off = (uint32_t)so;
+        *seed_len = (uint32_t)sl;
+        *count = 1u << f;
+        if (!out) return PSS_OK;            // (the sizes alone)
+        if (cap < (sl << f)) {
+            set_error("pss_icase_variants: %u variants of %llu bytes need more than the %llu bytes of out", 1u << f, (unsigned long long)sl,
+                      (unsigned long long)cap);
+            return PSS_EINVAL;
+        }
+        fold_spellings(pat + so, sl, f, out);
+        return PSS_OK;
+    });
+}
+
+extern "C" int pss_reader_search_icase_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, pss_result **out)
+{
+    return guarded([&]() -> int { return icase_plain(r, "pss_reader_search_icase_batch", qbytes, qoffsets, nq, SEARCH_FULL, out, nullptr); });
+}
+
+extern "C" int pss_reader_search_icase_ids_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq,
+                                                 pss_result **out)
+{
+    return guarded([&]() -> int { return icase_plain(r, "pss_reader_search_icase_ids_batch", qbytes, qoffsets, nq, SEARCH_IDS, out, nullptr); });
+}
+
+extern "C" int pss_reader_count_icase_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, uint64_t *counts)
+{
+    return guarded([&]() -> int { return icase_plain(r, "pss_reader_count_icase_batch", qbytes, qoffsets, nq, SEARCH_COUNTS, nullptr, counts); });
+}
 
 extern "C" int pss_reader_search_terms_icase_batch(pss_reader *r, const uint8_t *tbytes, const uint64_t *toffsets, uint32_t nterms,
                                                    const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *exclude, pss_result **out)
 {
     return guarded([&]() -> int {
-        IcaseGroups b;
-        PSS_TRY(terms_args(r, "pss_reader_search_terms_icase_batch", tbytes, toffsets, nterms, group_offsets, ngroups, exclude, out != nullptr));
-        PSS_TRY(icase_expand("pss_reader_search_terms_icase_batch", "term", tbytes, toffsets, nterms, &b));
-        return reader_batch_result(r, b.request(nterms, group_offsets, ngroups, exclude, nullptr, SEARCH_FULL), out);
+        return icase_terms(r, "pss_reader_search_terms_icase_batch", tbytes, toffsets, nterms, group_offsets, ngroups, exclude, SEARCH_FULL, out,
+                           nullptr);
     });
 }
 
@@ -1671,11 +1634,8 @@ extern "C" int pss_reader_search_terms_icase_ids_batch(pss_reader *r, const uint
                                                        pss_result **out)
 {
     return guarded([&]() -> int {
-        IcaseGroups b;
-        PSS_TRY(terms_args(r, "pss_reader_search_terms_icase_ids_batch", tbytes, toffsets, nterms, group_offsets, ngroups, exclude,
-                           out != nullptr));
-        PSS_TRY(icase_expand("pss_reader_search_terms_icase_ids_batch", "term", tbytes, toffsets, nterms, &b));
-        return reader_batch_result(r, b.request(nterms, group_offsets, ngroups, exclude, nullptr, SEARCH_IDS), out);
+        return icase_terms(r, "pss_reader_search_terms_icase_ids_batch", tbytes, toffsets, nterms, group_offsets, ngroups, exclude, SEARCH_IDS,
+                           out, nullptr);
     });
 }
 
@@ -1683,11 +1643,8 @@ extern "C" int pss_reader_count_terms_icase_batch(pss_reader *r, const uint8_t *
                                                   const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *exclude, uint64_t *counts)
 {
     return guarded([&]() -> int {
-        IcaseGroups b;
-        PSS_TRY(terms_args(r, "pss_reader_count_terms_icase_batch", tbytes, toffsets, nterms, group_offsets, ngroups, exclude,
-                           !ngroups || counts));
-        PSS_TRY(icase_expand("pss_reader_count_terms_icase_batch", "term", tbytes, toffsets, nterms, &b));
-        return reader_batch_counts(r, b.request(nterms, group_offsets, ngroups, exclude, nullptr, SEARCH_COUNTS), counts);
+        return icase_terms(r, "pss_reader_count_terms_icase_batch", tbytes, toffsets, nterms, group_offsets, ngroups, exclude, SEARCH_COUNTS,
+                           nullptr, counts);
     });
 }
 
@@ -1695,10 +1652,8 @@ extern "C" int pss_reader_search_seq_icase_batch(pss_reader *r, const uint8_t *s
                                                  const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *anchors, pss_result **out)
 {
     return guarded([&]() -> int {
-        IcaseGroups b;
-        PSS_TRY(seq_args(r, "pss_reader_search_seq_icase_batch", sbytes, soffsets, nsegs, group_offsets, ngroups, anchors, out != nullptr));
-        PSS_TRY(icase_expand("pss_reader_search_seq_icase_batch", "segment", sbytes, soffsets, nsegs, &b));
-        return reader_batch_result(r, b.request(nsegs, group_offsets, ngroups, nullptr, anchors, SEARCH_FULL), out);
+        return icase_seq(r, "pss_reader_search_seq_icase_batch", sbytes, soffsets, nsegs, group_offsets, ngroups, anchors, SEARCH_FULL, out,
+                         nullptr);
     });
 }
 
@@ -1707,10 +1662,8 @@ extern "C" int pss_reader_search_seq_icase_ids_batch(pss_reader *r, const uint8_
                                                      pss_result **out)
 {
     return guarded([&]() -> int {
-        IcaseGroups b;
-        PSS_TRY(seq_args(r, "pss_reader_search_seq_icase_ids_batch", sbytes, soffsets, nsegs, group_offsets, ngroups, anchors, out != nullptr));
-        PSS_TRY(icase_expand("pss_reader_search_seq_icase_ids_batch", "segment", sbytes, soffsets, nsegs, &b));
-        return reader_batch_result(r, b.request(nsegs, group_offsets, ngroups, nullptr, anchors, SEARCH_IDS), out);
+        return icase_seq(r, "pss_reader_search_seq_icase_ids_batch", sbytes, soffsets, nsegs, group_offsets, ngroups, anchors, SEARCH_IDS, out,
+                         nullptr);
     });
 }
 
@@ -1718,10 +1671,8 @@ extern "C" int pss_reader_count_seq_icase_batch(pss_reader *r, const uint8_t *sb
                                                 const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *anchors, uint64_t *counts)
 {
     return guarded([&]() -> int {
-        IcaseGroups b;
-        PSS_TRY(seq_args(r, "pss_reader_count_seq_icase_batch", sbytes, soffsets, nsegs, group_offsets, ngroups, anchors, !ngroups || counts));
-        PSS_TRY(icase_expand("pss_reader_count_seq_icase_batch", "segment", sbytes, soffsets, nsegs, &b));
-        return reader_batch_counts(r, b.request(nsegs, group_offsets, ngroups, nullptr, anchors, SEARCH_COUNTS), counts);
+        return icase_seq(r, "pss_reader_count_seq_icase_batch", sbytes, soffsets, nsegs, group_offsets, ngroups, anchors, SEARCH_COUNTS, nullptr,
+                         counts);
     });
 }
 

@@ -3,23 +3,21 @@
 // Part of search.hip: included there behind sequence_impl.h, whose group geometry (TG lanes per surviving hit) and pair
 // spaces it shares, and behind entry_scan_impl.h (fold8, fold_equal, entry_scan); not a header for anybody else.
 //
-// The suffix arrays are exact-byte, so the host turns every pattern into its SEED -- the longest window with at most F
+// The suffix arrays are exact-byte, so the host turns every term into its SEED -- the longest window with at most F
 // ASCII letters -- and the seed into its 2^f concrete spellings, in ascending byte order (fold_seed and fold_spellings below: what
-// pss_icase_variants shows).  The spellings of pattern g are the consecutive terms goff[g] .. goff[g + 1] of an
-// all-terms-shaped batch: the interval kernels answer every (spelling, chunk) pair unchanged.  Strings of one length in
-// ascending byte order have disjoint, ascending suffix-array intervals, so fold_union_kernel only adds the counts up, and
-// hit k of a (pattern, chunk) pair is found by walking the pair's at most 64 counts.  fold_hits_kernel verifies the
-// whole pattern around each seed hit under fold and takes the entry's bounds; fold_dedupe_kernel keeps the hit of an
-// entry's LEFTMOST folded match: hit_entry's dedupe, under fold (entry_scan<true>).  Every match alignment holds exactly one seed
-// occurrence, in exactly one spelling, so an entry keeps exactly one hit whatever mix of spellings it holds.
-// A pattern that holds a 0x0A occurs in no entry and is flagged void: its pairs count no hit.
-//
-// A case-insensitive GROUP batch (pss_reader_search_terms_icase_batch, pss_reader_search_seq_icase_batch)
-// has one level more: group -> terms -> spellings, and so three pair spaces -- (spelling, chunk), (term, chunk) and
-// (group, chunk).  fold_union_kernel runs over the (term, chunk) pairs and leaves t_cnt[term, c], the term's seed hits;
-// terms_driver_kernel<false> picks every (group, chunk) pair's driver from t_cnt; the Driven forms of the two kernels
-// below take the pair's pattern from its driver term; terms_verify_kernel<true> / seq_verify_kernel<true> check each
-// candidate entry against the group's other terms under fold.
+// pss_icase_variants shows).  A case-insensitive batch has three levels, group -> terms -> spellings, and so three pair
+// spaces -- (spelling, chunk), (term, chunk) and (group, chunk); a plain pattern is a group of one include term, an
+// all-terms group has its terms, a wildcard pattern its segments.  The spellings of term t are the
+// consecutive queries soff[t] .. soff[t + 1]: the interval kernels answer every (spelling, chunk) pair unchanged.  Strings
+// of one length in ascending byte order have disjoint, ascending suffix-array intervals, so fold_union_kernel only adds
+// the counts up per (term, chunk) pair, and hit k of such a pair is found by walking its at most 64 counts.
+// terms_driver_kernel<false> picks every (group, chunk) pair's driver term from those sums.  fold_hits_kernel verifies
+// the whole driver term around each of its seed hits under fold and takes the entry's bounds; fold_dedupe_kernel keeps
+// the hit of an entry's LEFTMOST folded match: hit_entry's dedupe, under fold (entry_scan<true>).  Every match alignment
+// holds exactly one seed occurrence, in exactly one spelling, so an entry keeps exactly one hit whatever mix of spellings
+// it holds.  terms_verify_kernel<true> / seq_verify_kernel<true> then check each candidate entry against the group's other
+// terms, or its segments in order, under fold.
+// A term that holds a 0x0A occurs in no entry and is flagged void: its pairs count no hit.
 
 // The seed of pat[0, len): the longest window with at most `letters` ASCII letters, the leftmost on a tie.  Returns its
 // letter count.  (Host code, declared in search.h: the C ABI expands the patterns before it states the request.)
@@ -56,7 +54,7 @@ void fold_spellings(const u8 *seed, u64 len, u32 f, u8 *out)
     }
 }
 
-// One lane per (pattern, chunk) pair: the hits of the pair are the hits of its spellings, one interval behind the other.
+// One lane per (term, chunk) pair: the hits of the pair are the hits of its spellings, one interval behind the other.
 // (Disjoint intervals of one suffix array: the sum is at most n and fits u32.)
 __global__ __launch_bounds__(256) void fold_union_kernel(u32 nc, const u64 *goff, const u8 *fvoid, const u32 *cnt, u64 ngq, u32 *p_cnt)
 {
@@ -69,20 +67,20 @@ __global__ __launch_bounds__(256) void fold_union_kernel(u32 nc, const u64 *goff
     p_cnt[gq] = sum;
 }
 
-// One lane per hit: hit k of a pair is suffix sa[lo[v, c] + k'] of the spelling v its walk over the pair's counts ends
-// in.  With di that text offset the match would start at m = di - seed_off: out of the chunk -> rejected before anything
-// is read.  Else the whole pattern at m under fold (the bytes outside the seed are what is unknown; the pattern holds no
-// 0x0A, so a match cannot leave its entry), and the entry's bounds.  A surviving hit leaves start, len and m.
-// Driven: the pairs are (group, chunk) pairs and the pattern of pair a is its driver term g_drv[a]; goff, fseed and foff
-// are indexed by term.  (A pair with hits has a driver that is neither void nor an exclude term: terms_driver_kernel.)
-template <bool Driven>
+// One lane per hit.  The pairs are (group, chunk) pairs and the pattern of pair a is its driver term g_drv[a]; goff
+// (the spelling offsets), fseed and foff are indexed by term.  (A pair with hits has a driver that is neither void nor an
+// exclude term: terms_driver_kernel.)  Hit k of a pair is suffix sa[lo[v, c] + k'] of the spelling v its walk over the
+// driver's counts ends in.  With di that text offset the match would start at m = di - seed_off: out of the chunk ->
+// rejected before anything is read.  Else the whole pattern at m under fold (the bytes outside the seed are what is
+// unknown; the pattern holds no 0x0A, so a match cannot leave its entry), and the entry's bounds.  A surviving hit leaves
+// start, len and m.
 __global__ __launch_bounds__(256) void fold_hits_kernel(const ChunkDesc *chunks, u32 nc, const u8 *fbytes, const u64 *foff,
                                                           const u32 *fseed, const u64 *goff, const u32 *lo, const u32 *cnt, u64 ngq,
                                                           const u64 *hit_off, u64 H, u32 *start_out, u32 *len_out, u32 *m_out, const u32 *g_drv)
 {
     for (u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x; t < H; t += (u64)gridDim.x * blockDim.x) {
         const u64 a = pair_of_hit(hit_off, ngq, t);
-        const u32 g = Driven ? g_drv[a] : (u32)(a / nc), c = (u32)(a % nc);
+        const u32 g = g_drv[a], c = (u32)(a % nc);
         const ChunkDesc ch = chunks[c];
         u32 k = (u32)(t - hit_off[a]);
         u32 v = (u32)goff[g];
@@ -116,10 +114,8 @@ __device__ __forceinline__ bool fold_starts_before(const ChunkDesc &ch, u32 s, u
 // TG lanes per hit that fold_hits_kernel left standing: the hit is kept iff no folded occurrence of the pattern starts
 // in [start, m) -- the leftmost match of the entry stands for it, whichever spelling's interval it came from.  The same
 // shape as terms_verify_kernel, for the same reasons: 64 bytes of entry per step, 32 hits per 256-thread workgroup,
-// grid-stride.  Every loop is bounded by m - start, an entry's length.
-// Driven: as for fold_hits_kernel, the pattern of pair a is its driver term g_drv[a] -- one value per hit, so the
-// group-wide-branch invariant of entry_scan holds as before.
-template <bool Driven>
+// grid-stride.  Every loop is bounded by m - start, an entry's length.  As for fold_hits_kernel, the pattern of pair a
+// is its driver term g_drv[a] -- one value per hit, so the group-wide-branch invariant of entry_scan holds.
 __global__ __launch_bounds__(256) void fold_dedupe_kernel(const ChunkDesc *chunks, u32 nc, const u8 *fbytes, const u64 *foff, u64 ngq,
                                                             const u64 *hit_off, u64 H, const u32 *start, const u32 *mpos, u32 *len,
                                                             const u32 *g_drv)
@@ -129,7 +125,7 @@ __global__ __launch_bounds__(256) void fold_dedupe_kernel(const ChunkDesc *chunk
     for (u64 t = ((u64)blockIdx.x * blockDim.x + threadIdx.x) / TG; t < H; t += step) {
         if (len[t] == kSkip) continue;
         const u64 a = pair_of_hit(hit_off, ngq, t);
-        const u32 g = Driven ? g_drv[a] : (u32)(a / nc);
+        const u32 g = g_drv[a];
         const ChunkDesc ch = chunks[(u32)(a % nc)];
         const bool dup = fold_starts_before(ch, start[t], mpos[t], fbytes + foff[g], (u32)(foff[g + 1] - foff[g]), gl, gbase);
         if (dup && gl == 0) len[t] = kSkip;

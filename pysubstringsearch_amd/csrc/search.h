@@ -92,17 +92,14 @@ struct SearchRequest {
     // its segments left to right without overlap, the first at the entry's start and / or the last at its end when anchored.
     // exclude is then unused and may be null.  Everything else as for an all-terms batch.
     const uint8_t *seq_anchors = nullptr;
-    // fold_seed (ngroups values), fold_bytes and fold_offsets (ngroups + 1), together with group_offsets: the case-insensitive
-    // search of fold_impl.h.  The rows are PATTERNS -- fold_bytes holds them folded to lower case, back to back -- and the nq
-    // terms of group g are the spellings of pattern g's seed, in ascending byte order; fold_seed[g] is the seed's offset inside
-    // the pattern.  Modes FULL, COUNTS and IDS; not with anchors, and with exclude or seq_anchors only as a group batch
-    // (spell_offsets below); always the general pipeline.
+    // fold_seed (nterms values), fold_bytes and fold_offsets (nterms + 1) and spell_offsets (nterms + 1 entries into the nq
+    // patterns), together with group_offsets: the case-insensitive search of fold_impl.h -- an all-terms batch
+    // (exclude) or a sequence batch (seq_anchors) under fold; a plain pattern is a group of one include term.  The rows are the
+    // ngroups groups, group_offsets index the nterms TERMS, exclude has nterms flags, fold_bytes holds the terms folded to lower
+    // case, back to back, fold_seed[t] is the offset of term t's seed inside it, and the nq patterns are the spellings of the
+    // terms' seeds: term t's are spell_offsets[t] .. spell_offsets[t + 1], in ascending byte order.  Modes FULL, COUNTS and
+    // IDS; not with anchors; always the general pipeline.
     const uint32_t *fold_seed = nullptr; const uint8_t *fold_bytes = nullptr; const uint64_t *fold_offsets = nullptr;
-    // spell_offsets (nterms + 1 entries into the nq patterns), together with fold_seed and group_offsets: a case-insensitive
-    // GROUP batch -- an all-terms batch (exclude) or a sequence batch (seq_anchors) under fold.  The rows are
-    // the ngroups groups, group_offsets index the nterms TERMS, exclude has nterms flags, fold_seed / fold_bytes / fold_offsets
-    // are per term, and the nq patterns are the spellings of the terms' seeds: term t's are spell_offsets[t] ..
-    // spell_offsets[t + 1], ascending.  Null: the two-level batch above, whose groups are the patterns themselves.
     const uint64_t *spell_offsets = nullptr; uint32_t nterms = 0;
     uint32_t rows() const { return group_offsets ? ngroups : nq; }     // rows of the result: queries, or groups of terms
     bool low_latency = false;            // one query through the resident kernel when it fits (an unanchored SEARCH_FULL batch only)

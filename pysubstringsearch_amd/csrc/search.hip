@@ -785,8 +785,8 @@ __global__ __launch_bounds__(MID_BLOCK) void mid_hit_scans_kernel(const u32 *len
 
 // One lane per hit: hit k of a pair is suffix sa[lo + k] of the pair's interval; hit_entry gives the entry's bounds, or
 // kSkip when an earlier hit of the pair's pattern stands for the entry.  The pattern of pair vq is query vq / nc -- or,
-// Driven (an all-terms or a sequence batch, whose pairs are (group, chunk) pairs), the driver term drv[vq] of the pair.
-template <bool Driven>
+// FromDriver (an all-terms or a sequence batch, whose pairs are (group, chunk) pairs), the driver term drv[vq] of the pair.
+template <bool FromDriver>
 __global__ __launch_bounds__(256) void hit_lines_kernel(const ChunkDesc *chunks, u32 nc, const u8 *qbytes,
                                                           const u64 *qoff, u64 nvq, const u32 *lo, const u64 *hit_off,
                                                           u64 H, const MidState *mid, u32 *start_out, u32 *len_out,
@@ -795,7 +795,7 @@ __global__ __launch_bounds__(256) void hit_lines_kernel(const ChunkDesc *chunks,
     if (mid) H = mid->flag ? 0 : mid->hits;      // mid pipeline: the hit count never visits the host
     for (u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x; t < H; t += (u64)gridDim.x * blockDim.x) {
         const u64 vq = pair_of_hit(hit_off, nvq, t);
-        const u32 q = Driven ? drv[vq] : (u32)(vq / nc), c = (u32)(vq % nc);
+        const u32 q = FromDriver ? drv[vq] : (u32)(vq / nc), c = (u32)(vq % nc);
         const ChunkDesc ch = chunks[c];
         const u8 *pat = qbytes + qoff[q];
         const u32 plen = (u32)(qoff[q + 1] - qoff[q]);
@@ -1758,8 +1758,7 @@ __global__ __launch_bounds__(256) void chunk_hits_kernel(const u32 *cnt, u64 nq,
 
 // ---- host driver of one batch -------------------------------------------------------------------------------------
 // search_batch_device reads top to bottom: empty batch -> stage_queries -> run_fused? -> launch_interval -> run_mid? ->
-// pick_drivers (an all-terms or a sequence batch) | union_spellings (a case-insensitive batch) | fold_drivers (a
-// case-insensitive group batch) -> run_general -> finish.
+// pick_drivers (an all-terms or a sequence batch) | fold_drivers (a case-insensitive batch) -> run_general -> finish.
 // The stages share one Batch: the request normalised into the few booleans they read, the
 // workspace every route needs, the timing events and the two outputs.
 namespace {
@@ -1784,8 +1783,7 @@ struct Batch {
     // the request, normalised once: nothing below asks for a mode again
     bool counts, device, ids, anchored, terms, sa_order;
     bool seq;                           // terms, and the groups are ordered sequences (sequence_impl.h)
-    bool fold;                          // terms, and the groups are the spellings of one pattern's seed each (fold_impl.h)
-    bool fgroups;                       // fold, and the spellings belong to TERMS of groups: three levels
+    bool fold;                          // terms under ASCII case folding: group -> terms -> spellings (fold_impl.h)
     const u32 nterm;                    // terms of such a batch (else 0) ...
     const u64 ntp;                      // ... and its (term, chunk) pairs
     bool tiny;                          // queries and offsets fit the 16 KiB of the pinned scratch
@@ -1797,7 +1795,7 @@ struct Batch {
     std::vector<u8> own_q;              // an anchored batch too large for the staging
     std::vector<u64> own_off;
     std::vector<u8> own_tflags;         // per-term flags of an all-terms batch
-    std::vector<u8> own_fvoid;          // a case-insensitive group batch: the void flags alone (what the union reads)
+    std::vector<u8> own_fvoid;          // a case-insensitive batch: the void flags alone (what the union reads)
     // workspace of every route
     u8 *d_q = nullptr, *d_aflags = nullptr, *d_edge = nullptr;
     u64 *d_qoff = nullptr, *d_hitoff = nullptr, *d_partial = nullptr, *d_total = nullptr, *d_qcount = nullptr, *h_small = nullptr;
@@ -1806,11 +1804,11 @@ struct Batch {
     u64 *d_goff = nullptr;                          // all-terms batch: group offsets, term flags, driver term per group pair
     u8 *d_tflags = nullptr, *d_sanch = nullptr;       // (d_sanch: a sequence batch's anchor byte per group)
     u32 *d_gdrv = nullptr;
-    u8 *d_fbytes = nullptr, *d_fvoid = nullptr;     // a case-insensitive batch: the folded patterns, their offsets and seed
-    u64 *d_foff = nullptr;                          // offsets, a void flag per pattern, the match start of every hit
+    u8 *d_fbytes = nullptr, *d_fvoid = nullptr;     // a case-insensitive batch: the folded terms, their offsets and seed
+    u64 *d_foff = nullptr;                          // offsets, a void flag per term, the match start of every hit,
     u32 *d_fseed = nullptr, *d_m = nullptr;
-    u64 *d_soff = nullptr;                          // a case-insensitive group batch: spelling offsets per term, seed hits
-    u32 *d_tcnt = nullptr;                          // per (term, chunk) pair
+    u64 *d_soff = nullptr;                          // spelling offsets per term, seed hits per (term, chunk) pair
+    u32 *d_tcnt = nullptr;
     // ... and of the mid and the general pipeline, sized by each: entry bounds per hit, the scans over them, the result
     u32 *d_start = nullptr, *d_len = nullptr;
     u64 *d_eidx = nullptr, *d_boff = nullptr, *d_entoff = nullptr;
@@ -1832,7 +1830,6 @@ struct Batch {
         terms = rq.group_offsets != nullptr;
         seq = terms && rq.seq_anchors != nullptr;
         fold = terms && rq.fold_seed != nullptr;
-        fgroups = fold && rq.spell_offsets != nullptr;
         // (counts do not depend on the order; one hit per entry has one order; an all-terms batch keeps its driver's text order)
         sa_order = rq.sa_order && !counts && !anchored && !terms;
         // (an anchored batch searches its rewritten queries: a newline in front of and / or behind every pattern)
@@ -1852,7 +1849,7 @@ struct Batch {
         p = ctx->slot[which].as<T>();
         return PSS_OK;
     }
-    int stage_queries(), run_fused(bool *served), launch_interval(), run_mid(bool *done), pick_drivers(), union_spellings(), fold_drivers(), run_general(), finish();
+    int stage_queries(), run_fused(bool *served), launch_interval(), run_mid(bool *done), pick_drivers(), fold_drivers(), run_general(), finish();
     int sa_order_hits(u32 grid, u64 H);
     int download_result(u64 E, u64 B, const u64 *d_starts, const u8 *d_bytes, bool via_stage);
     void leave_on_device(const u64 *d_starts, const u8 *d_bytes), set_totals(u64 hits, u64 kept, u64 E, u64 B);
@@ -1928,17 +1925,12 @@ int Batch::stage_queries()
     h_off = hq ? ho : rq.qoffsets;
     h_flags = hf;
     h_padded = hq != nullptr;
-    if (terms && !fold) {
-        own_tflags.resize(nq);
-        newline_flags(rq.qbytes, rq.qoffsets, nq, kTermVoid, own_tflags.data());
-        for (u32 t = 0; !seq && t < nq; ++t)                        // (no segment of a sequence batch excludes)
-            if (rq.exclude[t]) own_tflags[t] |= kTermExclude;
-    }
-    if (fgroups) {                      // (per TERM, from the folded terms: folding leaves a 0x0A alone)
-        own_fvoid.resize(nterm);
-        newline_flags(rq.fold_bytes, rq.fold_offsets, nterm, kTermVoid, own_fvoid.data());
-        own_tflags = own_fvoid;
-        for (u32 t = 0; !seq && t < nterm; ++t)                     // (no segment of a sequence batch excludes)
+    if (terms) {                        // (per TERM; under fold from the folded terms: folding leaves a 0x0A alone)
+        const u32 nt = fold ? nterm : nq;
+        own_tflags.resize(nt);
+        newline_flags(fold ? rq.fold_bytes : rq.qbytes, fold ? rq.fold_offsets : rq.qoffsets, nt, kTermVoid, own_tflags.data());
+        if (fold) own_fvoid = own_tflags;
+        for (u32 t = 0; !seq && t < nt; ++t)                        // (no segment of a sequence batch excludes)
             if (rq.exclude[t]) own_tflags[t] |= kTermExclude;
     }
     return PSS_OK;
@@ -2187,37 +2179,12 @@ int Batch::pick_drivers()
     return PSS_OK;
 }
 
-// Case-insensitive batch: from the (spelling, chunk) pairs to the (pattern, chunk) pairs.  The folded patterns go up
-// beside the spellings -- bytes (32 zero bytes behind them, as behind the staged terms), offsets, seed offsets, void flags
-// -- and one lane per pair adds up the counts of its spellings; a pair has no interval of its own (p_lo is not read).
-int Batch::union_spellings()
-{
-    const u64 ftotal = rq.fold_offsets[nrow];
-    const size_t goff_room = round_up(((size_t)nrow + 1) * 8, 64), seed_room = round_up((size_t)nrow * 4, 64);
-    const size_t void_room = round_up((size_t)nrow, 64), byte_room = round_up(ftotal + 32, 64);
-    PSS_TRY(take(Q_TERMS, 2 * goff_room + seed_room + void_room + byte_room + nrp * 4, d_goff));
-    d_foff = d_goff + goff_room / 8;
-    d_fseed = reinterpret_cast<u32 *>(d_foff + goff_room / 8);
-    d_fvoid = reinterpret_cast<u8 *>(d_fseed) + seed_room;
-    d_fbytes = d_fvoid + void_room;
-    p_cnt = reinterpret_cast<u32 *>(d_fbytes + byte_room);
-    own_tflags.resize(nrow);
-    newline_flags(rq.fold_bytes, rq.fold_offsets, nrow, kTermVoid, own_tflags.data());
-    PSS_HIP(hipMemcpyAsync(d_goff, rq.group_offsets, ((size_t)nrow + 1) * 8, hipMemcpyHostToDevice, s));
-    PSS_HIP(hipMemcpyAsync(d_foff, rq.fold_offsets, ((size_t)nrow + 1) * 8, hipMemcpyHostToDevice, s));
-    PSS_HIP(hipMemcpyAsync(d_fseed, rq.fold_seed, (size_t)nrow * 4, hipMemcpyHostToDevice, s));
-    PSS_HIP(hipMemcpyAsync(d_fvoid, own_tflags.data(), nrow, hipMemcpyHostToDevice, s));
-    PSS_HIP(hipMemsetAsync(d_fbytes + ftotal, 0, 32, s));
-    PSS_HIP(hipMemcpyAsync(d_fbytes, rq.fold_bytes, ftotal, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(fold_union_kernel, dim3((u32)((nrp + 255) / 256)), dim3(256), 0, s, nc, d_goff, d_fvoid, d_cnt, nrp, p_cnt);
-    return PSS_OK;
-}
-
-// Case-insensitive group batch: from the (spelling, chunk) pairs over the (term, chunk) pairs to the (group, chunk)
-// pairs.  What union_spellings sends up goes up per term -- spelling offsets, folded bytes (32 zero bytes behind them),
-// their offsets, seed offsets, void flags -- and with it what pick_drivers sends up: group offsets, term flags, anchor
-// bytes.  fold_union_kernel leaves every term's seed hits per chunk in d_tcnt; terms_driver_kernel picks the include term
-// with the fewest of them as the pair's driver.  Neither a term nor a pair has an interval of its own (p_lo is not read).
+// Case-insensitive batch: from the (spelling, chunk) pairs over the (term, chunk) pairs to the (group, chunk) pairs.
+// The folded terms go up beside the spellings, per term -- spelling offsets, folded bytes (32 zero bytes behind them, as
+// behind the staged terms), their offsets, seed offsets, void flags -- and with them what pick_drivers sends up: group
+// offsets, term flags, anchor bytes.  fold_union_kernel leaves every term's seed hits per chunk in d_tcnt;
+// terms_driver_kernel picks the include term with the fewest of them as the pair's driver.  Neither a term nor a pair has
+// an interval of its own (p_lo is not read).
 int Batch::fold_drivers()
 {
     const u64 ftotal = rq.fold_offsets[nterm];
@@ -2287,25 +2254,18 @@ int Batch::run_general()
         // every hit of every spelling against the whole pattern under fold; then the survivors against the entry in front of them
         PSS_TRY(take(Q_ORD_V0, H * 4, d_m));        // (the slot of the suffix-array order's values: that order is never a fold batch's)
         const u32 vgrid = (u32)std::min<u64>((u64)ctx->num_cus * 16, (H * TG + 255) / 256);
-        if (!fgroups) {
-            hipLaunchKernelGGL(fold_hits_kernel<false>, dim3(grid), dim3(256), 0, s, d_chunks, nc, d_fbytes, d_foff, d_fseed, d_goff, d_lo,
-                               d_cnt, nrp, d_hitoff, H, d_start, d_len, d_m, (const u32 *)nullptr);
-            hipLaunchKernelGGL(fold_dedupe_kernel<false>, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, d_fbytes, d_foff, nrp, d_hitoff, H,
-                               d_start, d_m, d_len, (const u32 *)nullptr);
-        } else {
-            // (a group batch: the same two steps for each pair's driver term -- one candidate per entry that holds it under
-            // fold -- then every candidate against the group's other terms, or its segments in order, under fold)
-            hipLaunchKernelGGL(fold_hits_kernel<true>, dim3(grid), dim3(256), 0, s, d_chunks, nc, d_fbytes, d_foff, d_fseed, d_soff, d_lo,
-                               d_cnt, nrp, d_hitoff, H, d_start, d_len, d_m, d_gdrv);
-            hipLaunchKernelGGL(fold_dedupe_kernel<true>, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, d_fbytes, d_foff, nrp, d_hitoff, H,
-                               d_start, d_m, d_len, d_gdrv);
-            if (seq)
-                hipLaunchKernelGGL(seq_verify_kernel<true>, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, d_fbytes, d_foff, d_goff, d_sanch,
-                                   nrp, d_hitoff, H, d_start, d_len);
-            else
-                hipLaunchKernelGGL(terms_verify_kernel<true>, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, d_fbytes, d_foff, d_goff,
-                                   d_tflags, d_tcnt, d_gdrv, nrp, d_hitoff, H, d_start, d_len);
-        }
+        // (the two steps for each pair's driver term -- one candidate per entry that holds it under fold -- then every
+        // candidate against the group's other terms, or its segments in order, under fold)
+        hipLaunchKernelGGL(fold_hits_kernel, dim3(grid), dim3(256), 0, s, d_chunks, nc, d_fbytes, d_foff, d_fseed, d_soff, d_lo, d_cnt,
+                           nrp, d_hitoff, H, d_start, d_len, d_m, d_gdrv);
+        hipLaunchKernelGGL(fold_dedupe_kernel, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, d_fbytes, d_foff, nrp, d_hitoff, H, d_start,
+                           d_m, d_len, d_gdrv);
+        if (seq)
+            hipLaunchKernelGGL(seq_verify_kernel<true>, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, d_fbytes, d_foff, d_goff, d_sanch,
+                               nrp, d_hitoff, H, d_start, d_len);
+        else if (nterm != nrow)     // (every group has an include term: as many terms as groups are one per group, and no other to look for)
+            hipLaunchKernelGGL(terms_verify_kernel<true>, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, d_fbytes, d_foff, d_goff,
+                               d_tflags, d_tcnt, d_gdrv, nrp, d_hitoff, H, d_start, d_len);
     } else if (terms) {
         // candidates: the entries that hold the pair's driver term; then every candidate against the group's other terms
         hipLaunchKernelGGL(hit_lines_kernel<true>, dim3(grid), dim3(256), 0, s, d_chunks, nc, d_q, d_qoff, nrp, p_lo, d_hitoff, H,
@@ -2392,17 +2352,14 @@ int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, const LineDes
         set_error("search: an anchored batch takes the general pipeline to a host result");
         return PSS_EINVAL;
     }
-    if (rq.group_offsets && (rq.anchors || (rq.nq && !rq.exclude && !rq.seq_anchors && !rq.fold_seed) || rq.mode == SEARCH_DEVICE || rq.low_latency)) {
+    if (rq.group_offsets && (rq.anchors || (rq.nq && !rq.exclude && !rq.seq_anchors) || rq.mode == SEARCH_DEVICE || rq.low_latency)) {
         set_error("search: an all-terms batch takes the general pipeline to a host result, and its terms are not anchored");
         return PSS_EINVAL;
     }
-    if (rq.fold_seed && (!rq.group_offsets || !rq.fold_bytes || !rq.fold_offsets || ((rq.exclude || rq.seq_anchors) && !rq.spell_offsets))) {
-        set_error("search: a case-insensitive batch is the spellings of its patterns' seeds in groups; exclusions or sequence anchors "
-                  "need the spelling offsets of a group batch");
-        return PSS_EINVAL;
-    }
-    if (rq.spell_offsets && (!rq.fold_seed || (rq.nterms && !rq.exclude && !rq.seq_anchors))) {
-        set_error("search: a case-insensitive group batch states its terms' seeds and either exclude flags or sequence anchors");
+    if ((rq.fold_seed || rq.spell_offsets) &&
+        !(rq.fold_seed && rq.spell_offsets && rq.group_offsets && rq.fold_bytes && rq.fold_offsets && (!rq.nterms || rq.exclude || rq.seq_anchors))) {
+        set_error("search: a case-insensitive batch states its groups, its terms' seeds, folded bytes and spelling offsets, and either "
+                  "exclude flags or sequence anchors");
         return PSS_EINVAL;
     }
     const u32 rows = rq.rows();
@@ -2429,10 +2386,8 @@ int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, const LineDes
         PSS_TRY(b.run_mid(&done));
         if (done) return b.finish();
     }
-    if (b.fgroups) {
+    if (b.fold) {
         PSS_TRY(b.fold_drivers());
-    } else if (b.fold) {
-        PSS_TRY(b.union_spellings());
     } else if (b.terms) {
         PSS_TRY(b.pick_drivers());
     }

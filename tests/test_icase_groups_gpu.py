@@ -496,6 +496,51 @@ def test_one_term_is_the_plain_case_insensitive_search(search_env):
         r.close()
 
 
+def test_a_batch_of_one_segment_globs_keeps_its_anchors():
+    """Every pattern has one segment, so the batch has as many terms as groups -- the shape of a plain case-insensitive
+    batch, which skips the all-terms verify.  A sequence batch never may: its anchors are checked there."""
+    rng = np.random.default_rng(315)
+    lines = mixed_case_lines(rng, 400, 0, 30) + [b'ab xYz7 cd', b'q XYZ7 r', b'mn xyz7xyz7 op', b'Ab', b'aB at the start', b'at the end AB']
+    lines = shuffled(rng, lines)
+    r, ref = chunks_of([lines[:200], lines[200:]])
+    try:
+        words = [b'xyz7', b'AB', b'p', b'mno', b'Nope', b'a*b']
+        batch = [pre + glob_escape(w) + post for w in words for pre, post in ((b'', b''), (b'', b'*'), (b'*', b''), (b'*', b'*'))]
+        assert all(len(glob_parse(p)[0]) == 1 for p in batch) and {glob_parse(p)[1] for p in batch} == {0, 1, 2, 3}
+        counts = check('glob', r, ref, batch).counts.tolist()
+        by_word = dict(zip(words, zip(*[iter(counts)] * 4)))            # (p, p*, *p, *p*) per word
+        assert by_word[b'xyz7'] == (0, 0, 0, 3)                         # (only in the middle of its entries)
+        assert by_word[b'AB'][0] >= 1 and by_word[b'AB'][0] < by_word[b'AB'][1] < by_word[b'AB'][3] > by_word[b'AB'][2]
+        assert any(c[1] != c[3] for c in by_word.values())
+    finally:
+        r.close()
+
+
+def test_one_term_groups_alone_and_beside_a_two_term_group():
+    """A batch of one-term groups skips the all-terms verify, the same groups beside a two-term group run it: the same ids
+    in the same order either way, and those of the plain case-insensitive call."""
+    rng = np.random.default_rng(316)
+    lines = mixed_case_lines(rng, 400, 0, 30) + [b'x ABCDEFGH', b'abcdefgh here', b'ABCDE only', b'xx abcdeg', b'aBcDe']
+    lines = shuffled(rng, lines)
+    r, ref = chunks_of([lines[:200], lines[200:]])
+    try:
+        words = [b'ab', b'ABC', b'p', b'abcdefgh', b'ab\ncd', b'NOPE', b'h HERE', b' ']
+        singles = [[w] for w in words]
+        plain = r.search_icase_ids_batch(words)
+        alone = r.search_all_ids_batch(singles, icase=True)
+        st = r.last_stats()
+        assert st['hits'] > st['entries'] > 100                         # (the seed `abcde` occurs where `abcdefgh` does not)
+        assert alone.counts.tolist() == r.count_all_bytes(singles, icase=True) == r.count_icase_bytes(words)
+        alone = check('all', r, ref, singles)
+        beside = check('all', r, ref, singles + [[b'ab', b'C']])
+        assert beside.counts.tolist()[:len(words)] == alone.counts.tolist() == plain.counts.tolist()
+        assert np.array_equal(beside.ids[:alone.ids.size], alone.ids) and np.array_equal(alone.ids, plain.ids)
+        assert alone.counts[words.index(b'ab\ncd')] == 0 and alone.counts[words.index(b'abcdefgh')] == 2
+        assert beside.counts[-1] > 0
+    finally:
+        r.close()
+
+
 # ---- 10. more candidates than the mid pipeline's 65 536 -------------------------------------------------------------------------
 
 def test_more_candidates_than_the_mid_pipeline_holds(tmp_path):
