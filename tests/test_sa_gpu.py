@@ -252,7 +252,9 @@ def test_sample_sort_forced_matches_libsais(oracle, monkeypatch, local):
     alphabets of 2 .. 256 symbols (keys of 11 .. 32 symbols), word-like repeats, long duplicated blocks (tie groups that
     cross buckets and tiles), both bucket-count shapes (B1 = B2 and B1 = 2 B2), every tie-resolution mode afterwards.
     The local sort in its three forms: bucket by bucket on a plan of padded lengths (round 5, the default), the whole
-    tile as one array (PSS_SS_SEG=0), and that on the window plan (PSS_SS_WINDOW_PLAN)."""
+    tile as one array (PSS_SS_SEG=0), and that on the window plan (PSS_SS_WINDOW_PLAN).
+    Any splitters give these bytes: what the sampler, the splitters and the plans do on their limits is held to a CPU
+    model in tests/test_ss_edges_gpu.py."""
     monkeypatch.setenv('PSS_SS', '1')
     monkeypatch.setenv('PSS_MSD', '0')
     if local == 'tile':
