@@ -4,7 +4,9 @@
 
 Every case is built twice through pss_sa_build_device -- PSS_ANCHOR=1 (the round is taken whenever ties outlive the
 text rounds, whatever the size of the text, with a random window) and PSS_ANCHOR=0 (rank rounds) -- and compared with
-the oracle's suffix array; prints which cases took the round and what it left.
+the oracle's suffix array; prints which cases took the round and what it left.  Every build that counted anchors of
+the text is also held to the numpy model of tests/anchor_texts.py: the window and hash width the host rule gives for the
+depth the build reached, and the model's number of anchors for them (model=... in the line; a difference is a MISMATCH).
 """
 import ctypes
 import os
@@ -17,6 +19,7 @@ sys.path.insert(0, '.')
 import torch  # noqa: E402
 
 from pysubstringsearch_amd import _ffi  # noqa: E402
+from tests import anchor_texts as A  # noqa: E402
 
 
 def build(t, **env):
@@ -39,6 +42,19 @@ def build(t, **env):
                 os.environ.pop(k, None)
             else:
                 os.environ[k] = v
+
+
+def model_check(t, st, omega):
+    """(the model's anchor count, whether window and count agree with the build) -- None when the build counted no anchors
+    of the text (no ties left for the round, or the run-length path, whose anchors are those of its reduced string)."""
+    if st['anchor_count'] == 0 or st['rle'] != 0 or st['anchor_w'] not in (4, 8):
+        return None, True
+    want = A.anchor_count(A.codes_of(t), int(st['anchor_omega']), int(st['anchor_w']))
+    ok = want == st['anchor_count']
+    if st['anchor_side'] == 0:
+        ok = ok and A.window_of(A.depth_of(st), omega) == (st['anchor_omega'], st['anchor_w'])
+        ok = ok and st['anchor'] == (1 if A.runs(t.size, st['anchor_omega'], want) else 0)
+    return want, ok
 
 
 def make_case(rng: random.Random):
@@ -130,10 +146,11 @@ def main():
         got0, st0 = build(t, PSS_ANCHOR=0, PSS_ANCHOR_OMEGA=None)
         ok0 = bool((got0 == exp).all())
         took += int(st['anchor'])
-        flag = '' if (ok and ok0 and st['anchor_left'] == 0) else '  <-- MISMATCH'
+        model, mok = model_check(t, st, omega)
+        flag = '' if (ok and ok0 and mok and st['anchor_left'] == 0) else '  <-- MISMATCH'
         bad += 0 if not flag else 1
         print(f'case {c}: kind={kind} alpha={alpha} n={t.size} omega={omega} ok={ok} ok0={ok0} anchor={st["anchor"]} '
-              f'w={st["anchor_w"]} om={st["anchor_omega"]} depth={st["anchor_depth"]} anchors={st["anchor_count"]} '
+              f'w={st["anchor_w"]} om={st["anchor_omega"]} depth={st["anchor_depth"]} anchors={st["anchor_count"]} model={model} '
               f'active={st["anchor_active"]} left={st["anchor_left"]} arounds={st["anchor_text_rounds"]}+{st["anchor_rounds"]} lv={st["anchor_levels"]} '
               f'rounds={st["rounds"]} vs {st0["rounds"]} per={st["periodic_rounds"]}/{st["periodic_members"]} vs {st0["periodic_rounds"]}/{st0["periodic_members"]} '
               f'ms={st["ms_total"]:.2f} vs {st0["ms_total"]:.2f}{flag}', flush=True)
