@@ -670,6 +670,57 @@ int pss_reader_search_seq_icase_ids_batch(pss_reader *r, const uint8_t *sbytes, 
 /* counts[g] = entries group g matches; nothing but ngroups counters comes down */
 int pss_reader_count_seq_icase_batch(pss_reader *r, const uint8_t *sbytes, const uint64_t *soffsets, uint32_t nsegs,
                                      const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *anchors, uint64_t *counts);
+/*
+ * Search within k mismatches (no reference counterpart): per pattern, the entries that hold it with at most k bytes
+ * SUBSTITUTED -- Hamming distance, `passw0rd` for `password` at k = 1.  Arguments as pss_reader_search_batch takes them, plus k:
+ * nq budgets, one per pattern, each 0 .. 3.
+ * Entry [start, end) is the bytes of a chunk's text up to the closing 0x0A, or up to the length n of the text for an
+ * unterminated last entry (whose last byte takes part, as in the case-insensitive search).  The entry matches pattern p within k
+ * mismatches iff some m in start .. end - |p| has at most k indices i with text[m + i] != p[i].  The window lies INSIDE THE
+ * ENTRY: a window that reaches over a newline is no match, even when the newline is one of its at most k differing bytes.
+ * Bytes are exact: nothing folds, and 0x80 .. 0xFF and 0x00 are bytes like any other.  One row per pattern, packed as
+ * pss_reader_search_batch (text) and pss_reader_search_ids_batch (ids) pack theirs; every entry at most once per pattern.  A
+ * pattern that holds 0x0A counts 0 and no hit is looked at.  k = 0 returns exactly what pss_reader_search_ids_batch returns for
+ * the pattern under the default order: the same ids in the same order.
+ * PSS_EINVAL (message in pss_last_error, *out / counts untouched): an empty pattern; a pattern of at most k bytes (every window
+ * would match it: the question is about entry lengths, not content); k > 3; offsets that do not start at 0 or that decrease; a
+ * null qbytes / qoffsets / k with nq > 0; a null out / counts; a pattern of more than 2^32 - 1 bytes; a null reader (judged
+ * last: a malformed batch is reported as such with or without one).
+ * The search: pigeonhole seeds and a verify step.  The host cuts pattern p of L bytes into k + 1 PIECES, piece j =
+ * p[j L / (k + 1), (j + 1) L / (k + 1)) in integer division -- non-empty because L > k; pss_near_pieces shows them.  k
+ * mismatches cannot touch all k + 1 pieces, so every window within budget holds at least one piece exactly, at its offset.  The
+ * pieces are the queries of the interval search; every hit of every piece is verified on the device: the window it implies must
+ * lie inside the chunk and inside the hit's entry, differ from the pattern in at most k bytes, and the piece must be the FIRST
+ * exact piece of that window (a window that holds two pieces exactly is one candidate, not two); then the entry in front of the
+ * window is scanned for an earlier window within budget -- the hit of the entry's LEFTMOST near match stands for the entry.
+ * Pieces may repeat (`abab`, k = 1) or nest, so a (pattern, chunk) pair's candidates are the plain sum of its pieces' interval
+ * hits, up to (k + 1) n; a pair whose sum passes 2^32 - 1 fails the batch with PSS_EINVAL before any hit is looked at.
+ * Order: pattern-major, chunk-major inside a pattern; inside one (pattern, chunk) pair by the index of the first exact piece of
+ * each entry's leftmost near match, and inside one piece by the suffix-array order of the suffix at that piece's occurrence; the
+ * same for the text and the id variant -- pss_reader_set_result_order has no effect.
+ * Whole-file, sharded and multi-device readers, and suffix arrays on the host tier, are served alike.
+ * pss_reader_last_stats: queries = patterns, hits = the sum over pieces and chunks of the piece's exact occurrences -- the
+ * candidates --, entries = what is returned; route = GENERAL | the interval bits (| COUNTS for the count call) -- there is no
+ * bit of its own.  The id variant builds the line tables on first use, the other two allocate nothing for them.
+ * The limit: the candidates follow the occurrences of the PIECES -- a short pattern at k = 3 has pieces of a byte or two, and
+ * every occurrence of such a piece is verified.
+ * Out of scope: insertions and deletions; k > 3; mismatches under ASCII case folding, inside all-terms groups or wildcard
+ * patterns; the fused, mid, resident and device-resident paths (a near batch always takes the general pipeline); the
+ * multi-process gather over RCCL (dist.ShardedReader); choosing pieces by rarity; a piece driving only where it is present.
+ */
+/* packed entry text, one row per pattern; k = nq budgets */
+int pss_reader_search_near_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, const uint8_t *k,
+                                 pss_result **out);
+/* u64 entry ids, packed as pss_reader_search_ids_batch packs them */
+int pss_reader_search_near_ids_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, const uint8_t *k,
+                                     pss_result **out);
+/* counts[q] = entries pattern q matches within k[q] mismatches; nothing but nq counters comes down */
+int pss_reader_count_near_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, const uint8_t *k,
+                                uint64_t *counts);
+/* The expansion of ONE pattern, on the host: no reader, no GPU.  offsets / lengths (room for k + 1 values each) receive the
+ * pieces' windows inside the pattern, left to right, *count = k + 1.
+ * PSS_EINVAL: an empty pattern, k > 3, len <= k, len > 2^32 - 1, a null offsets / lengths / count. */
+int pss_near_pieces(const uint8_t *pat, uint64_t len, uint32_t k, uint32_t *offsets, uint32_t *lengths, uint32_t *count);
 /* For the first `cap` resident chunks, in file order: index in the file and number of entries; *num = resident chunks. */
 int pss_reader_chunk_entries(pss_reader *r, uint64_t *chunk_index, uint64_t *entries, uint64_t cap, uint64_t *num);
 /*

@@ -28,7 +28,7 @@ except ImportError:   # pragma: no cover
     _pssglue = None
 
 __all__ = ['Writer', 'Reader', 'PackedResult', 'IdResult', 'DeviceResult', 'device_count', 'default_devices', 'release_workspace', 'workspace_bytes',
-           'glob_parse', 'glob_escape', 'icase_variants']
+           'glob_parse', 'glob_escape', 'icase_variants', 'near_pieces']
 
 
 def device_count() -> int:
@@ -153,6 +153,31 @@ def icase_variants(pattern: bytes, letters: typing.Optional[int] = None) -> typi
                                        ctypes.byref(cnt)))
     raw = buf.raw
     return int(off.value), [raw[i * ln.value:(i + 1) * ln.value] for i in range(cnt.value)]
+
+
+def near_pieces(pattern: bytes, k: int) -> typing.List[typing.Tuple[int, bytes]]:
+    """``[(offset, piece), ...]`` of a pattern as ``Reader.search_near_ids_batch`` searches it within ``k`` mismatches
+    (include/pss.h, pss_near_pieces): the ``k + 1`` non-empty pieces ``pattern[j * L // (k + 1) : (j + 1) * L // (k + 1)]``,
+    left to right.  ``k`` mismatches cannot touch all of them, so every window within budget holds one piece exactly, at
+    its offset.  ``ValueError`` for an empty pattern, for ``k`` outside 0 .. 3 and for a pattern of at most ``k`` bytes.
+    Host only: no device is touched."""
+    if not isinstance(pattern, (bytes, bytearray)):
+        raise TypeError(f'a pattern must be bytes, not {type(pattern).__name__}')
+    k = _near_budget(k)
+    pattern = bytes(pattern)
+    off, ln, cnt = (ctypes.c_uint32 * 4)(), (ctypes.c_uint32 * 4)(), ctypes.c_uint32()
+    _ffi.check(_lib.pss_near_pieces(pattern, len(pattern), k, off, ln, ctypes.byref(cnt)))
+    return [(int(off[j]), pattern[off[j]:off[j] + ln[j]]) for j in range(cnt.value)]
+
+
+def _near_budget(k) -> int:
+    """One mismatch budget: an int in 0 .. 3 (a bool, a float or a pattern in its place is a ``TypeError``)."""
+    if isinstance(k, bool) or not hasattr(k, '__index__'):
+        raise TypeError(f'a mismatch budget k must be an int, not {type(k).__name__}')
+    k = k.__index__()
+    if not 0 <= k <= 3:
+        raise ValueError(f'k = {k}: a mismatch budget is 0 .. 3')
+    return int(k)
 
 
 class Writer:
@@ -865,6 +890,63 @@ class Reader:
         """Extension: how many entries contain ``s`` (UTF-8 encoded) whatever the case of its ASCII letters (only they
         fold)."""
         return self.count_icase_bytes([_utf8(s, 'substring')])[0]
+
+    @staticmethod
+    def _near_args(patterns, k):
+        """(blob, offsets, budgets) of one batch within k mismatches.  ``k`` is an int for the batch or a sequence with one
+        int per pattern; ``ValueError`` for an empty pattern, a budget outside 0 .. 3, a pattern of at most its budget's
+        bytes, or another number of budgets than patterns."""
+        import numpy as np
+        if isinstance(patterns, (bytes, bytearray, str)):
+            raise TypeError(f"argument 'patterns': '{type(patterns).__name__}' object cannot be converted to a sequence of patterns")
+        patterns = list(patterns)
+        if isinstance(k, (bytes, bytearray, str)):
+            raise TypeError(f'a mismatch budget k must be an int (or one per pattern), not {type(k).__name__}')
+        if not hasattr(k, '__iter__'):
+            budgets = [_near_budget(k)] * len(patterns)
+        else:
+            budgets = [_near_budget(b) for b in k]
+            if len(budgets) != len(patterns):
+                raise ValueError(f'{len(budgets)} budgets for {len(patterns)} patterns')
+        for q, (pat, b) in enumerate(zip(patterns, budgets)):
+            if not isinstance(pat, (bytes, bytearray)):
+                raise TypeError(f'pattern {q}: a pattern must be bytes, not {type(pat).__name__}')
+            if len(pat) == 0:
+                raise ValueError(f'pattern {q} is empty (every entry contains the empty pattern)')
+            if len(pat) <= b:
+                raise ValueError(f'pattern {q} has {len(pat)} bytes and a budget of {b} mismatches: every window of its length matches it')
+        blob, offs = _pack_queries([bytes(p) for p in patterns])
+        return blob, offs, np.array(budgets, dtype=np.uint8)
+
+    def search_near_batch_packed(self, patterns: typing.Sequence[bytes], k=1) -> 'PackedResult':
+        """Extension: per pattern, the entries that hold it with at most ``k`` bytes SUBSTITUTED (Hamming distance:
+        ``passw0rd`` for ``password`` at ``k=1``), as a packed result like ``search_batch_packed``'s.  ``k`` is 0 .. 3, one
+        int for the batch or a sequence with one per pattern.  The window lies inside the entry; bytes are exact (nothing
+        folds); every entry at most once per pattern; a pattern holding a newline matches nothing.  ``ValueError`` for an
+        empty pattern, ``k > 3`` and a pattern of at most ``k`` bytes.  No insertions or deletions.  The pattern's ``k + 1``
+        pieces (``near_pieces``) are looked up and every hit is verified on the device, so the work follows the
+        occurrences of the pieces (include/pss.h, pss_reader_search_near_batch).  ``set_result_order`` has no effect."""
+        blob, offs, ks = self._near_args(patterns, k)
+        return self._query_batch('pss_reader_search_near_batch', (blob, offs), 'packed', ks)
+
+    def search_near_ids_batch(self, patterns: typing.Sequence[bytes], k=1) -> 'IdResult':
+        """Extension: the ids (``search_ids_batch``) of the entries ``search_near_batch_packed`` returns, in the same
+        order; ``counts[q]`` of them belong to pattern q.  ``k=0`` returns exactly what ``search_ids_batch`` returns."""
+        blob, offs, ks = self._near_args(patterns, k)
+        return self._query_batch('pss_reader_search_near_ids_batch', (blob, offs), 'ids', ks)
+
+    def count_near_bytes(self, patterns: typing.Sequence[bytes], k=1) -> typing.List[int]:
+        """Extension: how many entries hold each pattern within ``k`` mismatches; only the counters come back."""
+        blob, offs, ks = self._near_args(patterns, k)
+        return self._query_batch('pss_reader_count_near_batch', (blob, offs), 'counts', ks)
+
+    def search_near(self, s: str, k: int = 1) -> typing.List[str]:
+        """Extension: the entries that hold ``s`` (UTF-8 encoded) with at most ``k`` BYTES substituted."""
+        return _packed_strs(self.search_near_batch_packed([_utf8(s, 'substring')], _near_budget(k)))
+
+    def count_near(self, s: str, k: int = 1) -> int:
+        """Extension: how many entries hold ``s`` (UTF-8 encoded) with at most ``k`` bytes substituted."""
+        return self.count_near_bytes([_utf8(s, 'substring')], _near_budget(k))[0]
 
     @property
     def entry_counts(self) -> typing.Dict[int, int]:

@@ -305,6 +305,10 @@ def _load() -> ctypes.CDLL:
         'pss_reader_search_seq_icase_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, u32, vp, pvp]),
         'pss_reader_search_seq_icase_ids_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, u32, vp, pvp]),
         'pss_reader_count_seq_icase_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, u32, vp, vp]),
+        'pss_reader_search_near_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, pvp]),
+        'pss_reader_search_near_ids_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, pvp]),
+        'pss_reader_count_near_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, vp]),
+        'pss_near_pieces': (ctypes.c_int, [vp, u64, u32, ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(u32)]),
         'pss_icase_variants': (ctypes.c_int, [vp, u64, i32, vp, u64, ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(u32)]),
         'pss_reader_chunk_entries': (ctypes.c_int, [vp, vp, vp, u64, ctypes.POINTER(u64)]),
         'pss_merge_packed': (ctypes.c_int, [u32, u64, vp, vp, vp, vp, vp, vp, vp, vp]),

@@ -1676,6 +1676,154 @@ extern "C" int pss_reader_count_seq_icase_batch(pss_reader *r, const uint8_t *sb
     });
 }
 
+// ---- search within k mismatches: pattern -> pattern -> its k + 1 pieces (near_impl.h) ---------------
+
+namespace {
+
+constexpr uint32_t kNearMaxBudget = 3;
+
+// The patterns of a near batch as the interval search takes them: the pieces of every pattern back to back, the offsets
+// that say which pieces are whose and where each stands in its pattern, the budgets, and the groups of one include term
+// each (identity offsets, zero exclude flags).  The patterns' own bytes and offsets are the caller's.  It lives in the
+// entry point's frame, so it outlives the batch on every part of a multi-device reader.
+struct NearGroups {
+    std::vector<uint8_t> vbytes, no_exclude;
+    std::vector<uint64_t> voff, soff, one_each;
+    std::vector<uint32_t> poff;
+};
+
+// The three calls within k mismatches: their own argument checks, then every pattern cut into its pieces.  As for
+// icase_plain, a malformed batch is reported as such with or without a reader: the reader is looked at last.
+int near_plain(pss_reader *r, const char *who, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, const uint8_t *k,
+               SearchMode mode, pss_result **out, uint64_t *counts)
+{
+    if (!icase_out_ok(mode, nq, out, counts) || (nq && (!qbytes || !qoffsets || !k))) {
+        set_error("%s: bad arguments", who);
+        return PSS_EINVAL;
+    }
+    if (nq && qoffsets[0] != 0) {
+        set_error("%s: the pattern offsets start at %llu, not at 0", who, (unsigned long long)qoffsets[0]);
+        return PSS_EINVAL;
+    }
+    uint64_t npieces = 0;
+    for (uint32_t q = 0; q < nq; ++q) {
+        if (qoffsets[q + 1] < qoffsets[q]) {
+            set_error("%s: the pattern offsets decrease at pattern %u", who, q);
+            return PSS_EINVAL;
+        }
+        const uint64_t len = qoffsets[q + 1] - qoffsets[q];
+        if (len == 0) {
+            set_error("%s: pattern %u is empty (every entry contains the empty pattern)", who, q);
+            return PSS_EINVAL;
+        }
+        if (k[q] > kNearMaxBudget) {
+            set_error("%s: pattern %u has a budget of %u mismatches: 0 .. %u", who, q, (unsigned)k[q], kNearMaxBudget);
+            return PSS_EINVAL;
+        }
+        if (len <= k[q]) {
+            set_error("%s: pattern %u has %llu bytes and a budget of %u mismatches: every window of its length matches it "
+                      "(a pattern is longer than its budget)", who, q, (unsigned long long)len, (unsigned)k[q]);
+            return PSS_EINVAL;
+        }
+        if (len > 0xffffffffull) {
+            set_error("%s: pattern %u has more than 2^32 - 1 bytes (a chunk has fewer)", who, q);
+            return PSS_EINVAL;
+        }
+        npieces += (uint64_t)k[q] + 1;
+    }
+    if (npieces > 0xffffffffull) {
+        set_error("%s: the patterns are cut into more than the 2^32 - 1 pieces a batch takes", who);
+        return PSS_EINVAL;
+    }
+    if (!r) {
+        set_error("%s: bad arguments (no reader)", who);
+        return PSS_EINVAL;
+    }
+    NearGroups b;
+    b.voff.reserve(npieces + 1);
+    b.poff.reserve(npieces + 1);
+    b.voff.assign(1, 0);
+    b.soff.assign(1, 0);
+    b.soff.reserve((size_t)nq + 1);
+    for (uint32_t q = 0; q < nq; ++q) {
+        uint64_t off[kNearMaxBudget + 2];
+        near_pieces(qoffsets[q + 1] - qoffsets[q], k[q], off);
+        for (uint32_t j = 0; j <= k[q]; ++j) {
+            b.poff.push_back((uint32_t)off[j]);
+            b.voff.push_back(b.voff.back() + (off[j + 1] - off[j]));
+        }
+        b.soff.push_back(b.soff.back() + k[q] + 1);
+    }
+    // (the pieces of a pattern partition it, so back to back they are the patterns' bytes again)
+    b.vbytes.assign(qbytes, qbytes + (nq ? qoffsets[nq] : 0));
+    b.vbytes.push_back(0);                   // (data() of an empty vector may be null)
+    b.poff.push_back(0);
+    b.one_each.resize((size_t)nq + 1);
+    for (uint64_t g = 0; g <= nq; ++g) b.one_each[g] = g;
+    b.no_exclude.assign((size_t)nq + 1, 0);
+    static const uint8_t no_budget = 0;
+    static const uint64_t no_offset = 0;
+    SearchRequest rq{b.vbytes.data(), b.voff.data(), (uint32_t)npieces, mode, nullptr, b.one_each.data(), nq, b.no_exclude.data()};
+    rq.fold_bytes = b.vbytes.data();
+    rq.fold_offsets = nq ? qoffsets : &no_offset;
+    rq.spell_offsets = b.soff.data();
+    rq.nterms = nq;
+    rq.near_budget = nq ? k : &no_budget;
+    rq.piece_offsets = b.poff.data();
+    return icase_answer(r, rq, out, counts);
+}
+
+}  // namespace
+
+extern "C" int pss_near_pieces(const uint8_t *pat, uint64_t len, uint32_t k, uint32_t *offsets, uint32_t *lengths, uint32_t *count)
+{
+    return guarded([&]() -> int {
+        if (!pat || !len) {
+            set_error("pss_near_pieces: the pattern is empty (every entry contains the empty pattern)");
+            return PSS_EINVAL;
+        }
+        if (k > kNearMaxBudget) {
+            set_error("pss_near_pieces: a budget of %u mismatches: 0 .. %u", k, kNearMaxBudget);
+            return PSS_EINVAL;
+        }
+        if (len <= k) {
+            set_error("pss_near_pieces: a pattern of %llu bytes and a budget of %u mismatches: every window of its length matches it "
+                      "(a pattern is longer than its budget)", (unsigned long long)len, k);
+            return PSS_EINVAL;
+        }
+        if (len > 0xffffffffull || !offsets || !lengths || !count) {
+            set_error("pss_near_pieces: bad arguments (a pattern of %llu bytes)", (unsigned long long)len);
+            return PSS_EINVAL;
+        }
+        uint64_t off[kNearMaxBudget + 2];
+        near_pieces(len, k, off);
+        for (uint32_t j = 0; j <= k; ++j) {
+            offsets[j] = (uint32_t)off[j];
+            lengths[j] = (uint32_t)(off[j + 1] - off[j]);
+        }
+        *count = k + 1;
+        return PSS_OK;
+    });
+}
+
+extern "C" int pss_reader_search_near_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, const uint8_t *k,
+                                            pss_result **out)
+{
+    return guarded([&]() -> int { return near_plain(r, "pss_reader_search_near_batch", qbytes, qoffsets, nq, k, SEARCH_FULL, out, nullptr); });
+}
+
+extern "C" int pss_reader_search_near_ids_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, const uint8_t *k,
+                                                pss_result **out)
+{
+    return guarded([&]() -> int { return near_plain(r, "pss_reader_search_near_ids_batch", qbytes, qoffsets, nq, k, SEARCH_IDS, out, nullptr); });
+}
+
+extern "C" int pss_reader_count_near_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, const uint8_t *k,
+                                           uint64_t *counts)
+{
+    return guarded([&]() -> int { return near_plain(r, "pss_reader_count_near_batch", qbytes, qoffsets, nq, k, SEARCH_COUNTS, nullptr, counts); });
+}
+
 namespace {
 
 // ids[0 .. n) of ONE single-device reader: validation on the host (the reader knows every chunk's entry count once the

@@ -101,6 +101,14 @@ struct SearchRequest {
     // IDS; not with anchors; always the general pipeline.
     const uint32_t *fold_seed = nullptr; const uint8_t *fold_bytes = nullptr; const uint64_t *fold_offsets = nullptr;
     const uint64_t *spell_offsets = nullptr; uint32_t nterms = 0;
+    // near_budget (nterms bytes, 0 .. 3) and piece_offsets (nq u32 values), together with group_offsets, exclude, fold_bytes,
+    // fold_offsets and spell_offsets and WITHOUT fold_seed: the search within k mismatches of near_impl.h.  The
+    // rows are the ngroups = nterms patterns, each a group of one include term (identity group_offsets, zero exclude flags);
+    // fold_bytes holds the patterns themselves -- exact bytes, nothing is folded --, near_budget[t] is pattern t's budget k, and
+    // the nq queries are the patterns' PIECES: pattern t's k + 1 are spell_offsets[t] .. spell_offsets[t + 1], left to right,
+    // piece v at piece_offsets[v] inside its pattern (what fold_seed is per term, per piece).  Modes FULL, COUNTS and IDS; not
+    // with anchors, seq_anchors or low_latency; always the general pipeline, and sa_order has no say.
+    const uint8_t *near_budget = nullptr; const uint32_t *piece_offsets = nullptr;
     uint32_t rows() const { return group_offsets ? ngroups : nq; }     // rows of the result: queries, or groups of terms
     bool low_latency = false;            // one query through the resident kernel when it fits (an unanchored SEARCH_FULL batch only)
     // sa_order: the entries of one (query, chunk) pair come out in the reference's order -- suffix-array order of the FIRST hit
@@ -119,6 +127,10 @@ struct SearchRequest {
 // fold_spellings: the 2^f spellings of a seed of f letters back to back into out (len << f bytes), ascending bytewise.
 uint32_t fold_seed(const uint8_t *pat, uint64_t len, uint32_t letters, uint64_t *seed_off, uint64_t *seed_len);
 void fold_spellings(const uint8_t *seed, uint64_t len, uint32_t f, uint8_t *out);
+
+// Host side of the search within k mismatches (near_impl.h): the k + 1 pieces of a pattern of len > k bytes, piece j =
+// [off[j], off[j + 1]) with off[j] = j * len / (k + 1); off has k + 2 entries.
+void near_pieces(uint64_t len, uint32_t k, uint64_t *off);
 
 // The batch over the nc resident chunks of d_chunks (d_lines: their line tables, parallel to d_chunks; read by SEARCH_IDS
 // alone, nullptr where none were built).

@@ -1741,6 +1741,7 @@ static void newline_flags(const u8 *bytes, const u64 *off, u32 n, u8 set, u8 *fl
 #include "all_terms_impl.h"
 #include "sequence_impl.h"
 #include "fold_impl.h"
+#include "near_impl.h"
 
 // Suffix-array hits of the batch per chunk (pair p = query p / nc on chunk p % nc): one workgroup per chunk.
 __global__ __launch_bounds__(256) void chunk_hits_kernel(const u32 *cnt, u64 nq, u32 nc, u64 *out)
@@ -1758,7 +1759,8 @@ __global__ __launch_bounds__(256) void chunk_hits_kernel(const u32 *cnt, u64 nq,
 
 // ---- host driver of one batch -------------------------------------------------------------------------------------
 // search_batch_device reads top to bottom: empty batch -> stage_queries -> run_fused? -> launch_interval -> run_mid? ->
-// pick_drivers (an all-terms or a sequence batch) | fold_drivers (a case-insensitive batch) -> run_general -> finish.
+// pick_drivers (an all-terms or a sequence batch) | fold_drivers (a case-insensitive batch) | near_drivers (a batch within k
+// mismatches) -> run_general -> finish.
 // The stages share one Batch: the request normalised into the few booleans they read, the
 // workspace every route needs, the timing events and the two outputs.
 namespace {
@@ -1784,7 +1786,8 @@ struct Batch {
     bool counts, device, ids, anchored, terms, sa_order;
     bool seq;                           // terms, and the groups are ordered sequences (sequence_impl.h)
     bool fold;                          // terms under ASCII case folding: group -> terms -> spellings (fold_impl.h)
-    const u32 nterm;                    // terms of such a batch (else 0) ...
+    bool near;                          // patterns within k mismatches: pattern -> pattern -> pieces (near_impl.h)
+    const u32 nterm;                    // terms of such a batch, case-insensitive or near (else 0) ...
     const u64 ntp;                      // ... and its (term, chunk) pairs
     bool tiny;                          // queries and offsets fit the 16 KiB of the pinned scratch
     bool fused_ok, resident_ok, mid_ok; // routes this batch may take (each may still overflow into the next)
@@ -1809,6 +1812,9 @@ struct Batch {
     u32 *d_fseed = nullptr, *d_m = nullptr;
     u64 *d_soff = nullptr;                          // spelling offsets per term, seed hits per (term, chunk) pair
     u32 *d_tcnt = nullptr;
+    u8 *d_nk = nullptr;                             // a near batch: the budget per pattern, the offset of every piece in its
+    u32 *d_poff = nullptr;                          // pattern, and the flag of a pair whose pieces' hits pass 2^32 - 1
+    u64 *d_over = nullptr;
     // ... and of the mid and the general pipeline, sized by each: entry bounds per hit, the scans over them, the result
     u32 *d_start = nullptr, *d_len = nullptr;
     u64 *d_eidx = nullptr, *d_boff = nullptr, *d_entoff = nullptr;
@@ -1830,6 +1836,7 @@ struct Batch {
         terms = rq.group_offsets != nullptr;
         seq = terms && rq.seq_anchors != nullptr;
         fold = terms && rq.fold_seed != nullptr;
+        near = terms && rq.near_budget != nullptr;
         // (counts do not depend on the order; one hit per entry has one order; an all-terms batch keeps its driver's text order)
         sa_order = rq.sa_order && !counts && !anchored && !terms;
         // (an anchored batch searches its rewritten queries: a newline in front of and / or behind every pattern)
@@ -1849,7 +1856,7 @@ struct Batch {
         p = ctx->slot[which].as<T>();
         return PSS_OK;
     }
-    int stage_queries(), run_fused(bool *served), launch_interval(), run_mid(bool *done), pick_drivers(), fold_drivers(), run_general(), finish();
+    int stage_queries(), run_fused(bool *served), launch_interval(), run_mid(bool *done), pick_drivers(), fold_drivers(), near_drivers(), run_general(), finish();
     int sa_order_hits(u32 grid, u64 H);
     int download_result(u64 E, u64 B, const u64 *d_starts, const u8 *d_bytes, bool via_stage);
     void leave_on_device(const u64 *d_starts, const u8 *d_bytes), set_totals(u64 hits, u64 kept, u64 E, u64 B);
@@ -1925,11 +1932,12 @@ int Batch::stage_queries()
     h_off = hq ? ho : rq.qoffsets;
     h_flags = hf;
     h_padded = hq != nullptr;
-    if (terms) {                        // (per TERM; under fold from the folded terms: folding leaves a 0x0A alone)
-        const u32 nt = fold ? nterm : nq;
+    if (terms) {                        // (per TERM; under fold from the folded terms: folding leaves a 0x0A alone; a near batch
+        const bool whole = fold || near;    // from its patterns, not from their pieces)
+        const u32 nt = whole ? nterm : nq;
         own_tflags.resize(nt);
-        newline_flags(fold ? rq.fold_bytes : rq.qbytes, fold ? rq.fold_offsets : rq.qoffsets, nt, kTermVoid, own_tflags.data());
-        if (fold) own_fvoid = own_tflags;
+        newline_flags(whole ? rq.fold_bytes : rq.qbytes, whole ? rq.fold_offsets : rq.qoffsets, nt, kTermVoid, own_tflags.data());
+        if (whole) own_fvoid = own_tflags;
         for (u32 t = 0; !seq && t < nt; ++t)                        // (no segment of a sequence batch excludes)
             if (rq.exclude[t]) own_tflags[t] |= kTermExclude;
     }
@@ -2218,6 +2226,47 @@ int Batch::fold_drivers()
     return PSS_OK;
 }
 
+// Batch within k mismatches: from the (piece, chunk) pairs over the (pattern, chunk) pairs to themselves as (group, chunk)
+// pairs -- fold_drivers with other uploads.  The patterns go up beside their pieces -- piece offsets into the queries
+// (spell_offsets), the patterns' exact bytes (32 zero bytes behind them), their offsets, void flags, budgets, and every
+// piece's offset inside its pattern -- and with them the identity group offsets and the term flags.  near_union_kernel
+// leaves every pattern's piece hits per chunk in d_tcnt, added up in 64 bits; a pair past 2^32 - 1 raises d_over, whose copy
+// run_general reads with the hit total, before any hit buffer is reserved.  terms_driver_kernel picks every pair's one term.
+int Batch::near_drivers()
+{
+    const u64 ftotal = rq.fold_offsets[nterm];
+    const size_t goff_room = round_up(((size_t)nrow + 1) * 8, 64), toff_room = round_up(((size_t)nterm + 1) * 8, 64);
+    const size_t poff_room = round_up((size_t)nq * 4, 64), flag_room = round_up((size_t)nterm, 64);
+    const size_t byte_room = round_up(ftotal + 32, 64), tcnt_room = round_up((size_t)ntp * 4, 64);
+    PSS_TRY(take(Q_TERMS, goff_room + 2 * toff_room + 64 + poff_room + 3 * flag_room + byte_room + tcnt_room + nrp * 8, d_goff));
+    d_soff = d_goff + goff_room / 8;
+    d_foff = d_soff + toff_room / 8;
+    d_over = d_foff + toff_room / 8;
+    d_poff = reinterpret_cast<u32 *>(d_over + 8);
+    d_fvoid = reinterpret_cast<u8 *>(d_poff) + poff_room;
+    d_tflags = d_fvoid + flag_room;
+    d_nk = d_tflags + flag_room;
+    d_fbytes = d_nk + flag_room;
+    d_tcnt = reinterpret_cast<u32 *>(d_fbytes + byte_room);
+    d_gdrv = reinterpret_cast<u32 *>(reinterpret_cast<u8 *>(d_tcnt) + tcnt_room);
+    p_cnt = d_gdrv + nrp;
+    PSS_HIP(hipMemcpyAsync(d_goff, rq.group_offsets, ((size_t)nrow + 1) * 8, hipMemcpyHostToDevice, s));
+    PSS_HIP(hipMemcpyAsync(d_soff, rq.spell_offsets, ((size_t)nterm + 1) * 8, hipMemcpyHostToDevice, s));
+    PSS_HIP(hipMemcpyAsync(d_foff, rq.fold_offsets, ((size_t)nterm + 1) * 8, hipMemcpyHostToDevice, s));
+    PSS_HIP(hipMemcpyAsync(d_poff, rq.piece_offsets, (size_t)nq * 4, hipMemcpyHostToDevice, s));
+    PSS_HIP(hipMemcpyAsync(d_fvoid, own_fvoid.data(), nterm, hipMemcpyHostToDevice, s));
+    PSS_HIP(hipMemcpyAsync(d_tflags, own_tflags.data(), nterm, hipMemcpyHostToDevice, s));
+    PSS_HIP(hipMemcpyAsync(d_nk, rq.near_budget, nterm, hipMemcpyHostToDevice, s));
+    PSS_HIP(hipMemsetAsync(d_over, 0, 8, s));
+    PSS_HIP(hipMemsetAsync(d_fbytes + ftotal, 0, 32, s));
+    PSS_HIP(hipMemcpyAsync(d_fbytes, rq.fold_bytes, ftotal, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(near_union_kernel, dim3((u32)((ntp + 255) / 256)), dim3(256), 0, s, nc, d_soff, d_fvoid, d_cnt, ntp, d_tcnt, d_over);
+    hipLaunchKernelGGL(terms_driver_kernel<false>, dim3((u32)((nrp + 255) / 256)), dim3(256), 0, s, nc, d_goff, d_tflags,
+                       (const u32 *)nullptr, d_tcnt, nrp, d_gdrv, (u32 *)nullptr, p_cnt);
+    PSS_HIP(hipMemcpyAsync(h_small + 2, d_over, 8, hipMemcpyDeviceToHost, s));
+    return PSS_OK;
+}
+
 // General pipeline: every size comes down to the host before what it sizes is reserved -- hits, then kept hits (entries),
 // then bytes.
 int Batch::run_general()
@@ -2228,6 +2277,10 @@ int Batch::run_general()
     PSS_HIP(hipMemcpyAsync(h_small, d_total, 8, hipMemcpyDeviceToHost, s));
     PSS_HIP(hipStreamSynchronize(s));
     const u64 H = h_small[0];
+    if (near && h_small[2]) {   // (near_union_kernel: the one place a pair's 64-bit sum is judged; nothing is reserved yet)
+        set_error("search: the pieces of one pattern have more than 2^32 - 1 hits in one chunk: more than a batch within k mismatches takes");
+        return PSS_EINVAL;
+    }
     if (H == 0) {
         PSS_HIP(hipEventRecord(e2, s));
         if (device) {
@@ -2266,6 +2319,15 @@ int Batch::run_general()
         else if (nterm != nrow)     // (every group has an include term: as many terms as groups are one per group, and no other to look for)
             hipLaunchKernelGGL(terms_verify_kernel<true>, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, d_fbytes, d_foff, d_goff,
                                d_tflags, d_tcnt, d_gdrv, nrp, d_hitoff, H, d_start, d_len);
+    } else if (near) {
+        // every hit of every piece against the whole pattern inside its entry, kept as its alignment's first exact piece; then
+        // the survivors against the entry in front of them: the leftmost window within budget stands for the entry
+        PSS_TRY(take(Q_ORD_V0, H * 4, d_m));        // (as for a fold batch: the suffix-array order is never a near batch's)
+        const u32 vgrid = (u32)std::min<u64>((u64)ctx->num_cus * 16, (H * TG + 255) / 256);
+        hipLaunchKernelGGL(near_hits_kernel, dim3(grid), dim3(256), 0, s, d_chunks, nc, d_fbytes, d_foff, d_nk, d_poff, d_soff, d_lo, d_cnt,
+                           nrp, d_hitoff, H, d_start, d_len, d_m, d_gdrv);
+        hipLaunchKernelGGL(near_dedupe_kernel, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, d_fbytes, d_foff, d_nk, nrp, d_hitoff, H, d_start,
+                           d_m, d_len, d_gdrv);
     } else if (terms) {
         // candidates: the entries that hold the pair's driver term; then every candidate against the group's other terms
         hipLaunchKernelGGL(hit_lines_kernel<true>, dim3(grid), dim3(256), 0, s, d_chunks, nc, d_q, d_qoff, nrp, p_lo, d_hitoff, H,
@@ -2356,7 +2418,18 @@ int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, const LineDes
         set_error("search: an all-terms batch takes the general pipeline to a host result, and its terms are not anchored");
         return PSS_EINVAL;
     }
-    if ((rq.fold_seed || rq.spell_offsets) &&
+    if (rq.near_budget || rq.piece_offsets) {
+        bool ok = rq.near_budget && rq.piece_offsets && !rq.fold_seed && !rq.anchors && !rq.seq_anchors && rq.mode != SEARCH_DEVICE &&
+                  !rq.low_latency && rq.spell_offsets && rq.group_offsets && rq.fold_bytes && rq.fold_offsets && rq.exclude &&
+                  rq.ngroups == rq.nterms;
+        for (u32 g = 0; ok && g < rq.ngroups; ++g) ok = rq.group_offsets[g] == g && rq.group_offsets[g + 1] == (u64)g + 1;
+        if (!ok) {
+            set_error("search: a batch within k mismatches states its patterns as groups of one term each, with exclude flags, the "
+                      "patterns' bytes and offsets, piece offsets and budgets, and takes the general pipeline to a host result: no "
+                      "seeds, no anchors, no sequence anchors");
+            return PSS_EINVAL;
+        }
+    } else if ((rq.fold_seed || rq.spell_offsets) &&
         !(rq.fold_seed && rq.spell_offsets && rq.group_offsets && rq.fold_bytes && rq.fold_offsets && (!rq.nterms || rq.exclude || rq.seq_anchors))) {
         set_error("search: a case-insensitive batch states its groups, its terms' seeds, folded bytes and spelling offsets, and either "
                   "exclude flags or sequence anchors");
@@ -2388,6 +2461,8 @@ int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, const LineDes
     }
     if (b.fold) {
         PSS_TRY(b.fold_drivers());
+    } else if (b.near) {
+        PSS_TRY(b.near_drivers());
     } else if (b.terms) {
         PSS_TRY(b.pick_drivers());
     }
