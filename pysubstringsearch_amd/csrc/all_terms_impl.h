@@ -20,8 +20,8 @@ constexpr u8 kTermExclude = 1;
 constexpr u8 kTermVoid = 0x80;                   // the term holds a newline: it occurs in no entry
 
 // One lane per (group, chunk) pair: the driver term of the pair, its interval and its hit count.
-// Lo = false: the terms have no interval of their own (the terms of a case-insensitive group batch, fold_impl.h: cnt is
-// the sum over a term's spellings), so lo is not read and g_lo not written.
+// Lo = false: the terms have no interval of their own (the terms of a seeded batch, seed_impl.h: cnt is the sum over a
+// term's seed queries), so lo is not read and g_lo not written.
 template <bool Lo>
 __global__ __launch_bounds__(256) void terms_driver_kernel(u32 nc, const u64 *goff, const u8 *flags, const u32 *lo, const u32 *cnt,
                                                              u64 ngq, u32 *g_drv, u32 *g_lo, u32 *g_cnt)
@@ -64,7 +64,7 @@ __device__ __forceinline__ bool entry_holds(const ChunkDesc &ch, u32 s, u32 end,
 // end).  The true end is the closing newline or n -- not start + len, which is short by one for an unterminated last
 // entry.  An exclude term without a hit in the chunk cannot be in the entry and is not looked for.
 // Fold: the terms of a case-insensitive group batch (fold_impl.h).  qbytes / qoff are then the FOLDED terms and cnt the
-// terms' seed hits per chunk (fold_union_kernel); a term whose seed is absent from the chunk is absent itself, so the
+// terms' seed hits per chunk (seed_union_kernel); a term whose seed is absent from the chunk is absent itself, so the
 // exclude shortcut holds as it stands.  The group-wide-branch invariant of entry_scan holds for both forms alike: every
 // branch of the loop below depends on t, on what is read at t (l, s, e, the pair and through it g, c, drv) and on the
 // group's terms (f, cnt, `found` -- entry_scan's answer, the same in every lane of the group), never on gl.

@@ -1209,6 +1209,146 @@ extern "C" int pss_reader_search_ids_batch(pss_reader *r, const uint8_t *qbytes,
     });
 }
 
+// ---- what the entry points of the anchored, group and seeded batches share -----------------------------------------
+
+namespace {
+
+// The common end of those calls: the batch's answer by mode -- its counts, or its result.
+int answer_by_mode(pss_reader *r, const SearchRequest &rq, pss_result **out, uint64_t *counts)
+{
+    return rq.mode == SEARCH_COUNTS ? reader_batch_counts(r, rq, counts) : reader_batch_result(r, rq, out);
+}
+
+// Is the output argument that the mode asks for usable?  (No row: the counts may be null.)
+bool out_ok_by_mode(SearchMode mode, uint32_t rows, pss_result **out, const uint64_t *counts)
+{
+    return mode == SEARCH_COUNTS ? !rows || counts : out != nullptr;
+}
+
+// The offsets of a batch of plain patterns: they start at 0 and do not decrease, and no pattern is empty or has more than
+// 2^32 - 1 bytes.  each(q, len) is the batch's own check of pattern q, made once q is known non-empty; it states its own
+// error.
+template <typename Each>
+int pattern_args(const char *who, const uint64_t *qoffsets, uint32_t nq, Each each)
+{
+    if (nq && qoffsets[0] != 0) {
+        set_error("%s: the pattern offsets start at %llu, not at 0", who, (unsigned long long)qoffsets[0]);
+        return PSS_EINVAL;
+    }
+    for (uint32_t q = 0; q < nq; ++q) {
+        if (qoffsets[q + 1] < qoffsets[q]) {
+            set_error("%s: the pattern offsets decrease at pattern %u", who, q);
+            return PSS_EINVAL;
+        }
+        const uint64_t len = qoffsets[q + 1] - qoffsets[q];
+        if (len == 0) {
+            set_error("%s: pattern %u is empty (every entry contains the empty pattern)", who, q);
+            return PSS_EINVAL;
+        }
+        if (!each(q, len)) return PSS_EINVAL;
+        if (len > 0xffffffffull) {
+            set_error("%s: pattern %u has more than 2^32 - 1 bytes (a chunk has fewer)", who, q);
+            return PSS_EINVAL;
+        }
+    }
+    return PSS_OK;
+}
+
+uint32_t icase_letters(int32_t letters) { return letters <= 0 ? search_knobs().icase_seed_letters : (uint32_t)letters; }
+
+// The terms of a seeded batch (search.h) as the interval search takes them: the seed queries of every term back to back
+// (the spellings of its seed, or its pieces), the offsets that say which queries are whose, and the position of every
+// query inside its term; under fold beside them the terms folded to lower case.  A batch of plain patterns adds its groups
+// of one include term each: identity offsets and zero exclude flags.  It lives in the entry point's frame, so it outlives
+// the batch on every part of a multi-device reader.
+struct SeededGroups {
+    std::vector<uint8_t> vbytes, fbytes, no_exclude;
+    std::vector<uint64_t> voff, soff, foff, one_each;
+    std::vector<uint32_t> pos;
+    void one_term_each(uint32_t n)
+    {
+        one_each.resize((size_t)n + 1);
+        for (uint64_t g = 0; g <= n; ++g) one_each[g] = g;
+        no_exclude.assign((size_t)n + 1, 0);
+    }
+    // (the terms as they are verified: the folded ones; a near batch puts its patterns and budgets in their place)
+    SearchRequest request(uint32_t nterms, const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *exclude, const uint8_t *anchors,
+                          SearchMode mode) const
+    {
+        SearchRequest rq{vbytes.data(), voff.data(), (uint32_t)(voff.size() - 1), mode, nullptr, group_offsets, ngroups, exclude, anchors};
+        rq.term_bytes = fbytes.data();
+        rq.term_offsets = foff.data();
+        rq.nterms = nterms;
+        rq.seed_offsets = soff.data();
+        rq.seed_pos = pos.data();
+        return rq;
+    }
+};
+
+// The expansion of n terms (`noun`: "pattern", "term" or "segment") that pattern_args / terms_args / seq_args have passed:
+// every one non-empty.  What it holds is judged before anything is allocated for it.  At most 64 spellings per term: only a
+// batch of more than 2^26 terms can pass the limit, and only such a batch pays for a counting pass of its own.
+int icase_expand(const char *who, const char *noun, const uint8_t *tbytes, const uint64_t *toffsets, uint32_t n, SeededGroups *b)
+{
+    const uint32_t letters = icase_letters(0);
+    for (uint32_t t = 0; t < n; ++t)
+        if (toffsets[t + 1] - toffsets[t] > 0xffffffffull) {
+            set_error("%s: %s %u has more than 2^32 - 1 bytes (a chunk has fewer)", who, noun, t);
+            return PSS_EINVAL;
+        }
+    if (((uint64_t)n << letters) > 0xffffffffull) {
+        uint64_t count = 0;
+        for (uint32_t t = 0; t < n; ++t) {
+            uint64_t so = 0, sl = 0;
+            count += 1ull << fold_seed(tbytes + toffsets[t], toffsets[t + 1] - toffsets[t], letters, &so, &sl);
+            if (count > 0xffffffffull) {
+                set_error("%s: the %ss expand to more than the 2^32 - 1 terms an all-terms batch takes (at %s %u)", who, noun, noun, t);
+                return PSS_EINVAL;
+            }
+        }
+    }
+    std::vector<uint64_t> slen(n);
+    std::vector<uint32_t> seed(n);
+    std::vector<uint8_t> nletters(n);
+    uint64_t nspell = 0, vtotal = 0, ftotal = 0;
+    for (uint32_t t = 0; t < n; ++t) {
+        const uint64_t len = toffsets[t + 1] - toffsets[t];
+        uint64_t so = 0;
+        nletters[t] = (uint8_t)fold_seed(tbytes + toffsets[t], len, letters, &so, &slen[t]);
+        nspell += 1ull << nletters[t];
+        vtotal += slen[t] << nletters[t];
+        ftotal += len;
+        seed[t] = (uint32_t)so;             // (inside a term of less than 2^32 bytes)
+    }
+    b->fbytes.resize(ftotal + 1);
+    b->vbytes.resize(vtotal + 1);
+    b->voff.reserve(nspell + 1);
+    b->pos.reserve(nspell + 1);
+    b->soff.reserve((size_t)n + 1);
+    b->foff.reserve((size_t)n + 1);
+    b->voff.assign(1, 0);
+    b->soff.assign(1, 0);
+    b->foff.assign(1, 0);
+    for (uint32_t t = 0; t < n; ++t) {
+        const uint8_t *src = tbytes + toffsets[t];
+        const uint64_t len = toffsets[t + 1] - toffsets[t];
+        uint8_t *dst = b->fbytes.data() + b->foff.back();
+        for (uint64_t i = 0; i < len; ++i) dst[i] = (uint8_t)((uint8_t)(src[i] - 'A') < 26 ? src[i] | 0x20 : src[i]);
+        b->foff.push_back(b->foff.back() + len);
+        const uint32_t f = nletters[t];
+        fold_spellings(src + seed[t], slen[t], f, b->vbytes.data() + b->voff.back());
+        for (uint32_t v = 0; v < (1u << f); ++v) {          // (every spelling stands where the seed stands)
+            b->voff.push_back(b->voff.back() + slen[t]);
+            b->pos.push_back(seed[t]);
+        }
+        b->soff.push_back(b->soff.back() + (1ull << f));
+    }
+    b->pos.push_back(0);                    // (data() of an empty vector may be null)
+    return PSS_OK;
+}
+
+}  // namespace
+
 // ---- anchored search (anchored_impl.h) ---------------------------------------------------------------------------
 
 namespace {
@@ -1229,36 +1369,34 @@ int anchored_args(const pss_reader *r, const char *who, const uint64_t *qoffsets
     return PSS_OK;
 }
 
+int anchored_batch(pss_reader *r, const char *who, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, const uint8_t *anchors,
+                   SearchMode mode, pss_result **out, uint64_t *counts)
+{
+    PSS_TRY(anchored_args(r, who, qoffsets, nq, anchors, out_ok_by_mode(mode, nq, out, counts)));
+    return answer_by_mode(r, SearchRequest{qbytes, qoffsets, nq, mode, anchors}, out, counts);
+}
+
 }  // namespace
 
 extern "C" int pss_reader_search_anchored_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq,
                                                 const uint8_t *anchors, pss_result **out)
 {
-    return guarded([&]() -> int {
-        PSS_TRY(anchored_args(r, "pss_reader_search_anchored_batch", qoffsets, nq, anchors, out != nullptr));
-        return reader_batch_result(r, SearchRequest{qbytes, qoffsets, nq, SEARCH_FULL, anchors}, out);
-    });
+    return guarded([&]() -> int { return anchored_batch(r, "pss_reader_search_anchored_batch", qbytes, qoffsets, nq, anchors, SEARCH_FULL, out, nullptr); });
 }
 
 extern "C" int pss_reader_search_anchored_ids_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq,
                                                     const uint8_t *anchors, pss_result **out)
 {
-    return guarded([&]() -> int {
-        PSS_TRY(anchored_args(r, "pss_reader_search_anchored_ids_batch", qoffsets, nq, anchors, out != nullptr));
-        return reader_batch_result(r, SearchRequest{qbytes, qoffsets, nq, SEARCH_IDS, anchors}, out);
-    });
+    return guarded([&]() -> int { return anchored_batch(r, "pss_reader_search_anchored_ids_batch", qbytes, qoffsets, nq, anchors, SEARCH_IDS, out, nullptr); });
 }
 
 extern "C" int pss_reader_count_anchored_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq,
                                                const uint8_t *anchors, uint64_t *counts)
 {
-    return guarded([&]() -> int {
-        PSS_TRY(anchored_args(r, "pss_reader_count_anchored_batch", qoffsets, nq, anchors, !nq || counts));
-        return reader_batch_counts(r, SearchRequest{qbytes, qoffsets, nq, SEARCH_COUNTS, anchors}, counts);
-    });
+    return guarded([&]() -> int { return anchored_batch(r, "pss_reader_count_anchored_batch", qbytes, qoffsets, nq, anchors, SEARCH_COUNTS, nullptr, counts); });
 }
 
-// ---- all-terms search (all_terms_impl.h) -------------------------------------------------------------------------
+// ---- all-terms search (all_terms_impl.h), plain and case-insensitive (group -> terms -> spellings) ------
 
 namespace {
 
@@ -1315,42 +1453,39 @@ int terms_args(const pss_reader *r, const char *who, const uint8_t *tbytes, cons
     });
 }
 
-SearchRequest terms_request(const uint8_t *tbytes, const uint64_t *toffsets, uint32_t nterms, const uint64_t *group_offsets,
-                            uint32_t ngroups, const uint8_t *exclude, SearchMode mode)
+// The six all-terms calls: the argument checks, then the batch as it stands or, under icase, expanded into its seeds'
+// spellings.
+int terms_batch(pss_reader *r, const char *who, const uint8_t *tbytes, const uint64_t *toffsets, uint32_t nterms, const uint64_t *group_offsets,
+                uint32_t ngroups, const uint8_t *exclude, bool icase, SearchMode mode, pss_result **out, uint64_t *counts)
 {
-    return SearchRequest{tbytes, toffsets, nterms, mode, nullptr, group_offsets, ngroups, exclude};
+    PSS_TRY(terms_args(r, who, tbytes, toffsets, nterms, group_offsets, ngroups, exclude, out_ok_by_mode(mode, ngroups, out, counts)));
+    if (!icase) return answer_by_mode(r, SearchRequest{tbytes, toffsets, nterms, mode, nullptr, group_offsets, ngroups, exclude}, out, counts);
+    SeededGroups b;
+    PSS_TRY(icase_expand(who, "term", tbytes, toffsets, nterms, &b));
+    return answer_by_mode(r, b.request(nterms, group_offsets, ngroups, exclude, nullptr, mode), out, counts);
 }
 
 }  // namespace
 
-extern "C" int pss_reader_search_terms_batch(pss_reader *r, const uint8_t *tbytes, const uint64_t *toffsets, uint32_t nterms,
-                                             const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *exclude, pss_result **out)
+extern "C" int pss_reader_search_terms_batch(pss_reader *r, const uint8_t *tbytes, const uint64_t *toffsets, uint32_t nterms, const uint64_t *group_offsets,
+        uint32_t ngroups, const uint8_t *exclude, pss_result **out)
 {
-    return guarded([&]() -> int {
-        PSS_TRY(terms_args(r, "pss_reader_search_terms_batch", tbytes, toffsets, nterms, group_offsets, ngroups, exclude, out != nullptr));
-        return reader_batch_result(r, terms_request(tbytes, toffsets, nterms, group_offsets, ngroups, exclude, SEARCH_FULL), out);
-    });
+    return guarded([&]() -> int { return terms_batch(r, "pss_reader_search_terms_batch", tbytes, toffsets, nterms, group_offsets, ngroups, exclude, false, SEARCH_FULL, out, nullptr); });
 }
 
-extern "C" int pss_reader_search_terms_ids_batch(pss_reader *r, const uint8_t *tbytes, const uint64_t *toffsets, uint32_t nterms,
-                                                 const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *exclude, pss_result **out)
+extern "C" int pss_reader_search_terms_ids_batch(pss_reader *r, const uint8_t *tbytes, const uint64_t *toffsets, uint32_t nterms, const uint64_t *group_offsets,
+        uint32_t ngroups, const uint8_t *exclude, pss_result **out)
 {
-    return guarded([&]() -> int {
-        PSS_TRY(terms_args(r, "pss_reader_search_terms_ids_batch", tbytes, toffsets, nterms, group_offsets, ngroups, exclude, out != nullptr));
-        return reader_batch_result(r, terms_request(tbytes, toffsets, nterms, group_offsets, ngroups, exclude, SEARCH_IDS), out);
-    });
+    return guarded([&]() -> int { return terms_batch(r, "pss_reader_search_terms_ids_batch", tbytes, toffsets, nterms, group_offsets, ngroups, exclude, false, SEARCH_IDS, out, nullptr); });
 }
 
-extern "C" int pss_reader_count_terms_batch(pss_reader *r, const uint8_t *tbytes, const uint64_t *toffsets, uint32_t nterms,
-                                            const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *exclude, uint64_t *counts)
+extern "C" int pss_reader_count_terms_batch(pss_reader *r, const uint8_t *tbytes, const uint64_t *toffsets, uint32_t nterms, const uint64_t *group_offsets,
+        uint32_t ngroups, const uint8_t *exclude, uint64_t *counts)
 {
-    return guarded([&]() -> int {
-        PSS_TRY(terms_args(r, "pss_reader_count_terms_batch", tbytes, toffsets, nterms, group_offsets, ngroups, exclude, !ngroups || counts));
-        return reader_batch_counts(r, terms_request(tbytes, toffsets, nterms, group_offsets, ngroups, exclude, SEARCH_COUNTS), counts);
-    });
+    return guarded([&]() -> int { return terms_batch(r, "pss_reader_count_terms_batch", tbytes, toffsets, nterms, group_offsets, ngroups, exclude, false, SEARCH_COUNTS, nullptr, counts); });
 }
 
-// ---- wildcard search: segments in order (sequence_impl.h) --------------------------------------------------------
+// ---- wildcard search: segments in order (sequence_impl.h), plain and case-insensitive ------------------------------
 
 namespace {
 
@@ -1380,194 +1515,60 @@ int seq_args(const pss_reader *r, const char *who, const uint8_t *sbytes, const 
     });
 }
 
-SearchRequest seq_request(const uint8_t *sbytes, const uint64_t *soffsets, uint32_t nsegs, const uint64_t *group_offsets,
-                          uint32_t ngroups, const uint8_t *anchors, SearchMode mode)
+// The six sequence calls, as terms_batch: group -> segments, under icase -> spellings.
+int seq_batch(pss_reader *r, const char *who, const uint8_t *sbytes, const uint64_t *soffsets, uint32_t nsegs, const uint64_t *group_offsets,
+              uint32_t ngroups, const uint8_t *anchors, bool icase, SearchMode mode, pss_result **out, uint64_t *counts)
 {
-    return SearchRequest{sbytes, soffsets, nsegs, mode, nullptr, group_offsets, ngroups, nullptr, anchors};
+    PSS_TRY(seq_args(r, who, sbytes, soffsets, nsegs, group_offsets, ngroups, anchors, out_ok_by_mode(mode, ngroups, out, counts)));
+    if (!icase)
+        return answer_by_mode(r, SearchRequest{sbytes, soffsets, nsegs, mode, nullptr, group_offsets, ngroups, nullptr, anchors}, out, counts);
+    SeededGroups b;
+    PSS_TRY(icase_expand(who, "segment", sbytes, soffsets, nsegs, &b));
+    return answer_by_mode(r, b.request(nsegs, group_offsets, ngroups, nullptr, anchors, mode), out, counts);
 }
 
 }  // namespace
 
-extern "C" int pss_reader_search_seq_batch(pss_reader *r, const uint8_t *sbytes, const uint64_t *soffsets, uint32_t nsegs,
-                                           const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *anchors, pss_result **out)
+extern "C" int pss_reader_search_seq_batch(pss_reader *r, const uint8_t *sbytes, const uint64_t *soffsets, uint32_t nsegs, const uint64_t *group_offsets,
+        uint32_t ngroups, const uint8_t *anchors, pss_result **out)
 {
-    return guarded([&]() -> int {
-        PSS_TRY(seq_args(r, "pss_reader_search_seq_batch", sbytes, soffsets, nsegs, group_offsets, ngroups, anchors, out != nullptr));
-        return reader_batch_result(r, seq_request(sbytes, soffsets, nsegs, group_offsets, ngroups, anchors, SEARCH_FULL), out);
-    });
+    return guarded([&]() -> int { return seq_batch(r, "pss_reader_search_seq_batch", sbytes, soffsets, nsegs, group_offsets, ngroups, anchors, false, SEARCH_FULL, out, nullptr); });
 }
 
-extern "C" int pss_reader_search_seq_ids_batch(pss_reader *r, const uint8_t *sbytes, const uint64_t *soffsets, uint32_t nsegs,
-                                               const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *anchors, pss_result **out)
+extern "C" int pss_reader_search_seq_ids_batch(pss_reader *r, const uint8_t *sbytes, const uint64_t *soffsets, uint32_t nsegs, const uint64_t *group_offsets,
+        uint32_t ngroups, const uint8_t *anchors, pss_result **out)
 {
-    return guarded([&]() -> int {
-        PSS_TRY(seq_args(r, "pss_reader_search_seq_ids_batch", sbytes, soffsets, nsegs, group_offsets, ngroups, anchors, out != nullptr));
-        return reader_batch_result(r, seq_request(sbytes, soffsets, nsegs, group_offsets, ngroups, anchors, SEARCH_IDS), out);
-    });
+    return guarded([&]() -> int { return seq_batch(r, "pss_reader_search_seq_ids_batch", sbytes, soffsets, nsegs, group_offsets, ngroups, anchors, false, SEARCH_IDS, out, nullptr); });
 }
 
-extern "C" int pss_reader_count_seq_batch(pss_reader *r, const uint8_t *sbytes, const uint64_t *soffsets, uint32_t nsegs,
-                                          const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *anchors, uint64_t *counts)
+extern "C" int pss_reader_count_seq_batch(pss_reader *r, const uint8_t *sbytes, const uint64_t *soffsets, uint32_t nsegs, const uint64_t *group_offsets,
+        uint32_t ngroups, const uint8_t *anchors, uint64_t *counts)
 {
-    return guarded([&]() -> int {
-        PSS_TRY(seq_args(r, "pss_reader_count_seq_batch", sbytes, soffsets, nsegs, group_offsets, ngroups, anchors, !ngroups || counts));
-        return reader_batch_counts(r, seq_request(sbytes, soffsets, nsegs, group_offsets, ngroups, anchors, SEARCH_COUNTS), counts);
-    });
+    return guarded([&]() -> int { return seq_batch(r, "pss_reader_count_seq_batch", sbytes, soffsets, nsegs, group_offsets, ngroups, anchors, false, SEARCH_COUNTS, nullptr, counts); });
 }
 
 // ---- case-insensitive search: group -> terms -> the spellings of a seed (fold_impl.h) --------------
 
 namespace {
 
-uint32_t icase_letters(int32_t letters) { return letters <= 0 ? search_knobs().icase_seed_letters : (uint32_t)letters; }
-
-// The terms (patterns, or segments) of a case-insensitive batch as the interval search takes them: the spellings of every
-// term's seed, the offsets that say which spellings are whose, and beside them the terms folded to lower case with their
-// seeds' offsets.  A batch of plain patterns adds its groups of one include term each: identity offsets and zero exclude
-// flags.  It lives in the entry point's frame, so it outlives the batch on every part of a multi-device reader.
-struct IcaseGroups {
-    std::vector<uint8_t> vbytes, fbytes, no_exclude;
-    std::vector<uint64_t> voff, soff, foff, one_each;
-    std::vector<uint32_t> seed;
-    SearchRequest request(uint32_t nterms, const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *exclude, const uint8_t *anchors,
-                          SearchMode mode) const
-    {
-        SearchRequest rq{vbytes.data(), voff.data(), (uint32_t)(voff.size() - 1), mode, nullptr, group_offsets, ngroups, exclude, anchors};
-        rq.fold_seed = seed.data();
-        rq.fold_bytes = fbytes.data();
-        rq.fold_offsets = foff.data();
-        rq.spell_offsets = soff.data();
-        rq.nterms = nterms;
-        return rq;
-    }
-};
-
-// The expansion of n terms (`noun`: "pattern", "term" or "segment") that icase_plain / terms_args / seq_args have passed:
-// every one non-empty.  What it holds is judged before anything is allocated for it.  At most 64 spellings per term: only a
-// batch of more than 2^26 terms can pass the limit, and only such a batch pays for a counting pass of its own.
-int icase_expand(const char *who, const char *noun, const uint8_t *tbytes, const uint64_t *toffsets, uint32_t n, IcaseGroups *b)
-{
-    const uint32_t letters = icase_letters(0);
-    for (uint32_t t = 0; t < n; ++t)
-        if (toffsets[t + 1] - toffsets[t] > 0xffffffffull) {
-            set_error("%s: %s %u has more than 2^32 - 1 bytes (a chunk has fewer)", who, noun, t);
-            return PSS_EINVAL;
-        }
-    if (((uint64_t)n << letters) > 0xffffffffull) {
-        uint64_t count = 0;
-        for (uint32_t t = 0; t < n; ++t) {
-            uint64_t so = 0, sl = 0;
-            count += 1ull << fold_seed(tbytes + toffsets[t], toffsets[t + 1] - toffsets[t], letters, &so, &sl);
-            if (count > 0xffffffffull) {
-                set_error("%s: the %ss expand to more than the 2^32 - 1 terms an all-terms batch takes (at %s %u)", who, noun, noun, t);
-                return PSS_EINVAL;
-            }
-        }
-    }
-    b->seed.resize((size_t)n + 1);          // (+ 1: data() of an empty vector may be null)
-    std::vector<uint64_t> slen(n);
-    std::vector<uint8_t> nletters(n);
-    uint64_t nspell = 0, vtotal = 0, ftotal = 0;
-    for (uint32_t t = 0; t < n; ++t) {
-        const uint64_t len = toffsets[t + 1] - toffsets[t];
-        uint64_t so = 0;
-        nletters[t] = (uint8_t)fold_seed(tbytes + toffsets[t], len, letters, &so, &slen[t]);
-        nspell += 1ull << nletters[t];
-        vtotal += slen[t] << nletters[t];
-        ftotal += len;
-        b->seed[t] = (uint32_t)so;          // (inside a term of less than 2^32 bytes)
-    }
-    b->fbytes.resize(ftotal + 1);
-    b->vbytes.resize(vtotal + 1);
-    b->voff.reserve(nspell + 1);
-    b->soff.reserve((size_t)n + 1);
-    b->foff.reserve((size_t)n + 1);
-    b->voff.assign(1, 0);
-    b->soff.assign(1, 0);
-    b->foff.assign(1, 0);
-    for (uint32_t t = 0; t < n; ++t) {
-        const uint8_t *src = tbytes + toffsets[t];
-        const uint64_t len = toffsets[t + 1] - toffsets[t];
-        uint8_t *dst = b->fbytes.data() + b->foff.back();
-        for (uint64_t i = 0; i < len; ++i) dst[i] = (uint8_t)((uint8_t)(src[i] - 'A') < 26 ? src[i] | 0x20 : src[i]);
-        b->foff.push_back(b->foff.back() + len);
-        const uint32_t f = nletters[t];
-        fold_spellings(src + b->seed[t], slen[t], f, b->vbytes.data() + b->voff.back());
-        for (uint32_t v = 0; v < (1u << f); ++v) b->voff.push_back(b->voff.back() + slen[t]);
-        b->soff.push_back(b->soff.back() + (1ull << f));
-    }
-    return PSS_OK;
-}
-
-// The common end of the nine case-insensitive calls: the result of the batch, or its counts.
-int icase_answer(pss_reader *r, const SearchRequest &rq, pss_result **out, uint64_t *counts)
-{
-    return rq.mode == SEARCH_COUNTS ? reader_batch_counts(r, rq, counts) : reader_batch_result(r, rq, out);
-}
-
-// Is the call's own output argument usable?  (No row: the counts may be null.)
-bool icase_out_ok(SearchMode mode, uint32_t rows, pss_result **out, const uint64_t *counts)
-{
-    return mode == SEARCH_COUNTS ? !rows || counts : out != nullptr;
-}
-
 // The three plain case-insensitive calls: their own argument checks, then every pattern as a group of one include term.
 // The reader is looked at last, as for the all-terms calls: a malformed batch is reported as such with or without one.
 int icase_plain(pss_reader *r, const char *who, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, SearchMode mode,
                 pss_result **out, uint64_t *counts)
 {
-    if (!icase_out_ok(mode, nq, out, counts) || (nq && (!qbytes || !qoffsets))) {
+    if (!out_ok_by_mode(mode, nq, out, counts) || (nq && (!qbytes || !qoffsets))) {
         set_error("%s: bad arguments", who);
         return PSS_EINVAL;
     }
-    if (nq && qoffsets[0] != 0) {
-        set_error("%s: the pattern offsets start at %llu, not at 0", who, (unsigned long long)qoffsets[0]);
-        return PSS_EINVAL;
-    }
-    for (uint32_t q = 0; q < nq; ++q) {
-        if (qoffsets[q + 1] < qoffsets[q]) {
-            set_error("%s: the pattern offsets decrease at pattern %u", who, q);
-            return PSS_EINVAL;
-        }
-        if (qoffsets[q + 1] == qoffsets[q]) {
-            set_error("%s: pattern %u is empty (every entry contains the empty pattern)", who, q);
-            return PSS_EINVAL;
-        }
-        if (qoffsets[q + 1] - qoffsets[q] > 0xffffffffull) {
-            set_error("%s: pattern %u has more than 2^32 - 1 bytes (a chunk has fewer)", who, q);
-            return PSS_EINVAL;
-        }
-    }
-    IcaseGroups b;
+    PSS_TRY(pattern_args(who, qoffsets, nq, [](uint32_t, uint64_t) { return true; }));
+    SeededGroups b;
     PSS_TRY(icase_expand(who, "pattern", qbytes, qoffsets, nq, &b));
     if (!r) {
         set_error("%s: bad arguments (no reader)", who);
         return PSS_EINVAL;
     }
-    b.one_each.resize((size_t)nq + 1);
-    for (uint64_t g = 0; g <= nq; ++g) b.one_each[g] = g;
-    b.no_exclude.assign((size_t)nq + 1, 0);
-    return icase_answer(r, b.request(nq, b.one_each.data(), nq, b.no_exclude.data(), nullptr, mode), out, counts);
-}
-
-// The three case-insensitive all-terms calls: group -> terms -> spellings.
-int icase_terms(pss_reader *r, const char *who, const uint8_t *tbytes, const uint64_t *toffsets, uint32_t nterms,
-                const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *exclude, SearchMode mode, pss_result **out, uint64_t *counts)
-{
-    IcaseGroups b;
-    PSS_TRY(terms_args(r, who, tbytes, toffsets, nterms, group_offsets, ngroups, exclude, icase_out_ok(mode, ngroups, out, counts)));
-    PSS_TRY(icase_expand(who, "term", tbytes, toffsets, nterms, &b));
-    return icase_answer(r, b.request(nterms, group_offsets, ngroups, exclude, nullptr, mode), out, counts);
-}
-
-// ... and the three case-insensitive wildcard calls: group -> segments -> spellings.
-int icase_seq(pss_reader *r, const char *who, const uint8_t *sbytes, const uint64_t *soffsets, uint32_t nsegs, const uint64_t *group_offsets,
-              uint32_t ngroups, const uint8_t *anchors, SearchMode mode, pss_result **out, uint64_t *counts)
-{
-    IcaseGroups b;
-    PSS_TRY(seq_args(r, who, sbytes, soffsets, nsegs, group_offsets, ngroups, anchors, icase_out_ok(mode, ngroups, out, counts)));
-    PSS_TRY(icase_expand(who, "segment", sbytes, soffsets, nsegs, &b));
-    return icase_answer(r, b.request(nsegs, group_offsets, ngroups, nullptr, anchors, mode), out, counts);
+    b.one_term_each(nq);
+    return answer_by_mode(r, b.request(nq, b.one_each.data(), nq, b.no_exclude.data(), nullptr, mode), out, counts);
 }
 
 }  // namespace
@@ -1620,60 +1621,40 @@ extern "C" int pss_reader_count_icase_batch(pss_reader *r, const uint8_t *qbytes
     return guarded([&]() -> int { return icase_plain(r, "pss_reader_count_icase_batch", qbytes, qoffsets, nq, SEARCH_COUNTS, nullptr, counts); });
 }
 
-extern "C" int pss_reader_search_terms_icase_batch(pss_reader *r, const uint8_t *tbytes, const uint64_t *toffsets, uint32_t nterms,
-                                                   const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *exclude, pss_result **out)
+extern "C" int pss_reader_search_terms_icase_batch(pss_reader *r, const uint8_t *tbytes, const uint64_t *toffsets, uint32_t nterms, const uint64_t *group_offsets,
+        uint32_t ngroups, const uint8_t *exclude, pss_result **out)
 {
-    return guarded([&]() -> int {
-        return icase_terms(r, "pss_reader_search_terms_icase_batch", tbytes, toffsets, nterms, group_offsets, ngroups, exclude, SEARCH_FULL, out,
-                           nullptr);
-    });
+    return guarded([&]() -> int { return terms_batch(r, "pss_reader_search_terms_icase_batch", tbytes, toffsets, nterms, group_offsets, ngroups, exclude, true, SEARCH_FULL, out, nullptr); });
 }
 
-extern "C" int pss_reader_search_terms_icase_ids_batch(pss_reader *r, const uint8_t *tbytes, const uint64_t *toffsets, uint32_t nterms,
-                                                       const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *exclude,
-                                                       pss_result **out)
+extern "C" int pss_reader_search_terms_icase_ids_batch(pss_reader *r, const uint8_t *tbytes, const uint64_t *toffsets, uint32_t nterms, const uint64_t *group_offsets,
+        uint32_t ngroups, const uint8_t *exclude, pss_result **out)
 {
-    return guarded([&]() -> int {
-        return icase_terms(r, "pss_reader_search_terms_icase_ids_batch", tbytes, toffsets, nterms, group_offsets, ngroups, exclude, SEARCH_IDS,
-                           out, nullptr);
-    });
+    return guarded([&]() -> int { return terms_batch(r, "pss_reader_search_terms_icase_ids_batch", tbytes, toffsets, nterms, group_offsets, ngroups, exclude, true, SEARCH_IDS, out, nullptr); });
 }
 
-extern "C" int pss_reader_count_terms_icase_batch(pss_reader *r, const uint8_t *tbytes, const uint64_t *toffsets, uint32_t nterms,
-                                                  const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *exclude, uint64_t *counts)
+extern "C" int pss_reader_count_terms_icase_batch(pss_reader *r, const uint8_t *tbytes, const uint64_t *toffsets, uint32_t nterms, const uint64_t *group_offsets,
+        uint32_t ngroups, const uint8_t *exclude, uint64_t *counts)
 {
-    return guarded([&]() -> int {
-        return icase_terms(r, "pss_reader_count_terms_icase_batch", tbytes, toffsets, nterms, group_offsets, ngroups, exclude, SEARCH_COUNTS,
-                           nullptr, counts);
-    });
+    return guarded([&]() -> int { return terms_batch(r, "pss_reader_count_terms_icase_batch", tbytes, toffsets, nterms, group_offsets, ngroups, exclude, true, SEARCH_COUNTS, nullptr, counts); });
 }
 
-extern "C" int pss_reader_search_seq_icase_batch(pss_reader *r, const uint8_t *sbytes, const uint64_t *soffsets, uint32_t nsegs,
-                                                 const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *anchors, pss_result **out)
+extern "C" int pss_reader_search_seq_icase_batch(pss_reader *r, const uint8_t *sbytes, const uint64_t *soffsets, uint32_t nsegs, const uint64_t *group_offsets,
+        uint32_t ngroups, const uint8_t *anchors, pss_result **out)
 {
-    return guarded([&]() -> int {
-        return icase_seq(r, "pss_reader_search_seq_icase_batch", sbytes, soffsets, nsegs, group_offsets, ngroups, anchors, SEARCH_FULL, out,
-                         nullptr);
-    });
+    return guarded([&]() -> int { return seq_batch(r, "pss_reader_search_seq_icase_batch", sbytes, soffsets, nsegs, group_offsets, ngroups, anchors, true, SEARCH_FULL, out, nullptr); });
 }
 
-extern "C" int pss_reader_search_seq_icase_ids_batch(pss_reader *r, const uint8_t *sbytes, const uint64_t *soffsets, uint32_t nsegs,
-                                                     const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *anchors,
-                                                     pss_result **out)
+extern "C" int pss_reader_search_seq_icase_ids_batch(pss_reader *r, const uint8_t *sbytes, const uint64_t *soffsets, uint32_t nsegs, const uint64_t *group_offsets,
+        uint32_t ngroups, const uint8_t *anchors, pss_result **out)
 {
-    return guarded([&]() -> int {
-        return icase_seq(r, "pss_reader_search_seq_icase_ids_batch", sbytes, soffsets, nsegs, group_offsets, ngroups, anchors, SEARCH_IDS, out,
-                         nullptr);
-    });
+    return guarded([&]() -> int { return seq_batch(r, "pss_reader_search_seq_icase_ids_batch", sbytes, soffsets, nsegs, group_offsets, ngroups, anchors, true, SEARCH_IDS, out, nullptr); });
 }
 
-extern "C" int pss_reader_count_seq_icase_batch(pss_reader *r, const uint8_t *sbytes, const uint64_t *soffsets, uint32_t nsegs,
-                                                const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *anchors, uint64_t *counts)
+extern "C" int pss_reader_count_seq_icase_batch(pss_reader *r, const uint8_t *sbytes, const uint64_t *soffsets, uint32_t nsegs, const uint64_t *group_offsets,
+        uint32_t ngroups, const uint8_t *anchors, uint64_t *counts)
 {
-    return guarded([&]() -> int {
-        return icase_seq(r, "pss_reader_count_seq_icase_batch", sbytes, soffsets, nsegs, group_offsets, ngroups, anchors, SEARCH_COUNTS, nullptr,
-                         counts);
-    });
+    return guarded([&]() -> int { return seq_batch(r, "pss_reader_count_seq_icase_batch", sbytes, soffsets, nsegs, group_offsets, ngroups, anchors, true, SEARCH_COUNTS, nullptr, counts); });
 }
 
 // ---- search within k mismatches: pattern -> pattern -> its k + 1 pieces (near_impl.h) ---------------
@@ -1682,55 +1663,30 @@ namespace {
 
 constexpr uint32_t kNearMaxBudget = 3;
 
-// The patterns of a near batch as the interval search takes them: the pieces of every pattern back to back, the offsets
-// that say which pieces are whose and where each stands in its pattern, the budgets, and the groups of one include term
-// each (identity offsets, zero exclude flags).  The patterns' own bytes and offsets are the caller's.  It lives in the
-// entry point's frame, so it outlives the batch on every part of a multi-device reader.
-struct NearGroups {
-    std::vector<uint8_t> vbytes, no_exclude;
-    std::vector<uint64_t> voff, soff, one_each;
-    std::vector<uint32_t> poff;
-};
-
-// The three calls within k mismatches: their own argument checks, then every pattern cut into its pieces.  As for
-// icase_plain, a malformed batch is reported as such with or without a reader: the reader is looked at last.
+// The three calls within k mismatches: their own argument checks, then every pattern cut into its pieces -- the seed
+// queries of a group of one include term.  The patterns' own bytes and offsets are the caller's.  As for icase_plain, a
+// malformed batch is reported as such with or without a reader: the reader is looked at last.
 int near_plain(pss_reader *r, const char *who, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, const uint8_t *k,
                SearchMode mode, pss_result **out, uint64_t *counts)
 {
-    if (!icase_out_ok(mode, nq, out, counts) || (nq && (!qbytes || !qoffsets || !k))) {
+    if (!out_ok_by_mode(mode, nq, out, counts) || (nq && (!qbytes || !qoffsets || !k))) {
         set_error("%s: bad arguments", who);
         return PSS_EINVAL;
     }
-    if (nq && qoffsets[0] != 0) {
-        set_error("%s: the pattern offsets start at %llu, not at 0", who, (unsigned long long)qoffsets[0]);
-        return PSS_EINVAL;
-    }
     uint64_t npieces = 0;
-    for (uint32_t q = 0; q < nq; ++q) {
-        if (qoffsets[q + 1] < qoffsets[q]) {
-            set_error("%s: the pattern offsets decrease at pattern %u", who, q);
-            return PSS_EINVAL;
-        }
-        const uint64_t len = qoffsets[q + 1] - qoffsets[q];
-        if (len == 0) {
-            set_error("%s: pattern %u is empty (every entry contains the empty pattern)", who, q);
-            return PSS_EINVAL;
-        }
+    PSS_TRY(pattern_args(who, qoffsets, nq, [&](uint32_t q, uint64_t len) {
         if (k[q] > kNearMaxBudget) {
             set_error("%s: pattern %u has a budget of %u mismatches: 0 .. %u", who, q, (unsigned)k[q], kNearMaxBudget);
-            return PSS_EINVAL;
+            return false;
         }
         if (len <= k[q]) {
             set_error("%s: pattern %u has %llu bytes and a budget of %u mismatches: every window of its length matches it "
                       "(a pattern is longer than its budget)", who, q, (unsigned long long)len, (unsigned)k[q]);
-            return PSS_EINVAL;
-        }
-        if (len > 0xffffffffull) {
-            set_error("%s: pattern %u has more than 2^32 - 1 bytes (a chunk has fewer)", who, q);
-            return PSS_EINVAL;
+            return false;
         }
         npieces += (uint64_t)k[q] + 1;
-    }
+        return true;
+    }));
     if (npieces > 0xffffffffull) {
         set_error("%s: the patterns are cut into more than the 2^32 - 1 pieces a batch takes", who);
         return PSS_EINVAL;
@@ -1739,9 +1695,9 @@ int near_plain(pss_reader *r, const char *who, const uint8_t *qbytes, const uint
         set_error("%s: bad arguments (no reader)", who);
         return PSS_EINVAL;
     }
-    NearGroups b;
+    SeededGroups b;
     b.voff.reserve(npieces + 1);
-    b.poff.reserve(npieces + 1);
+    b.pos.reserve(npieces + 1);
     b.voff.assign(1, 0);
     b.soff.assign(1, 0);
     b.soff.reserve((size_t)nq + 1);
@@ -1749,7 +1705,7 @@ int near_plain(pss_reader *r, const char *who, const uint8_t *qbytes, const uint
         uint64_t off[kNearMaxBudget + 2];
         near_pieces(qoffsets[q + 1] - qoffsets[q], k[q], off);
         for (uint32_t j = 0; j <= k[q]; ++j) {
-            b.poff.push_back((uint32_t)off[j]);
+            b.pos.push_back((uint32_t)off[j]);
             b.voff.push_back(b.voff.back() + (off[j + 1] - off[j]));
         }
         b.soff.push_back(b.soff.back() + k[q] + 1);
@@ -1757,20 +1713,15 @@ int near_plain(pss_reader *r, const char *who, const uint8_t *qbytes, const uint
     // (the pieces of a pattern partition it, so back to back they are the patterns' bytes again)
     b.vbytes.assign(qbytes, qbytes + (nq ? qoffsets[nq] : 0));
     b.vbytes.push_back(0);                   // (data() of an empty vector may be null)
-    b.poff.push_back(0);
-    b.one_each.resize((size_t)nq + 1);
-    for (uint64_t g = 0; g <= nq; ++g) b.one_each[g] = g;
-    b.no_exclude.assign((size_t)nq + 1, 0);
+    b.pos.push_back(0);
+    b.one_term_each(nq);
     static const uint8_t no_budget = 0;
     static const uint64_t no_offset = 0;
-    SearchRequest rq{b.vbytes.data(), b.voff.data(), (uint32_t)npieces, mode, nullptr, b.one_each.data(), nq, b.no_exclude.data()};
-    rq.fold_bytes = b.vbytes.data();
-    rq.fold_offsets = nq ? qoffsets : &no_offset;
-    rq.spell_offsets = b.soff.data();
-    rq.nterms = nq;
+    SearchRequest rq = b.request(nq, b.one_each.data(), nq, b.no_exclude.data(), nullptr, mode);
+    rq.term_bytes = b.vbytes.data();
+    rq.term_offsets = nq ? qoffsets : &no_offset;
     rq.near_budget = nq ? k : &no_budget;
-    rq.piece_offsets = b.poff.data();
-    return icase_answer(r, rq, out, counts);
+    return answer_by_mode(r, rq, out, counts);
 }
 
 }  // namespace

@@ -1,7 +1,7 @@
 // entry_scan_impl.h -- the one scan of a stretch of an entry for a pattern, by TG lanes together: what the verify kernels
-// of all_terms_impl.h and sequence_impl.h and the dedupe kernel of fold_impl.h are built on.
+// of all_terms_impl.h and sequence_impl.h and the dedupe of seed_impl.h under fold are built on.
 // Part of search.hip: included there behind the entry helpers (cmp_suffix, load_text8, zero_bytes) and in front of the
-// three files above; not a header for anybody else.
+// files above; not a header for anybody else.
 
 constexpr u32 TG = 8;                            // lanes per candidate entry: 64 bytes per step
 constexpr u32 kNone = 0xffffffffu;               // entry_scan: no occurrence

@@ -92,23 +92,22 @@ struct SearchRequest {
     // its segments left to right without overlap, the first at the entry's start and / or the last at its end when anchored.
     // exclude is then unused and may be null.  Everything else as for an all-terms batch.
     const uint8_t *seq_anchors = nullptr;
-    // fold_seed (nterms values), fold_bytes and fold_offsets (nterms + 1) and spell_offsets (nterms + 1 entries into the nq
-    // patterns), together with group_offsets: the case-insensitive search of fold_impl.h -- an all-terms batch
-    // (exclude) or a sequence batch (seq_anchors) under fold; a plain pattern is a group of one include term.  The rows are the
-    // ngroups groups, group_offsets index the nterms TERMS, exclude has nterms flags, fold_bytes holds the terms folded to lower
-    // case, back to back, fold_seed[t] is the offset of term t's seed inside it, and the nq patterns are the spellings of the
-    // terms' seeds: term t's are spell_offsets[t] .. spell_offsets[t + 1], in ascending byte order.  Modes FULL, COUNTS and
-    // IDS; not with anchors; always the general pipeline.
-    const uint32_t *fold_seed = nullptr; const uint8_t *fold_bytes = nullptr; const uint64_t *fold_offsets = nullptr;
-    const uint64_t *spell_offsets = nullptr; uint32_t nterms = 0;
-    // near_budget (nterms bytes, 0 .. 3) and piece_offsets (nq u32 values), together with group_offsets, exclude, fold_bytes,
-    // fold_offsets and spell_offsets and WITHOUT fold_seed: the search within k mismatches of near_impl.h.  The
-    // rows are the ngroups = nterms patterns, each a group of one include term (identity group_offsets, zero exclude flags);
-    // fold_bytes holds the patterns themselves -- exact bytes, nothing is folded --, near_budget[t] is pattern t's budget k, and
-    // the nq queries are the patterns' PIECES: pattern t's k + 1 are spell_offsets[t] .. spell_offsets[t + 1], left to right,
-    // piece v at piece_offsets[v] inside its pattern (what fold_seed is per term, per piece).  Modes FULL, COUNTS and IDS; not
-    // with anchors, seq_anchors or low_latency; always the general pipeline, and sa_order has no say.
-    const uint8_t *near_budget = nullptr; const uint32_t *piece_offsets = nullptr;
+    // seed_offsets (nterms + 1 entries into the nq patterns), seed_pos (nq values), term_bytes and term_offsets (nterms + 1),
+    // together with group_offsets: a SEEDED batch (seed_impl.h).  The rows are the ngroups groups, group_offsets
+    // index the nterms TERMS -- whole patterns, term_bytes back to back, as they are verified --, exclude has nterms flags, and
+    // the nq patterns are the terms' exact SEED QUERIES: term t's are seed_offsets[t] .. seed_offsets[t + 1], query v at
+    // seed_pos[v] inside its term.  Modes FULL, COUNTS and IDS; not with anchors or low_latency; always the general pipeline,
+    // and sa_order has no say.
+    //   near_budget null: the case-insensitive search of fold_impl.h -- an all-terms batch (exclude) or a
+    //   sequence batch (seq_anchors) under fold; a plain pattern is a group of one include term.  term_bytes holds the terms
+    //   folded to lower case, and a term's queries are the spellings of its seed, in ascending byte order, all at the seed's
+    //   offset.
+    //   near_budget (nterms bytes, 0 .. 3): the search within k mismatches of near_impl.h.  The groups are
+    //   the ngroups = nterms patterns, one include term each (identity group_offsets, zero exclude flags, no seq_anchors);
+    //   term_bytes holds the patterns themselves -- exact bytes, nothing is folded --, near_budget[t] is pattern t's budget k,
+    //   and its queries are its k + 1 pieces, left to right.
+    const uint8_t *term_bytes = nullptr; const uint64_t *term_offsets = nullptr; uint32_t nterms = 0;
+    const uint64_t *seed_offsets = nullptr; const uint32_t *seed_pos = nullptr; const uint8_t *near_budget = nullptr;
     uint32_t rows() const { return group_offsets ? ngroups : nq; }     // rows of the result: queries, or groups of terms
     bool low_latency = false;            // one query through the resident kernel when it fits (an unanchored SEARCH_FULL batch only)
     // sa_order: the entries of one (query, chunk) pair come out in the reference's order -- suffix-array order of the FIRST hit

@@ -22,6 +22,9 @@
 //   K3 emit              copies entry bytes into the packed result
 //   K3' emit_ids         ids mode: one u64 entry id per kept hit instead of the copy
 //                        (rank over the chunk's line index, line_index_impl.h)
+// The entry-level kinds put their own kernels in K2's place (the *_impl.h files included below): anchored_impl.h,
+// all_terms_impl.h, sequence_impl.h, and seed_impl.h -- the one seeded verify path of the case-insensitive search
+// (fold_impl.h) and the search within k mismatches (near_impl.h), which differ in their compare alone.
 //
 // Output order: query-major, inside a query chunk-major, inside a chunk
 // suffix-array order of the kept hit (the reference's inter-chunk order is
@@ -1740,6 +1743,7 @@ static void newline_flags(const u8 *bytes, const u64 *off, u32 n, u8 set, u8 *fl
 #include "entry_scan_impl.h"
 #include "all_terms_impl.h"
 #include "sequence_impl.h"
+#include "seed_impl.h"
 #include "fold_impl.h"
 #include "near_impl.h"
 
@@ -1759,8 +1763,8 @@ __global__ __launch_bounds__(256) void chunk_hits_kernel(const u32 *cnt, u64 nq,
 
 // ---- host driver of one batch -------------------------------------------------------------------------------------
 // search_batch_device reads top to bottom: empty batch -> stage_queries -> run_fused? -> launch_interval -> run_mid? ->
-// pick_drivers (an all-terms or a sequence batch) | fold_drivers (a case-insensitive batch) | near_drivers (a batch within k
-// mismatches) -> run_general -> finish.
+// pick_drivers (an all-terms or a sequence batch) | seed_drivers (a seeded batch: case-insensitive, or within k mismatches)
+// -> run_general -> finish.
 // The stages share one Batch: the request normalised into the few booleans they read, the
 // workspace every route needs, the timing events and the two outputs.
 namespace {
@@ -1785,9 +1789,9 @@ struct Batch {
     // the request, normalised once: nothing below asks for a mode again
     bool counts, device, ids, anchored, terms, sa_order;
     bool seq;                           // terms, and the groups are ordered sequences (sequence_impl.h)
-    bool fold;                          // terms under ASCII case folding: group -> terms -> spellings (fold_impl.h)
-    bool near;                          // patterns within k mismatches: pattern -> pattern -> pieces (near_impl.h)
-    const u32 nterm;                    // terms of such a batch, case-insensitive or near (else 0) ...
+    bool seeded;                        // terms looked up through seed queries: group -> terms -> queries (seed_impl.h)
+    bool near;                          // ... within k mismatches (near_impl.h); else under fold (fold_impl.h, 4.14)
+    const u32 nterm;                    // terms of a seeded batch (else 0) ...
     const u64 ntp;                      // ... and its (term, chunk) pairs
     bool tiny;                          // queries and offsets fit the 16 KiB of the pinned scratch
     bool fused_ok, resident_ok, mid_ok; // routes this batch may take (each may still overflow into the next)
@@ -1798,7 +1802,7 @@ struct Batch {
     std::vector<u8> own_q;              // an anchored batch too large for the staging
     std::vector<u64> own_off;
     std::vector<u8> own_tflags;         // per-term flags of an all-terms batch
-    std::vector<u8> own_fvoid;          // a case-insensitive batch: the void flags alone (what the union reads)
+    std::vector<u8> own_fvoid;          // a seeded batch: the void flags alone (what the union reads)
     // workspace of every route
     u8 *d_q = nullptr, *d_aflags = nullptr, *d_edge = nullptr;
     u64 *d_qoff = nullptr, *d_hitoff = nullptr, *d_partial = nullptr, *d_total = nullptr, *d_qcount = nullptr, *h_small = nullptr;
@@ -1807,13 +1811,11 @@ struct Batch {
     u64 *d_goff = nullptr;                          // all-terms batch: group offsets, term flags, driver term per group pair
     u8 *d_tflags = nullptr, *d_sanch = nullptr;       // (d_sanch: a sequence batch's anchor byte per group)
     u32 *d_gdrv = nullptr;
-    u8 *d_fbytes = nullptr, *d_fvoid = nullptr;     // a case-insensitive batch: the folded terms, their offsets and seed
-    u64 *d_foff = nullptr;                          // offsets, a void flag per term, the match start of every hit,
-    u32 *d_fseed = nullptr, *d_m = nullptr;
-    u64 *d_soff = nullptr;                          // spelling offsets per term, seed hits per (term, chunk) pair
-    u32 *d_tcnt = nullptr;
-    u8 *d_nk = nullptr;                             // a near batch: the budget per pattern, the offset of every piece in its
-    u32 *d_poff = nullptr;                          // pattern, and the flag of a pair whose pieces' hits pass 2^32 - 1
+    u8 *d_fbytes = nullptr, *d_fvoid = nullptr;     // a seeded batch: the terms as they are verified, their offsets, a void flag
+    u64 *d_foff = nullptr, *d_soff = nullptr;       // per term, the queries' offsets per term and positions per query, the seed
+    u32 *d_pos = nullptr, *d_tcnt = nullptr;        // hits per (term, chunk) pair, the match start of every hit; a near batch:
+    u32 *d_m = nullptr;                             // the budget per pattern and the flag of a pair whose pieces' hits pass
+    u8 *d_nk = nullptr;                             // 2^32 - 1 (both null under fold)
     u64 *d_over = nullptr;
     // ... and of the mid and the general pipeline, sized by each: entry bounds per hit, the scans over them, the result
     u32 *d_start = nullptr, *d_len = nullptr;
@@ -1826,8 +1828,8 @@ struct Batch {
     Batch(DeviceCtx *c, const ChunkDesc *chunks, const LineDesc *lines, u32 nchunks, const SearchRequest &r, HostResult *out,
           pss_search_stats *stats)
         : ctx(c), s(c->stream), d_chunks(chunks), d_lines(lines), rq(r), res(out), st(stats), knobs(search_knobs()), nq(r.nq),
-          nc(nchunks), nvq((u64)r.nq * nchunks), nrow(r.rows()), nrp((u64)r.rows() * nchunks), nterm(r.spell_offsets ? r.nterms : 0u),
-          ntp((u64)(r.spell_offsets ? r.nterms : 0u) * nchunks), e0(c->search_ev[0]), e1(c->search_ev[1]), e2(c->search_ev[2])
+          nc(nchunks), nvq((u64)r.nq * nchunks), nrow(r.rows()), nrp((u64)r.rows() * nchunks), nterm(r.seed_offsets ? r.nterms : 0u),
+          ntp((u64)(r.seed_offsets ? r.nterms : 0u) * nchunks), e0(c->search_ev[0]), e1(c->search_ev[1]), e2(c->search_ev[2])
     {
         counts = rq.mode == SEARCH_COUNTS;
         device = rq.mode == SEARCH_DEVICE;
@@ -1835,8 +1837,8 @@ struct Batch {
         anchored = rq.anchors != nullptr;
         terms = rq.group_offsets != nullptr;
         seq = terms && rq.seq_anchors != nullptr;
-        fold = terms && rq.fold_seed != nullptr;
-        near = terms && rq.near_budget != nullptr;
+        seeded = terms && rq.seed_offsets != nullptr;
+        near = seeded && rq.near_budget != nullptr;
         // (counts do not depend on the order; one hit per entry has one order; an all-terms batch keeps its driver's text order)
         sa_order = rq.sa_order && !counts && !anchored && !terms;
         // (an anchored batch searches its rewritten queries: a newline in front of and / or behind every pattern)
@@ -1856,7 +1858,7 @@ struct Batch {
         p = ctx->slot[which].as<T>();
         return PSS_OK;
     }
-    int stage_queries(), run_fused(bool *served), launch_interval(), run_mid(bool *done), pick_drivers(), fold_drivers(), near_drivers(), run_general(), finish();
+    int stage_queries(), run_fused(bool *served), launch_interval(), run_mid(bool *done), pick_drivers(), seed_drivers(), run_general(), finish();
     int sa_order_hits(u32 grid, u64 H);
     int download_result(u64 E, u64 B, const u64 *d_starts, const u8 *d_bytes, bool via_stage);
     void leave_on_device(const u64 *d_starts, const u8 *d_bytes), set_totals(u64 hits, u64 kept, u64 E, u64 B);
@@ -1932,12 +1934,11 @@ int Batch::stage_queries()
     h_off = hq ? ho : rq.qoffsets;
     h_flags = hf;
     h_padded = hq != nullptr;
-    if (terms) {                        // (per TERM; under fold from the folded terms: folding leaves a 0x0A alone; a near batch
-        const bool whole = fold || near;    // from its patterns, not from their pieces)
-        const u32 nt = whole ? nterm : nq;
+    if (terms) {                        // (per TERM; a seeded batch from its terms, not from their queries: folding leaves a 0x0A alone)
+        const u32 nt = seeded ? nterm : nq;
         own_tflags.resize(nt);
-        newline_flags(whole ? rq.fold_bytes : rq.qbytes, whole ? rq.fold_offsets : rq.qoffsets, nt, kTermVoid, own_tflags.data());
-        if (whole) own_fvoid = own_tflags;
+        newline_flags(seeded ? rq.term_bytes : rq.qbytes, seeded ? rq.term_offsets : rq.qoffsets, nt, kTermVoid, own_tflags.data());
+        if (seeded) own_fvoid = own_tflags;
         for (u32 t = 0; !seq && t < nt; ++t)                        // (no segment of a sequence batch excludes)
             if (rq.exclude[t]) own_tflags[t] |= kTermExclude;
     }
@@ -2187,83 +2188,54 @@ int Batch::pick_drivers()
     return PSS_OK;
 }
 
-// Case-insensitive batch: from the (spelling, chunk) pairs over the (term, chunk) pairs to the (group, chunk) pairs.
-// The folded terms go up beside the spellings, per term -- spelling offsets, folded bytes (32 zero bytes behind them, as
-// behind the staged terms), their offsets, seed offsets, void flags -- and with them what pick_drivers sends up: group
-// offsets, term flags, anchor bytes.  fold_union_kernel leaves every term's seed hits per chunk in d_tcnt;
+// Seeded batch: from the (query, chunk) pairs over the (term, chunk) pairs to the (group, chunk) pairs.  The terms go up
+// beside their seed queries -- the queries' offsets per term, the terms' bytes (32 zero bytes behind them, as behind the
+// staged queries) and offsets, every query's position inside its term, void flags -- and with them what pick_drivers sends
+// up: group offsets, term flags, anchor bytes.  The anchor bytes have room in a sequence batch alone; the budgets and the
+// overflow flag in a near batch alone.  seed_union_kernel leaves every term's seed hits per chunk in d_tcnt;
 // terms_driver_kernel picks the include term with the fewest of them as the pair's driver.  Neither a term nor a pair has
-// an interval of its own (p_lo is not read).
-int Batch::fold_drivers()
+// an interval of its own (p_lo is not read).  A near pair past 2^32 - 1 hits raises d_over, whose copy run_general reads
+// with the hit total, before any hit buffer is reserved; a fold batch passes no flag (disjoint intervals: the sum is at
+// most n) and so neither clears nor fetches one.
+int Batch::seed_drivers()
 {
-    const u64 ftotal = rq.fold_offsets[nterm];
+    const u64 ttotal = rq.term_offsets[nterm];
     const size_t goff_room = round_up(((size_t)nrow + 1) * 8, 64), toff_room = round_up(((size_t)nterm + 1) * 8, 64);
-    const size_t seed_room = round_up((size_t)nterm * 4, 64), flag_room = round_up((size_t)nterm, 64);
-    const size_t anch_room = seq ? round_up((size_t)nrow, 64) : 0, byte_room = round_up(ftotal + 32, 64);
-    const size_t tcnt_room = round_up((size_t)ntp * 4, 64);
-    PSS_TRY(take(Q_TERMS, goff_room + 2 * toff_room + seed_room + 2 * flag_room + anch_room + byte_room + tcnt_room + nrp * 8, d_goff));
+    const size_t over_room = near ? 64 : 0, pos_room = round_up((size_t)nq * 4, 64), flag_room = round_up((size_t)nterm, 64);
+    const size_t budget_room = near ? flag_room : 0, anch_room = seq ? round_up((size_t)nrow, 64) : 0;
+    const size_t byte_room = round_up(ttotal + 32, 64), tcnt_room = round_up((size_t)ntp * 4, 64);
+    PSS_TRY(take(Q_TERMS, goff_room + 2 * toff_room + over_room + pos_room + 2 * flag_room + budget_room + anch_room + byte_room +
+                              tcnt_room + nrp * 8, d_goff));
     d_soff = d_goff + goff_room / 8;
     d_foff = d_soff + toff_room / 8;
-    d_fseed = reinterpret_cast<u32 *>(d_foff + toff_room / 8);
-    d_fvoid = reinterpret_cast<u8 *>(d_fseed) + seed_room;
-    d_tflags = d_fvoid + flag_room;
-    d_sanch = d_tflags + flag_room;
-    d_fbytes = d_sanch + anch_room;
-    d_tcnt = reinterpret_cast<u32 *>(d_fbytes + byte_room);
-    d_gdrv = reinterpret_cast<u32 *>(reinterpret_cast<u8 *>(d_tcnt) + tcnt_room);
+    u8 *p = reinterpret_cast<u8 *>(d_foff + toff_room / 8);
+    d_over = near ? reinterpret_cast<u64 *>(p) : nullptr;
+    d_pos = reinterpret_cast<u32 *>(p += over_room);
+    d_fvoid = (p += pos_room);
+    d_tflags = (p += flag_room);
+    d_nk = near ? p + flag_room : nullptr;
+    d_sanch = (p += flag_room + budget_room);
+    d_fbytes = (p += anch_room);
+    d_tcnt = reinterpret_cast<u32 *>(p += byte_room);
+    d_gdrv = reinterpret_cast<u32 *>(p + tcnt_room);
     p_cnt = d_gdrv + nrp;
     PSS_HIP(hipMemcpyAsync(d_goff, rq.group_offsets, ((size_t)nrow + 1) * 8, hipMemcpyHostToDevice, s));
-    PSS_HIP(hipMemcpyAsync(d_soff, rq.spell_offsets, ((size_t)nterm + 1) * 8, hipMemcpyHostToDevice, s));
-    PSS_HIP(hipMemcpyAsync(d_foff, rq.fold_offsets, ((size_t)nterm + 1) * 8, hipMemcpyHostToDevice, s));
-    PSS_HIP(hipMemcpyAsync(d_fseed, rq.fold_seed, (size_t)nterm * 4, hipMemcpyHostToDevice, s));
+    PSS_HIP(hipMemcpyAsync(d_soff, rq.seed_offsets, ((size_t)nterm + 1) * 8, hipMemcpyHostToDevice, s));
+    PSS_HIP(hipMemcpyAsync(d_foff, rq.term_offsets, ((size_t)nterm + 1) * 8, hipMemcpyHostToDevice, s));
+    PSS_HIP(hipMemcpyAsync(d_pos, rq.seed_pos, (size_t)nq * 4, hipMemcpyHostToDevice, s));
     PSS_HIP(hipMemcpyAsync(d_fvoid, own_fvoid.data(), nterm, hipMemcpyHostToDevice, s));
     PSS_HIP(hipMemcpyAsync(d_tflags, own_tflags.data(), nterm, hipMemcpyHostToDevice, s));
     if (seq) PSS_HIP(hipMemcpyAsync(d_sanch, rq.seq_anchors, nrow, hipMemcpyHostToDevice, s));
-    PSS_HIP(hipMemsetAsync(d_fbytes + ftotal, 0, 32, s));
-    PSS_HIP(hipMemcpyAsync(d_fbytes, rq.fold_bytes, ftotal, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(fold_union_kernel, dim3((u32)((ntp + 255) / 256)), dim3(256), 0, s, nc, d_soff, d_fvoid, d_cnt, ntp, d_tcnt);
+    if (near) {
+        PSS_HIP(hipMemcpyAsync(d_nk, rq.near_budget, nterm, hipMemcpyHostToDevice, s));
+        PSS_HIP(hipMemsetAsync(d_over, 0, 8, s));
+    }
+    PSS_HIP(hipMemsetAsync(d_fbytes + ttotal, 0, 32, s));
+    PSS_HIP(hipMemcpyAsync(d_fbytes, rq.term_bytes, ttotal, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(seed_union_kernel, dim3((u32)((ntp + 255) / 256)), dim3(256), 0, s, nc, d_soff, d_fvoid, d_cnt, ntp, d_tcnt, d_over);
     hipLaunchKernelGGL(terms_driver_kernel<false>, dim3((u32)((nrp + 255) / 256)), dim3(256), 0, s, nc, d_goff, d_tflags,
                        (const u32 *)nullptr, d_tcnt, nrp, d_gdrv, (u32 *)nullptr, p_cnt);
-    return PSS_OK;
-}
-
-// Batch within k mismatches: from the (piece, chunk) pairs over the (pattern, chunk) pairs to themselves as (group, chunk)
-// pairs -- fold_drivers with other uploads.  The patterns go up beside their pieces -- piece offsets into the queries
-// (spell_offsets), the patterns' exact bytes (32 zero bytes behind them), their offsets, void flags, budgets, and every
-// piece's offset inside its pattern -- and with them the identity group offsets and the term flags.  near_union_kernel
-// leaves every pattern's piece hits per chunk in d_tcnt, added up in 64 bits; a pair past 2^32 - 1 raises d_over, whose copy
-// run_general reads with the hit total, before any hit buffer is reserved.  terms_driver_kernel picks every pair's one term.
-int Batch::near_drivers()
-{
-    const u64 ftotal = rq.fold_offsets[nterm];
-    const size_t goff_room = round_up(((size_t)nrow + 1) * 8, 64), toff_room = round_up(((size_t)nterm + 1) * 8, 64);
-    const size_t poff_room = round_up((size_t)nq * 4, 64), flag_room = round_up((size_t)nterm, 64);
-    const size_t byte_room = round_up(ftotal + 32, 64), tcnt_room = round_up((size_t)ntp * 4, 64);
-    PSS_TRY(take(Q_TERMS, goff_room + 2 * toff_room + 64 + poff_room + 3 * flag_room + byte_room + tcnt_room + nrp * 8, d_goff));
-    d_soff = d_goff + goff_room / 8;
-    d_foff = d_soff + toff_room / 8;
-    d_over = d_foff + toff_room / 8;
-    d_poff = reinterpret_cast<u32 *>(d_over + 8);
-    d_fvoid = reinterpret_cast<u8 *>(d_poff) + poff_room;
-    d_tflags = d_fvoid + flag_room;
-    d_nk = d_tflags + flag_room;
-    d_fbytes = d_nk + flag_room;
-    d_tcnt = reinterpret_cast<u32 *>(d_fbytes + byte_room);
-    d_gdrv = reinterpret_cast<u32 *>(reinterpret_cast<u8 *>(d_tcnt) + tcnt_room);
-    p_cnt = d_gdrv + nrp;
-    PSS_HIP(hipMemcpyAsync(d_goff, rq.group_offsets, ((size_t)nrow + 1) * 8, hipMemcpyHostToDevice, s));
-    PSS_HIP(hipMemcpyAsync(d_soff, rq.spell_offsets, ((size_t)nterm + 1) * 8, hipMemcpyHostToDevice, s));
-    PSS_HIP(hipMemcpyAsync(d_foff, rq.fold_offsets, ((size_t)nterm + 1) * 8, hipMemcpyHostToDevice, s));
-    PSS_HIP(hipMemcpyAsync(d_poff, rq.piece_offsets, (size_t)nq * 4, hipMemcpyHostToDevice, s));
-    PSS_HIP(hipMemcpyAsync(d_fvoid, own_fvoid.data(), nterm, hipMemcpyHostToDevice, s));
-    PSS_HIP(hipMemcpyAsync(d_tflags, own_tflags.data(), nterm, hipMemcpyHostToDevice, s));
-    PSS_HIP(hipMemcpyAsync(d_nk, rq.near_budget, nterm, hipMemcpyHostToDevice, s));
-    PSS_HIP(hipMemsetAsync(d_over, 0, 8, s));
-    PSS_HIP(hipMemsetAsync(d_fbytes + ftotal, 0, 32, s));
-    PSS_HIP(hipMemcpyAsync(d_fbytes, rq.fold_bytes, ftotal, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(near_union_kernel, dim3((u32)((ntp + 255) / 256)), dim3(256), 0, s, nc, d_soff, d_fvoid, d_cnt, ntp, d_tcnt, d_over);
-    hipLaunchKernelGGL(terms_driver_kernel<false>, dim3((u32)((nrp + 255) / 256)), dim3(256), 0, s, nc, d_goff, d_tflags,
-                       (const u32 *)nullptr, d_tcnt, nrp, d_gdrv, (u32 *)nullptr, p_cnt);
-    PSS_HIP(hipMemcpyAsync(h_small + 2, d_over, 8, hipMemcpyDeviceToHost, s));
+    if (near) PSS_HIP(hipMemcpyAsync(h_small + 2, d_over, 8, hipMemcpyDeviceToHost, s));
     return PSS_OK;
 }
 
@@ -2277,7 +2249,8 @@ int Batch::run_general()
     PSS_HIP(hipMemcpyAsync(h_small, d_total, 8, hipMemcpyDeviceToHost, s));
     PSS_HIP(hipStreamSynchronize(s));
     const u64 H = h_small[0];
-    if (near && h_small[2]) {   // (near_union_kernel: the one place a pair's 64-bit sum is judged; nothing is reserved yet)
+    if (near && h_small[2]) {   // (seed_union_kernel's flag: the one place a pair's 64-bit sum is judged, out of a test's reach and
+                                // checked by reading; nothing is reserved yet)
         set_error("search: the pieces of one pattern have more than 2^32 - 1 hits in one chunk: more than a batch within k mismatches takes");
         return PSS_EINVAL;
     }
@@ -2303,31 +2276,25 @@ int Batch::run_general()
     else if (anchored)
         hipLaunchKernelGGL(anchored_hits_kernel, dim3(grid), dim3(256), 0, s, d_chunks, nc, d_aflags, nrp, p_lo, d_edge,
                            d_hitoff, H, d_start, d_len);
-    else if (fold) {
-        // every hit of every spelling against the whole pattern under fold; then the survivors against the entry in front of them
-        PSS_TRY(take(Q_ORD_V0, H * 4, d_m));        // (the slot of the suffix-array order's values: that order is never a fold batch's)
+    else if (seeded) {
+        // every hit of every seed query against the whole driver term at its match start (under fold, or within the budget inside
+        // its entry and as its alignment's first exact piece); then the survivors against the entry in front of them: one
+        // candidate per entry, its leftmost match
+        PSS_TRY(take(Q_ORD_V0, H * 4, d_m));        // (the slot of the suffix-array order's values: that order is never a seeded batch's)
         const u32 vgrid = (u32)std::min<u64>((u64)ctx->num_cus * 16, (H * TG + 255) / 256);
-        // (the two steps for each pair's driver term -- one candidate per entry that holds it under fold -- then every
-        // candidate against the group's other terms, or its segments in order, under fold)
-        hipLaunchKernelGGL(fold_hits_kernel, dim3(grid), dim3(256), 0, s, d_chunks, nc, d_fbytes, d_foff, d_fseed, d_soff, d_lo, d_cnt,
-                           nrp, d_hitoff, H, d_start, d_len, d_m, d_gdrv);
-        hipLaunchKernelGGL(fold_dedupe_kernel, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, d_fbytes, d_foff, nrp, d_hitoff, H, d_start,
-                           d_m, d_len, d_gdrv);
+        const SeedTerms T{d_fbytes, d_foff, d_soff, d_pos, d_nk};
+        auto *hits = near ? seed_hits_kernel<NearMatch> : seed_hits_kernel<FoldMatch>;
+        auto *dedupe = near ? seed_dedupe_kernel<NearMatch> : seed_dedupe_kernel<FoldMatch>;
+        hipLaunchKernelGGL(hits, dim3(grid), dim3(256), 0, s, d_chunks, nc, T, d_lo, d_cnt, nrp, d_hitoff, H, d_start, d_len, d_m, d_gdrv);
+        hipLaunchKernelGGL(dedupe, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, T, nrp, d_hitoff, H, d_start, d_m, d_len, d_gdrv);
+        // (every candidate against the group's other terms, or its segments in order: under fold alone -- a near batch is no
+        // sequence and has one term per group)
         if (seq)
             hipLaunchKernelGGL(seq_verify_kernel<true>, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, d_fbytes, d_foff, d_goff, d_sanch,
                                nrp, d_hitoff, H, d_start, d_len);
         else if (nterm != nrow)     // (every group has an include term: as many terms as groups are one per group, and no other to look for)
             hipLaunchKernelGGL(terms_verify_kernel<true>, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, d_fbytes, d_foff, d_goff,
                                d_tflags, d_tcnt, d_gdrv, nrp, d_hitoff, H, d_start, d_len);
-    } else if (near) {
-        // every hit of every piece against the whole pattern inside its entry, kept as its alignment's first exact piece; then
-        // the survivors against the entry in front of them: the leftmost window within budget stands for the entry
-        PSS_TRY(take(Q_ORD_V0, H * 4, d_m));        // (as for a fold batch: the suffix-array order is never a near batch's)
-        const u32 vgrid = (u32)std::min<u64>((u64)ctx->num_cus * 16, (H * TG + 255) / 256);
-        hipLaunchKernelGGL(near_hits_kernel, dim3(grid), dim3(256), 0, s, d_chunks, nc, d_fbytes, d_foff, d_nk, d_poff, d_soff, d_lo, d_cnt,
-                           nrp, d_hitoff, H, d_start, d_len, d_m, d_gdrv);
-        hipLaunchKernelGGL(near_dedupe_kernel, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, d_fbytes, d_foff, d_nk, nrp, d_hitoff, H, d_start,
-                           d_m, d_len, d_gdrv);
     } else if (terms) {
         // candidates: the entries that hold the pair's driver term; then every candidate against the group's other terms
         hipLaunchKernelGGL(hit_lines_kernel<true>, dim3(grid), dim3(256), 0, s, d_chunks, nc, d_q, d_qoff, nrp, p_lo, d_hitoff, H,
@@ -2418,22 +2385,22 @@ int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, const LineDes
         set_error("search: an all-terms batch takes the general pipeline to a host result, and its terms are not anchored");
         return PSS_EINVAL;
     }
-    if (rq.near_budget || rq.piece_offsets) {
-        bool ok = rq.near_budget && rq.piece_offsets && !rq.fold_seed && !rq.anchors && !rq.seq_anchors && rq.mode != SEARCH_DEVICE &&
-                  !rq.low_latency && rq.spell_offsets && rq.group_offsets && rq.fold_bytes && rq.fold_offsets && rq.exclude &&
-                  rq.ngroups == rq.nterms;
-        for (u32 g = 0; ok && g < rq.ngroups; ++g) ok = rq.group_offsets[g] == g && rq.group_offsets[g + 1] == (u64)g + 1;
+    if (rq.seed_offsets || rq.seed_pos || rq.near_budget) {
+        // a seeded batch carries its groups, its terms and the queries' offsets and positions, and either exclude flags or
+        // sequence anchors; it excludes anchors, SEARCH_DEVICE and low_latency; a budget adds: identity groups of one include
+        // term each, no sequence anchors
+        bool ok = rq.seed_offsets && rq.seed_pos && rq.group_offsets && rq.term_bytes && rq.term_offsets &&
+                  (!rq.nterms || rq.exclude || rq.seq_anchors) && !rq.anchors && rq.mode != SEARCH_DEVICE && !rq.low_latency;
+        if (rq.near_budget) {
+            ok = ok && !rq.seq_anchors && rq.exclude && rq.ngroups == rq.nterms;
+            for (u32 g = 0; ok && g < rq.ngroups; ++g) ok = rq.group_offsets[g] == g && rq.group_offsets[g + 1] == (u64)g + 1;
+        }
         if (!ok) {
-            set_error("search: a batch within k mismatches states its patterns as groups of one term each, with exclude flags, the "
-                      "patterns' bytes and offsets, piece offsets and budgets, and takes the general pipeline to a host result: no "
-                      "seeds, no anchors, no sequence anchors");
+            set_error("search: a seeded batch states its groups, its terms' bytes and offsets, the seed queries' offsets and positions, "
+                      "and either exclude flags or sequence anchors; with budgets its groups are one include term each and it has no "
+                      "sequence anchors");
             return PSS_EINVAL;
         }
-    } else if ((rq.fold_seed || rq.spell_offsets) &&
-        !(rq.fold_seed && rq.spell_offsets && rq.group_offsets && rq.fold_bytes && rq.fold_offsets && (!rq.nterms || rq.exclude || rq.seq_anchors))) {
-        set_error("search: a case-insensitive batch states its groups, its terms' seeds, folded bytes and spelling offsets, and either "
-                  "exclude flags or sequence anchors");
-        return PSS_EINVAL;
     }
     const u32 rows = rq.rows();
     memset(st, 0, sizeof *st);
@@ -2459,10 +2426,8 @@ int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, const LineDes
         PSS_TRY(b.run_mid(&done));
         if (done) return b.finish();
     }
-    if (b.fold) {
-        PSS_TRY(b.fold_drivers());
-    } else if (b.near) {
-        PSS_TRY(b.near_drivers());
+    if (b.seeded) {
+        PSS_TRY(b.seed_drivers());
     } else if (b.terms) {
         PSS_TRY(b.pick_drivers());
     }
