@@ -704,7 +704,7 @@ int pss_reader_count_seq_icase_batch(pss_reader *r, const uint8_t *sbytes, const
  * bit of its own.  The id variant builds the line tables on first use, the other two allocate nothing for them.
  * The limit: the candidates follow the occurrences of the PIECES -- a short pattern at k = 3 has pieces of a byte or two, and
  * every occurrence of such a piece is verified.
- * Out of scope: insertions and deletions; k > 3; mismatches under ASCII case folding, inside all-terms groups or wildcard
+ * Out of scope: insertions and deletions (the search within k edits below has them); k > 3; mismatches under ASCII case folding, inside all-terms groups or wildcard
  * patterns; the fused, mid, resident and device-resident paths (a near batch always takes the general pipeline); the
  * multi-process gather over RCCL (dist.ShardedReader); choosing pieces by rarity; a piece driving only where it is present.
  */
@@ -721,6 +721,51 @@ int pss_reader_count_near_batch(pss_reader *r, const uint8_t *qbytes, const uint
  * pieces' windows inside the pattern, left to right, *count = k + 1.
  * PSS_EINVAL: an empty pattern, k > 3, len <= k, len > 2^32 - 1, a null offsets / lengths / count. */
 int pss_near_pieces(const uint8_t *pat, uint64_t len, uint32_t k, uint32_t *offsets, uint32_t *lengths, uint32_t *count);
+/*
+ * Search within k edits (no reference counterpart): per pattern, the entries that hold it with at most k bytes INSERTED,
+ * DELETED or SUBSTITUTED -- Levenshtein distance over bytes: `pasword`, `passsword` and `passw0rd` for `password` at k = 1.
+ * Arguments, packing, the ids variant and the count call as for the search within k mismatches above; k is nq budgets, 0 .. 3.
+ * An entry with true bytes e -- text[start, newline), or text[start, n) for an unterminated last entry -- matches pattern p
+ * within k edits iff some substring w of e has lev(w, p) <= k, where an insertion, a deletion and a substitution of a single
+ * BYTE cost 1 each.  w lies inside the entry because e holds no newline: a match never reaches over a newline, even where
+ * "delete the newline" would be one of its edits.  Bytes are exact: nothing folds, and 0x00 and 0x80 .. 0xFF are bytes like
+ * any other.  Every entry at most once per pattern.  A pattern that holds 0x0A matches nothing and no hit is looked at (near's
+ * rule, kept so that the two calls agree).  k = 0 returns exactly what pss_reader_search_ids_batch returns, order included; for
+ * every k the answer contains, as a set, what pss_reader_search_near_ids_batch returns at the same k.
+ * PSS_EINVAL (message in pss_last_error, *out / counts untouched): an empty pattern; a pattern of at most k bytes (deleting all
+ * of it would match every entry); k > 3; and every malformed batch the near calls name, with or without a reader (the reader is
+ * judged last).
+ * The search: near's pieces (pss_near_pieces serves both kinds), the same seed queries at the same positions.  k edits cannot
+ * touch all k + 1 pieces, so every w within budget holds some piece j exactly -- but, unlike under mismatches, not at a known
+ * offset inside w.  A CANDIDATE is (piece j, exact occurrence at text offset d); with off_j / len_j the piece's window in p it
+ * STANDS iff lc + rc <= k, where
+ *   lc = the least lev(text[a, d), p[0, off_j)) over a in [entry start, d] and
+ *   rc = the least lev(text[d + len_j, b), p[off_j + len_j, L)) over b in [d + len_j, entry end];
+ * the two sides are independent, the left computed within k and the right within k - lc, each as a banded DP of at most 7 cells a
+ * row that stops at a newline, at 0 and at n.  An entry matches iff one of its candidates stands.  The ONE hit kept per entry is
+ * the standing candidate with the smallest d and, among equal d (two pieces are exact at one d only when one is a prefix of the
+ * other, as `aab` + `aa`), the smallest j: a hit is dropped when an earlier piece stands at its d, and the entry in front of d is
+ * scanned for a standing candidate.
+ * Order: pattern-major, chunk-major inside a pattern; inside one (pattern, chunk) pair by the piece index j of each entry's kept
+ * candidate, and inside one piece by the suffix-array order of the suffix at d; the same for text and ids --
+ * pss_reader_set_result_order has no effect.  Whole-file, sharded and multi-device readers, and suffix arrays on the host tier,
+ * are served alike.
+ * pss_reader_last_stats: as for the near calls -- hits = the sum over pieces and chunks of the pieces' exact occurrences,
+ * entries = what is returned, route = GENERAL | the interval bits (| COUNTS); no bit of its own.
+ * The limits: near's (every occurrence of every piece is verified), and an entry DENSE with occurrences of a piece: the scan
+ * in front of a hit runs both DPs at every such occurrence, lane by lane.
+ * Out of scope: edits under ASCII case folding, inside all-terms groups or wildcard patterns; k > 3; a transposition as one
+ * edit; the fused, mid, resident and device-resident paths; choosing pieces by rarity.
+ */
+/* packed entry text, one row per pattern; k = nq budgets */
+int pss_reader_search_edit_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, const uint8_t *k,
+                                 pss_result **out);
+/* u64 entry ids, packed as pss_reader_search_ids_batch packs them */
+int pss_reader_search_edit_ids_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, const uint8_t *k,
+                                     pss_result **out);
+/* counts[q] = entries pattern q matches within k[q] edits; nothing but nq counters comes down */
+int pss_reader_count_edit_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, const uint8_t *k,
+                                uint64_t *counts);
 /* For the first `cap` resident chunks, in file order: index in the file and number of entries; *num = resident chunks. */
 int pss_reader_chunk_entries(pss_reader *r, uint64_t *chunk_index, uint64_t *entries, uint64_t cap, uint64_t *num);
 /*

@@ -892,11 +892,13 @@ class Reader:
         return self.count_icase_bytes([_utf8(s, 'substring')])[0]
 
     @staticmethod
-    def _near_args(patterns, k):
-        """(blob, offsets, budgets) of one batch within k mismatches.  ``k`` is an int for the batch or a sequence with one
-        int per pattern; ``ValueError`` for an empty pattern, a budget outside 0 .. 3, a pattern of at most its budget's
-        bytes, or another number of budgets than patterns."""
+    def _near_args(patterns, k, edits=False):
+        """(blob, offsets, budgets) of one batch within k mismatches, or within k edits (``edits``, a bool).  ``k`` is an int
+        for the batch or a sequence with one int per pattern; ``ValueError`` for an empty pattern, a budget outside 0 .. 3,
+        a pattern of at most its budget's bytes, or another number of budgets than patterns."""
         import numpy as np
+        if not isinstance(edits, bool):
+            raise TypeError(f"argument 'edits' must be a bool, not {type(edits).__name__}")
         if isinstance(patterns, (bytes, bytearray, str)):
             raise TypeError(f"argument 'patterns': '{type(patterns).__name__}' object cannot be converted to a sequence of patterns")
         patterns = list(patterns)
@@ -913,40 +915,52 @@ class Reader:
                 raise TypeError(f'pattern {q}: a pattern must be bytes, not {type(pat).__name__}')
             if len(pat) == 0:
                 raise ValueError(f'pattern {q} is empty (every entry contains the empty pattern)')
+            if len(pat) <= b and edits:
+                raise ValueError(f'pattern {q} has {len(pat)} bytes and a budget of {b} edits: deleting all of it matches every entry')
             if len(pat) <= b:
                 raise ValueError(f'pattern {q} has {len(pat)} bytes and a budget of {b} mismatches: every window of its length matches it')
         blob, offs = _pack_queries([bytes(p) for p in patterns])
         return blob, offs, np.array(budgets, dtype=np.uint8)
 
-    def search_near_batch_packed(self, patterns: typing.Sequence[bytes], k=1) -> 'PackedResult':
+    def search_near_batch_packed(self, patterns: typing.Sequence[bytes], k=1, edits: bool = False) -> 'PackedResult':
         """Extension: per pattern, the entries that hold it with at most ``k`` bytes SUBSTITUTED (Hamming distance:
         ``passw0rd`` for ``password`` at ``k=1``), as a packed result like ``search_batch_packed``'s.  ``k`` is 0 .. 3, one
         int for the batch or a sequence with one per pattern.  The window lies inside the entry; bytes are exact (nothing
         folds); every entry at most once per pattern; a pattern holding a newline matches nothing.  ``ValueError`` for an
         empty pattern, ``k > 3`` and a pattern of at most ``k`` bytes.  No insertions or deletions.  The pattern's ``k + 1``
         pieces (``near_pieces``) are looked up and every hit is verified on the device, so the work follows the
-        occurrences of the pieces (include/pss.h, pss_reader_search_near_batch).  ``set_result_order`` has no effect."""
-        blob, offs, ks = self._near_args(patterns, k)
-        return self._query_batch('pss_reader_search_near_batch', (blob, offs), 'packed', ks)
+        occurrences of the pieces (include/pss.h, pss_reader_search_near_batch).  ``set_result_order`` has no effect.
 
-    def search_near_ids_batch(self, patterns: typing.Sequence[bytes], k=1) -> 'IdResult':
+        ``edits=True``: the budget counts EDITS -- bytes inserted, deleted or substituted (Levenshtein distance over bytes:
+        ``pasword``, ``passsword`` and ``passw0rd`` for ``password`` at ``k=1``).  An entry matches iff some substring of it
+        is within ``k`` edits of the pattern; the substring lies inside the entry.  Everything else as above: the same
+        pieces, every occurrence of a piece verified on the device (include/pss.h, pss_reader_search_edit_batch).  The
+        answer contains the answer without ``edits`` at the same ``k``."""
+        blob, offs, ks = self._near_args(patterns, k, edits)
+        return self._query_batch('pss_reader_search_edit_batch' if edits else 'pss_reader_search_near_batch', (blob, offs), 'packed', ks)
+
+    def search_near_ids_batch(self, patterns: typing.Sequence[bytes], k=1, edits: bool = False) -> 'IdResult':
         """Extension: the ids (``search_ids_batch``) of the entries ``search_near_batch_packed`` returns, in the same
-        order; ``counts[q]`` of them belong to pattern q.  ``k=0`` returns exactly what ``search_ids_batch`` returns."""
-        blob, offs, ks = self._near_args(patterns, k)
-        return self._query_batch('pss_reader_search_near_ids_batch', (blob, offs), 'ids', ks)
+        order; ``counts[q]`` of them belong to pattern q.  ``k=0`` returns exactly what ``search_ids_batch`` returns.
+        ``edits=True``: the entries within ``k`` edits instead (``search_near_batch_packed``); ``k=0`` is the same."""
+        blob, offs, ks = self._near_args(patterns, k, edits)
+        return self._query_batch('pss_reader_search_edit_ids_batch' if edits else 'pss_reader_search_near_ids_batch', (blob, offs), 'ids', ks)
 
-    def count_near_bytes(self, patterns: typing.Sequence[bytes], k=1) -> typing.List[int]:
-        """Extension: how many entries hold each pattern within ``k`` mismatches; only the counters come back."""
-        blob, offs, ks = self._near_args(patterns, k)
-        return self._query_batch('pss_reader_count_near_batch', (blob, offs), 'counts', ks)
+    def count_near_bytes(self, patterns: typing.Sequence[bytes], k=1, edits: bool = False) -> typing.List[int]:
+        """Extension: how many entries hold each pattern within ``k`` mismatches (``edits=True``: within ``k`` edits); only
+        the counters come back."""
+        blob, offs, ks = self._near_args(patterns, k, edits)
+        return self._query_batch('pss_reader_count_edit_batch' if edits else 'pss_reader_count_near_batch', (blob, offs), 'counts', ks)
 
-    def search_near(self, s: str, k: int = 1) -> typing.List[str]:
-        """Extension: the entries that hold ``s`` (UTF-8 encoded) with at most ``k`` BYTES substituted."""
-        return _packed_strs(self.search_near_batch_packed([_utf8(s, 'substring')], _near_budget(k)))
+    def search_near(self, s: str, k: int = 1, edits: bool = False) -> typing.List[str]:
+        """Extension: the entries that hold ``s`` (UTF-8 encoded) with at most ``k`` BYTES substituted -- with
+        ``edits=True``: inserted, deleted or substituted."""
+        return _packed_strs(self.search_near_batch_packed([_utf8(s, 'substring')], _near_budget(k), edits))
 
-    def count_near(self, s: str, k: int = 1) -> int:
-        """Extension: how many entries hold ``s`` (UTF-8 encoded) with at most ``k`` bytes substituted."""
-        return self.count_near_bytes([_utf8(s, 'substring')], _near_budget(k))[0]
+    def count_near(self, s: str, k: int = 1, edits: bool = False) -> int:
+        """Extension: how many entries hold ``s`` (UTF-8 encoded) with at most ``k`` bytes substituted -- with
+        ``edits=True``: inserted, deleted or substituted."""
+        return self.count_near_bytes([_utf8(s, 'substring')], _near_budget(k), edits)[0]
 
     @property
     def entry_counts(self) -> typing.Dict[int, int]:

@@ -1657,18 +1657,21 @@ extern "C" int pss_reader_count_seq_icase_batch(pss_reader *r, const uint8_t *sb
     return guarded([&]() -> int { return seq_batch(r, "pss_reader_count_seq_icase_batch", sbytes, soffsets, nsegs, group_offsets, ngroups, anchors, true, SEARCH_COUNTS, nullptr, counts); });
 }
 
-// ---- search within k mismatches: pattern -> pattern -> its k + 1 pieces (near_impl.h) ---------------
+// ---- search within k mismatches or k edits: pattern -> pattern -> its k + 1 pieces (near_impl.h; -----
+// ---- edit_impl.h, 4.17) ---------------------------------------------------------------------------------------------
 
 namespace {
 
 constexpr uint32_t kNearMaxBudget = 3;
 
-// The three calls within k mismatches: their own argument checks, then every pattern cut into its pieces -- the seed
-// queries of a group of one include term.  The patterns' own bytes and offsets are the caller's.  As for icase_plain, a
-// malformed batch is reported as such with or without a reader: the reader is looked at last.
+// The three calls within k mismatches and the three within k edits (`edits`: what the budget counts, and the one
+// difference of the request): their own argument checks, then every pattern cut into its pieces -- the seed queries of a
+// group of one include term.  The patterns' own bytes and offsets are the caller's.  As for icase_plain, a malformed batch
+// is reported as such with or without a reader: the reader is looked at last.
 int near_plain(pss_reader *r, const char *who, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, const uint8_t *k,
-               SearchMode mode, pss_result **out, uint64_t *counts)
+               bool edits, SearchMode mode, pss_result **out, uint64_t *counts)
 {
+    const char *unit = edits ? "edits" : "mismatches";
     if (!out_ok_by_mode(mode, nq, out, counts) || (nq && (!qbytes || !qoffsets || !k))) {
         set_error("%s: bad arguments", who);
         return PSS_EINVAL;
@@ -1676,12 +1679,13 @@ int near_plain(pss_reader *r, const char *who, const uint8_t *qbytes, const uint
     uint64_t npieces = 0;
     PSS_TRY(pattern_args(who, qoffsets, nq, [&](uint32_t q, uint64_t len) {
         if (k[q] > kNearMaxBudget) {
-            set_error("%s: pattern %u has a budget of %u mismatches: 0 .. %u", who, q, (unsigned)k[q], kNearMaxBudget);
+            set_error("%s: pattern %u has a budget of %u %s: 0 .. %u", who, q, (unsigned)k[q], unit, kNearMaxBudget);
             return false;
         }
         if (len <= k[q]) {
-            set_error("%s: pattern %u has %llu bytes and a budget of %u mismatches: every window of its length matches it "
-                      "(a pattern is longer than its budget)", who, q, (unsigned long long)len, (unsigned)k[q]);
+            set_error("%s: pattern %u has %llu bytes and a budget of %u %s: %s "
+                      "(a pattern is longer than its budget)", who, q, (unsigned long long)len, (unsigned)k[q], unit,
+                      edits ? "deleting all of it matches every entry" : "every window of its length matches it");
             return false;
         }
         npieces += (uint64_t)k[q] + 1;
@@ -1721,6 +1725,7 @@ int near_plain(pss_reader *r, const char *who, const uint8_t *qbytes, const uint
     rq.term_bytes = b.vbytes.data();
     rq.term_offsets = nq ? qoffsets : &no_offset;
     rq.near_budget = nq ? k : &no_budget;
+    rq.near_edits = edits;
     return answer_by_mode(r, rq, out, counts);
 }
 
@@ -1760,19 +1765,37 @@ extern "C" int pss_near_pieces(const uint8_t *pat, uint64_t len, uint32_t k, uin
 extern "C" int pss_reader_search_near_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, const uint8_t *k,
                                             pss_result **out)
 {
-    return guarded([&]() -> int { return near_plain(r, "pss_reader_search_near_batch", qbytes, qoffsets, nq, k, SEARCH_FULL, out, nullptr); });
+    return guarded([&]() -> int { return near_plain(r, "pss_reader_search_near_batch", qbytes, qoffsets, nq, k, false, SEARCH_FULL, out, nullptr); });
 }
 
 extern "C" int pss_reader_search_near_ids_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, const uint8_t *k,
                                                 pss_result **out)
 {
-    return guarded([&]() -> int { return near_plain(r, "pss_reader_search_near_ids_batch", qbytes, qoffsets, nq, k, SEARCH_IDS, out, nullptr); });
+    return guarded([&]() -> int { return near_plain(r, "pss_reader_search_near_ids_batch", qbytes, qoffsets, nq, k, false, SEARCH_IDS, out, nullptr); });
 }
 
 extern "C" int pss_reader_count_near_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, const uint8_t *k,
                                            uint64_t *counts)
 {
-    return guarded([&]() -> int { return near_plain(r, "pss_reader_count_near_batch", qbytes, qoffsets, nq, k, SEARCH_COUNTS, nullptr, counts); });
+    return guarded([&]() -> int { return near_plain(r, "pss_reader_count_near_batch", qbytes, qoffsets, nq, k, false, SEARCH_COUNTS, nullptr, counts); });
+}
+
+extern "C" int pss_reader_search_edit_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, const uint8_t *k,
+                                            pss_result **out)
+{
+    return guarded([&]() -> int { return near_plain(r, "pss_reader_search_edit_batch", qbytes, qoffsets, nq, k, true, SEARCH_FULL, out, nullptr); });
+}
+
+extern "C" int pss_reader_search_edit_ids_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, const uint8_t *k,
+                                                pss_result **out)
+{
+    return guarded([&]() -> int { return near_plain(r, "pss_reader_search_edit_ids_batch", qbytes, qoffsets, nq, k, true, SEARCH_IDS, out, nullptr); });
+}
+
+extern "C" int pss_reader_count_edit_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, const uint8_t *k,
+                                           uint64_t *counts)
+{
+    return guarded([&]() -> int { return near_plain(r, "pss_reader_count_edit_batch", qbytes, qoffsets, nq, k, true, SEARCH_COUNTS, nullptr, counts); });
 }
 
 namespace {

@@ -83,6 +83,7 @@ __device__ __forceinline__ bool near_scan(const ChunkDesc &ch, u32 from, u32 las
 // The compare of the seeded path (seed_impl.h) within a budget.  The queries v0 .. v1 are the pattern's at most 4 pieces,
 // piece w at T.pos[w] inside it; the hit came from piece v.
 struct NearMatch {
+    static constexpr bool kFixedWindow = true;      // a mismatch moves nothing: the window is [di - pos, di - pos + L), as under fold
     // After the frame's reject (1. di >= pos and m + L <= n: the whole window is readable) the hit stands iff:
     //   2. the entry around di (a piece holds no newline, so it lies inside one entry) -- its TRUE end is the closing newline
     //      or n, not start + len, which is short by one for an unterminated last entry -- ...

@@ -106,8 +106,11 @@ struct SearchRequest {
     //   the ngroups = nterms patterns, one include term each (identity group_offsets, zero exclude flags, no seq_anchors);
     //   term_bytes holds the patterns themselves -- exact bytes, nothing is folded --, near_budget[t] is pattern t's budget k,
     //   and its queries are its k + 1 pieces, left to right.
+    //   near_edits, with near_budget alone: the budget counts EDITS -- insertions, deletions and substitutions of single
+    //   bytes (edit_impl.h) -- instead of substitutions.  Everything else of the request is near's.
     const uint8_t *term_bytes = nullptr; const uint64_t *term_offsets = nullptr; uint32_t nterms = 0;
     const uint64_t *seed_offsets = nullptr; const uint32_t *seed_pos = nullptr; const uint8_t *near_budget = nullptr;
+    bool near_edits = false;
     uint32_t rows() const { return group_offsets ? ngroups : nq; }     // rows of the result: queries, or groups of terms
     bool low_latency = false;            // one query through the resident kernel when it fits (an unanchored SEARCH_FULL batch only)
     // sa_order: the entries of one (query, chunk) pair come out in the reference's order -- suffix-array order of the FIRST hit

@@ -24,7 +24,8 @@
 //                        (rank over the chunk's line index, line_index_impl.h)
 // The entry-level kinds put their own kernels in K2's place (the *_impl.h files included below): anchored_impl.h,
 // all_terms_impl.h, sequence_impl.h, and seed_impl.h -- the one seeded verify path of the case-insensitive search
-// (fold_impl.h) and the search within k mismatches (near_impl.h), which differ in their compare alone.
+// (fold_impl.h), the search within k mismatches (near_impl.h) and the search within k edits (edit_impl.h), which differ in
+// their compare alone.
 //
 // Output order: query-major, inside a query chunk-major, inside a chunk
 // suffix-array order of the kept hit (the reference's inter-chunk order is
@@ -1746,6 +1747,7 @@ static void newline_flags(const u8 *bytes, const u64 *off, u32 n, u8 set, u8 *fl
 #include "seed_impl.h"
 #include "fold_impl.h"
 #include "near_impl.h"
+#include "edit_impl.h"
 
 // Suffix-array hits of the batch per chunk (pair p = query p / nc on chunk p % nc): one workgroup per chunk.
 __global__ __launch_bounds__(256) void chunk_hits_kernel(const u32 *cnt, u64 nq, u32 nc, u64 *out)
@@ -1791,6 +1793,7 @@ struct Batch {
     bool seq;                           // terms, and the groups are ordered sequences (sequence_impl.h)
     bool seeded;                        // terms looked up through seed queries: group -> terms -> queries (seed_impl.h)
     bool near;                          // ... within k mismatches (near_impl.h); else under fold (fold_impl.h, 4.14)
+    bool edits;                         // near, and the budget counts edits: EditMatch in NearMatch's place (edit_impl.h, 4.17)
     const u32 nterm;                    // terms of a seeded batch (else 0) ...
     const u64 ntp;                      // ... and its (term, chunk) pairs
     bool tiny;                          // queries and offsets fit the 16 KiB of the pinned scratch
@@ -1839,6 +1842,7 @@ struct Batch {
         seq = terms && rq.seq_anchors != nullptr;
         seeded = terms && rq.seed_offsets != nullptr;
         near = seeded && rq.near_budget != nullptr;
+        edits = near && rq.near_edits;
         // (counts do not depend on the order; one hit per entry has one order; an all-terms batch keeps its driver's text order)
         sa_order = rq.sa_order && !counts && !anchored && !terms;
         // (an anchored batch searches its rewritten queries: a newline in front of and / or behind every pattern)
@@ -2251,7 +2255,8 @@ int Batch::run_general()
     const u64 H = h_small[0];
     if (near && h_small[2]) {   // (seed_union_kernel's flag: the one place a pair's 64-bit sum is judged, out of a test's reach and
                                 // checked by reading; nothing is reserved yet)
-        set_error("search: the pieces of one pattern have more than 2^32 - 1 hits in one chunk: more than a batch within k mismatches takes");
+        set_error("search: the pieces of one pattern have more than 2^32 - 1 hits in one chunk: more than a batch within k %s takes",
+                  edits ? "edits" : "mismatches");
         return PSS_EINVAL;
     }
     if (H == 0) {
@@ -2278,13 +2283,13 @@ int Batch::run_general()
                            d_hitoff, H, d_start, d_len);
     else if (seeded) {
         // every hit of every seed query against the whole driver term at its match start (under fold, or within the budget inside
-        // its entry and as its alignment's first exact piece); then the survivors against the entry in front of them: one
-        // candidate per entry, its leftmost match
+        // its entry and as its alignment's first exact piece; under edits: the piece's two sides within the budget); then the
+        // survivors against the entry in front of them: one candidate per entry, its leftmost match
         PSS_TRY(take(Q_ORD_V0, H * 4, d_m));        // (the slot of the suffix-array order's values: that order is never a seeded batch's)
         const u32 vgrid = (u32)std::min<u64>((u64)ctx->num_cus * 16, (H * TG + 255) / 256);
         const SeedTerms T{d_fbytes, d_foff, d_soff, d_pos, d_nk};
-        auto *hits = near ? seed_hits_kernel<NearMatch> : seed_hits_kernel<FoldMatch>;
-        auto *dedupe = near ? seed_dedupe_kernel<NearMatch> : seed_dedupe_kernel<FoldMatch>;
+        auto *hits = edits ? seed_hits_kernel<EditMatch> : near ? seed_hits_kernel<NearMatch> : seed_hits_kernel<FoldMatch>;
+        auto *dedupe = edits ? seed_dedupe_kernel<EditMatch> : near ? seed_dedupe_kernel<NearMatch> : seed_dedupe_kernel<FoldMatch>;
         hipLaunchKernelGGL(hits, dim3(grid), dim3(256), 0, s, d_chunks, nc, T, d_lo, d_cnt, nrp, d_hitoff, H, d_start, d_len, d_m, d_gdrv);
         hipLaunchKernelGGL(dedupe, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, T, nrp, d_hitoff, H, d_start, d_m, d_len, d_gdrv);
         // (every candidate against the group's other terms, or its segments in order: under fold alone -- a near batch is no
@@ -2385,12 +2390,13 @@ int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, const LineDes
         set_error("search: an all-terms batch takes the general pipeline to a host result, and its terms are not anchored");
         return PSS_EINVAL;
     }
-    if (rq.seed_offsets || rq.seed_pos || rq.near_budget) {
+    if (rq.seed_offsets || rq.seed_pos || rq.near_budget || rq.near_edits) {
         // a seeded batch carries its groups, its terms and the queries' offsets and positions, and either exclude flags or
         // sequence anchors; it excludes anchors, SEARCH_DEVICE and low_latency; a budget adds: identity groups of one include
-        // term each, no sequence anchors
+        // term each, no sequence anchors; near_edits says how a budget is counted and is legal with one alone
         bool ok = rq.seed_offsets && rq.seed_pos && rq.group_offsets && rq.term_bytes && rq.term_offsets &&
                   (!rq.nterms || rq.exclude || rq.seq_anchors) && !rq.anchors && rq.mode != SEARCH_DEVICE && !rq.low_latency;
+        ok = ok && (rq.near_budget || !rq.near_edits);
         if (rq.near_budget) {
             ok = ok && !rq.seq_anchors && rq.exclude && rq.ngroups == rq.nterms;
             for (u32 g = 0; ok && g < rq.ngroups; ++g) ok = rq.group_offsets[g] == g && rq.group_offsets[g + 1] == (u64)g + 1;
@@ -2398,7 +2404,7 @@ int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, const LineDes
         if (!ok) {
             set_error("search: a seeded batch states its groups, its terms' bytes and offsets, the seed queries' offsets and positions, "
                       "and either exclude flags or sequence anchors; with budgets its groups are one include term each and it has no "
-                      "sequence anchors");
+                      "sequence anchors; budgets count edits only where there are budgets");
             return PSS_EINVAL;
         }
     }

@@ -13,10 +13,13 @@
 // by walking the counts of those queries.  With di the text offset of a seed hit and pos the position of its query
 // inside the term, the term would start at m = di - pos: seed_hits_kernel verifies the whole term there (Match::at) and
 // seed_dedupe_kernel keeps the hit of the entry's LEFTMOST match (Match::before).  What "the term stands at m" means is
-// the Match's: FoldMatch compares under ASCII case folding, NearMatch exact bytes within a budget.
+// the Match's: FoldMatch compares under ASCII case folding, NearMatch exact bytes within a budget of mismatches.  A third,
+// EditMatch (edit_impl.h), allows insertions and deletions too: it has no fixed window, so for it m is di
+// itself, Match::at asks whether the CANDIDATE (piece, di) stands and Match::before whether one stands in front of di.
 // A term that holds a 0x0A occurs in no entry and is flagged void: its pairs count no hit.
 //
-// Bounds, for both kernels and both kinds.  A window that is read lies in [0, n): seed_hits_kernel rejects di < pos and
+// Bounds, for both kernels and the two kinds with a fixed window (edit_impl.h states its own: it walks byte by byte and
+// stops at the entry's ends).  A window that is read lies in [0, n): seed_hits_kernel rejects di < pos and
 // m + L > n before anything is read, and every window the dedupe looks at starts before m and so ends before m + L <= n.
 // Text loads are load_text8 at a byte of such a window or 8 past a start position: at most 23 bytes past a start position
 // and 15 past a compared range (the text is readable 128 bytes past n).  A term is read by load_u64_unaligned at one of
@@ -69,7 +72,10 @@ __global__ __launch_bounds__(256) void seed_union_kernel(u32 nc, const u64 *soff
 // sa[lo[v, c] + k'] of the query v its walk over the driver's counts ends in.  With di that text offset the term would
 // start at m = di - pos[v]: out of the chunk -> rejected before anything is read.  Else Match::at says whether the term
 // stands at m and, where it does, leaves the bounds of the entry around di in ls / ll.  A surviving hit leaves start, len
-// and m.
+// and m.  That reject is right for a Match with a FIXED WINDOW (Match::kFixedWindow: fold, near).  Under edits
+// (EditMatch) it is wrong -- a deletion left of the piece lets the match start behind di - pos, one right of it lets it
+// end before di - pos + L, so a match flush with the chunk's start or end would be lost --: there the frame passes di
+// through, m is di itself, and what m_out[t] means is "the position the dedupe looks before".
 template <typename Match>
 __global__ __launch_bounds__(256) void seed_hits_kernel(const ChunkDesc *chunks, u32 nc, SeedTerms T, const u32 *lo, const u32 *cnt, u64 ngq,
                                                           const u64 *hit_off, u64 H, u32 *start_out, u32 *len_out, u32 *m_out, const u32 *g_drv)
@@ -89,8 +95,8 @@ __global__ __launch_bounds__(256) void seed_hits_kernel(const ChunkDesc *chunks,
         const u32 di = ch.sa[lo[(u64)v * nc + c] + k];
         const u32 pos = T.pos[v], plen = (u32)(T.off[g + 1] - T.off[g]);
         u32 ls = 0, ll = kSkip, m = 0;
-        if (di >= pos && (u64)(di - pos) + plen <= ch.n) {
-            m = di - pos;
+        if (!Match::kFixedWindow || (di >= pos && (u64)(di - pos) + plen <= ch.n)) {
+            m = Match::kFixedWindow ? di - pos : di;
             Match::at(ch, T, g, v0, v1, v, di, m, plen, ls, ll);
         }
         start_out[t] = ls;
