@@ -15,7 +15,7 @@ import typing
 
 import numpy as np
 
-from tests.entry_id_ref import IdChunk
+from tests.entry_id_ref import IdChunk, IdRef
 
 START, END, ENTRY = 1, 2, 3
 ANCHOR_OF = {'start': START, 'end': END, 'entry': ENTRY}
@@ -51,19 +51,9 @@ class AnchoredChunk(IdChunk):
         return (np.uint64(self.index) << np.uint64(32)) | line
 
 
-class AnchoredRef:
-    """The chunks of one index (or the ones a shard holds: `indices` = their indexes in the file)."""
-
-    def __init__(self, texts: typing.Sequence[bytes], indices: typing.Optional[typing.Sequence[int]] = None):
-        indices = list(range(len(texts))) if indices is None else list(indices)
-        self.chunks = [AnchoredChunk(t, i) for t, i in zip(texts, indices)]
-
-    @classmethod
-    def from_index(cls, path: str, keep=lambda c: True) -> 'AnchoredRef':
-        from tests.search_ref import SearchRef
-        texts = [ch.text for ch in SearchRef.from_index(path).chunks]
-        held = [c for c in range(len(texts)) if keep(c)]
-        return cls([texts[c] for c in held], held)
+class AnchoredRef(IdRef):
+    """IdRef over AnchoredChunk: the same chunks, shards and entry texts; search_ids takes the anchor as well."""
+    chunk_cls = AnchoredChunk
 
     def search_ids(self, pat: bytes, anchor: typing.Union[int, str]) -> np.ndarray:
         """Ids of the entries pat matches under anchor over every chunk, ascending."""

@@ -46,10 +46,11 @@ class IdChunk(Chunk):
 
 class IdRef:
     """The chunks of one index (or the ones a shard holds: `indices` = their indexes in the file)."""
+    chunk_cls = IdChunk             # (a reference of another kind of search names its own chunk class here)
 
     def __init__(self, texts: typing.Sequence[bytes], indices: typing.Optional[typing.Sequence[int]] = None):
         indices = list(range(len(texts))) if indices is None else list(indices)
-        self.chunks = [IdChunk(t, i) for t, i in zip(texts, indices)]
+        self.chunks = [self.chunk_cls(t, i) for t, i in zip(texts, indices)]
 
     @classmethod
     def from_index(cls, path: str, keep=lambda c: True) -> 'IdRef':

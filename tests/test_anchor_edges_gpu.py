@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 from tests import anchor_texts as A
-from tests.test_sa_gpu import _sa_device
+from tests.util import sa_device
 
 pytestmark = pytest.mark.gpu
 
@@ -57,7 +57,7 @@ def _build(monkeypatch, case, forced=None, note=None, flags=8, side=False, **env
     if forced:
         monkeypatch.setenv('PSS_ANCHOR_OMEGA', str(forced))
     st = {}
-    sa = _sa_device(np.asarray(t), st, flags=flags)
+    sa = sa_device(np.asarray(t), st, flags=flags)
     note = (note, t.size, forced, env)
     depth = A.depth_of(st)
     got = {k: int(st[k]) for k in ('anchor', 'anchor_omega', 'anchor_w', 'anchor_count', 'anchor_depth', 'anchor_levels', 'anchor_side')}

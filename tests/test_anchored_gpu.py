@@ -11,56 +11,19 @@ workgroup and than the mid pipeline hold, work that follows the answer (last_sta
 interval routes, placement (two parts on one device, a shard, a suffix array on the host tier, order='sa', no line table
 before the id variant runs), errors, and the conveniences."""
 import ctypes
-import sys
 
 import numpy as np
 import pytest
 
 import pysubstringsearch
 from pysubstringsearch_amd import _ffi
+from tests import search_harness as H
 from tests.anchored_ref import AnchoredRef
+from tests.search_harness import FILLER, R, device_reader, filler, make_index, per_row as per_query
 
 pytestmark = pytest.mark.gpu
 
-R = _ffi.ROUTES
 KINDS = ('start', 'end', 'entry')
-FILLER = b'abcdefghijklmnop'
-INTERVAL = R['INTERVAL_LANE'] | R['INTERVAL_GROUP'] | R['INTERVAL_WAVE']
-
-
-def filler(rng, n):
-    return bytes(np.frombuffer(FILLER, np.uint8)[rng.integers(0, len(FILLER), n)])
-
-
-def make_index(tmp_path, name, data, max_chunk_len=None):
-    assert b'\r' not in data
-    src = tmp_path / (name + '.txt')
-    src.write_bytes(data)
-    p = str(tmp_path / (name + '.idx'))
-    w = pysubstringsearch.Writer(p, max_chunk_len)
-    w.add_entries_from_file_lines(str(src))
-    w.close()
-    return p
-
-
-def device_chunk(text):
-    """(text, suffix array) of one chunk in HBM, as torch tensors."""
-    import torch
-    t = np.frombuffer(text, dtype=np.uint8).copy()
-    sa = np.empty(len(text), dtype=np.int32)
-    _ffi.check(_ffi.lib.pss_sa_build(t.ctypes.data, sa.ctypes.data, len(text), 0))
-    return torch.from_numpy(t).cuda(), torch.from_numpy(sa).cuda()
-
-
-def device_reader(texts):
-    """A reader filled through pss_reader_add_chunk_device: the only way to a text without a closing newline."""
-    h = ctypes.c_void_p()
-    _ffi.check(_ffi.lib.pss_reader_create(0, ctypes.byref(h)))
-    r = pysubstringsearch.Reader._from_handle(h)
-    for t in texts:
-        dt, ds = device_chunk(t)
-        _ffi.check(_ffi.lib.pss_reader_add_chunk_device(h, dt.data_ptr(), ds.data_ptr(), len(t)))
-    return r
 
 
 def all_kinds(patterns):
@@ -69,80 +32,10 @@ def all_kinds(patterns):
     return pats, [k for _ in patterns for k in KINDS]
 
 
-def report_routes(routes):
-    """tests/test_search_edges_gpu.py ends by asserting that a batch finished on every PSS_ROUTE_* bit of include/pss.h
-    and was compared with a brute-force reference.  Only the anchored calls set PSS_ROUTE_ANCHORED and they are compared
-    here, so the routes of the batches that check() has compared go into that module's record when it is part of the
-    session (it runs after this one).  Run on its own, that module cannot see the anchored route."""
-    edges = sys.modules.get(__name__.replace('test_anchored_gpu', 'test_search_edges_gpu'))   # collected, or absent
-    if edges is not None:
-        for rt in routes:
-            edges.SEEN[0] |= edges.finished(rt)
-
-
-def check(r, ref, patterns, anchors, texts=True, interval=None):
-    """patterns under anchors (one word, or one per pattern) on reader r against ref (the chunks r holds).  Returns the
-    IdResult."""
-    patterns = list(patterns)
-    kinds = [anchors] * len(patterns) if isinstance(anchors, str) else list(anchors)
-    res = r.search_anchored_ids_batch(patterns, anchors)
-    st = r.last_stats()
-    ids, counts = res.ids, res.counts.tolist()
-    assert ids.dtype == np.uint64 and not ids.flags.writeable
-    assert len(counts) == len(patterns) and sum(counts) == ids.size
-    assert st['entries'] == ids.size and st['result_bytes'] == 8 * ids.size and st['queries'] == len(patterns)
-    live = bool(patterns) and r.num_chunks > 0
-    routes = []
-
-    def route_ok(st, counting):
-        if not live:
-            return
-        route = st['route']
-        routes.append(route)
-        assert route & R['GENERAL'] and route & R['ANCHORED'], hex(route)
-        assert not route & (R['MID'] | R['MID_OVERFLOW'] | R['SMALL_BLOCK'] | R['SMALL_WAVE'] | R['SMALL_OVERFLOW'] | R['RESIDENT'] |
-                            R['SA_ORDER']), hex(route)
-        assert bool(route & R['COUNTS']) == counting, hex(route)
-        assert route & INTERVAL, hex(route)
-        if interval is not None:
-            assert route & INTERVAL == interval, hex(route)
-
-    route_ok(st, False)
-    hits = st['hits']
-    assert hits >= ids.size
-    assert counts == r.count_anchored_bytes(patterns, anchors)
-    st = r.last_stats()
-    route_ok(st, True)
-    assert st['hits'] == hits and st['entries'] == ids.size and st['queries'] == len(patterns)
-    pos = 0
-    for q, k, c in zip(patterns, kinds, counts):
-        got = ids[pos:pos + c]
-        pos += c
-        want = ref.search_ids(q, k)
-        assert np.unique(got).size == got.size, (q[:40], k, 'an id twice')
-        assert np.array_equal(np.sort(got), want), (q[:40], k, got[:8], want[:8])
-    # the same entries, in the same order, as the packed text result
-    pk = r.search_anchored_batch_packed(patterns, anchors)
-    st = r.last_stats()
-    route_ok(st, False)
-    assert st['hits'] == hits and st['entries'] == ids.size and st['result_bytes'] == pk.data.size
-    by_id = r.entries_by_id_packed(ids)
-    assert pk.counts.tolist() == counts
-    assert np.array_equal(by_id.offsets, pk.offsets)
-    assert np.array_equal(by_id.data, pk.data)
-    if texts:       # ... and each is the text the reference has under that id
-        data, o = pk.data.tobytes(), pk.offsets.tolist()
-        assert [data[o[i]:o[i + 1]] for i in range(ids.size)] == [ref.entry(i) for i in ids.tolist()]
-    report_routes(routes)
-    return res
-
-
-def per_query(res):
-    out, pos = [], 0
-    for c in res.counts.tolist():
-        out.append(res.ids[pos:pos + c])
-        pos += c
-    return out
+def check(r, ref, patterns, anchors, **kw):
+    """patterns under anchors (one word, or one per pattern) on reader r against ref (the chunks r holds).  The batches
+    compared here are the only ones that show PSS_ROUTE_ANCHORED to the route record of tests/search_harness.py."""
+    return H.check(H.ANCHORED, r, ref, (list(patterns), anchors), **kw)
 
 
 # ---- chunk edges -------------------------------------------------------------------------------------------------
@@ -413,65 +306,9 @@ def test_placement(tmp_path, search_env):
     data = b'\n'.join(lines) + b'\n'
     p = make_index(tmp_path, 'place', data, 4000)
     ref = AnchoredRef.from_index(p)
-    nchunks = len(ref.chunks)
-    assert nchunks >= 5
+    assert len(ref.chunks) >= 5
     base_pats = [b'', b'a', b'ab', b'HEAD', b'p'] + [ch.entry(0) for ch in ref.chunks] + [lines[int(i)] for i in rng.integers(0, len(lines), 30)]
-    pats, kinds = all_kinds(base_pats)
-    whole = pysubstringsearch.Reader(p)
-    try:
-        # the line tables are absent until the id variant is called
-        fresh = whole.residency
-        text = whole.search_anchored_batch_packed(pats, kinds)
-        counts = whole.count_anchored_bytes(pats, kinds)
-        assert whole.residency == fresh
-        base = check(whole, ref, pats, kinds)
-        assert whole.residency['hbm_bytes'] > fresh['hbm_bytes']
-        assert base.counts.tolist() == counts == text.counts.tolist()
-        again = whole.search_anchored_batch_packed(pats, kinds)
-        assert np.array_equal(again.data, text.data) and np.array_equal(again.offsets, text.offsets)
-        hbm = fresh['hbm_bytes']
-        chunk_of = (base.ids >> np.uint64(32)).astype(np.int64)
-        query_of = np.repeat(np.arange(len(pats)), base.counts.astype(np.int64))
-        assert (np.diff(chunk_of)[np.diff(query_of) == 0] >= 0).all()                     # chunk-major inside a query
-        # order='sa' gives the identical result, without the sort
-        sa = pysubstringsearch.Reader(p, order='sa')
-        try:
-            got = check(sa, ref, pats, kinds)
-            assert np.array_equal(got.ids, base.ids)
-            pk = sa.search_anchored_batch_packed(pats, kinds)
-            assert np.array_equal(pk.data, text.data) and np.array_equal(pk.offsets, text.offsets)
-        finally:
-            sa.close()
-        # devices=[0, 0]: part-major inside a query; the ids of one file mean the same in every part
-        multi = pysubstringsearch.Reader(p, devices=[0, 0])
-        try:
-            got = check(multi, ref, pats, kinds)
-            assert got.counts.tolist() == base.counts.tolist()
-            key = np.lexsort((np.arange(base.ids.size), chunk_of % 2, query_of))
-            assert np.array_equal(got.ids, base.ids[key])
-        finally:
-            multi.close()
-        # shard (1, 2): the whole reader's ids of the odd chunks -- the file's chunk indexes -- in the same order
-        shard = pysubstringsearch.Reader(p, shard=(1, 2))
-        try:
-            sref = AnchoredRef.from_index(p, keep=lambda c: c % 2 == 1)
-            got = check(shard, sref, pats, kinds)
-            assert np.array_equal(got.ids, base.ids[chunk_of % 2 == 1])
-            assert got.ids.size and ((got.ids >> np.uint64(32)) % np.uint64(2) == 1).all()
-        finally:
-            shard.close()
-    finally:
-        whole.close()
-    # one suffix array too many for the budget: it stays in pinned host memory
-    search_env(PSS_READER_HBM_BUDGET=hbm - 1, PSS_READER_AUTO_RESIDENCY=0)
-    tier = pysubstringsearch.Reader(p)
-    try:
-        assert tier.residency['host_chunks'] >= 1
-        got = check(tier, ref, pats, kinds)
-        assert np.array_equal(got.ids, base.ids)
-        assert tier.residency['host_chunks'] >= 1
-    finally:
-        tier.close()
+    H.placement(H.ANCHORED, p, all_kinds(base_pats), search_env, ref=ref)
 
 
 # ---- errors ---------------------------------------------------------------------------------------------------------

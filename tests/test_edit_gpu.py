@@ -1,6 +1,6 @@
 """Search within k edits (Reader.search_near_ids_batch / search_near_batch_packed / count_near_bytes with edits=True, and
 the str conveniences) against the brute-force reference of tests/edit_ref.py -- a Sellers scan over every true entry.
-Every pattern of every batch goes through one check(), the one of tests/test_near_gpu.py with the edit calls in it:
+Every pattern of every batch goes through one check(), the one of tests/search_harness.py under its EDIT kind:
   * per pattern, the sorted ids equal the reference's and no id appears twice; the counts equal the count call's;
   * the ids come in the stated order: chunk-major, inside a chunk by the piece index j of each entry's kept candidate
     (d, j) -- the standing candidate with the smallest d, then the smallest j --, inside one piece by the suffix at d;
@@ -20,72 +20,22 @@ import pytest
 
 import pysubstringsearch
 from pysubstringsearch_amd import _ffi, near_pieces
+from tests import search_harness as H
 from tests.edit_ref import EditRef
-from tests.test_near_gpu import FILLER, INTERVAL, WORD, R, device_reader, filler, make_index, per_pattern
+from tests.search_harness import FILLER, R, device_reader, filler, make_index, per_row as per_pattern
 
 pytestmark = pytest.mark.gpu
 
+WORD = b'qrstuvwxyz1234567890QRSTUVWXYZ'          # (no byte of the filler, no byte twice)
 
-def check(r, ref, patterns, k, texts=True, order=True, interval=None):
+
+def check(r, ref, patterns, k, **kw):
     """patterns within k edits (one int, or one per pattern) on reader r against ref (the chunks r holds).  Returns the IdResult."""
-    patterns = list(patterns)
-    ks = [k] * len(patterns) if isinstance(k, int) else list(k)
-    res = r.search_near_ids_batch(patterns, k, edits=True)
-    st = r.last_stats()
-    ids, counts = res.ids, res.counts.tolist()
-    assert ids.dtype == np.uint64 and not ids.flags.writeable
-    assert len(counts) == len(patterns) and sum(counts) == ids.size
-    assert st['entries'] == ids.size and st['result_bytes'] == 8 * ids.size and st['queries'] == len(patterns)
-    live = bool(patterns) and r.num_chunks > 0
-
-    def route_ok(st, counting):
-        if not live:
-            return
-        route = st['route']
-        assert route & R['GENERAL'], hex(route)
-        assert not route & (R['ANCHORED'] | R['MID'] | R['MID_OVERFLOW'] | R['SMALL_BLOCK'] | R['SMALL_WAVE'] | R['SMALL_OVERFLOW'] |
-                            R['RESIDENT'] | R['SA_ORDER']), hex(route)
-        assert bool(route & R['COUNTS']) == counting, hex(route)
-        assert route & INTERVAL, hex(route)
-        if interval is not None:
-            assert route & INTERVAL == interval, hex(route)
-
-    route_ok(st, False)
-    hits = st['hits']
-    assert hits == sum(ref.piece_hits(p, kk) for p, kk in zip(patterns, ks)), 'hits'
-    assert counts == r.count_near_bytes(patterns, k, edits=True)
-    st = r.last_stats()
-    route_ok(st, True)
-    assert st['hits'] == hits and st['entries'] == ids.size and st['queries'] == len(patterns)
-    pos = 0
-    for p, kk, c in zip(patterns, ks, counts):
-        got = ids[pos:pos + c]
-        pos += c
-        want = ref.search_edit_ids(p, kk)
-        assert np.unique(got).size == got.size, (p, kk, 'an id twice')
-        assert np.array_equal(np.sort(got), want), (p[:120], kk, np.sort(got)[:8], want[:8])
-        if order:
-            assert np.array_equal(got, ref.ordered_ids(p, kk)), (p[:120], kk, 'order')
-    # the same entries, in the same order, as the packed text result
-    pk = r.search_near_batch_packed(patterns, k, edits=True)
-    st = r.last_stats()
-    route_ok(st, False)
-    assert st['hits'] == hits and st['entries'] == ids.size and st['result_bytes'] == pk.data.size
-    by_id = r.entries_by_id_packed(ids)
-    assert pk.counts.tolist() == counts
-    assert np.array_equal(by_id.offsets, pk.offsets)
-    assert np.array_equal(by_id.data, pk.data)
-    if texts:       # ... and each is the text the reference has under that id
-        data, o = pk.data.tobytes(), pk.offsets.tolist()
-        assert [data[o[i]:o[i + 1]] for i in range(ids.size)] == [ref.entry(i) for i in ids.tolist()]
-    return res
+    return H.check(H.EDIT, r, ref, (list(patterns), k), **kw)
 
 
 def one_chunk(lines, closed=True):
-    """(reader, reference, text) of one chunk handed over on the device."""
-    data = b'\n'.join(lines) + (b'\n' if closed else b'')
-    assert len(data) < 1_000_000
-    return device_reader([data]), EditRef([data]), data
+    return H.one_chunk(EditRef, lines, closed)
 
 
 def edited(p, ops):
@@ -427,57 +377,9 @@ def test_placement(tmp_path, search_env):
     patterns += [ch.entry(0)[1:9] for ch in ref.chunks if len(ch.entry(0)) >= 5]                     # a deletion at offset 0 of every chunk
     patterns += [lines[int(i)][1:8] for i in rng.integers(0, len(lines), 12) if len(lines[int(i)]) >= 8]
     ks = [min(int(rng.integers(0, 3)), len(q) - 1) for q in patterns]
-    whole = pysubstringsearch.Reader(p)
-    try:
-        # the line tables are absent until the id variant is called
-        fresh = whole.residency
-        text = whole.search_near_batch_packed(patterns, ks, edits=True)
-        counts = whole.count_near_bytes(patterns, ks, edits=True)
-        assert whole.residency == fresh
-        base = check(whole, ref, patterns, ks)
-        assert whole.residency['hbm_bytes'] > fresh['hbm_bytes']
-        assert base.counts.tolist() == counts == text.counts.tolist() and base.ids.size > 100
-        hbm = fresh['hbm_bytes']
-        chunk_of = (base.ids >> np.uint64(32)).astype(np.int64)
-        group_of = np.repeat(np.arange(len(patterns)), base.counts.astype(np.int64))
-        assert (np.diff(chunk_of)[np.diff(group_of) == 0] >= 0).all() and np.unique(chunk_of).size >= 5      # chunk-major inside a pattern
-        # order='sa' has no effect
-        sa = pysubstringsearch.Reader(p, order='sa')
-        try:
-            got = check(sa, ref, patterns, ks)
-            assert np.array_equal(got.ids, base.ids)
-        finally:
-            sa.close()
-        # devices=[0, 0]: the merge is keyed by patterns -- part-major inside a pattern
-        multi = pysubstringsearch.Reader(p, devices=[0, 0])
-        try:
-            got = check(multi, ref, patterns, ks, order=False)
-            assert got.counts.tolist() == base.counts.tolist()
-            key = np.lexsort((np.arange(base.ids.size), chunk_of % 2, group_of))
-            assert np.array_equal(got.ids, base.ids[key])
-        finally:
-            multi.close()
-        # shard (1, 2): the whole reader's ids of the odd chunks, in the same order
-        shard = pysubstringsearch.Reader(p, shard=(1, 2))
-        try:
-            sref = EditRef.from_index(p, keep=lambda c: c % 2 == 1)
-            got = check(shard, sref, patterns, ks)
-            assert np.array_equal(got.ids, base.ids[chunk_of % 2 == 1])
-            assert got.ids.size and ((got.ids >> np.uint64(32)) % np.uint64(2) == 1).all()
-        finally:
-            shard.close()
-    finally:
-        whole.close()
-    # one suffix array too many for the budget: it stays in pinned host memory
-    search_env(PSS_READER_HBM_BUDGET=hbm - 1, PSS_READER_AUTO_RESIDENCY=0)
-    tier = pysubstringsearch.Reader(p)
-    try:
-        assert tier.residency['host_chunks'] >= 1
-        got = check(tier, ref, patterns, ks)
-        assert np.array_equal(got.ids, base.ids)
-        assert tier.residency['host_chunks'] >= 1
-    finally:
-        tier.close()
+    # devices=[0, 0]: the merge is part-major inside a pattern, so the stated order is not compared there
+    base = H.placement(H.EDIT, p, (patterns, ks), search_env, order_multi=False, ref=ref)
+    assert base.ids.size > 100 and np.unique(base.ids >> np.uint64(32)).size >= 5
 
 
 def test_an_empty_chunk_list_and_an_empty_batch():

@@ -16,29 +16,14 @@ import pytest
 
 import pysubstringsearch
 from pysubstringsearch_amd import _ffi
+from tests import search_harness as H
 from tests.entry_id_ref import IdRef
+from tests.search_harness import FILLER, R, device_chunk, filler, make_index
 
 pytestmark = pytest.mark.gpu
 
-R = _ffi.ROUTES
 LINE_BLOCK = 256                # bytes of text per entry of the line table (search.h, kLineShift = 8)
 EDGE = 1024                     # the largest block PSS_LINE_BLOCK_SHIFT allows: an edge of it is an edge of every size
-FILLER = b'abcdefghijklmnop'    # marker queries use none of these bytes
-
-
-def filler(rng, n):
-    return bytes(np.frombuffer(FILLER, np.uint8)[rng.integers(0, len(FILLER), n)])
-
-
-def make_index(tmp_path, name, data, max_chunk_len=None):
-    assert b'\r' not in data
-    src = tmp_path / (name + '.txt')
-    src.write_bytes(data)
-    p = str(tmp_path / (name + '.idx'))
-    w = pysubstringsearch.Writer(p, max_chunk_len)
-    w.add_entries_from_file_lines(str(src))
-    w.close()
-    return p
 
 
 def table_bytes(ref, block=LINE_BLOCK):
@@ -46,37 +31,9 @@ def table_bytes(ref, block=LINE_BLOCK):
     return sum(((len(ch.text) + block - 1) // block + 2) * 4 for ch in ref.chunks if len(ch.text))
 
 
-def check(r, ref, queries, texts=True):
+def check(r, ref, queries, **kw):
     """queries through search_ids_batch on reader r against ref (the chunks r holds).  Returns the IdResult."""
-    queries = list(queries)
-    res = r.search_ids_batch(queries)
-    st = r.last_stats()
-    ids, counts = res.ids, res.counts.tolist()
-    assert ids.dtype == np.uint64 and not ids.flags.writeable
-    assert len(counts) == len(queries) and sum(counts) == ids.size
-    assert st['entries'] == ids.size and st['result_bytes'] == 8 * ids.size and st['queries'] == len(queries)
-    if queries and r.num_chunks:
-        assert st['route'] & R['GENERAL'], hex(st['route'])
-        assert not st['route'] & (R['MID'] | R['SMALL_BLOCK'] | R['SMALL_WAVE'] | R['RESIDENT'] | R['COUNTS']), hex(st['route'])
-        assert bool(st['route'] & R['SA_ORDER']) == (r.result_order == 'sa'), hex(st['route'])
-    assert counts == r.count_multiple_bytes(queries)
-    pos = 0
-    for q, c in zip(queries, counts):
-        got = ids[pos:pos + c]
-        pos += c
-        want = ref.search_ids(q)
-        assert np.unique(got).size == got.size, (q[:40], 'an id twice')
-        assert np.array_equal(np.sort(got), want), (q[:40], got[:8], want[:8])
-    # the same entries, in the same order, as the packed search
-    pk = r.search_batch_packed(queries)
-    by_id = r.entries_by_id_packed(ids)
-    assert pk.counts.tolist() == counts
-    assert np.array_equal(by_id.offsets, pk.offsets)
-    assert np.array_equal(by_id.data, pk.data)
-    assert by_id.counts.tolist() == [1] * ids.size
-    if texts:       # ... and each is the text the reference has under that id
-        assert r.entries_by_id(ids) == [ref.entry(i) for i in ids.tolist()]
-    return res
+    return H.check(H.PLAIN, r, ref, list(queries), **kw)
 
 
 def edge_text(rng, close=True):
@@ -206,15 +163,6 @@ def test_line_numbers_of_an_indexed_file(tmp_path):
             shard.entry_ordinals(shard.search_ids('alpha'))
     finally:
         shard.close()
-
-
-def device_chunk(text):
-    """(text, suffix array) of one chunk in HBM, as torch tensors."""
-    import torch
-    t = np.frombuffer(text, dtype=np.uint8).copy()
-    sa = np.empty(len(text), dtype=np.int32)
-    _ffi.check(_ffi.lib.pss_sa_build(t.ctypes.data, sa.ctypes.data, len(text), 0))
-    return torch.from_numpy(t).cuda(), torch.from_numpy(sa).cuda()
 
 
 def test_chunks_handed_over_on_the_device(search_env):

@@ -19,48 +19,11 @@ import pytest
 
 import pysubstringsearch
 from pysubstringsearch_amd import _ffi, glob_escape, glob_parse
+from tests import search_harness as H
 from tests.glob_ref import GlobRef
+from tests.search_harness import R, device_reader, filler, make_index, per_row as per_pattern
 
 pytestmark = pytest.mark.gpu
-
-R = _ffi.ROUTES
-FILLER = b'abcdefghijklmnop'
-INTERVAL = R['INTERVAL_LANE'] | R['INTERVAL_GROUP'] | R['INTERVAL_WAVE']
-
-
-def filler(rng, n):
-    return bytes(np.frombuffer(FILLER, np.uint8)[rng.integers(0, len(FILLER), n)])
-
-
-def make_index(tmp_path, name, data, max_chunk_len=None):
-    assert b'\r' not in data
-    src = tmp_path / (name + '.txt')
-    src.write_bytes(data)
-    p = str(tmp_path / (name + '.idx'))
-    w = pysubstringsearch.Writer(p, max_chunk_len)
-    w.add_entries_from_file_lines(str(src))
-    w.close()
-    return p
-
-
-def device_chunk(text):
-    """(text, suffix array) of one chunk in HBM, as torch tensors."""
-    import torch
-    t = np.frombuffer(text, dtype=np.uint8).copy()
-    sa = np.empty(len(text), dtype=np.int32)
-    _ffi.check(_ffi.lib.pss_sa_build(t.ctypes.data, sa.ctypes.data, len(text), 0))
-    return torch.from_numpy(t).cuda(), torch.from_numpy(sa).cuda()
-
-
-def device_reader(texts):
-    """A reader filled through pss_reader_add_chunk_device: the only way to a text without a closing newline."""
-    h = ctypes.c_void_p()
-    _ffi.check(_ffi.lib.pss_reader_create(0, ctypes.byref(h)))
-    r = pysubstringsearch.Reader._from_handle(h)
-    for t in texts:
-        dt, ds = device_chunk(t)
-        _ffi.check(_ffi.lib.pss_reader_add_chunk_device(h, dt.data_ptr(), ds.data_ptr(), len(t)))
-    return r
 
 
 def glob(segments, anchors=0):
@@ -71,64 +34,9 @@ def glob(segments, anchors=0):
     return p
 
 
-def check(r, ref, patterns, texts=True, interval=None):
+def check(r, ref, patterns, **kw):
     """patterns on reader r against ref (the chunks r holds).  Returns the IdResult."""
-    patterns = list(patterns)
-    res = r.search_glob_ids_batch(patterns)
-    st = r.last_stats()
-    ids, counts = res.ids, res.counts.tolist()
-    assert ids.dtype == np.uint64 and not ids.flags.writeable
-    assert len(counts) == len(patterns) and sum(counts) == ids.size
-    assert st['entries'] == ids.size and st['result_bytes'] == 8 * ids.size and st['queries'] == len(patterns)
-    live = bool(patterns) and r.num_chunks > 0
-
-    def route_ok(st, counting):
-        if not live:
-            return
-        route = st['route']
-        assert route & R['GENERAL'], hex(route)
-        assert not route & (R['ANCHORED'] | R['MID'] | R['MID_OVERFLOW'] | R['SMALL_BLOCK'] | R['SMALL_WAVE'] | R['SMALL_OVERFLOW'] |
-                            R['RESIDENT'] | R['SA_ORDER']), hex(route)
-        assert bool(route & R['COUNTS']) == counting, hex(route)
-        assert route & INTERVAL, hex(route)
-        if interval is not None:
-            assert route & INTERVAL == interval, hex(route)
-
-    route_ok(st, False)
-    hits = st['hits']
-    assert hits >= ids.size
-    assert counts == r.count_glob_bytes(patterns)
-    st = r.last_stats()
-    route_ok(st, True)
-    assert st['hits'] == hits and st['entries'] == ids.size and st['queries'] == len(patterns)
-    pos = 0
-    for g, c in zip(patterns, counts):
-        got = ids[pos:pos + c]
-        pos += c
-        want = ref.search_glob_ids(g)
-        assert np.unique(got).size == got.size, (g, 'an id twice')
-        assert np.array_equal(np.sort(got), want), (g[:120], got[:8], want[:8])
-    # the same entries, in the same order, as the packed text result
-    pk = r.search_glob_batch_packed(patterns)
-    st = r.last_stats()
-    route_ok(st, False)
-    assert st['hits'] == hits and st['entries'] == ids.size and st['result_bytes'] == pk.data.size
-    by_id = r.entries_by_id_packed(ids)
-    assert pk.counts.tolist() == counts
-    assert np.array_equal(by_id.offsets, pk.offsets)
-    assert np.array_equal(by_id.data, pk.data)
-    if texts:       # ... and each is the text the reference has under that id
-        data, o = pk.data.tobytes(), pk.offsets.tolist()
-        assert [data[o[i]:o[i + 1]] for i in range(ids.size)] == [ref.entry(i) for i in ids.tolist()]
-    return res
-
-
-def per_pattern(res):
-    out, pos = [], 0
-    for c in res.counts.tolist():
-        out.append(res.ids[pos:pos + c])
-        pos += c
-    return out
+    return H.check(H.GLOB, r, ref, list(patterns), **kw)
 
 
 def one_chunk(tmp_path, name, lines):
@@ -508,67 +416,12 @@ def test_placement(tmp_path, search_env):
     data = b'\n'.join(lines) + b'\n'
     p = make_index(tmp_path, 'place', data, 4000)
     ref = GlobRef.from_index(p)
-    nchunks = len(ref.chunks)
-    assert nchunks >= 5
+    assert len(ref.chunks) >= 5
     patterns = [b'*a*b*', b'*b*a*', b'a*b', b'HEAD*0*', b'*HEAD*a*b*', b'*p*', b'*ab*cd*', b'*a*b*c*d*', b'*MISS*a*', b'e*', b'*e', b'HEAD*']
     patterns += [glob([ch.entry(0)], 3) for ch in ref.chunks if ch.entry(0)]                    # the entry at offset 0 of every chunk
     patterns += [glob([lines[int(i)][:2], lines[int(i)][-2:]], int(rng.integers(0, 4))) for i in rng.integers(0, len(lines), 30)
                  if len(lines[int(i)]) >= 4]
-    whole = pysubstringsearch.Reader(p)
-    try:
-        # the line tables are absent until the id variant is called
-        fresh = whole.residency
-        text = whole.search_glob_batch_packed(patterns)
-        counts = whole.count_glob_bytes(patterns)
-        assert whole.residency == fresh
-        base = check(whole, ref, patterns)
-        assert whole.residency['hbm_bytes'] > fresh['hbm_bytes']
-        assert base.counts.tolist() == counts == text.counts.tolist() and base.ids.size > 100
-        again = whole.search_glob_batch_packed(patterns)
-        assert np.array_equal(again.data, text.data) and np.array_equal(again.offsets, text.offsets)
-        hbm = fresh['hbm_bytes']
-        chunk_of = (base.ids >> np.uint64(32)).astype(np.int64)
-        group_of = np.repeat(np.arange(len(patterns)), base.counts.astype(np.int64))
-        assert (np.diff(chunk_of)[np.diff(group_of) == 0] >= 0).all()                     # chunk-major inside a pattern
-        # order='sa' has no effect
-        sa = pysubstringsearch.Reader(p, order='sa')
-        try:
-            got = check(sa, ref, patterns)
-            assert np.array_equal(got.ids, base.ids)
-            pk = sa.search_glob_batch_packed(patterns)
-            assert np.array_equal(pk.data, text.data) and np.array_equal(pk.offsets, text.offsets)
-        finally:
-            sa.close()
-        # devices=[0, 0]: the merge is keyed by patterns -- part-major inside a pattern
-        multi = pysubstringsearch.Reader(p, devices=[0, 0])
-        try:
-            got = check(multi, ref, patterns)
-            assert got.counts.tolist() == base.counts.tolist()
-            key = np.lexsort((np.arange(base.ids.size), chunk_of % 2, group_of))
-            assert np.array_equal(got.ids, base.ids[key])
-        finally:
-            multi.close()
-        # shard (1, 2): the whole reader's ids of the odd chunks, in the same order
-        shard = pysubstringsearch.Reader(p, shard=(1, 2))
-        try:
-            sref = GlobRef.from_index(p, keep=lambda c: c % 2 == 1)
-            got = check(shard, sref, patterns)
-            assert np.array_equal(got.ids, base.ids[chunk_of % 2 == 1])
-            assert got.ids.size and ((got.ids >> np.uint64(32)) % np.uint64(2) == 1).all()
-        finally:
-            shard.close()
-    finally:
-        whole.close()
-    # one suffix array too many for the budget: it stays in pinned host memory
-    search_env(PSS_READER_HBM_BUDGET=hbm - 1, PSS_READER_AUTO_RESIDENCY=0)
-    tier = pysubstringsearch.Reader(p)
-    try:
-        assert tier.residency['host_chunks'] >= 1
-        got = check(tier, ref, patterns)
-        assert np.array_equal(got.ids, base.ids)
-        assert tier.residency['host_chunks'] >= 1
-    finally:
-        tier.close()
+    assert H.placement(H.GLOB, p, patterns, search_env, ref=ref).ids.size > 100
 
 
 # ---- 9. errors and the conveniences -------------------------------------------------------------------------------------

@@ -20,82 +20,18 @@ import pytest
 
 import pysubstringsearch
 from pysubstringsearch_amd import _ffi, glob_escape, glob_parse, icase_variants
+from tests import search_harness as H
 from tests.icase_groups_ref import IcaseGroupsRef
 from tests.icase_ref import folded_occurrences
-from tests.test_icase_gpu import INTERVAL, PAIRS_0X20, device_reader, filler, make_index, mangle, mixed_case_lines
+from tests.icase_texts import PAIRS_0X20, mangle, mixed_case_lines
+from tests.search_harness import R, device_reader, filler, make_index, per_row as per_group
 
 pytestmark = pytest.mark.gpu
 
-R = _ffi.ROUTES
 
-
-def calls_of(kind, r):
-    if kind == 'all':
-        return r.search_all_ids_batch, r.search_all_batch_packed, r.count_all_bytes
-    return r.search_glob_ids_batch, r.search_glob_batch_packed, r.count_glob_bytes
-
-
-def check(kind, r, ref, batch, texts=True, order=True, interval=None):
-    """batch (groups for kind 'all', glob patterns for kind 'glob') on reader r against ref (the chunks r holds).
-    Returns the IdResult."""
-    batch = list(batch)
-    ids_call, packed_call, count_call = calls_of(kind, r)
-    res = ids_call(batch, icase=True)
-    st = r.last_stats()
-    ids, counts = res.ids, res.counts.tolist()
-    assert ids.dtype == np.uint64 and not ids.flags.writeable
-    assert len(counts) == len(batch) and sum(counts) == ids.size
-    live = bool(batch) and r.num_chunks > 0
-    want_hits = ref.hits(kind, batch) if live else 0
-
-    def stats_ok(st, counting, result_bytes):
-        assert st['queries'] == len(batch)
-        assert st['hits'] == want_hits, (st['hits'], want_hits)
-        assert st['entries'] == ids.size
-        if result_bytes is not None:
-            assert st['result_bytes'] == result_bytes
-        if not live:
-            return
-        route = st['route']
-        assert route & R['GENERAL'], hex(route)
-        assert not route & (R['ANCHORED'] | R['MID'] | R['MID_OVERFLOW'] | R['SMALL_BLOCK'] | R['SMALL_WAVE'] | R['SMALL_OVERFLOW'] |
-                            R['RESIDENT'] | R['SA_ORDER']), hex(route)
-        assert bool(route & R['COUNTS']) == counting, hex(route)
-        assert route & INTERVAL, hex(route)
-        if interval is not None:
-            assert route & INTERVAL == interval, hex(route)
-
-    stats_ok(st, False, 8 * ids.size)
-    assert counts == count_call(batch, icase=True)
-    stats_ok(r.last_stats(), True, None)
-    pos = 0
-    for g, c in zip(batch, counts):
-        got = ids[pos:pos + c]
-        pos += c
-        want = ref.search_all_ids(g) if kind == 'all' else ref.search_glob_ids(g)
-        assert np.unique(got).size == got.size, (g, 'an id twice')
-        assert np.array_equal(np.sort(got), want), (g, got[:8], want[:8])
-        if order:
-            assert np.array_equal(got, ref.ordered_ids(kind, g)), (g, 'order')
-    # the same entries, in the same order, as the packed text result
-    pk = packed_call(batch, icase=True)
-    stats_ok(r.last_stats(), False, pk.data.size)
-    by_id = r.entries_by_id_packed(ids)
-    assert pk.counts.tolist() == counts
-    assert np.array_equal(by_id.offsets, pk.offsets)
-    assert np.array_equal(by_id.data, pk.data)
-    if texts:       # ... and each is the text the reference has under that id
-        data, o = pk.data.tobytes(), pk.offsets.tolist()
-        assert [data[o[i]:o[i + 1]] for i in range(ids.size)] == [ref.entry(i) for i in ids.tolist()]
-    return res
-
-
-def per_group(res):
-    out, pos = [], 0
-    for c in res.counts.tolist():
-        out.append(res.ids[pos:pos + c])
-        pos += c
-    return out
+def check(kind, r, ref, batch, **kw):
+    """batch (groups for kind 'all', glob patterns for kind 'glob') on reader r against ref (the chunks r holds)."""
+    return H.check(H.ICASE_ALL if kind == 'all' else H.ICASE_GLOB, r, ref, list(batch), **kw)
 
 
 def chunks_of(lines_per_chunk, closed=True):
@@ -633,59 +569,9 @@ def test_placement(tmp_path, search_env):
             groups.append([ln[1:4].swapcase(), ln[4:8].swapcase()])
             globs.append(b'*' + ln[1:4].swapcase() + b'*' + ln[5:8].swapcase() + b'*')
 
-    def both(r, rf, **kw):
-        return check('all', r, rf, groups, **kw), check('glob', r, rf, globs, **kw)
-
-    whole = pysubstringsearch.Reader(p)
-    try:
-        # the line tables are absent until the id variant is called
-        fresh = whole.residency
-        whole.search_all_batch_packed(groups, icase=True), whole.count_glob_bytes(globs, icase=True)
-        assert whole.residency == fresh
-        base = both(whole, ref)
-        assert whole.residency['hbm_bytes'] > fresh['hbm_bytes']
-        hbm = fresh['hbm_bytes']
-        assert base[0].ids.size > 50 and base[1].ids.size > 50
-        chunk_of = [(b.ids >> np.uint64(32)).astype(np.int64) for b in base]
-        group_of = [np.repeat(np.arange(b.counts.size), b.counts.astype(np.int64)) for b in base]
-        for c, g in zip(chunk_of, group_of):
-            assert (np.diff(c)[np.diff(g) == 0] >= 0).all()                                       # chunk-major inside a group
-        # order='sa' has no effect
-        sa = pysubstringsearch.Reader(p, order='sa')
-        try:
-            for got, b in zip(both(sa, ref), base):
-                assert np.array_equal(got.ids, b.ids)
-        finally:
-            sa.close()
-        # devices=[0, 0]: the merge is keyed by groups -- part-major inside a group
-        multi = pysubstringsearch.Reader(p, devices=[0, 0])
-        try:
-            for got, b, c, g in zip(both(multi, ref, order=False), base, chunk_of, group_of):
-                assert got.counts.tolist() == b.counts.tolist()
-                key = np.lexsort((np.arange(b.ids.size), c % 2, g))
-                assert np.array_equal(got.ids, b.ids[key])
-        finally:
-            multi.close()
-        # shard (1, 2): the whole reader's ids of the odd chunks, in the same order
-        shard = pysubstringsearch.Reader(p, shard=(1, 2))
-        try:
-            sref = IcaseGroupsRef.from_index(p, keep=lambda c: c % 2 == 1)
-            for got, b, c in zip(both(shard, sref), base, chunk_of):
-                assert np.array_equal(got.ids, b.ids[c % 2 == 1]) and got.ids.size
-        finally:
-            shard.close()
-    finally:
-        whole.close()
-    # one suffix array too many for the budget: it stays in pinned host memory
-    search_env(PSS_READER_HBM_BUDGET=hbm - 1, PSS_READER_AUTO_RESIDENCY=0)
-    tier = pysubstringsearch.Reader(p)
-    try:
-        assert tier.residency['host_chunks'] >= 1
-        for got, b in zip(both(tier, ref), base):
-            assert np.array_equal(got.ids, b.ids)
-        assert tier.residency['host_chunks'] >= 1
-    finally:
-        tier.close()
+    # devices=[0, 0]: the merge is part-major inside a group, so the stated order is not compared there
+    assert H.placement(H.ICASE_ALL, p, groups, search_env, order_multi=False, ref=ref).ids.size > 50
+    assert H.placement(H.ICASE_GLOB, p, globs, search_env, order_multi=False, ref=ref).ids.size > 50
 
 
 # ---- 13. errors -----------------------------------------------------------------------------------------------------------------
@@ -695,7 +581,7 @@ def test_errors(shape_index):
     r = pysubstringsearch.Reader(p)
     try:
         before = check('all', r, ref, [[b'ab', b'C']])
-        for call in calls_of('all', r):
+        for call in (r.search_all_ids_batch, r.search_all_batch_packed, r.count_all_bytes):
             for bad in ([[b'']], [[b'ab', b'']], [([b'a'], [b''])], [[]], [([], [b'a'])]):
                 with pytest.raises(ValueError):
                     call(bad, icase=True)
@@ -704,7 +590,7 @@ def test_errors(shape_index):
                     call(bad, icase=True)
             with pytest.raises(TypeError):
                 call([[b'ab']], icase=1)
-        for call in calls_of('glob', r):
+        for call in (r.search_glob_ids_batch, r.search_glob_batch_packed, r.count_glob_bytes):
             for bad in ([b''], [b'*'], [b'ab', b'**']):
                 with pytest.raises(ValueError):
                     call(bad, icase=True)

@@ -20,8 +20,8 @@ SYMBOLS = ('pss_reader_search_terms_icase_batch', 'pss_reader_search_terms_icase
 
 
 def test_the_pairs_are_the_ones_the_plain_icase_tests_use():
-    from tests import test_icase_gpu
-    assert PAIRS_0X20 == test_icase_gpu.PAIRS_0X20
+    from tests import icase_texts
+    assert PAIRS_0X20 == icase_texts.PAIRS_0X20
 
 
 # ---- the reference against hand-written cases -----------------------------------------------------------------------------

@@ -9,7 +9,7 @@ import pytest
 
 from tests import local_rows_texts as L
 from tests import sa_edge_texts as E
-from tests.test_sa_gpu import _sa_device
+from tests.util import sa_device
 
 pytestmark = pytest.mark.gpu
 
@@ -39,7 +39,7 @@ def test_rows_and_records(oracle, monkeypatch, name, route):
         monkeypatch.setenv(k, val)
     t, want, v = _case(oracle, name)
     st = {}
-    sa = _sa_device(np.array(t), st)                      # (a writable copy: the text itself is shared between the routes)
+    sa = sa_device(np.array(t), st)                      # (a writable copy: the text itself is shared between the routes)
     note = (name, route)
     print(note, {k: st[k] for k in ('msd', 'msd_tiles', 'msd_slow_tiles', 'msd_finished', 'sum_active', 'rounds')},
           'model tiles', E.tile_count(t, route != 'msd_order'), 'finished', v.m.n_finished, 'left', v.m.n_left)

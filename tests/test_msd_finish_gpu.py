@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from tests import msd_finish_texts as F
-from tests.test_sa_gpu import _sa_device
+from tests.util import sa_device
 
 pytestmark = pytest.mark.gpu
 
@@ -52,7 +52,7 @@ def _model(key, t, fmt):
 
 def _build(t, want, f, note=None):
     st = {}
-    sa = _sa_device(np.asarray(t), st)
+    sa = sa_device(np.asarray(t), st)
     assert np.array_equal(sa, want), note
     assert st['msd'] == 1 and st['rle'] == 0 and st['period_path'] == 0, note
     assert (st['code_bits'], st['key_chars'], st['key_bits']) == (f.b, f.kc, f.kb), note      # the model's format is the sort's
@@ -296,5 +296,5 @@ def test_nothing_left(oracle, monkeypatch):
     mu = F.Model(u, F.Format(u.size, int(np.unique(u).size)))
     assert mu.n_finished == 0 and mu.n_left == 0
     su = {}
-    assert np.array_equal(_sa_device(u, su), oracle.sa(u))
+    assert np.array_equal(sa_device(u, su), oracle.sa(u))
     assert (su['sum_active'], su['rounds'], su['msd_finished']) == (0, 0, 0)

@@ -87,29 +87,10 @@ def test_known_multi_chunk_layout(oracle, tmp_path):
     assert r.search_multiple(['te', 'en']).count('ten') == 4   # duplicates across queries are kept
 
 
-def _kat_input(k, oracle):
-    from tests.util import gen_corpus
-    fib = [b'a', b'ab']
-    while len(fib[-1]) < 987:
-        fib.append(fib[-1] + fib[-2])
-    rng = np.random.default_rng(12345)
-    perm = rng.permutation(256).astype(np.uint8).tobytes()
-    zfn = np.array([0, 255, 10], dtype=np.uint8)[rng.integers(0, 3, 4096)].tobytes()
-    table = {
-        'a1000_nl': b'a' * 1000 + b'\n', 'fibonacci_987': fib[-1], 'perm256': perm, 'zero_ff_nl_4k': zfn,
-        'periodic_64x64': (b'a' * 63 + b'\n') * 64, 'all_zero_5000': b'\x00' * 5000,
-        'zeros_tail': b'\xff' * 4097 + b'\x00' * 17,
-        'readme_chunk': b'some short string\nanother but now a longer string\nmore text to add\n',
-    }
-    if k['name'] in table:
-        return table[k['name']]
-    kinds = {'lines_1MiB': 0, 'words_1MiB': 1, 'runs_1MiB': 2, 'periodic_1MiB': 3}
-    return gen_corpus(kinds[k['name']], 1 << 20).tobytes()
-
-
 def test_sa_kats_restatement(oracle):
+    from tests.util import kat_input
     for k in load('sa_kats.json')['kats']:
-        data = _kat_input(k, oracle)
+        data = kat_input(k)
         assert hashlib.sha256(data).hexdigest() == k['text_sha256'], k['name']
         if k['name'] in ('runs_1MiB', 'periodic_1MiB'):
             continue   # O(n log n) rounds x 1 MiB on CPU: covered by the GPU test

@@ -210,10 +210,9 @@ def test_one_mib_chunks_batch(tmp_path, oracle):
 
 
 def test_sa_kats_gpu():
-    from tests.test_oracle import _kat_input
-    from tests.util import sa_gpu
+    from tests.util import kat_input, sa_gpu
     for k in load('sa_kats.json')['kats']:
-        data = _kat_input(k, None)
+        data = kat_input(k)
         sa = sa_gpu(data)
         assert hashlib.sha256(sa.tobytes()).hexdigest() == k['sa_sha256'], k['name']
         if 'sa' in k:

@@ -10,8 +10,7 @@ import numpy as np
 import pytest
 
 from tests import sa_edge_texts as E
-from tests.test_sa_gpu import _sa_device
-from tests.util import gen_corpus
+from tests.util import gen_corpus, sa_device
 
 pytestmark = pytest.mark.gpu
 
@@ -30,7 +29,7 @@ def _case(oracle, key, make):
 
 def _build(t, want, note=None):
     st = {}
-    sa = _sa_device(np.asarray(t), st)
+    sa = sa_device(np.asarray(t), st)
     assert np.array_equal(sa, want), note
     assert st['rle'] == 0 and st['period_path'] == 0, note          # the sort and the rounds made this suffix array
     return st
@@ -224,7 +223,7 @@ def _builds(oracle, note):
     out = []
     for i, (t, want) in enumerate(_switch_texts(oracle)):
         st = {}
-        sa = _sa_device(np.asarray(t), st)
+        sa = sa_device(np.asarray(t), st)
         assert np.array_equal(sa, want), (note, i)
         st['n'] = t.size
         out.append(st)
@@ -250,7 +249,7 @@ def test_no_sample_at_2p24(oracle, monkeypatch, kind):
     _env(monkeypatch, PSS_NO_SAMPLE=1)
     t = gen_corpus(kind, 1 << 24)
     st = {}
-    sa = _sa_device(t, st, flags=8)
+    sa = sa_device(t, st, flags=8)
     assert hashlib.sha256(sa.tobytes()).hexdigest() == hashlib.sha256(oracle.sa(t).tobytes()).hexdigest()
     assert st['plan_hint'] == 0
     if kind == 0:

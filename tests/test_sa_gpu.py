@@ -6,7 +6,7 @@ import random
 import numpy as np
 import pytest
 
-from tests.util import gen_corpus, sa_gpu
+from tests.util import gen_corpus, sa_device, sa_gpu
 
 pytestmark = pytest.mark.gpu
 
@@ -165,20 +165,6 @@ def test_radix_sort_pairs_stable(n, bits):
 
 # ---- hybrid MSD initial sort (msd_sort.hip) ----
 
-def _sa_device(host, stats=None, flags=0):
-    import ctypes
-    import torch
-    from pysubstringsearch_amd import _ffi
-    n = host.size
-    dT = torch.from_numpy(host).cuda()
-    dSA = torch.empty(n, dtype=torch.int32, device='cuda')
-    st = _ffi.SaStats()
-    _ffi.check(_ffi.lib.pss_sa_build_device(dT.data_ptr(), dSA.data_ptr(), n, 0, flags, ctypes.byref(st)))
-    if stats is not None:
-        stats.update(st.as_dict())
-    return dSA.cpu().numpy()
-
-
 @pytest.mark.parametrize('slow_local', [False, True])
 def test_msd_initial_sort_forced_matches_libsais(oracle, monkeypatch, slow_local):
     """PSS_MSD=1 takes the hybrid MSD initial sort (two 10-bit partition passes over 8-byte elements +
@@ -200,7 +186,7 @@ def test_msd_initial_sort_forced_matches_libsais(oracle, monkeypatch, slow_local
             if rng.random() < 0.4:
                 t[rng.integers(0, n, max(1, n // 50))] = 10
             st = {}
-            sa = _sa_device(t, st)
+            sa = sa_device(t, st)
             took += int(st['msd'])
             assert np.array_equal(sa, oracle.sa(t)), (n, alpha, st['msd'])
     assert took > 40        # the path really ran (it declines only when a key or a bucket does not fit)
@@ -216,13 +202,13 @@ def test_msd_crowded_bins_and_oversized_buckets(oracle, monkeypatch):
     line = bytes(rng.integers(97, 123, 200).astype(np.uint8)) + b'\n'
     t = np.frombuffer(line * 3000, dtype=np.uint8).copy()              # 3000 copies: buckets of <= 3000 equal keys
     st = {}
-    sa = _sa_device(t, st)
+    sa = sa_device(t, st)
     assert np.array_equal(sa, oracle.sa(t))
     assert st['msd'] == 1 and st['msd_slow_tiles'] > 0
     mix = np.concatenate([rng.integers(97, 123, 1 << 20).astype(np.uint8), np.full(1 << 18, 97, np.uint8),
                           rng.integers(97, 123, 1 << 18).astype(np.uint8)])
     st = {}
-    sa = _sa_device(mix, st)
+    sa = sa_device(mix, st)
     assert np.array_equal(sa, oracle.sa(mix))
     assert st['msd'] == 0 and st['msd_max_bucket'] > 4088               # declined after the exact bucket count
 
@@ -233,12 +219,12 @@ def test_msd_is_chosen_for_high_entropy_text_only(oracle):
     from tests.util import gen_corpus
     st = {}
     t = gen_corpus(0, 1 << 24)
-    sa = _sa_device(t, st)
+    sa = sa_device(t, st)
     assert st['msd'] == 1 and st['msd_max_bucket'] <= 4088 and st['msd_slow_tiles'] == 0
     assert hashlib.sha256(sa.tobytes()).hexdigest() == hashlib.sha256(oracle.sa(t).tobytes()).hexdigest()
     st = {}
     t = gen_corpus(1, 1 << 24)
-    sa = _sa_device(t, st)
+    sa = sa_device(t, st)
     assert st['msd'] == 0
     assert hashlib.sha256(sa.tobytes()).hexdigest() == hashlib.sha256(oracle.sa(t).tobytes()).hexdigest()
 
@@ -279,7 +265,7 @@ def test_sample_sort_forced_matches_libsais(oracle, monkeypatch, local):
         else:
             monkeypatch.delenv('PSS_MODE', raising=False)
         st = {}
-        sa = _sa_device(t, st)
+        sa = sa_device(t, st)
         took += st['ss']
         assert st['ss'] == 1 and st['ss_max_bucket'] <= 4088, (trial, st['ss'], st['ss_max_bucket'])
         assert np.array_equal(sa, oracle.sa(t)), (trial, n, alpha)
@@ -293,7 +279,7 @@ def test_sample_sort_is_chosen_for_natural_text(oracle):
     for kind, want_ss, want_msd in ((1, 1, 0), (0, 0, 1)):
         t = gen_corpus(kind, 1 << 24)
         st = {}
-        sa = _sa_device(t, st)
+        sa = sa_device(t, st)
         assert (st['ss'], st['msd']) == (want_ss, want_msd), (kind, st['ss'], st['msd'])
         assert hashlib.sha256(sa.tobytes()).hexdigest() == hashlib.sha256(oracle.sa(t).tobytes()).hexdigest()
 
@@ -314,11 +300,11 @@ def test_initial_sort_plan_is_reused_and_checked(oracle, monkeypatch, front):
     lines = gen_corpus(0, n)
     want = hashlib.sha256(oracle.sa(lines).tobytes()).hexdigest()
     st = {}
-    _sa_device(lines, st, flags=8)       # (flags bit 3: a cold build, whatever earlier tests left on the device)
+    sa_device(lines, st, flags=8)       # (flags bit 3: a cold build, whatever earlier tests left on the device)
     # a first chunk whose symbols are close to uniform goes to the MSD sort on its symbol counts alone (plan_hint 3)
     assert (st['plan_hint'], st['msd']) == (3 if front else 0, 1)
     st = {}
-    sa = _sa_device(lines, st)
+    sa = sa_device(lines, st)
     assert (st['plan_hint'], st['msd']) == (2 if front else 1, 1)
     assert hashlib.sha256(sa.tobytes()).hexdigest() == want
     if front:
@@ -336,12 +322,12 @@ def test_initial_sort_plan_is_reused_and_checked(oracle, monkeypatch, front):
         odd[n // 3] = 126
         assert 126 not in np.unique(lines)
         st = {}
-        sa = _sa_device(odd, st)
+        sa = sa_device(odd, st)
         assert (st['plan_hint'], st['msd']) == (3, 1)           # (rebuilt without the plan: a first chunk again)
         assert hashlib.sha256(sa.tobytes()).hexdigest() == hashlib.sha256(oracle.sa(odd).tobytes()).hexdigest()
         # ... which is the plan now; the old text is over a subset of that alphabet and takes the larger table
         st = {}
-        sa = _sa_device(lines, st)
+        sa = sa_device(lines, st)
         assert (st['plan_hint'], st['msd'], st['sigma']) == (2, 1, len(np.unique(odd)))
         assert hashlib.sha256(sa.tobytes()).hexdigest() == want
     # same alphabet, crowded prefixes: a small vocabulary over the bytes of `lines`
@@ -353,19 +339,19 @@ def test_initial_sort_plan_is_reused_and_checked(oracle, monkeypatch, front):
     crowded = np.concatenate([vocab[-1]] + [vocab[i] for i in picks])[:n].copy()
     assert len(crowded) == n and np.array_equal(np.unique(crowded), alphabet)
     st = {}
-    sa = _sa_device(crowded, st)
+    sa = sa_device(crowded, st)
     if front:
         assert (st['plan_hint'], st['msd'], st['ss']) == (0, 0, 1)                                 # planned, refused, rebuilt
     else:
         assert (st['plan_hint'], st['msd'], st['ss']) == (1, 0, 1) and st['msd_max_bucket'] > 4088    # hinted, refused
     assert hashlib.sha256(sa.tobytes()).hexdigest() == hashlib.sha256(oracle.sa(crowded).tobytes()).hexdigest()
     st = {}
-    _sa_device(lines, st)
+    sa_device(lines, st)
     assert (st['plan_hint'], st['msd']) == (3 if front else 0, 1)      # the refusal cleared the plan
-    _sa_device(lines, {})
+    sa_device(lines, {})
     monkeypatch.setenv('PSS_NO_PLAN_CACHE', '1')              # (the build reads its switches on every call)
     st = {}
-    sa = _sa_device(lines, st)
+    sa = sa_device(lines, st)
     assert (st['plan_hint'], st['msd']) == (0, 1)
     assert hashlib.sha256(sa.tobytes()).hexdigest() == want
 
@@ -383,11 +369,11 @@ def test_sample_sort_plan_is_reused_across_chunks(oracle, monkeypatch):
     assert np.array_equal(np.unique(a), np.unique(b_)) and not np.array_equal(a, b_)
 
     def check(t, st):
-        sa = _sa_device(t, st)
+        sa = sa_device(t, st)
         assert hashlib.sha256(sa.tobytes()).hexdigest() == hashlib.sha256(oracle.sa(t).tobytes()).hexdigest()
 
     st = {}
-    _sa_device(a, st, flags=8)
+    sa_device(a, st, flags=8)
     assert (st['plan_hint'], st['ss'], st['ss_planned']) == (0, 1, 0)
     for t in (b_, a):
         st = {}
@@ -395,7 +381,7 @@ def test_sample_sort_plan_is_reused_across_chunks(oracle, monkeypatch):
         assert (st['plan_hint'], st['ss'], st['ss_planned'], st['msd']) == (2, 1, 1, 0)
     # a cold build forgets, and leaves a new plan
     st = {}
-    _sa_device(b_, st, flags=8)
+    sa_device(b_, st, flags=8)
     assert (st['plan_hint'], st['ss_planned']) == (0, 0)
     # a chunk a few entries shorter: the same geometry, the plan holds (splitters whose index lies beyond this chunk's end
     # are numbers like any other)
@@ -410,22 +396,22 @@ def test_sample_sort_plan_is_reused_across_chunks(oracle, monkeypatch):
     assert (st['ss'], st['ss_planned']) == (1, 0)
     # equal keys where no remembered splitter separates them (300 000 times one byte in the middle of the chunk): refused,
     # the build starts over with a sample of its own; the next chunk does not try the plan at once, the one after does
-    _sa_device(a, {}, flags=8)
+    sa_device(a, {}, flags=8)
     odd = a.copy()
     odd[1 << 23:(1 << 23) + 300000] = a[0]
     st = {}
     check(odd, st)
     assert (st['ss'], st['ss_planned'], st['ss_plan_refused']) == (1, 0, 1) and st['ms_restarts'] > 0, (st['ss_planned'], st['ss_plan_refused'])
     st = {}
-    _sa_device(b_, st)
+    sa_device(b_, st)
     assert (st['plan_hint'], st['ss_planned'], st['ss_plan_refused']) == (2, 0, 0)
     st = {}
     check(a, st)
     assert (st['ss_planned'], st['ss_plan_refused']) == (1, 0)
     monkeypatch.setenv('PSS_NO_PLAN_CACHE', '1')
-    _sa_device(a, {})
+    sa_device(a, {})
     st = {}
-    _sa_device(b_, st)
+    sa_device(b_, st)
     assert (st['plan_hint'], st['ss'], st['ss_planned']) == (0, 1, 0)
 
 
@@ -439,7 +425,7 @@ def test_sample_sort_samples_the_whole_text(oracle):
     t = gen_corpus(1, n)
     t[n - 50000:n - 20000] = ord('q')         # a run longer than 7 tiles where no sample used to fall
     st = {}
-    sa = _sa_device(t, st, flags=8)
+    sa = sa_device(t, st, flags=8)
     assert st['ss'] == 1 and st['ss_max_bucket'] <= 4088, (st['ss'], st['ss_max_bucket'])
     assert hashlib.sha256(sa.tobytes()).hexdigest() == hashlib.sha256(oracle.sa(t).tobytes()).hexdigest()
 
@@ -460,7 +446,7 @@ def test_real_files_chunk(oracle):
     t = np.frombuffer(raw, dtype=np.uint8).copy()
     t[-1] = 10
     st = {}
-    sa = _sa_device(t, st, flags=8)
+    sa = sa_device(t, st, flags=8)
     assert hashlib.sha256(sa.tobytes()).hexdigest() == hashlib.sha256(oracle.sa(t).tobytes()).hexdigest()
     assert st['anchor_left'] == 0            # (which sorts the build took depends on the files; on this image: sample sort + anchors)
 
@@ -523,7 +509,7 @@ def test_periodic_text_closed_form(oracle, monkeypatch, case):
         t = _periodic(b'ab', n, b'a' + bytes(rng.integers(97, 99, 1024).astype(np.uint8)))   # ('a' where 'b' was due) tail too long: declined
         taken = False
     st = {}
-    sa = _sa_device(t, st)
+    sa = sa_device(t, st)
     assert st['period_path'] == (1 if taken else 0), (case, st['period'], st['period_extent'])
     assert hashlib.sha256(sa.tobytes()).hexdigest() == hashlib.sha256(oracle.sa(t).tobytes()).hexdigest(), case
 
@@ -541,7 +527,7 @@ def test_periodic_text_random_words_and_tails(oracle):
         n = int(rng.integers(4 * 8192, 60000))
         t = _periodic(w, n, tail)
         st = {}
-        sa = _sa_device(t, st)
+        sa = sa_device(t, st)
         took += st['period_path']
         assert np.array_equal(sa, oracle.sa(t)), (w, tail, n, st['period'], st['period_extent'])
     assert took >= 60          # (a random word that is itself a repetition has a shorter period; a few are declined for size)
@@ -593,7 +579,7 @@ def test_rle_path_forced_matches_libsais(oracle, monkeypatch, expansion):
     cases.append(_runs_text(rng, (1 << 21) + 77, 2, 8192))
     for t in cases:
         st = {}
-        sa = _sa_device(t, st)
+        sa = sa_device(t, st)
         assert st['rle'] in (1, 2)
         walked += st['rle'] == 2
         assert np.array_equal(sa, oracle.sa(t)), (t.size, st['runs'])
@@ -630,7 +616,7 @@ def test_rle_path_is_chosen_for_long_runs_only(oracle, monkeypatch):
     for kind, want in ((0, 0), (1, 0), (2, 1), (3, 1)):
         st = {}
         t = gen_corpus(kind, 1 << 22)
-        sa = _sa_device(t, st)
+        sa = sa_device(t, st)
         assert (st['rle'] > 0) == bool(want), kind
         assert hashlib.sha256(sa.tobytes()).hexdigest() == hashlib.sha256(oracle.sa(t).tobytes()).hexdigest()
     rng = np.random.default_rng(9)
@@ -638,17 +624,17 @@ def test_rle_path_is_chosen_for_long_runs_only(oracle, monkeypatch):
     for o in rng.integers(0, t.size - 30000, 10):
         t[o:o + int(rng.integers(1000, 20000))] = 0                                    # zero padding inside random bytes
     st = {}
-    sa = _sa_device(t, st)
+    sa = sa_device(t, st)
     assert st['rle'] == 0 and st['runs'] * 8 > t.size                                 # runs are long but few: not worth it
     assert np.array_equal(sa, oracle.sa(t))
     t = _runs_text(rng, 1 << 20, 4, 64)
     st = {}
-    sa = _sa_device(t, st)
+    sa = sa_device(t, st)
     assert st['rle'] == 2
     assert np.array_equal(sa, oracle.sa(t))
     monkeypatch.setenv('PSS_RLE', '0')
     st = {}
-    sa0 = _sa_device(t, st)
+    sa0 = sa_device(t, st)
     assert st['rle'] == 0 and np.array_equal(sa0, sa)
 
 
@@ -863,13 +849,13 @@ def test_periodic_runs_inside_rank_rounds(oracle, monkeypatch, anchor):
     for t in _periodic_stretch_cases():
         want = oracle.sa(t)
         st = {}
-        got = _sa_device(t, st)
+        got = sa_device(t, st)
         assert (got == want).all()
         assert st['anchor_left'] == 0
         took += int(st['periodic_rounds'] > 0)
         monkeypatch.setenv('PSS_PERIODIC', '0')
         st0 = {}
-        got0 = _sa_device(t, st0)
+        got0 = sa_device(t, st0)
         monkeypatch.delenv('PSS_PERIODIC')
         assert (got0 == want).all() and st0['periodic_rounds'] == 0
         if st['periodic_rounds'] and anchor == '0':

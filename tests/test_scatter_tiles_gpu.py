@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 from tests import scatter_tile_texts as S
-from tests.test_sa_gpu import _sa_device
+from tests.util import sa_device
 
 pytestmark = pytest.mark.gpu
 
@@ -42,7 +42,7 @@ def test_tiles_of_both_passes(oracle, monkeypatch, name, order):
         monkeypatch.setenv('PSS_MSD_LSD', ORDERS[order])
     t, want = _case(oracle, name)
     st = {}
-    sa = _sa_device(np.array(t), st)                      # (a writable copy: the text itself is shared between the orders)
+    sa = sa_device(np.array(t), st)                      # (a writable copy: the text itself is shared between the orders)
     note = (name, order)
     print(note, {k: st[k] for k in ('msd', 'msd_tiles', 'msd_max_bucket', 'code_bits', 'key_chars', 'key_bits')})
     assert np.array_equal(sa, want), note

@@ -11,19 +11,15 @@ import pytest
 
 import pysubstringsearch
 from pysubstringsearch_amd import _ffi
+from tests.search_harness import filler
 from tests.search_ref import SearchRef
 
 pytestmark = pytest.mark.gpu
 
 R = _ffi.ROUTES
 MID_CAP = 65536                 # hits the mid pipeline takes (search.hip, MID_MAX)
-FILLER = b'abcdefghijklmnop'    # marker queries use none of these bytes
 MISSES = [b'\x01MISS0', b'QQ', b'MKAx~', b'zzzzzzzzzzzzzzzzzzzz']
 MIXED = [b'MKA', b'\x01MISS0', b'MKB', b'MKD', b'abc', b'QQ', b'MKD' + b'x', b'MKA\n']      # hits and misses, 8 queries
-
-
-def filler(rng, n):
-    return bytes(np.frombuffer(FILLER, np.uint8)[rng.integers(0, len(FILLER), n)])
 
 
 class Index:

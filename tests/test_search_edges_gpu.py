@@ -15,24 +15,14 @@ import pytest
 
 import pysubstringsearch
 from pysubstringsearch_amd import _ffi
+from tests.search_harness import FUSED, SEEN, filler, finished, make_index
 from tests.search_ref import SearchRef
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 R = _ffi.ROUTES
-SEEN = [0]                      # union of the routes that FINISHED a batch in this module (and of the overflow bits)
 SM_MAX_HITS = 1024              # hits of one pair that the wave kernel takes (search.hip); the block path takes 1024 per workgroup
-FUSED = R['SMALL_BLOCK'] | R['SMALL_WAVE']
-
-
-def finished(rt):
-    """The route bits of a batch without the routes that overflowed (a later route answered in their place)."""
-    if rt & R['SMALL_OVERFLOW']:
-        rt &= ~FUSED
-    if rt & R['MID_OVERFLOW']:
-        rt &= ~R['MID']
-    return rt
 
 
 def expect_route(rt, want, what=''):
@@ -43,25 +33,6 @@ def expect_route(rt, want, what=''):
         assert not rt & R['SMALL_OVERFLOW'], (what, 'the fused kernel overflowed', hex(rt))
     if want & R['MID'] and not want & R['MID_OVERFLOW']:
         assert not rt & R['MID_OVERFLOW'], (what, 'the mid pipeline overflowed', hex(rt))
-
-
-FILLER = b'abcdefghijklmnop'    # marker queries use none of these bytes
-
-
-def filler(rng, n):
-    return bytes(np.frombuffer(FILLER, np.uint8)[rng.integers(0, len(FILLER), n)])
-
-
-def make_index(tmp_path, name, data, max_chunk_len=None):
-    """HIP Writer over the lines of `data` (no '\\r' before a '\\n': the line rule would strip it)."""
-    assert b'\r\n' not in data
-    src = tmp_path / (name + '.txt')
-    src.write_bytes(data)
-    p = str(tmp_path / (name + '.idx'))
-    w = pysubstringsearch.Writer(p, max_chunk_len)
-    w.add_entries_from_file_lines(str(src))
-    w.close()
-    return p
 
 
 class Case:

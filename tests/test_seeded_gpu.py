@@ -1,7 +1,7 @@
 """What only the one seeded verify path (seed_impl.h) can break: the case-insensitive and the near
 batches share one host stage, one workspace layout and one kernel frame.  Every batch here goes through the check() of
-its own kind -- tests/test_icase_gpu.py, tests/test_icase_groups_gpu.py, tests/test_near_gpu.py, tests/test_entry_ids_gpu.py:
-ids, packed text and counts against the brute-force references, in full.
+tests/search_harness.py under its own kind -- near, case-insensitive, case-insensitive groups and globs, plain ids: ids,
+packed text and counts against the brute-force references, in full.
   1. The kinds alternate on one reader: void flags, budgets, the overflow flag and the seed positions of an earlier batch
      of the other kind and another size lie in the same grow-only workspace slot.
   2. Seed positions are per QUERY: neighbours in one batch differ in both seed position and spelling count, and every
@@ -14,10 +14,7 @@ from tests.entry_id_ref import IdRef
 from tests.icase_groups_ref import IcaseGroupsRef
 from tests.icase_ref import IcaseRef
 from tests.near_ref import NearRef
-from tests.test_entry_ids_gpu import check as check_plain
-from tests.test_icase_gpu import check as check_icase, device_reader, per_pattern
-from tests.test_icase_groups_gpu import check as check_groups, per_group
-from tests.test_near_gpu import check as check_near
+from tests.search_harness import ICASE, ICASE_ALL, ICASE_GLOB, NEAR, PLAIN, check, device_reader, per_row
 
 pytestmark = pytest.mark.gpu
 
@@ -44,17 +41,17 @@ def test_kinds_alternate_on_one_reader():
     r = device_reader(texts)
     try:
         for _ in range(2):
-            res = per_pattern(check_near(r, refs['near'], near5, budgets5))
+            res = per_row(check(NEAR, r, refs['near'], (near5, budgets5)))
             assert res[0].size and res[1].size > res[0].size and res[2].size == 0 and res[3].size and res[4].size
-            res = per_pattern(check_icase(r, refs['icase'], icase3))
+            res = per_row(check(ICASE, r, refs['icase'], icase3))
             assert all(x.size >= 3 for x in res)
-            res = per_group(check_groups('all', r, refs['groups'], groups))
+            res = per_row(check(ICASE_ALL, r, refs['groups'], groups))
             assert all(x.size for x in res)
-            res = per_group(check_groups('glob', r, refs['groups'], globs))
+            res = per_row(check(ICASE_GLOB, r, refs['groups'], globs))
             assert all(x.size for x in res)
-            res = per_pattern(check_near(r, refs['near'], near2, budgets2))
+            res = per_row(check(NEAR, r, refs['near'], (near2, budgets2)))
             assert all(x.size for x in res)
-            res = check_plain(r, refs['plain'], [b'timeout', b'500', b'ERROR', b'nope'])
+            res = check(PLAIN, r, refs['plain'], [b'timeout', b'500', b'ERROR', b'nope'])
             assert all(c > 0 for c in res.counts.tolist()[:3]) and res.counts[3] == 0
     finally:
         r.close()
@@ -92,9 +89,9 @@ def test_seed_positions_are_per_query(search_env):
     assert ref.seed_hits(seeds[1][1][0]) == 6 and ref.seed_hits(b'1a2') == 4 and ref.seed_hits(b'#=') == 4
     r = device_reader(texts)
     try:
-        res = per_pattern(check_icase(r, ref, patterns))
+        res = per_row(check(ICASE, r, ref, patterns))
         assert [x.size for x in res] == [2, 2, 2]
-        res2 = per_group(check_groups('all', r, gref, [[p] for p in patterns]))
+        res2 = per_row(check(ICASE_ALL, r, gref, [[p] for p in patterns]))
         assert all(np.array_equal(a, b) for a, b in zip(res, res2))
     finally:
         r.close()

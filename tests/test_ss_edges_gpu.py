@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 from tests import ss_edge_texts as X
-from tests.test_sa_gpu import _sa_device
+from tests.util import sa_device
 
 pytestmark = pytest.mark.gpu
 
@@ -43,7 +43,7 @@ def _build(monkeypatch, case, plan, mode=None, note=None):
     if mode:
         monkeypatch.setenv('PSS_MODE', mode)
     st = {}
-    sa = _sa_device(np.asarray(t), st)
+    sa = sa_device(np.asarray(t), st)
     note = (note, plan, mode)
     assert np.array_equal(sa, want), note
     assert st['rle'] == 0 and st['period_path'] == 0, note

@@ -19,7 +19,7 @@ import pysubstringsearch  # noqa: E402
 from oracle import oracle as O  # noqa: E402
 from pysubstringsearch_amd import Reader  # noqa: E402
 from tests import search_fuzz_cases  # noqa: E402
-from tests.test_search_fuzz_gpu import run_case  # noqa: E402
+from tests.search_harness import run_case  # noqa: E402
 
 KIND_SWITCHES = ('PSS_LANE_SEARCH_MIN', 'PSS_WAVE_SEARCH', 'PSS_NO_GROUP_SEARCH', 'PSS_NO_SEARCH_STAGE', 'PSS_NO_PINNED_RESULTS',
                  'PSS_NO_MID_PIPELINE', 'PSS_SAMPLE_SHIFT', 'PSS_NO_KEY_SAMPLES', 'PSS_ICASE_SEED_LETTERS', 'PSS_NO_SMALL_PATH',

@@ -18,23 +18,15 @@ warmed up, then timed `--reps` times with a host clock around the whole leg (eve
 synchronise); the legs alternate for `--rounds` rounds.  Reported: median / min / max per leg and round, the spread of the
 medians across the rounds, hits against entries and the device time (last_stats) of the leg's last search call.  No
 threshold: a record, not a test."""
-import argparse
 import collections
-import ctypes
 import json
-import os
 import re
 import statistics
-import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-
-from icase_timing import CHUNK_BYTES, commit_hash, mangle_words  # noqa: E402
+from icase_timing import mangle_words
+from timing_common import arguments, commit_hash, medians, per_row, time_legs, words_reader, write_json
 
 
 def pick_pairs(text: bytes, count: int):
@@ -48,47 +40,15 @@ def pick_pairs(text: bytes, count: int):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'icase_groups_vs_host.json'))
-    ap.add_argument('--commit', default=None, help='commit the library was built from (default: git rev-parse HEAD)')
-    ap.add_argument('--groups', type=int, default=32)
-    ap.add_argument('--warmup', type=int, default=3)
-    ap.add_argument('--reps', type=int, default=10)
-    ap.add_argument('--rounds', type=int, default=3)
-    args = ap.parse_args()
-
-    import torch
-
-    import pysubstringsearch_amd as P
-    from pysubstringsearch_amd import _ffi
-    if P.device_count() < 1:
-        raise SystemExit('no HIP device: nothing to measure')
-
-    n = CHUNK_BYTES
-    text = np.empty(n, dtype=np.uint8)
-    _ffi.check(_ffi.lib.pss_gen_corpus(_ffi.CORPUS_WORDS, text.ctypes.data, n, 0))
-    text[n - 1] = 0x0A
-    mangle_words(text, np.random.default_rng(20))
+    args = arguments('icase_groups_vs_host.json', ('--groups', 32))
+    r, text, _ = words_reader(edit=lambda t: mangle_words(t, np.random.default_rng(20)))
     pairs = pick_pairs(text.tobytes(), args.groups)
-    groups = [[f, r.upper()] for f, r in pairs]
+    groups = [[f, x.upper()] for f, x in pairs]
     terms = [t for g in groups for t in g]
-    order = [(f.upper(), r) if g % 2 == 0 else (r.upper(), f) for g, (f, r) in enumerate(pairs)]
+    order = [(f.upper(), x) if g % 2 == 0 else (x.upper(), f) for g, (f, x) in enumerate(pairs)]
     globs = [b'*' + a + b'*' + b + b'*' for a, b in order]
     regexes = [re.compile(b'.*' + re.escape(a) + b'.*' + re.escape(b) + b'.*', re.IGNORECASE | re.DOTALL) for a, b in order]
-    sa = np.empty(n, dtype=np.int32)
-    _ffi.check(_ffi.lib.pss_sa_build(text.ctypes.data, sa.ctypes.data, n, 0))
-
-    h = ctypes.c_void_p()
-    _ffi.check(_ffi.lib.pss_reader_create(0, ctypes.byref(h)))
-    r = P.Reader._from_handle(h)
-    dt, ds = torch.from_numpy(text).cuda(), torch.from_numpy(sa).cuda()
-    _ffi.check(_ffi.lib.pss_reader_add_chunk_device(h, dt.data_ptr(), ds.data_ptr(), n))
-    del dt, ds
     seen = {}
-
-    def per_row(res):
-        b = np.concatenate(([0], np.cumsum(res.counts.astype(np.int64))))
-        return [res.ids[b[g]:b[g + 1]] for g in range(len(res.counts))]
 
     def all_device():
         res = r.search_all_ids_batch(groups, icase=True)
@@ -124,24 +84,9 @@ def main():
             if not np.array_equal(np.sort(x), np.sort(y)):
                 raise SystemExit(f'{dev}, row {g}: {x.size} ids against {y.size} of {host}')
 
-    runs = []
-    for _ in range(args.rounds):
-        for name, call in legs.items():
-            times = []
-            for i in range(args.warmup + args.reps):
-                t0 = time.perf_counter()
-                out = call()
-                t = time.perf_counter() - t0
-                if i >= args.warmup:
-                    times.append(t * 1e3)
-            st = seen[name]
-            runs.append({'leg': name, 'median_ms': round(statistics.median(times), 4), 'min_ms': round(min(times), 4),
-                         'max_ms': round(max(times), 4), 'reps': args.reps, 'entries': int(sum(x.size for x in out)),
-                         'queries_search_call': int(st['queries']), 'hits_search_call': int(st['hits']),
-                         'entries_search_call': int(st['entries']), 'ms_device_search_call': round(st['ms_device'], 4),
-                         'ms_interval_search_call': round(st['ms_interval'], 4), 'route': hex(st['route'])})
+    runs = time_legs(legs, seen, args.warmup, args.reps, args.rounds)
     r.close()
-    summary = {name: [x['median_ms'] for x in runs if x['leg'] == name] for name in legs}
+    summary = medians(runs, legs)
     med = {name: statistics.median(v) for name, v in summary.items()}
     out = {'what': 'search_all_ids_batch(groups, icase=True), 32 groups [frequent, RARE], vs search_icase_ids_batch over the 64 terms + '
                    'np.intersect1d per group on the host; search_glob_ids_batch(patterns, icase=True), 32 patterns *FREQUENT*RARE* / '
@@ -150,16 +95,13 @@ def main():
                    '(packing the batch in Python and the host-side work included), median / min / max over reps after warm-up; the legs '
                    'alternate; the device answers were compared with the host legs row by row before the timing; hits / entries / '
                    'ms_device are last_stats() of the leg\'s last search call',
-           'commit': args.commit or commit_hash(), 'chunk_bytes': n, 'pairs': [[f.decode(), x.decode()] for f, x in pairs],
+           'commit': args.commit or commit_hash(), 'chunk_bytes': text.size, 'pairs': [[f.decode(), x.decode()] for f, x in pairs],
            'warmup': args.warmup, 'reps': args.reps, 'rounds': args.rounds, 'runs': runs, 'summary': summary,
            'median_of_medians_ms': {k: round(v, 4) for k, v in med.items()},
            'spread_of_medians_ms': {k: [round(min(v), 4), round(max(v), 4)] for k, v in summary.items()},
            'all_host_over_all_device': round(med['all_host'] / med['all_device'], 2),
            'glob_host_over_glob_device': round(med['glob_host'] / med['glob_device'], 2)}
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, 'w') as f:
-        json.dump(out, f, indent=1)
-        f.write('\n')
+    write_json(out, args.out)
     print(json.dumps({'median_of_medians_ms': out['median_of_medians_ms'], 'spread_of_medians_ms': out['spread_of_medians_ms'],
                       'all_host_over_all_device': out['all_host_over_all_device'],
                       'glob_host_over_glob_device': out['glob_host_over_glob_device']}))

@@ -23,7 +23,8 @@ import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from timing_common import ROOT, spread, write_json
+
 CHUNKS, CHUNK_BYTES, CORPUS_WORDS = 15, 1 << 20, 1
 
 
@@ -62,7 +63,7 @@ def ok(L, rc):
         raise RuntimeError(f'libpss error {rc}: {buf.value.decode("utf-8", "replace")}')
 
 
-def make_index(L, path, nq, seed=1):
+def write_index(L, path, nq, seed=1):
     """The index file and the query batch (blob, u64 offsets)."""
     rng = np.random.default_rng(seed)
     queries = []
@@ -97,8 +98,7 @@ def timed(L, call, h, blob, offs, warmup, reps):
         L.pss_result_free(res)
         if i >= warmup:
             times.append(dt * 1e3)
-    return {'median_ms': round(statistics.median(times), 4), 'min_ms': round(min(times), 4), 'max_ms': round(max(times), 4),
-            'reps': reps, 'entries': entries, 'bytes': nbytes}
+    return {**spread(times, reps), 'entries': entries, 'bytes': nbytes}
 
 
 def child(args):
@@ -106,7 +106,7 @@ def child(args):
     out = {'lib': os.path.basename(args.lib)}
     with tempfile.TemporaryDirectory() as d:
         p = os.path.join(d, 'words15.idx')
-        blob, offs = make_index(L, p, args.queries)
+        blob, offs = write_index(L, p, args.queries)
         out['queries'] = len(offs) - 1
 
         def open_reader():
@@ -190,10 +190,7 @@ def main():
                       'ids_median_ms': last['ids']['median_ms'], 'packed_median_ms_same_run': last['packed']['median_ms'],
                       'entries': last['ids']['entries'], 'ids_bytes': last['ids']['bytes'], 'packed_bytes': last['packed']['bytes'],
                       'line_tables_build_per_chunk_ms': last['ids']['build_per_chunk_ms'], 'line_table_bytes': last['ids']['table_bytes']}
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, 'w') as f:
-        json.dump(out, f, indent=1)
-        f.write('\n')
+    write_json(out, args.out)
     print(json.dumps(out['summary']))
 
 

@@ -1,6 +1,6 @@
 import sys, numpy as np
 sys.path.insert(0, '.')
-import tests.test_fullsize_gpu as T
+import tests.fullsize_corpus as T
 reader, texts, sas = T._corpus_reader(29, 15, keep_sa=False, kind='words')
 for qmin in (10, 12, 16):
     q = T._batch(texts, 100000, qmin=qmin)
