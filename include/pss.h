@@ -218,6 +218,10 @@ int32_t pss_sa_build(const uint8_t *T, int32_t *SA, int32_t n, int32_t device);
  * device left behind first (a COLD build: what the first chunk of a corpus sees;
  * bench.py's value_cold).  This is the timed region of bench.py: inputs resident,
  * no PCIe. */
+#define PSS_SA_PROFILE 1u                   /* bit 0 */
+#define PSS_SA_NO_PLAN 2u                   /* bit 1 */
+#define PSS_SA_NO_FIRST_CHUNK_SHORTCUT 4u   /* bit 2 */
+#define PSS_SA_COLD 8u                      /* bit 3 */
 int32_t pss_sa_build_device(const void *d_T, void *d_SA, int32_t n, int32_t device,
                             uint32_t flags, pss_sa_stats *stats);
 

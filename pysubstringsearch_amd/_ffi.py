@@ -15,6 +15,9 @@ PSS_OK, PSS_EINVAL, PSS_ENOMEM, PSS_EIO, PSS_ETOOBIG, PSS_EDEVICE, PSS_EFORMAT =
 CORPUS_LINES, CORPUS_WORDS, CORPUS_RUNS, CORPUS_PERIODIC = 0, 1, 2, 3
 CORPUS_REPEAT_LINE, CORPUS_DUP_BLOCKS, CORPUS_MIXED, CORPUS_SOURCE = 4, 5, 6, 7
 
+# flags of pss_sa_build_device (include/pss.h)
+SA_PROFILE, SA_NO_PLAN, SA_NO_FIRST_CHUNK_SHORTCUT, SA_COLD = 1, 2, 4, 8
+
 
 class SaStats(ctypes.Structure):
     _fields_ = [

@@ -19,6 +19,7 @@
 
 #include "../../include/pss.h"
 
+#include "build_plan.h"
 #include "knobs.h"
 
 namespace pss {
@@ -157,28 +158,9 @@ struct DeviceCtx {
     static constexpr size_t kResidentMailboxOff = 24576;   // inside the first 32 KiB of the arena (search.hip, SM_OFF_*)
     int ensure_resident();               // stream + arena, once
     void stop_resident();                // tells a running kernel to leave and waits for it (cheap when none runs)
-    // Which initial sort the last build on this device took, and for what kind of text (the byte values present, the
-    // size class): consecutive chunks of one corpus take the same one, so the next build skips the sizing sample that
-    // would only say so again (sa_build.hip; a wrong guess is caught by the sorts' own exact checks and costs one restart).
-    uint32_t plan_present[8] = {};
-    uint32_t plan_logn = 0;
-    int plan_path = 0;                   // 0 none, 1 hybrid MSD, 2 sample sort
-    uint8_t plan_lut[256] = {};          // ... and its byte -> code table (the next build recodes with it inside the sort)
-    uint32_t plan_sigma = 0;
-    // ... 2: it took the sample sort, whose sorted sample (slot S_SSPLAN of sa_build.hip) cuts the next chunk of that
-    // exact size and alphabet too
-    uint64_t ss_plan_tag = 0;            // ss_geometry_tag() of the text the sample came from (0: none)
-    uint32_t ss_plan_radix = 0;
-    bool ss_refused_note = false;        // (the running build started over because the plan's sample was refused)
-    uint32_t ss_plan_skip = 0, ss_plan_backoff = 0;      // builds that go by before the plan is tried again after a refusal
-    // ... and whether its anchors were sorted beside the text round (sa_build.hip, SideAnchors): the depth that side line
-    // was started for, the size class and the bits per symbol.  The next chunk of that kind starts its side line at once --
-    // beside the initial sort as well -- instead of waiting for a sample of its ties to show copies.
-    uint64_t side_plan_heff = 0;
-    uint32_t side_plan_logn = 0;
-    int side_plan_b = 0;
-    double restart_ms = 0.0;             // device time of the attempts the running build gave up (sa_build.hip, start_over)
-    int restart_depth = 0;
+    // What the last build on this device leaves for the next one: its choice of initial sort, the sample sort's kept
+    // sample, the depth of its side line (build_plan.h).
+    BuildPlan plan;
     // Two pinned staging buffers + a copy stream: file <-> HBM transfers are
     // double-buffered so the PCIe copy of piece i overlaps the file I/O of piece i+1.
     static constexpr size_t kStage = (size_t)64 << 20;

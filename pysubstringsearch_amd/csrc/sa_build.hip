@@ -217,7 +217,6 @@ int suffix_rounds_integer(DeviceCtx *ctx, uint32_t m, uint64_t *K[2], uint32_t *
     const size_t sort_ws = radix_sort_workspace_bytes();
     PSS_TRY(ctx->slot[S_WORK].reserve(sort_ws + 65536));
     u8 *work = ctx->slot[S_WORK].as<u8>();
-    u8 *small = work + sort_ws;                       // the same 64 KiB of small device state as in sa_build_device
     RoundsIO io;
     io.n = m;
     io.SA = SA_out;
@@ -237,11 +236,7 @@ int suffix_rounds_integer(DeviceCtx *ctx, uint32_t m, uint64_t *K[2], uint32_t *
     io.msd_active = 0;
     io.no_sparse = false;
     io.work = work;
-    io.d_agg_head = reinterpret_cast<u32 *>(small + 4096);
-    io.d_agg_cnt = reinterpret_cast<u32 *>(small + 8192);
-    io.d_red = reinterpret_cast<u64 *>(small + 12288);
-    io.d_counters = reinterpret_cast<u32 *>(small + 12288 + 64);
-    io.h_small = static_cast<u32 *>(ctx->pinned);
+    SmallState(work + sort_ws, ctx->pinned).lend(io);
     io.profile = false;
     SortStats ss;
     pss_sa_stats local;
@@ -250,34 +245,127 @@ int suffix_rounds_integer(DeviceCtx *ctx, uint32_t m, uint64_t *K[2], uint32_t *
     return PSS_OK;
 }
 
-int sa_build_device(DeviceCtx *ctx, const void *d_T, void *d_SA, int32_t n_in, uint32_t flags, pss_sa_stats *stats)
-{
-    pss_sa_stats st;
-    memset(&st, 0, sizeof st);
-    if (n_in < 0 || (n_in > 0 && (d_T == nullptr || d_SA == nullptr))) {
-        set_error("pss_sa_build: bad arguments");
-        return PSS_EINVAL;
-    }
-    const u32 n = (u32)n_in;
-    const bool profile = flags & 1u;
-    if (flags & 8u) {                // a cold build: nothing of earlier builds on this device is used
-        ctx->plan_path = 0;
-        ctx->ss_plan_skip = ctx->ss_plan_backoff = 0;
-        ctx->side_plan_heff = 0;
-        flags &= ~8u;                // (a restart of THIS build keeps what it has learnt)
-    }
-    const Knobs knobs = Knobs::read();
-    hipStream_t s = ctx->stream;
-    if (n < 2) {
-        if (n == 1) PSS_HIP(hipMemsetAsync(d_SA, 0, 4, s));
-        PSS_HIP(hipStreamSynchronize(s));
-        if (stats) *stats = st;
-        return PSS_OK;
-    }
-    const u8 *T = static_cast<const u8 *>(d_T);
-    u32 *SA = static_cast<u32 *>(d_SA);
+// ---- host driver of one build ---------------------------------------------------------------------------------------
+// sa_build_device makes attempts until one finishes; an attempt whose shortcut did not hold (a remembered plan, the symbol
+// counts of a first chunk) gives up and says with which flags to start over.  One attempt is one Build, and Build::run
+// reads top to bottom: carve -> start_clock -> [screen_text -> try_run_length -> try_periodic] -> choose_codes ->
+// make_codes -> size_key -> try_msd -> try_sample_sort -> remember_plan -> lsd_passes -> run_rounds -> finish.
+// The stages share one Build: the request normalised into the few values they read, the carved workspace, the timer,
+// the side line and the statistics.  What one build leaves for the next on its device is ctx->plan (build_plan.h).
+namespace {
 
-    const size_t n_pad = round_up((size_t)n, 16) + 64;
+// What the attempts a build gave up leave for the one that finishes it.
+struct Abandoned {
+    double ms = 0.0;                    // their device time (ms_restarts, part of ms_total)
+    bool ss_refused = false;            // one of them started over because the plan's sample was refused
+};
+
+enum class Next { go_on, finished, start_over };       // what a stage says: the next stage | the suffix array is written | give_up() has run
+
+struct Build {
+    DeviceCtx *ctx;
+    hipStream_t s;
+    BuildPlan &plan;
+    Abandoned &past;
+    pss_sa_stats *stats;
+    // the request, normalised once
+    const u8 *T;
+    u32 *SA;
+    const u32 n;
+    const uint32_t flags;
+    uint32_t again_flags = 0;           // ... of the next attempt, when this one gave up
+    const Knobs knobs;
+    const bool profile;
+    bool plain;                         // every switch at its default, and no build without shortcuts asked for
+    uint32_t logn = 0;                  // floor(log2 n): the size class
+    const bool aligned;                 // T is 16-byte aligned
+    bool fronted;                       // no alphabet pass: the remembered table, codes made inside the MSD sort's first pass
+    bool shortcut_ok;                   // a first chunk may go to the MSD sort on its symbol counts alone (-> fresh)
+    const size_t n_pad;
+    const int grid_stream;
+    // the workspace
+    u8 *work = nullptr, *codes = nullptr;
+    SmallState sm{};
+    u64 *K[2] = {};
+    u32 *V[2] = {}, *ISA = nullptr, *P[2] = {}, *GRP = nullptr;
+    u32 *h_small = nullptr;
+    BuildTimer timer;
+    SideAnchors side;
+    pss_sa_stats st;
+    // screen_text
+    u8 *h_head = nullptr;
+    u32 head_len = 0, text_runs = 0;
+    bool look_for_period = false;
+    // choose_codes
+    u8 lut[256];
+    u32 sigma = 0;
+    int b = 1, plus_one = 0, kmax = 0, key_chars = 0;
+    bool fresh = false, front_any = false, forced_chars = false;
+    // size_key
+    SortStats ss;
+    uint32_t present_bits[8] = {};
+    int hint = 0, key_drop = 0, key_bits0 = 0, final_buf = 0, cur = 0;
+    bool msd_screen_ok = false, sampled = false, ties = false;
+    u32 *v_scratch = nullptr;
+    // the initial sort
+    bool sorted = false, msd_fused = false;             // sorted: by the MSD sort or the sample sort (else the LSD passes do it)
+    u32 msd_active = 0;
+
+    Build(DeviceCtx *c, const u8 *text, u32 *sa, u32 len, uint32_t fl, Abandoned &gone, pss_sa_stats *out)
+        : ctx(c), s(c->stream), plan(c->plan), past(gone), stats(out), T(text), SA(sa), n(len), flags(fl), knobs(Knobs::read()),
+          profile(fl & PSS_SA_PROFILE), aligned((reinterpret_cast<uintptr_t>(text) & 15u) == 0), n_pad(round_up((size_t)len, 16) + 64),
+          grid_stream(c->num_cus * 8)
+    {
+        memset(&st, 0, sizeof st);
+        while ((2u << logn) <= n && logn < 31) ++logn;
+        plain = knobs.key_chars == 0 && !knobs.no_sample && !knobs.no_flags && knobs.msd < 0 && knobs.ss < 0 &&
+                knobs.key_drop < 0 && knobs.mode < 0 && !knobs.no_msd_fuse && !knobs.no_plan && knobs.rle < 0 &&
+                knobs.period != 0 && (flags & PSS_SA_NO_PLAN) == 0;
+        // The plan of the previous build on this device (see size_key): when it took the MSD sort on a text of this size class
+        // and every switch is at its default, this build does not look at its alphabet first either -- it recodes with the
+        // remembered byte -> code table inside the sort's first histogram pass (msd_hist_raw_kernel: the alphabet pass, the
+        // recode pass and a host round trip fold into it, 0.4 ms at n = 2^29), which also checks that every byte has a code
+        // there.  A text over a subset of the remembered alphabet is sorted correctly with the larger table; a new byte, a
+        // crowded bucket, or anything else the sort declines for starts the build over without the plan -- the run-length
+        // and periodic-text checks, which this shortcut skips, then take place as always.
+        fronted = plan.fronted(logn, aligned, plain, knobs.no_front);
+        shortcut_ok = plain && !knobs.no_front && (flags & PSS_SA_NO_FIRST_CHUNK_SHORTCUT) == 0 && n >= kPlanMinN;
+    }
+    int run(Next *next);
+    int carve(), start_clock(), screen_text(), try_run_length(Next *next), try_periodic(Next *next);
+    void choose_codes(), remember_plan();
+    int make_codes(), size_key(), try_msd(Next *next), try_sample_sort(Next *next), sample_sort(Next *next), lsd_passes(), run_rounds();
+    int give_up(uint32_t new_flags, Next *next), finish(bool early);
+    bool ss_room();
+    int active_handover(MsdActive *act);
+};
+
+int Build::run(Next *next)
+{
+    *next = Next::go_on;
+    PSS_TRY(carve());
+    PSS_TRY(start_clock());
+    if (!fronted) {
+        PSS_TRY(screen_text());
+        PSS_TRY(try_run_length(next));
+        if (*next == Next::go_on) PSS_TRY(try_periodic(next));
+        if (*next == Next::finished) return finish(true);
+    }
+    choose_codes();
+    PSS_TRY(make_codes());
+    PSS_TRY(size_key());
+    PSS_TRY(try_msd(next));
+    if (*next == Next::go_on) PSS_TRY(try_sample_sort(next));
+    if (*next == Next::start_over) return PSS_OK;
+    remember_plan();
+    PSS_TRY(lsd_passes());
+    PSS_TRY(run_rounds());
+    *next = Next::finished;
+    return finish(false);
+}
+
+int Build::carve()
+{
     PSS_TRY(ctx->slot[S_CODES].reserve(n_pad));
     PSS_TRY(ctx->slot[S_K0].reserve((size_t)n * 8));
     PSS_TRY(ctx->slot[S_K1].reserve((size_t)n * 8));
@@ -289,144 +377,151 @@ int sa_build_device(DeviceCtx *ctx, const void *d_T, void *d_SA, int32_t n_in, u
     PSS_TRY(ctx->slot[S_GRP].reserve((size_t)n * 4));
     const size_t sort_ws = radix_sort_workspace_bytes();
     PSS_TRY(ctx->slot[S_WORK].reserve(sort_ws + 65536));
-    u8 *work = ctx->slot[S_WORK].as<u8>();
-    u8 *small = work + sort_ws;                       // 64 KiB of small device state
-    u32 *d_present = reinterpret_cast<u32 *>(small);              // [256] presence, [256] sampled counts
-    u8 *d_lut = small + 2048;                                     // [256]
-    u32 *d_agg_head = reinterpret_cast<u32 *>(small + 4096);      // [1024]
-    u32 *d_agg_cnt = reinterpret_cast<u32 *>(small + 8192);       // [1024]
-    u64 *d_red = reinterpret_cast<u64 *>(small + 12288);          // [2]
-    u32 *d_counters = reinterpret_cast<u32 *>(small + 12288 + 64);
+    work = ctx->slot[S_WORK].as<u8>();
+    sm = SmallState(work + sort_ws, ctx->pinned);
+    h_small = sm.h_small;
+    codes = ctx->slot[S_CODES].as<u8>();
+    K[0] = ctx->slot[S_K0].as<u64>(); K[1] = ctx->slot[S_K1].as<u64>();
+    V[0] = ctx->slot[S_V0].as<u32>(); V[1] = ctx->slot[S_V1].as<u32>();
+    ISA = ctx->slot[S_ISA].as<u32>();
+    P[0] = ctx->slot[S_P0].as<u32>(); P[1] = ctx->slot[S_P1].as<u32>();
+    GRP = ctx->slot[S_GRP].as<u32>();
+    return PSS_OK;
+}
 
-    u8 *codes = ctx->slot[S_CODES].as<u8>();
-    u64 *K[2] = {ctx->slot[S_K0].as<u64>(), ctx->slot[S_K1].as<u64>()};
-    u32 *V[2] = {ctx->slot[S_V0].as<u32>(), ctx->slot[S_V1].as<u32>()};
-    u32 *ISA = ctx->slot[S_ISA].as<u32>();
-    u32 *P[2] = {ctx->slot[S_P0].as<u32>(), ctx->slot[S_P1].as<u32>()};
-    u32 *GRP = ctx->slot[S_GRP].as<u32>();
-    u32 *h_small = static_cast<u32 *>(ctx->pinned);
-
-    BuildTimer timer;
+int Build::start_clock()
+{
     PSS_HIP(hipEventCreate(&timer.ev0));
     PSS_HIP(hipEventCreate(&timer.ev1));
     PSS_HIP(hipEventCreate(&timer.ev_mid));
     PSS_HIP(hipEventRecord(timer.ev0, s));
-    // A build that starts over (a plan that did not hold) reports the time of the attempts it gave up as well.
-    if (ctx->restart_depth == 0) {
-        ctx->restart_ms = 0.0;
-        ctx->ss_refused_note = false;
-    }
-    SideAnchors side;
-    auto start_over = [&](uint32_t new_flags) -> int {
-        side.join();                         // (the next attempt has a side line of its own, in the same helper context)
-        PSS_HIP(hipEventRecord(timer.ev1, s));
-        PSS_HIP(hipStreamSynchronize(s));
-        float gone = 0.f;
-        PSS_HIP(hipEventElapsedTime(&gone, timer.ev0, timer.ev1));
-        ctx->restart_ms += gone;
-        ctx->restart_depth += 1;
-        const int rc = sa_build_device(ctx, d_T, d_SA, n_in, new_flags, stats);
-        ctx->restart_depth -= 1;
-        return rc;
-    };
+    return PSS_OK;
+}
 
-    // ---- 0. alphabet ----
-    const int grid_stream = ctx->num_cus * 8;
-    u32 *d_runs = d_counters + 40;
-    // The plan of the previous build on this device (see step 1): when it took the MSD sort on a text of this size class
-    // and every switch is at its default, this build does not look at its alphabet first either -- it recodes with the
-    // remembered byte -> code table inside the sort's first histogram pass (msd_hist_raw_kernel: the alphabet pass, the
-    // recode pass and a host round trip fold into it, 0.4 ms at n = 2^29), which also checks that every byte has a code
-    // there.  A text over a subset of the remembered alphabet is sorted correctly with the larger table; a new byte, a
-    // crowded bucket, or anything else the sort declines for starts the build over without the plan -- the run-length
-    // and periodic-text checks, which this shortcut skips, then take place as always.
-    uint32_t logn = 0;
-    while ((2u << logn) <= n && logn < 31) ++logn;
-    const bool plain = knobs.key_chars == 0 && !knobs.no_sample && !knobs.no_flags && knobs.msd < 0 && knobs.ss < 0 &&
-                       knobs.key_drop < 0 && knobs.mode < 0 && !knobs.no_msd_fuse && !knobs.no_plan && knobs.rle < 0 &&
-                       knobs.period != 0 && (flags & 2u) == 0;
-    const bool fronted = plain && !knobs.no_front && n >= (1u << 24) && ctx->plan_path == 1 && ctx->plan_logn == logn &&
-                         (reinterpret_cast<uintptr_t>(T) & 15u) == 0;
-    if (!fronted) {
-        PSS_HIP(hipMemsetAsync(d_present, 0, 2048, s));
-        PSS_HIP(hipMemsetAsync(d_runs, 0, 4, s));
-        hipLaunchKernelGGL(sa_symbols_kernel, dim3(grid_stream), dim3(256), 0, s, T, n, d_present, d_present + 256, d_runs);
-        const bool screen_dups = plain && !knobs.no_front && (flags & 4u) == 0 && n >= (1u << 24);      // (only the shortcut of a first chunk asks)
-        PSS_HIP(hipMemsetAsync(d_runs + 1, 0, 4, s));
-        if (screen_dups) hipLaunchKernelGGL(dup_screen_kernel, dim3(1), dim3(1024), 0, s, T, n, d_runs + 1);
-        PSS_HIP(hipMemcpyAsync(h_small, d_present, 2048, hipMemcpyDeviceToHost, s));
-        PSS_HIP(hipMemcpyAsync(h_small + 512, d_runs, 8, hipMemcpyDeviceToHost, s));
-        // (the head of the text rides along: does it repeat one word?  -- see below)
-        u8 *h_head = static_cast<u8 *>(ctx->pinned) + 32768;         // the search path's query staging; builds and searches take turns
-        const u32 head_len = std::min<u32>(n, kPeriodProbe);
-        const bool look_for_period = knobs.period != 0 && n >= 4 * kPeriodProbe;
-        if (look_for_period) PSS_HIP(hipMemcpyAsync(h_head, T, head_len, hipMemcpyDeviceToHost, s));
-        PSS_HIP(hipStreamSynchronize(s));
-        // Long runs of equal bytes (every suffix inside a run is tied with its neighbours for as long as the run
-        // lasts: the worst case of prefix doubling): sort the run heads as a string of one symbol per run, then
-        // every other suffix falls into place with one short radix sort (rle_build.hip).
-        const u32 text_runs = h_small[512];
-        st.runs = text_runs;
-        if (knobs.rle == 1 || (knobs.rle < 0 && n >= 4096 && (u64)text_runs * 8 <= (u64)n)) {
-            RleStats rls;
-            PSS_TRY(rle_suffix_array(ctx, T, n, text_runs, SA, profile, &rls, &st));
-            st.rle = rls.columns ? 2 : 1;
-            st.rle_id_bits = rls.id_bits;
-            st.rle_ms_table = rls.ms_table;
-            st.rle_ms_reduced = rls.ms_reduced;
-            st.rle_ms_expand = rls.ms_expand;
-            for (int c = 0; c < 256; ++c) st.sigma += h_small[c] ? 1u : 0u;
-            PSS_HIP(hipEventRecord(timer.ev1, s));
-            PSS_HIP(hipStreamSynchronize(s));
-            float ms = 0.f;
-            PSS_HIP(hipEventElapsedTime(&ms, timer.ev0, timer.ev1));
-            st.ms_total = ms + ctx->restart_ms;
-            st.ms_restarts = ctx->restart_ms;
-            if (stats) *stats = st;
-            return PSS_OK;
-        }
-        // One word written over and over (a text whose first m bytes have a small period, with at most a few bytes behind):
-        // the worst case of prefix doubling that is not a run of one byte.  The head of the text says whether it is worth
-        // a pass to find out how far the repetition goes; if it covers the text, the suffix array has a closed form
-        // (rle_build.h).
-        if (look_for_period) {
-            const u32 p = period_of_head(h_head, head_len);
-            if (p) {
-                u32 m = 0;
-                PSS_TRY(period_extent(ctx, T, n, p, &m));
-                st.period = p;
-                st.period_extent = m;
-                bool accepted = false;
-                if (n - m <= kPeriodTailMax) {
-                    std::vector<u8> word(h_head, h_head + p);           // (period_extent reuses the pinned scratch)
-                    PSS_TRY(period_suffix_array(ctx, T, n, p, m, word.data(), SA, &accepted));
-                }
-                if (accepted) {
-                    st.period_path = 1;
-                    for (int c = 0; c < 256; ++c) st.sigma += h_small[c] ? 1u : 0u;
-                    PSS_HIP(hipEventRecord(timer.ev1, s));
-                    PSS_HIP(hipStreamSynchronize(s));
-                    float ms = 0.f;
-                    PSS_HIP(hipEventElapsedTime(&ms, timer.ev0, timer.ev1));
-                    st.ms_total = ms + ctx->restart_ms;
-            st.ms_restarts = ctx->restart_ms;
-                    if (stats) *stats = st;
-                    return PSS_OK;
-                }
-            }
+// This attempt's shortcut did not hold: the build starts over with new_flags, and reports the time of the attempts it
+// gave up as well.
+int Build::give_up(uint32_t new_flags, Next *next)
+{
+    side.join();                             // (the next attempt has a side line of its own, in the same helper context)
+    PSS_HIP(hipEventRecord(timer.ev1, s));
+    PSS_HIP(hipStreamSynchronize(s));
+    float gone = 0.f;
+    PSS_HIP(hipEventElapsedTime(&gone, timer.ev0, timer.ev1));
+    past.ms += gone;
+    again_flags = new_flags;
+    *next = Next::start_over;
+    return PSS_OK;
+}
+
+// The one epilogue.  early: the run-length or the periodic-text exit, which know the alphabet from the presence table
+// alone and have no initial sort to report.
+int Build::finish(bool early)
+{
+    if (early)
+        for (int c = 0; c < 256; ++c) st.sigma += h_small[c] ? 1u : 0u;
+    PSS_HIP(hipEventRecord(timer.ev1, s));
+    PSS_HIP(hipStreamSynchronize(s));
+    float ms = 0.f;
+    PSS_HIP(hipEventElapsedTime(&ms, timer.ev0, timer.ev1));
+    st.ms_total = ms + past.ms;
+    st.ms_restarts = past.ms;
+    if (!early) {
+        st.ss_plan_refused = past.ss_refused ? 1 : 0;
+        PSS_HIP(hipEventElapsedTime(&ms, timer.ev0, timer.ev_mid));
+        st.ms_initial = ms;
+        st.ms_sort = ss.ms;
+        st.sort_launches = ss.launches;
+        st.sort_elems = ss.elems;
+        st.ms_pairs = ss.ms_pairs;
+        st.pairs_launches = ss.pairs_launches;
+        st.pairs_elems = ss.pairs_elems;
+        st.ms_text = ss.ms_text;
+        st.text_launches = ss.text_launches;
+        for (int i = 0; i < 9; ++i) {
+            st.fs_ms[i] = ss.fs_ms[i];
+            st.fs_launches[i] = ss.fs_launches[i];
+            st.fs_elems[i] = ss.fs_elems[i];
         }
     }
-    u8 lut[256];
-    u32 sigma = 0;
+    if (stats) *stats = st;
+    return PSS_OK;
+}
+
+// ---- 0. alphabet ----
+// Which byte values occur, sampled counts, runs of equal bytes, copies among sampled places, the head of the text: one
+// wait for all of them.
+int Build::screen_text()
+{
+    PSS_HIP(hipMemsetAsync(sm.present, 0, 2048, s));
+    PSS_HIP(hipMemsetAsync(sm.runs, 0, 4, s));
+    hipLaunchKernelGGL(sa_symbols_kernel, dim3(grid_stream), dim3(256), 0, s, T, n, sm.present, sm.counts, sm.runs);
+    PSS_HIP(hipMemsetAsync(sm.dups, 0, 4, s));
+    if (shortcut_ok) hipLaunchKernelGGL(dup_screen_kernel, dim3(1), dim3(1024), 0, s, T, n, sm.dups);      // (only the shortcut of a first chunk asks)
+    PSS_HIP(hipMemcpyAsync(h_small, sm.present, 2048, hipMemcpyDeviceToHost, s));
+    PSS_HIP(hipMemcpyAsync(h_small + 512, sm.runs, 8, hipMemcpyDeviceToHost, s));      // runs, dups
+    // (the head of the text rides along: does it repeat one word?  -- see try_periodic)
+    h_head = static_cast<u8 *>(ctx->pinned) + 32768;             // the search path's query staging; builds and searches take turns
+    head_len = std::min<u32>(n, kPeriodProbe);
+    look_for_period = knobs.period != 0 && n >= 4 * kPeriodProbe;
+    if (look_for_period) PSS_HIP(hipMemcpyAsync(h_head, T, head_len, hipMemcpyDeviceToHost, s));
+    PSS_HIP(hipStreamSynchronize(s));
+    text_runs = h_small[512];
+    st.runs = text_runs;
+    return PSS_OK;
+}
+
+// Long runs of equal bytes (every suffix inside a run is tied with its neighbours for as long as the run
+// lasts: the worst case of prefix doubling): sort the run heads as a string of one symbol per run, then
+// every other suffix falls into place with one short radix sort (rle_build.hip).
+int Build::try_run_length(Next *next)
+{
+    if (!(knobs.rle == 1 || (knobs.rle < 0 && n >= 4096 && (u64)text_runs * 8 <= (u64)n))) return PSS_OK;
+    RleStats rls;
+    PSS_TRY(rle_suffix_array(ctx, T, n, text_runs, SA, profile, &rls, &st));
+    st.rle = rls.columns ? 2 : 1;
+    st.rle_id_bits = rls.id_bits;
+    st.rle_ms_table = rls.ms_table;
+    st.rle_ms_reduced = rls.ms_reduced;
+    st.rle_ms_expand = rls.ms_expand;
+    *next = Next::finished;
+    return PSS_OK;
+}
+
+// One word written over and over (a text whose first m bytes have a small period, with at most a few bytes behind):
+// the worst case of prefix doubling that is not a run of one byte.  The head of the text says whether it is worth
+// a pass to find out how far the repetition goes; if it covers the text, the suffix array has a closed form
+// (rle_build.h).
+int Build::try_periodic(Next *next)
+{
+    if (!look_for_period) return PSS_OK;
+    const u32 p = period_of_head(h_head, head_len);
+    if (!p) return PSS_OK;
+    u32 m = 0;
+    PSS_TRY(period_extent(ctx, T, n, p, &m));
+    st.period = p;
+    st.period_extent = m;
+    bool accepted = false;
+    if (n - m <= kPeriodTailMax) {
+        std::vector<u8> word(h_head, h_head + p);           // (period_extent reuses the pinned scratch)
+        PSS_TRY(period_suffix_array(ctx, T, n, p, m, word.data(), SA, &accepted));
+    }
+    if (accepted) {
+        st.period_path = 1;
+        *next = Next::finished;
+    }
+    return PSS_OK;
+}
+
+// The byte -> code table and what follows from the size of the alphabet.
+void Build::choose_codes()
+{
     if (fronted) {
-        memcpy(lut, ctx->plan_lut, 256);
-        sigma = ctx->plan_sigma;
+        memcpy(lut, plan.lut, 256);
+        sigma = plan.sigma;
     } else {
         for (int c = 0; c < 256; ++c) lut[c] = h_small[c] ? (u8)(++sigma) : 0;   // codes 1..sigma
     }
-    int b = 1;
     while ((1u << b) <= sigma) ++b;               // codes 0..sigma need b bits
-    int plus_one = 0;
     if (sigma == 256) {
         // 257 code points do not fit a byte: keep the raw bytes and let the key
         // packer add 1 to every in-text symbol (9-bit codes, 0 = past the end).
@@ -434,16 +529,15 @@ int sa_build_device(DeviceCtx *ctx, const void *d_T, void *d_SA, int32_t n_in, u
         plus_one = 1;
         for (int c = 0; c < 256; ++c) lut[c] = (u8)c;
     }
-    int kmax = 64 / b;
+    kmax = 64 / b;
     if (kmax > 16) kmax = 16;
     // A first chunk (no plan yet) whose symbols are close to uniform -- log lines, identifiers, hex, base64: sum p^2 below
     // 0.035; natural language sits at 0.065 and above -- goes to the MSD sort the way a planned chunk does: the sort's
     // first histogram pass recodes the raw text with the table just built, no recode pass, no sizing sample (0.4 ms and a
     // host round trip: what the sample would say is what the symbol counts say already).  The sort's exact bucket check
-    // still decides; a decline starts the build over along the long road (flags bit 2), at the price of the passes made.
-    bool fresh = false;
-    if (!fronted && plain && !knobs.no_front && (flags & 4u) == 0 && n >= (1u << 24) && sigma >= 2 && sigma < 256 &&
-        (reinterpret_cast<uintptr_t>(T) & 15u) == 0) {
+    // still decides; a decline starts the build over along the long road (PSS_SA_NO_FIRST_CHUNK_SHORTCUT), at the price of
+    // the passes made.
+    if (!fronted && shortcut_ok && sigma >= 2 && sigma < 256 && aligned) {
         double tot = 0, c2 = 0;
         for (int c = 0; c < 256; ++c) tot += h_small[256 + c];
         for (int c = 0; c < 256 && tot > 0; ++c) {
@@ -455,88 +549,105 @@ int sa_build_device(DeviceCtx *ctx, const void *d_T, void *d_SA, int32_t n_in, u
         fresh = tot > 0 && c2 < 0.035 && h_small[513] < 8;
         st.dup_screen = h_small[513];
     }
-    const bool front_any = fronted || fresh;
-    int key_chars = front_any ? kmax : choose_key_chars(h_small + 256, n, b, kmax);
-    const bool forced_chars = knobs.key_chars >= 1 && knobs.key_chars <= kmax;
+    front_any = fronted || fresh;
+    key_chars = front_any ? kmax : choose_key_chars(h_small + 256, n, b, kmax);
+    forced_chars = knobs.key_chars >= 1 && knobs.key_chars <= kmax;
     if (forced_chars) key_chars = knobs.key_chars;
     st.sigma = sigma;
     st.code_bits = (u32)b;
     st.key_chars = (u32)key_chars;
+}
+
+// The table goes up; the codes are either left to the MSD sort (front_any) or made here, and then the side line may start.
+int Build::make_codes()
+{
     memcpy(h_small + 1024, lut, 256);
-    PSS_HIP(hipMemcpyAsync(d_lut, h_small + 1024, 256, hipMemcpyHostToDevice, s));
-    u32 *d_bad = d_counters + 44;
+    PSS_HIP(hipMemcpyAsync(sm.lut, h_small + 1024, 256, hipMemcpyHostToDevice, s));
     if (front_any) {
-        // the codes are made by the sort (below); their padding past n and the flag for a byte without a code
+        // the codes are made by the sort (try_msd); their padding past n and the flag for a byte without a code
         const size_t tail0 = (size_t)n & ~(size_t)15;
         PSS_HIP(hipMemsetAsync(codes + tail0, 0, n_pad - tail0, s));
-        PSS_HIP(hipMemsetAsync(d_bad, 0, 4, s));
-    } else {
-        hipLaunchKernelGGL(sa_recode_kernel, dim3(grid_stream), dim3(256), 0, s, T, n, (u32)n_pad, d_lut, codes);
-        // The previous chunk on this device sorted its anchors beside its text round (text with copies in it), and this
-        // chunk will reach the same depth the same way (same size class, same bits per symbol, the sample sort's key of
-        // as many symbols): its side line starts NOW, beside the initial sort as well.  Should the build take another
-        // road -- no ties worth an anchor round, a shallower depth -- the result is thrown away (anchor_side = 2).
-        if (plain && knobs.side != 0 && knobs.anchor != 0 && ctx->side_plan_heff != 0 && ctx->side_plan_logn == logn &&
-            ctx->side_plan_b == b && n >= (1u << 24) && (flags & 2u) == 0) {
-            int kt0 = 64 / b;
-            if (kt0 > 16) kt0 = 16;
-            const int kc0 = ss_key_chars(n, plus_one ? 257u : sigma + 1u);
-            if (kc0 > 0 && (u64)kc0 + (u64)kt0 == ctx->side_plan_heff) {
-                PSS_HIP(hipEventRecord(timer.ev_mid, s));         // (recorded again below, where the initial sort ends)
-                PSS_TRY(side_start(ctx, knobs, side, n, codes, b, plus_one, ctx->side_plan_heff, timer.ev_mid));
-            }
+        PSS_HIP(hipMemsetAsync(sm.bad, 0, 4, s));
+        return PSS_OK;
+    }
+    hipLaunchKernelGGL(sa_recode_kernel, dim3(grid_stream), dim3(256), 0, s, T, n, (u32)n_pad, sm.lut, codes);
+    // The previous chunk on this device sorted its anchors beside its text round (text with copies in it), and this
+    // chunk will reach the same depth the same way (same size class, same bits per symbol, the sample sort's key of
+    // as many symbols): its side line starts NOW, beside the initial sort as well.  Should the build take another
+    // road -- no ties worth an anchor round, a shallower depth -- the result is thrown away (anchor_side = 2).
+    const u64 h_eff = plan.side_depth(logn, b, plain);
+    if (h_eff != 0 && knobs.side != 0 && knobs.anchor != 0) {
+        int kt0 = 64 / b;
+        if (kt0 > 16) kt0 = 16;
+        const int kc0 = ss_key_chars(n, plus_one ? 257u : sigma + 1u);
+        if (kc0 > 0 && (u64)kc0 + (u64)kt0 == h_eff) {
+            PSS_HIP(hipEventRecord(timer.ev_mid, s));         // (recorded again in lsd_passes, where the initial sort ends)
+            PSS_TRY(side_start(ctx, knobs, side, n, codes, b, plus_one, h_eff, timer.ev_mid));
         }
     }
+    return PSS_OK;
+}
 
-    // ---- 1. initial sort on the first key_chars symbols ----
-    SortStats ss;
-    int key_drop = 0;
-    bool msd_screen_ok = false, sampled = false;
+// ---- 1. initial sort on the first key_chars symbols ----
+// How long a key, from the plan's hint or a sizing sample, and where the pass that finishes the sort writes.
+int Build::size_key()
+{
     // The plan of the previous build on this device, if it was for the same kind of text (same byte values present, same
     // size class) and every switch is at its default: 1 = it took the MSD sort.  The sizing sample (0.4 ms and a host
     // round trip at n = 2^29) would only repeat what it said then; the MSD sort's own exact bucket check still decides.
     // When it declines, the sample sort is next as always; if that declines too, the build starts over with the sample
     // (the LSD passes want the key length it measures).
-    uint32_t present_bits[8] = {};
     for (int c = 0; c < 256; ++c)
         if (plus_one || lut[c]) present_bits[c >> 5] |= 1u << (c & 31);
-    int hint = 0;
-    if (front_any) hint = 1;
-    else if (plain && n >= (1u << 24) && ctx->plan_path && ctx->plan_logn == logn && memcmp(ctx->plan_present, present_bits, 32) == 0)
-        hint = ctx->plan_path;
+    hint = front_any ? 1 : plan.hint(logn, present_bits, plain);
     st.plan_hint = (uint64_t)(fronted ? 2 : (fresh ? 3 : hint));
     if (hint) {
         sampled = true;
         msd_screen_ok = hint == 1;
     } else if (n >= (1u << 24) && !forced_chars && knobs.key_chars == 0 && !knobs.no_sample) {
-        PSS_TRY(size_initial_key(ctx, codes, n, b, kmax, plus_one, K, V, work, d_counters + 16, h_small, profile, &ss,
-                                 &key_chars, &key_drop, &msd_screen_ok));
+        PSS_TRY(size_initial_key(ctx, codes, n, b, kmax, plus_one, K, V, work, sm.tied, h_small, profile, &ss, &key_chars, &key_drop,
+                                 &msd_screen_ok));
         st.key_chars = (u32)key_chars;
         sampled = true;
     }
     if (knobs.key_drop >= 0 && knobs.key_drop < b && key_chars > 1) key_drop = knobs.key_drop;
-    TextKeys tk{codes, b, key_chars, plus_one, key_drop};
-    const int key_bits0 = key_chars * b - key_drop;
+    key_bits0 = key_chars * b - key_drop;
     st.key_bits = (u64)key_bits0;
     // The sorted suffix indices of the initial sort ARE the suffix array (ties are reordered
     // later, inside their slots): let the pass that finishes the sort write straight into the
     // caller's SA buffer.  The text pass writes buffer 0 and the passes alternate, so the
     // buffer that receives the last pass is known up front.
     const int passes0 = (key_bits0 + 7) / 8;
-    const int final_buf = (passes0 - 1) & 1;
-    u32 *const v_scratch = V[final_buf];
+    final_buf = (passes0 - 1) & 1;
+    v_scratch = V[final_buf];
     V[final_buf] = SA;
-    int cur = 0;
     // With >= 2 passes the sort carries tie flags instead of consumed digits (radix_sort.hip, fs_*):
     // the last pass writes only the suffix indices with bit 31 = "tied with my predecessor", and
     // the rerank reads 4-byte flagged values instead of comparing 8-byte keys.
-    const bool ties = passes0 >= 2 && !knobs.no_flags;
-    // Hybrid MSD sort (msd_sort.hip): two global partition passes over 8-byte elements, then every joint
-    // bucket sorted in LDS.  Taken when the key the sizing asked for (<= 48 bits) is covered by what an
-    // element can carry, and the sorted sample shows no crowded 20-bit prefix; the exact bucket check
-    // inside can still decline, then the LSD passes run as before.
-    bool msd_done = false, msd_fused = false;
-    u32 msd_active = 0;
+    ties = passes0 >= 2 && !knobs.no_flags;
+    return PSS_OK;
+}
+
+// The local sorts of both initial sorts hand over the active list of the first rerank (SA slot, suffix, group rank of
+// every suffix tied with a neighbour) in the buffers round 0 would fill: P[1], the free value buffer, G[1].
+// Staging: the first element buffer (free once the second partition pass has read it).
+int Build::active_handover(MsdActive *act)
+{
+    PSS_TRY(ctx->slot[S_GRP2].reserve((size_t)n * 4));
+    act->pos = ctx->slot[S_P1].as<u32>();
+    act->idx = (final_buf == 0) ? V[1] : V[0];
+    act->grp = ctx->slot[S_GRP2].as<u32>();
+    act->st_pos = reinterpret_cast<u32 *>(K[0]);
+    act->st_idx = reinterpret_cast<u32 *>(K[0]) + n;
+    return PSS_OK;
+}
+
+// Hybrid MSD sort (msd_sort.hip): two global partition passes over 8-byte elements, then every joint
+// bucket sorted in LDS.  Taken when the key the sizing asked for (<= 48 bits) is covered by what an
+// element can carry, and the sorted sample shows no crowded 20-bit prefix; the exact bucket check
+// inside can still decline, then the LSD passes run as before.
+int Build::try_msd(Next *next)
+{
     if (ties && knobs.msd != 0) {
         // (at n = 2^29 an element holds 45 key bits after the first pass; smaller texts leave room for up to 48)
         const char *cap_env = knob("PSS_MSD_KEY_CAP");
@@ -560,32 +671,24 @@ int sa_build_device(DeviceCtx *ctx, const void *d_T, void *d_SA, int32_t n_in, u
             TextKeys mk{codes, b, kc, plus_one, mdrop};
             MsdStats ms;
             bool accepted = false;
-            // The local sort hands over the active list of the first rerank (SA slot, suffix, group rank of every
-            // suffix tied with a neighbour) in the buffers round 0 would fill: P[1], the free value buffer, G[1].
-            // Staging: the first element buffer (free once the second partition pass has read it).
-            PSS_TRY(ctx->slot[S_GRP2].reserve((size_t)n * 4));
             MsdActive act;
-            act.pos = ctx->slot[S_P1].as<u32>();
-            act.idx = (final_buf == 0) ? V[1] : V[0];
-            act.grp = ctx->slot[S_GRP2].as<u32>();
-            act.st_pos = reinterpret_cast<u32 *>(K[0]);
-            act.st_idx = reinterpret_cast<u32 *>(K[0]) + n;
-            const MsdFront front{T, d_lut, d_bad};
+            PSS_TRY(active_handover(&act));
+            const MsdFront front{T, sm.lut, sm.bad};
             PSS_TRY(msd_suffix_sort(ctx, &mk, n, kb, K, SA, ctx->slot[S_P0].p, h_small, profile, &ms, &accepted,
                                     knobs.no_msd_fuse ? nullptr : &act, front_any ? &front : nullptr));
             if (front_any && !accepted) {
                 // the plan did not hold for this text (a byte outside the remembered alphabet, a crowded bucket): all
                 // over again without it -- the alphabet pass, the run-length and periodic-text checks, the sample
                 // (a first chunk taken on its symbol counts alone: the same, with that shortcut switched off)
-                ctx->plan_path = 0;
-                return start_over(fresh ? (flags | 4u) : flags);
+                plan.refuse();
+                return give_up(fresh ? (flags | PSS_SA_NO_FIRST_CHUNK_SHORTCUT) : flags, next);
             }
             msd_fused = accepted && !knobs.no_msd_fuse;
             msd_active = act.count;
             st.msd_buckets = ms.buckets;
             st.msd_max_bucket = ms.max_bucket;
             if (accepted) {
-                msd_done = true;
+                sorted = true;
                 key_chars = kc;
                 key_drop = mdrop;
                 st.key_chars = (u32)kc;
@@ -604,118 +707,122 @@ int sa_build_device(DeviceCtx *ctx, const void *d_T, void *d_SA, int32_t n_in, u
             }
         }
     }
-    if (front_any && !msd_done) {            // (the sort was not even tried: nothing has made the codes)
-        ctx->plan_path = 0;
-        return start_over(fresh ? (flags | 4u) : flags);
+    if (front_any && !sorted) {              // (the sort was not even tried: nothing has made the codes)
+        plan.refuse();
+        return give_up(fresh ? (flags | PSS_SA_NO_FIRST_CHUNK_SHORTCUT) : flags, next);
     }
-    // Natural text (some 20-bit prefix holds far more suffixes than a tile, and a 64-bit key leaves most suffixes tied
-    // anyway): sample sort over 16-byte [key | index] elements (ss_sort_impl.h) -- splitters from a sorted sample cut the
-    // text's own distribution into tile-sized buckets, the key is twice as long.
-    if (!msd_done && ties && knobs.ss != 0 && (knobs.ss == 1 || (n >= (1u << 24) && !forced_chars && knobs.key_chars == 0)) &&
-        ss_sample_count(n) != 0) {
-        const u32 S = ss_sample_count(n);
-        // The two element buffers (16 n bytes each: 17 GB at n = 2^29) are the largest allocation of the build.  Where HBM
-        // is short -- a Reader resident on the same device -- the sort DECLINES instead of failing the build: the LSD
-        // passes below need nothing beyond the buffers every build has.
-        bool ss_room = ctx->slot[S_SSA].reserve((size_t)n * 16 + 256) == PSS_OK && ctx->slot[S_SSB].reserve((size_t)n * 16 + 256) == PSS_OK;
-        if (!ss_room) {
-            (void)hipGetLastError();
-            ctx->slot[S_SSA].release();
-            ctx->slot[S_SSB].release();
-            set_error("%s", "");
-            st.ss_declined_nomem = 1;
-        }
-        if (ss_room) {
-        PSS_TRY(ctx->slot[S_GRP2].reserve((size_t)n * 4));
-        SsBuffers sb;
-        sb.A[0] = ctx->slot[S_SSA].p;
-        sb.A[1] = ctx->slot[S_SSB].p;
-        sb.digits = reinterpret_cast<uint16_t *>(ctx->slot[S_P1].p);      // 2 n + 128 bytes of the 4 n
-        sb.E0 = GRP;                                                       // 16 S <= 4 n bytes each
-        sb.E = ISA;
-        sb.K[0] = K[0]; sb.K[1] = K[1];
-        sb.V[0] = v_scratch; sb.V[1] = (final_buf == 0) ? V[1] : V[0];     // (never the caller's SA buffer)
-        sb.sort_work = work;
-        // the plan: the previous chunk of this corpus (same size, same alphabet) left its sorted sample behind
-        const u32 radix = plus_one ? 257u : sigma + 1u;
-        // (the same sample size, bucket counts, index bits and symbols per key: chunks of one Writer differ by an entry or two)
-        const u64 tag = ss_geometry_tag(n, radix);
-        const bool planned = hint == 2 && tag != 0 && ctx->ss_plan_tag == tag && ctx->ss_plan_radix == radix && ctx->slot[S_SSPLAN].p != nullptr &&
-                             ctx->ss_plan_skip == 0;
-        if (planned) sb.sample_in = ctx->slot[S_SSPLAN].p;
-        else if (plain && ctx->slot[S_SSPLAN].reserve((size_t)S * 16) == PSS_OK) sb.sample_keep = ctx->slot[S_SSPLAN].p;
-        ctx->ss_plan_tag = 0;                                              // (valid again once this sort has been accepted)
-        MsdActive act;
-        act.pos = ctx->slot[S_P1].as<u32>();
-        act.idx = (final_buf == 0) ? V[1] : V[0];
-        act.grp = ctx->slot[S_GRP2].as<u32>();
-        act.st_pos = reinterpret_cast<u32 *>(K[0]);
-        act.st_idx = reinterpret_cast<u32 *>(K[0]) + n;
-        TextKeys sk{codes, b, 0, plus_one, 0};
-        SsStats sst;
-        bool accepted = false;
-        PSS_TRY(ss_suffix_sort(ctx, &sk, plus_one ? 257u : sigma + 1u, n, sb, SA, ctx->slot[S_P0].p, h_small, profile, &sst, &accepted,
-                               &act));
-        if (planned && !accepted) {
-            // The previous chunk's splitters left a bucket beyond a tile (real files: millions of suffixes with one key --
-            // blanks -- sit where the files put them, not where the last chunk had them).  The build starts over without the
-            // plan, and the next chunks do not try it again at once: 1, 3, 7, ... builds go by first.
-            ctx->ss_plan_backoff = std::min(63u, 2 * ctx->ss_plan_backoff + 1);
-            ctx->ss_plan_skip = ctx->ss_plan_backoff;
-            ctx->ss_refused_note = true;
-            ctx->plan_path = 0;               // all over again without the plan: this may not be natural text at all
-            return start_over(flags);
-        } else if (accepted) {
-            if (planned) ctx->ss_plan_backoff = 0;
-            else if (hint == 2 && ctx->ss_plan_skip) --ctx->ss_plan_skip;      // (a chunk that went by without trying)
-        }
-        st.ss_buckets = sst.buckets;
-        st.ss_max_bucket = sst.max_bucket;
-        st.ss_samples = sst.samples;
-        if (accepted) {
-            msd_done = true;
-            msd_fused = false;          // ties come back as flags in the suffix array (groups cross the tiles of this sort)
-            key_chars = sst.key_chars;
-            key_drop = 0;
-            st.key_chars = (u32)key_chars;
-            st.key_bits = (u64)key_chars * b;
-            st.ss = 1;
-            st.ss_tiles = sst.tiles;
-            st.ss_ms_sample = sst.ms_sample;
-            st.ss_ms_g1 = sst.ms_g1;
-            st.ss_ms_g2 = sst.ms_g2;
-            st.ss_ms_local = sst.ms_local;
-            cur = final_buf;
-            ss.launches = 4;
-            ss.elems = 4ull * n;
-            if (sb.sample_in || sb.sample_keep) {
-                ctx->ss_plan_tag = tag;
-                ctx->ss_plan_radix = radix;
-            }
-            st.ss_planned = sb.sample_in ? 1 : 0;
-        }
-        }
+    return PSS_OK;
+}
+
+// The two element buffers of the sample sort (16 n bytes each: 17 GB at n = 2^29) are the largest allocation of the
+// build.  Where HBM is short -- a Reader resident on the same device -- the sort DECLINES instead of failing the build:
+// the LSD passes need nothing beyond the buffers every build has.
+bool Build::ss_room()
+{
+    if (ctx->slot[S_SSA].reserve((size_t)n * 16 + 256) == PSS_OK && ctx->slot[S_SSB].reserve((size_t)n * 16 + 256) == PSS_OK) return true;
+    (void)hipGetLastError();
+    ctx->slot[S_SSA].release();
+    ctx->slot[S_SSB].release();
+    set_error("%s", "");
+    st.ss_declined_nomem = 1;
+    return false;
+}
+
+// Natural text (some 20-bit prefix holds far more suffixes than a tile, and a 64-bit key leaves most suffixes tied
+// anyway): sample sort over 16-byte [key | index] elements (ss_sort_impl.h) -- splitters from a sorted sample cut the
+// text's own distribution into tile-sized buckets, the key is twice as long.
+int Build::try_sample_sort(Next *next)
+{
+    if (!sorted && ties && knobs.ss != 0 && (knobs.ss == 1 || (n >= (1u << 24) && !forced_chars && knobs.key_chars == 0)) &&
+        ss_sample_count(n) != 0 && ss_room()) {
+        PSS_TRY(sample_sort(next));
+        if (*next == Next::start_over) return PSS_OK;
     }
-    if (hint && !msd_done) {
+    if (hint && !sorted) {
         // Neither the remembered sort nor the sample sort took this text: forget the plan and size the key the long way.
-        ctx->plan_path = 0;
-        return start_over(flags);
+        plan.refuse();
+        return give_up(flags, next);
     }
-    if (plain && n >= (1u << 24) && !fronted) {
-        // (the MSD sort's own exact check can refuse a text; the sample sort takes any text, and a bucket beyond a tile --
-        // with remembered splitters as unlikely as with fresh ones -- declines: both start over without the plan)
-        ctx->plan_path = st.msd ? 1 : (st.ss && ctx->ss_plan_tag != 0 ? 2 : 0);
-        ctx->plan_logn = logn;
-        memcpy(ctx->plan_present, present_bits, 32);
-        memcpy(ctx->plan_lut, lut, 256);
-        ctx->plan_sigma = sigma;
+    return PSS_OK;
+}
+
+int Build::sample_sort(Next *next)
+{
+    const u32 S = ss_sample_count(n);
+    MsdActive act;
+    PSS_TRY(active_handover(&act));
+    SsBuffers sb;
+    sb.A[0] = ctx->slot[S_SSA].p;
+    sb.A[1] = ctx->slot[S_SSB].p;
+    sb.digits = reinterpret_cast<uint16_t *>(ctx->slot[S_P1].p);      // 2 n + 128 bytes of the 4 n
+    sb.E0 = GRP;                                                       // 16 S <= 4 n bytes each
+    sb.E = ISA;
+    sb.K[0] = K[0]; sb.K[1] = K[1];
+    sb.V[0] = v_scratch; sb.V[1] = (final_buf == 0) ? V[1] : V[0];     // (never the caller's SA buffer)
+    sb.sort_work = work;
+    // the plan: the previous chunk of this corpus (same size, same alphabet) left its sorted sample behind
+    const u32 radix = plus_one ? 257u : sigma + 1u;
+    const u64 tag = ss_geometry_tag(n, radix);
+    const bool planned = plan.ss_usable(hint, tag, radix) && ctx->slot[S_SSPLAN].p != nullptr;
+    if (planned) sb.sample_in = ctx->slot[S_SSPLAN].p;
+    else if (plain && ctx->slot[S_SSPLAN].reserve((size_t)S * 16) == PSS_OK) sb.sample_keep = ctx->slot[S_SSPLAN].p;
+    plan.ss_begin();
+    TextKeys sk{codes, b, 0, plus_one, 0};
+    SsStats sst;
+    bool accepted = false;
+    PSS_TRY(ss_suffix_sort(ctx, &sk, radix, n, sb, SA, ctx->slot[S_P0].p, h_small, profile, &sst, &accepted, &act));
+    if (planned && !accepted) {
+        // The previous chunk's splitters left a bucket beyond a tile (real files: millions of suffixes with one key --
+        // blanks -- sit where the files put them, not where the last chunk had them).
+        plan.ss_refused();
+        past.ss_refused = true;
+        return give_up(flags, next);
     }
-    if (msd_done) {
+    st.ss_buckets = sst.buckets;
+    st.ss_max_bucket = sst.max_bucket;
+    st.ss_samples = sst.samples;
+    if (!accepted) return PSS_OK;
+    plan.ss_accepted(planned, hint, sb.sample_in || sb.sample_keep, tag, radix);
+    sorted = true;
+    msd_fused = false;          // ties come back as flags in the suffix array (groups cross the tiles of this sort)
+    key_chars = sst.key_chars;
+    key_drop = 0;
+    st.key_chars = (u32)key_chars;
+    st.key_bits = (u64)key_chars * b;
+    st.ss = 1;
+    st.ss_tiles = sst.tiles;
+    st.ss_ms_sample = sst.ms_sample;
+    st.ss_ms_g1 = sst.ms_g1;
+    st.ss_ms_g2 = sst.ms_g2;
+    st.ss_ms_local = sst.ms_local;
+    cur = final_buf;
+    ss.launches = 4;
+    ss.elems = 4ull * n;
+    st.ss_planned = sb.sample_in ? 1 : 0;
+    return PSS_OK;
+}
+
+// (a build that was fronted took the plan's table and has nothing new to say)
+void Build::remember_plan()
+{
+    if (!fronted) plan.remember_sort(logn, plain, present_bits, lut, sigma, st.msd != 0, st.ss != 0);
+}
+
+// Neither of the two took the text: the LSD passes.  The initial sort ends here in every case.
+int Build::lsd_passes()
+{
+    TextKeys tk{codes, b, key_chars, plus_one, key_drop};
+    if (sorted) {
     } else if (ties) PSS_TRY(suffix_sort_flags(ctx, K, V, n, key_bits0, &tk, work, &cur, profile, &ss));
     else PSS_TRY(radix_sort_pairs(ctx, K, V, n, key_bits0, 0xffffffffu, &tk, 0, work, &cur, profile, &ss));
     st.initial_passes = (u32)ss.launches;
     PSS_HIP(hipEventRecord(timer.ev_mid, s));
-    // ---- 2. rerank + compaction, 3. doubling rounds ----
+    return PSS_OK;
+}
+
+// ---- 2. rerank + compaction, 3. doubling rounds ----
+int Build::run_rounds()
+{
     RoundsIO io;
     io.n = n;
     io.SA = SA;
@@ -735,41 +842,42 @@ int sa_build_device(DeviceCtx *ctx, const void *d_T, void *d_SA, int32_t n_in, u
     io.msd_active = msd_active;
     io.no_sparse = st.ss != 0;
     io.work = work;
-    io.d_agg_head = d_agg_head; io.d_agg_cnt = d_agg_cnt; io.d_red = d_red; io.d_counters = d_counters; io.h_small = h_small;
+    sm.lend(io);
     io.profile = profile;
     io.side = &side;
     PSS_TRY(refine_rounds(ctx, knobs, io, ss, st));
     side.join();
     if (side.started && st.anchor_side == 0) st.anchor_side = 2;      // started for nothing
-    if (plain && n >= (1u << 24)) {
-        ctx->side_plan_heff = st.anchor_side == 1 ? side.h_eff : 0;
-        ctx->side_plan_logn = logn;
-        ctx->side_plan_b = b;
-    }
-    PSS_HIP(hipEventRecord(timer.ev1, s));
-    PSS_HIP(hipStreamSynchronize(s));
-    float ms = 0.f;
-    PSS_HIP(hipEventElapsedTime(&ms, timer.ev0, timer.ev1));
-    st.ss_plan_refused = ctx->ss_refused_note ? 1 : 0;
-    st.ms_total = ms + ctx->restart_ms;
-            st.ms_restarts = ctx->restart_ms;
-    PSS_HIP(hipEventElapsedTime(&ms, timer.ev0, timer.ev_mid));
-    st.ms_initial = ms;
-    st.ms_sort = ss.ms;
-    st.sort_launches = ss.launches;
-    st.sort_elems = ss.elems;
-    st.ms_pairs = ss.ms_pairs;
-    st.pairs_launches = ss.pairs_launches;
-    st.pairs_elems = ss.pairs_elems;
-    st.ms_text = ss.ms_text;
-    st.text_launches = ss.text_launches;
-    for (int i = 0; i < 9; ++i) {
-        st.fs_ms[i] = ss.fs_ms[i];
-        st.fs_launches[i] = ss.fs_launches[i];
-        st.fs_elems[i] = ss.fs_elems[i];
-    }
-    if (stats) *stats = st;
+    plan.remember_side(logn, b, plain, st.anchor_side == 1 ? side.h_eff : 0);
     return PSS_OK;
+}
+
+}  // namespace
+
+int sa_build_device(DeviceCtx *ctx, const void *d_T, void *d_SA, int32_t n_in, uint32_t flags, pss_sa_stats *stats)
+{
+    if (n_in < 0 || (n_in > 0 && (d_T == nullptr || d_SA == nullptr))) {
+        set_error("pss_sa_build: bad arguments");
+        return PSS_EINVAL;
+    }
+    if (flags & PSS_SA_COLD) {       // a cold build: nothing of earlier builds on this device is used
+        ctx->plan.forget();
+        flags &= ~PSS_SA_COLD;       // (a restart of THIS build keeps what it has learnt)
+    }
+    if (n_in < 2) {
+        if (n_in == 1) PSS_HIP(hipMemsetAsync(d_SA, 0, 4, ctx->stream));
+        PSS_HIP(hipStreamSynchronize(ctx->stream));
+        if (stats) memset(stats, 0, sizeof *stats);
+        return PSS_OK;
+    }
+    Abandoned past;
+    for (;;) {
+        Build build(ctx, static_cast<const u8 *>(d_T), static_cast<u32 *>(d_SA), (u32)n_in, flags, past, stats);
+        Next next;
+        PSS_TRY(build.run(&next));
+        if (next == Next::finished) return PSS_OK;
+        flags = build.again_flags;
+    }
 }
 
 }  // namespace pss

@@ -41,6 +41,32 @@ struct RoundsIO {
     struct SideAnchors *side = nullptr;      // the side line of the build these rounds belong to (it may be under way already)
 };
 
+// The 64 KiB of small device state that follow the radix sort's workspace in slot S_WORK of a context, and the pinned
+// host scratch its counters are read through.
+struct SmallState {
+    u32 *present, *counts;      // [256] byte values that occur, [256] their sampled counts (one 2048-byte block)
+    u8 *lut;                    // [256] byte -> code
+    u32 *agg_head, *agg_cnt;    // [1024] each
+    u64 *red;                   // [2]
+    u32 *counters;              // the rounds' own cells, and behind them:
+    u32 *tied;                  // [16] tied counts of the sizing sample
+    u32 *runs, *dups;           // runs of equal bytes | sampled places seen before (neighbours: one copy fetches both)
+    u32 *bad;                   // a byte of the text had no code in the table the MSD sort was given
+    u32 *h_small;
+    SmallState() = default;     // (a Build's, before carve())
+    SmallState(u8 *small, void *pinned)
+        : present(reinterpret_cast<u32 *>(small)), counts(present + 256), lut(small + 2048),
+          agg_head(reinterpret_cast<u32 *>(small + 4096)), agg_cnt(reinterpret_cast<u32 *>(small + 8192)),
+          red(reinterpret_cast<u64 *>(small + 12288)), counters(reinterpret_cast<u32 *>(small + 12288 + 64)), tied(counters + 16),
+          runs(counters + 40), dups(counters + 41), bad(counters + 44), h_small(static_cast<u32 *>(pinned))
+    {
+    }
+    void lend(RoundsIO &io) const
+    {
+        io.d_agg_head = agg_head; io.d_agg_cnt = agg_cnt; io.d_red = red; io.d_counters = counters; io.h_small = h_small;
+    }
+};
+
 static int anchor_rank_keys(DeviceCtx *ctx, const Knobs &knobs, const RoundsIO &outer, u64 h, const u32 *syms,
                             const u32 *cur_ranks, u32 *akey, pss_sa_stats &st, bool *ok);
 
@@ -92,7 +118,6 @@ static int side_start(DeviceCtx *ctx, const Knobs &knobs, SideAnchors &side, u32
     }
     if (after) PSS_HIP(hipStreamWaitEvent(hc->stream, after, 0));
     u8 *hw = hc->slot[S_WORK].as<u8>();
-    u8 *hsmall = hw + sort_ws;
     RoundsIO o2;
     memset(&o2, 0, sizeof o2);
     o2.n = n;
@@ -102,11 +127,7 @@ static int side_start(DeviceCtx *ctx, const Knobs &knobs, SideAnchors &side, u32
     o2.b = b;
     o2.plus_one = plus_one;
     o2.work = hw;
-    o2.d_agg_head = reinterpret_cast<u32 *>(hsmall + 4096);
-    o2.d_agg_cnt = reinterpret_cast<u32 *>(hsmall + 8192);
-    o2.d_red = reinterpret_cast<u64 *>(hsmall + 12288);
-    o2.d_counters = reinterpret_cast<u32 *>(hsmall + 12288 + 64);
-    o2.h_small = static_cast<u32 *>(hc->pinned);
+    SmallState(hw + sort_ws, hc->pinned).lend(o2);
     o2.level = 0;
     side.h_eff = h_eff;
     side.akey = hc->slot[S_ISA].as<u32>();

@@ -456,6 +456,23 @@ def test_io_pool_is_done_with_a_batch_before_its_waiter_returns(tmp_path):
         assert r.returncode == 0, threads + ': ' + r.stdout[-1000:] + r.stderr[-1000:]
 
 
+def test_build_plan_rules_on_the_cpu(tmp_path):
+    """What a build leaves for the next build on its device (csrc/build_plan.h: the remembered initial sort, the sample
+    sort's kept sample and its back-off, the side line's depth) is plain C++ without HIP.  tests/native/build_plan.cpp
+    replays the build sequences of the two plan tests of tests/test_sa_gpu.py on a bare BuildPlan, with the same
+    plan_hint / planned / refused values at every step, then the whole back-off row 1, 3, 7, 15, 31, 63, 63, every
+    argument of the hint and what a cold build forgets.  Built with g++ under AddressSanitizer + UBSan against that
+    header alone: no library, no device."""
+    csrc = os.path.join(ROOT, 'pysubstringsearch_amd', 'csrc')
+    exe = str(tmp_path / 'build_plan')
+    r = subprocess.run(['g++', '-O1', '-g', '-std=c++17', '-Wall', '-Wextra', '-fsanitize=address,undefined',
+                        '-fno-sanitize-recover=undefined', '-I' + csrc,
+                        os.path.join(ROOT, 'tests', 'native', 'build_plan.cpp'), '-o', exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and 'build_plan: ok' in r.stdout, r.stdout[-1000:] + r.stderr[-2000:]
+
+
 def test_host_logic_under_sanitizers(tmp_path):
     """The host side of the library (capi.cpp: container writer / reader, argument checks, packed-result merge;
     common.cpp; corpus.cpp) rebuilt with -fsanitize=address,undefined (`make asan`) and driven through the host tests of

@@ -415,6 +415,40 @@ def test_sample_sort_plan_is_reused_across_chunks(oracle, monkeypatch):
     assert (st['plan_hint'], st['ss'], st['ss_planned']) == (0, 1, 0)
 
 
+def test_early_exits_share_the_epilogue(oracle):
+    """The run-length exit and the periodic-text exit leave the build before the initial sort, through the same epilogue
+    as every other build: the oracle's bytes, and the statistics field by field -- what the two exits fill (the values
+    of a build of these texts as it was before the exits shared the epilogue), and zero in what only a build with an
+    initial sort fills.  4096 bytes in 512 runs of 8 are the smallest text and the exact runs * 8 <= n edge of the
+    run-length path; 32 768 bytes are the smallest text the period screen looks at, and one byte less must not take
+    the closed form."""
+    def build(t):
+        st = {}
+        sa = sa_device(t, st, flags=8)
+        assert (sa == oracle.sa(t)).all()
+        return st
+
+    sorted_only = ('ms_initial', 'initial_passes', 'plan_hint', 'msd', 'ss')
+    st = build(np.frombuffer((b'a' * 8 + b'b' * 8) * 256, dtype=np.uint8).copy())
+    print({k: st[k] for k in ('rle', 'period_path', 'sigma', 'runs', 'rounds', 'sum_active', 'rle_id_bits', 'ms_total', 'ms_restarts') + sorted_only})
+    assert (st['rle'], st['period_path'], st['sigma'], st['runs']) == (2, 0, 4, 512)
+    # (sigma 4 for a text of two byte values is what this exit has always reported: it counts the presence table in the
+    # pinned scratch after the run-length path has used that scratch for its own counters)
+    assert (st['rounds'], st['sum_active'], st['rle_id_bits']) == (9, 4106, 4)
+    assert st['ms_total'] > 0 and st['ms_restarts'] == 0
+    assert all(st[k] == 0 for k in sorted_only), {k: st[k] for k in sorted_only}
+    ab = np.frombuffer(b'ab' * 16384, dtype=np.uint8).copy()
+    st = build(ab)
+    print({k: st[k] for k in ('rle', 'period_path', 'sigma', 'runs', 'period', 'period_extent', 'ms_total', 'ms_restarts') + sorted_only})
+    assert (st['rle'], st['period_path'], st['sigma'], st['runs']) == (0, 1, 2, 32768)
+    assert (st['period'], st['period_extent'], st['rounds']) == (2, 32768, 0)
+    assert st['ms_total'] > 0 and st['ms_restarts'] == 0
+    assert all(st[k] == 0 for k in sorted_only), {k: st[k] for k in sorted_only}
+    st = build(ab[:32767].copy())
+    assert (st['rle'], st['period_path'], st['period'], st['sigma'], st['runs']) == (0, 0, 0, 2, 32767)
+    assert st['initial_passes'] == 4 and st['ms_initial'] > 0 and st['ms_total'] > st['ms_initial']
+
+
 def test_sample_sort_samples_the_whole_text(oracle):
     """Regression (tests/tools/real_text.py, 412 MB of real source files): the sample took one position from every
     stride of floor(n / S) bytes, so the last n mod S positions of a text whose length is no multiple of the sample size
