@@ -1,6 +1,7 @@
 // msd_sort.h -- initial suffix sort as a hybrid MSD radix sort (see msd_sort.hip).
 #pragma once
 #include "common.h"
+#include "msd_layout.h"
 #include "radix_sort.h"
 
 namespace pss {
@@ -29,16 +30,17 @@ struct MsdActive {
     uint32_t count = 0;                      // out: entries in the list
 };
 
-// Bytes of workspace msd_suffix_sort needs besides the two 8 n-byte element buffers.
-size_t msd_workspace_bytes(uint32_t n);
-// Largest key width (bits of packed key >> drop) the 8-byte elements can carry for n suffixes.
+// The workspace of both sorts (`work`, besides their element buffers) is laid out in ONE place: MsdWork of msd_layout.h.
+// msd_workspace_bytes(n) (same header) is the end of that layout, whichever route a sort takes.
+// Largest key width (bits of packed key >> drop) the 8-byte elements can carry for n suffixes, in the order the
+// switches choose (msd_layout.h: the same for a given order).
 int msd_max_key_bits(uint32_t n);
 
 // Same contract as suffix_sort_flags: sa_out[i] = index of the i-th smallest suffix by the low key_bits
 // of (packed text key >> text->drop), bit 31 = "same key as my predecessor".  The order among equal
 // keys is unspecified (suffix_sort_flags leaves them by index; nothing downstream relies on that).
 // *accepted = false (and sa_out untouched) when some joint bucket exceeds what a workgroup sorts in
-// LDS: the caller then uses suffix_sort_flags.  h_small: >= 64 bytes of pinned host memory.
+// LDS: the caller then uses suffix_sort_flags.  h_small: >= 64 bytes of pinned host memory.  work: msd_workspace_bytes(n).
 // `front` (optional): the codes do not exist yet -- the first histogram pass makes them on its way through the raw text
 // (codes[i] = lut[T[i]], the buffer behind text->codes is written; its padding past n must be zero already) and raises
 // *bad when a byte has no code in `lut` (then the sort declines: *accepted = false, stats->bad_symbol = 1).
@@ -79,8 +81,9 @@ uint32_t ss_sample_count(uint32_t n);
 int ss_key_chars(uint32_t n, uint32_t radix);
 uint64_t ss_geometry_tag(uint32_t n, uint32_t radix);
 // Same contract as suffix_sort_flags / msd_suffix_sort without `active` (bit 31 of sa_out[i] = "same key as my
-// predecessor"); the key is the first ss_key_chars() symbols.  `work`: msd_workspace_bytes(n).
+// predecessor": ties always come back as flags, groups of equal keys cross the tiles of this sort); the key is the first
+// ss_key_chars() symbols.  `work`: msd_workspace_bytes(n), of which the sort uses the thirteen shared tables of MsdWork.
 int ss_suffix_sort(DeviceCtx *ctx, const TextKeys *text, uint32_t radix, uint32_t n, const SsBuffers &buf, uint32_t *sa_out,
-                   void *work, uint32_t *h_small, bool profile, SsStats *stats, bool *accepted, MsdActive *active);
+                   void *work, uint32_t *h_small, bool profile, SsStats *stats, bool *accepted);
 
 }  // namespace pss

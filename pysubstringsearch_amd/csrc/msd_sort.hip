@@ -67,37 +67,8 @@
 
 namespace pss {
 
-constexpr int MSD_D = 10;
-constexpr u32 MSD_BINS = 1u << MSD_D;
-constexpr int MSD_BLOCK = 512;
+// (geometry constants, MsdRange / MsdTile / MsdTile2 and the workspace: msd_layout.h)
 constexpr int MSD_WAVES = MSD_BLOCK / kWave;
-constexpr int MSD_IPT = 16;
-constexpr u32 MSD_TILE = MSD_BLOCK * MSD_IPT;        // 8192 elements
-constexpr u32 MSD_WIN = 6144;                        // buckets whose start falls into one window of this size share a tile ...
-#ifndef PSS_LS_WINDOW
-#define PSS_LS_WINDOW 8                              // (members of its bin every element of the local sort reads unconditionally)
-#endif
-constexpr u32 MSD_TILE_CAP = 8184 - PSS_LS_WINDOW;   // ... unless that is more than a tile holds: then the window's last bucket goes alone
-                                                     // (the window's worth of slots behind a tile's last element hold the ranking's
-                                                     //  sentinels, the eight after those the fast kernel's scalars)
-constexpr u32 MSD_MAX_BUCKET = 4088;                 // a bucket must fit a tile on its own (the last eight slots of the LDS tile
-                                                     // carry the fast kernel's scalars: MSD_TILE_CAP)
-constexpr int MSD_TAG_BITS = MSD_D + 1;              // an element entering the local sort carries the low 11 bits of its joint bucket number ...
-constexpr u32 MSD_TAG_SPAN = 1u << MSD_TAG_BITS;     // ... so a tile never crosses a multiple of 2048 buckets: inside it the tags only grow
-constexpr int MSD_RAW_TAG_BITS = 6;                  // LSD order: the tag is the joint bucket number mod 64 (= d mod 64) ...
-constexpr u32 MSD_RAW_TAG_SPAN = 1u << MSD_RAW_TAG_BITS;   // ... and a tile stays inside one aligned block of 64 joint buckets
-constexpr u32 MSD_G1_RANGES = 1024;
-constexpr u32 MSD_G2_RANGE = 16 * MSD_TILE;          // elements per G2 range (a piece of one G1 bucket)
-
-struct MsdRange {
-    u32 seg, start, end;
-};
-
-// A tile of the look-back pass: a piece of one d-region (count 0: an empty region, which still owes its row of the
-// joint table), the region's digit, bit 31 = the region's last tile
-struct MsdTile2 {
-    u32 start, count, d_last;
-};
 
 struct MsdArgs {
     // text source (G1)
@@ -537,7 +508,6 @@ __global__ __launch_bounds__(MSD_BLOCK, 4) void msd_scatter_kernel(MsdArgs a)
 // the 128-byte lines it touches (docs/history 4.3).  LDS stages 8192 elements at a time: the tile goes through in two
 // pieces by destination position.  (The whole tile in one piece -- 128 KiB of the CU's 160, one round of writes, two
 // barriers fewer -- was measured in both kernels and is no faster: DESIGN 4.2.)
-constexpr u32 MSD_TILE2 = 16384;
 constexpr int MSD_PIECES2 = MSD_TILE2 / MSD_TILE;    // 2
 
 template <bool FROM_TEXT, int BLOCK, bool LSD = false>
@@ -964,10 +934,6 @@ __global__ __launch_bounds__(256) void msd_tiles_kernel(const u32 *cstart, u32 n
         if (msd_tile_head(cstart, ne, n, k, tp)) tile_first[rank[k]] = k;
     }
 }
-
-struct MsdTile {
-    u32 e0, count, tag0, nb;      // first element, elements, tag of the first bucket, buckets
-};
 
 // ---- output of a sorted tile ------------------------------------------------------------------------
 
@@ -1659,619 +1625,6 @@ __global__ __launch_bounds__(MSD_BLOCK, 4) void msd_local_fast_kernel(const u64 
 
 #include "ss_sort_impl.h"
 
-// ---- host --------------------------------------------------------------------------------------
-
-// Upper bound on the tiles of the plan: at most two per MSD_WIN window (msd_tile_head) plus one per aligned block
-// of MSD_TAG_SPAN non-empty / MSD_RAW_TAG_SPAN joint buckets.
-static size_t msd_max_tiles(uint32_t n)
-{
-    return (size_t)n / (SS_WIN / 2) + ((size_t)MSD_BINS * MSD_BINS) / MSD_RAW_TAG_SPAN + 8;  // (the smaller window of the two paths, the
-                                                                                             //  finer block rule: LSD order)
-}
-
-static size_t msd_max_tiles2(uint32_t n) { return (size_t)n / MSD_TILE2 + MSD_BINS + 8; }
-
-// LSD order + look-back: the default wherever its 30-bit look-back words hold the positions.  PSS_MSD_LSD=0: the two
-// passes in MSD order with the second histogram pass (rounds 2-5).
-static bool msd_use_lsd(uint32_t n)
-{
-    const char *e = knob("PSS_MSD_LSD");
-    return !(e && atoi(e) == 0) && n < (1u << 30);
-}
-
-size_t msd_workspace_bytes(uint32_t n)
-{
-    const size_t max_ranges2 = (size_t)n / MSD_G2_RANGE + MSD_BINS + 8;
-    const size_t nbk = (size_t)MSD_BINS * MSD_BINS;
-    return max_ranges2 * MSD_BINS * 4                 // T
-           + (MSD_BINS + 8) * 4                       // J1
-           + (nbk + 8) * 4                            // J
-           + max_ranges2 * sizeof(MsdRange) + (MSD_BINS + 8) * 4 + 64   // ranges, seg_first, counters
-           + (nbk + 8) * 8                            // scan output (ranks)
-           + (nbk + 8) * 4                            // compacted starts
-           + (msd_max_tiles(n) + 32) * 8              // tile_first, then the tiles left to the general kernel
-           + (msd_max_tiles(n) + 32) * 16             // blocks of active records per tile + their final offsets
-           + (msd_max_tiles(n) + 32) * sizeof(MsdTile)
-           + (SC_MAX_BLOCKS + 8) * 8 + 8192
-           // LSD order: counts of the first digit per range, the look-back tiles and their words, joint numbers of the buckets
-           + (size_t)MSD_BINS * MSD_G1_RANGES * 4 + (MSD_BINS + 8) * 4
-           + msd_max_tiles2(n) * (sizeof(MsdTile2) + (size_t)MSD_BINS * 4)
-           + (nbk + 8) * 4 + 4096;
-}
-
-int msd_max_key_bits(uint32_t n)
-{
-    int ib = 1;
-    while ((1ull << ib) < (u64)n) ++ib;
-    // [bucket tag | K - 20 key bits | ib index bits] must fit 64 bits after the second pass (an 11-bit tag, or 6 bits in LSD
-    // order), and [K - 10 key bits | ib index bits] after the first
-    const int after2 = 64 + MSD_D - (msd_use_lsd(n) ? MSD_RAW_TAG_BITS : MSD_TAG_BITS) - ib + MSD_D;
-    return std::min(after2, 64 + MSD_D - ib);
-}
-
-int msd_suffix_sort(DeviceCtx *ctx, const TextKeys *text, uint32_t n, int key_bits, uint64_t *A[2], uint32_t *sa_out,
-                    void *work, uint32_t *h_small, bool profile, MsdStats *stats, bool *accepted, MsdActive *active,
-                    const MsdFront *front)
-{
-    *accepted = false;
-    hipStream_t s = ctx->stream;
-    int ib = 1;
-    while ((1ull << ib) < (u64)n) ++ib;
-    if (key_bits < 2 * MSD_D + 1 || key_bits > msd_max_key_bits(n) || n < 2) {
-        set_error("msd_suffix_sort: key of %d bits does not fit (n = %u)", key_bits, n);
-        return PSS_EINVAL;
-    }
-    const size_t max_ranges2 = (size_t)n / MSD_G2_RANGE + MSD_BINS + 8;
-    const size_t nbk = (size_t)MSD_BINS * MSD_BINS;
-    u8 *w = static_cast<u8 *>(work);
-    size_t o = 0;
-    auto carve = [&](size_t bytes) { u8 *p = w + o; o = round_up(o + bytes, 256); return p; };
-    u32 *T = reinterpret_cast<u32 *>(carve(max_ranges2 * MSD_BINS * 4));
-    u32 *J1 = reinterpret_cast<u32 *>(carve((MSD_BINS + 8) * 4));
-    u32 *J = reinterpret_cast<u32 *>(carve((nbk + 8) * 4));
-    MsdRange *ranges2 = reinterpret_cast<MsdRange *>(carve(max_ranges2 * sizeof(MsdRange)));
-    u32 *seg_first = reinterpret_cast<u32 *>(carve((MSD_BINS + 8) * 4));
-    u32 *counters = reinterpret_cast<u32 *>(carve(64));
-    u64 *ranks = reinterpret_cast<u64 *>(carve((nbk + 8) * 8));
-    u32 *cstart = reinterpret_cast<u32 *>(carve((nbk + 8) * 4));
-    const size_t max_tiles = msd_max_tiles(n);
-    MsdTile *tiles_all = reinterpret_cast<MsdTile *>(carve((max_tiles + 16) * sizeof(MsdTile)));
-    u32 *tile_first = reinterpret_cast<u32 *>(carve((max_tiles + 16) * 8));
-    u32 *blk_cnt = reinterpret_cast<u32 *>(carve((max_tiles + 8) * 4));
-    u64 *dst_off = reinterpret_cast<u64 *>(carve((max_tiles + 8) * 8));
-    u64 *partial = reinterpret_cast<u64 *>(carve((SC_MAX_BLOCKS + 8) * 8));
-    u64 *d_total = partial + SC_MAX_BLOCKS;
-    const bool lsd = msd_use_lsd(n);
-    const size_t max_tiles2 = msd_max_tiles2(n);
-    u32 *T2 = nullptr, *Jb = nullptr, *status = nullptr, *cj = nullptr;
-    MsdTile2 *tiles2 = nullptr;
-    if (lsd) {
-        T2 = reinterpret_cast<u32 *>(carve((size_t)MSD_BINS * MSD_G1_RANGES * 4));
-        Jb = reinterpret_cast<u32 *>(carve((MSD_BINS + 8) * 4));
-        tiles2 = reinterpret_cast<MsdTile2 *>(carve(max_tiles2 * sizeof(MsdTile2)));
-        status = reinterpret_cast<u32 *>(carve(max_tiles2 * MSD_BINS * 4));
-        cj = reinterpret_cast<u32 *>(carve((nbk + 8) * 4));
-    }
-
-    MsdArgs a;
-    memset(&a, 0, sizeof a);
-    a.codes = text->codes;
-    a.code_bits = text->code_bits;
-    a.key_chars = text->key_chars;
-    a.plus_one = text->plus_one;
-    a.key_drop = text->drop;
-    a.n = n;
-    a.key_bits = key_bits;
-    a.idx_bits = ib;
-    const u32 num_tiles = (u32)(((u64)n + MSD_TILE - 1) / MSD_TILE);
-    a.tiles_per_range1 = (num_tiles + MSD_G1_RANGES - 1) / MSD_G1_RANGES;
-    a.num_ranges1 = (num_tiles + a.tiles_per_range1 - 1) / a.tiles_per_range1;
-    a.T = T;
-    a.J1 = J1;
-    a.J = J;
-    a.ranges2 = ranges2;
-    a.seg_first = seg_first;
-    a.counters = counters;
-    a.lsd = lsd ? 1 : 0;
-    a.T2 = T2;
-    a.Jb = Jb;
-    a.tiles2 = tiles2;
-    a.status = status;
-
-    hipEvent_t ev[8] = {};
-    int nev = 0;
-    struct EvGuard {
-        hipEvent_t *e;
-        int *n;
-        ~EvGuard()
-        {
-            for (int i = 0; i < *n; ++i) (void)hipEventDestroy(e[i]);
-        }
-    } guard{ev, &nev};
-    auto mark = [&]() -> int {
-        if (profile && nev < 8) {
-            PSS_HIP(hipEventCreate(&ev[nev]));
-            PSS_HIP(hipEventRecord(ev[nev], s));
-            ++nev;
-        }
-        return PSS_OK;
-    };
-
-    PSS_HIP(hipMemsetAsync(counters, 0, 64, s));
-    // ---- G1: text -> A[0] by the top 10 key bits ----
-    a.out = A[0];
-    if (front) {
-        a.raw = front->raw;
-        a.lut = front->lut;
-        a.codes_out = const_cast<u8 *>(text->codes);
-        a.bad = front->bad;
-        hipLaunchKernelGGL(msd_hist_raw_kernel, dim3(a.num_ranges1), dim3(MSD_BLOCK), 0, s, a);
-    } else {
-        hipLaunchKernelGGL(msd_hist_kernel<true>, dim3(a.num_ranges1), dim3(MSD_BLOCK), 0, s, a);
-    }
-    static_assert(MSD_G1_RANGES <= 1024, "msd_offsets1_kernel takes four ranges per thread");
-    hipLaunchKernelGGL(msd_offsets1_kernel, dim3(MSD_BINS), dim3(256), 0, s, T, a.num_ranges1, seg_first);   // totals: scratch
-    hipLaunchKernelGGL(msd_offsets1b_kernel, dim3(1), dim3(MSD_BINS), 0, s, (const u32 *)seg_first, J1, n);
-    if (lsd) {
-        // the first digit's bucket starts from the same pass over the text (the per-range prefixes in T2 are not used)
-        hipLaunchKernelGGL(msd_offsets1_kernel, dim3(MSD_BINS), dim3(256), 0, s, T2, a.num_ranges1, seg_first);
-        hipLaunchKernelGGL(msd_offsets1b_kernel, dim3(1), dim3(MSD_BINS), 0, s, (const u32 *)seg_first, Jb, n);
-        // (the words of the look-back pass: zero = nothing published)
-        PSS_HIP(hipMemsetAsync(status, 0, max_tiles2 * MSD_BINS * 4, s));
-    }
-    PSS_TRY(mark());
-    // 16384-element scatter tiles (whole-line runs), 1024 threads: 2.2 -> 1.9 ms (from the text) and 2.8 -> 2.45 ms
-    // (second pass, with its sixteen loads per thread issued before the ranking atomics) at 2^29; 512 threads x 32 elements
-    // spill.  PSS_MSD_SCATTER=1: the 8192-element kernels.
-    const bool wide = lsd || !(knob("PSS_MSD_SCATTER") && atoi(knob("PSS_MSD_SCATTER")) == 1);
-    if (lsd) hipLaunchKernelGGL((msd_scatter2_kernel<true, 1024, true>), dim3(a.num_ranges1), dim3(1024), 0, s, a);
-    else if (wide) hipLaunchKernelGGL((msd_scatter2_kernel<true, 1024>), dim3(a.num_ranges1), dim3(1024), 0, s, a);
-    else hipLaunchKernelGGL(msd_scatter_kernel<true>, dim3(a.num_ranges1), dim3(MSD_BLOCK), 0, s, a);
-    PSS_TRY(mark());
-    a.in = A[0];
-    a.out = A[1];
-    if (lsd) {
-        // ---- second pass in one sweep: A[0] -> A[1] by the first digit, tile order kept (look-back); leaves J ----
-        hipLaunchKernelGGL(msd_tiles2_kernel, dim3(1), dim3(MSD_BINS), 0, s, (const u32 *)J1, tiles2, counters);
-        PSS_TRY(mark());
-        const u32 grid2 = std::min<u32>((u32)max_tiles2, (u32)ctx->num_cus);      // one 1024-thread workgroup per CU (~100 VGPRs)
-        hipLaunchKernelGGL(msd_scatter_lb_kernel, dim3(grid2), dim3(1024), 0, s, a);
-        PSS_TRY(mark());
-    } else {
-        // ---- G2: A[0] -> A[1], every G1 bucket by the next 10 bits ----
-        hipLaunchKernelGGL(msd_ranges_kernel, dim3(1), dim3(MSD_BINS), 0, s, J1, ranges2, seg_first, counters);
-        a.dense = ranks;
-        hipLaunchKernelGGL(msd_hist_kernel<false>, dim3((u32)max_ranges2), dim3(MSD_BLOCK), 0, s, a);
-        hipLaunchKernelGGL(msd_offsets_kernel, dim3(MSD_BINS), dim3(MSD_BINS), 0, s, T, (const u32 *)seg_first, (const u32 *)J1, J,
-                           0u, n, MSD_BINS);
-    }
-    // ---- plan: non-empty joint buckets, largest bucket, tiles ----
-    PSS_TRY(device_excl_scan(ctx, InNonEmpty{J}, nbk, partial, d_total, ranks));
-    hipLaunchKernelGGL(msd_compact_kernel, dim3(1024), dim3(256), 0, s, J, (u32)nbk, ranks, cstart, counters, cj);
-    const int rem_bits = key_bits - 2 * MSD_D;
-    MsdEmit em{};
-    const int fused = active != nullptr;
-    if (fused) em = MsdEmit{active->st_pos, active->st_idx, blk_cnt};
-    // LSD order: nothing between here and the local sort needs the host -- the counts stay on the device (the scans run
-    // over all 2^20 bucket numbers), the local sort checks the plan's verdict itself, ONE round trip afterwards tells the
-    // host everything (rounds 2-5: three, ~0.1 ms of idle GPU each at n = 2^29).
-    const bool one_trip = lsd && !knob("PSS_MSD_SLOW_LOCAL");
-    u64 *d_total2 = d_total + 1;
-    u32 *const fail_list_dev = tile_first + max_tiles + 16;      // (tile_first has 2 (max_tiles + 16) slots)
-    if (one_trip) {
-        const TilePlan tpd{MSD_WIN, MSD_TILE_CAP, cj};
-        PSS_TRY(device_excl_scan(ctx, InTileHeadDev{cstart, d_total, n, tpd}, nbk, partial, d_total2, ranks));
-        hipLaunchKernelGGL(msd_tiles_dev_kernel, dim3(1024), dim3(256), 0, s, cstart, (const u64 *)d_total, n, ranks, (const u64 *)d_total2,
-                           tile_first, tpd);
-        hipLaunchKernelGGL(msd_tile_desc_kernel, dim3((u32)((max_tiles + 255) / 256)), dim3(256), 0, s, cstart, tile_first, 0u, 0u, n,
-                           tiles_all, (const u32 *)cj, (const u64 *)d_total2, (const u64 *)d_total);
-        PSS_TRY(mark());            // (events 2 .. 5: second pass, then the local sort)
-        hipLaunchKernelGGL(msd_local_fast_kernel, dim3(2u * (u32)ctx->num_cus), dim3(MSD_BLOCK), 0, s, A[1], (const MsdTile *)tiles_all, 0u,
-                           rem_bits, ib, sa_out, fail_list_dev, counters + 4, fused, em, (const u64 *)d_total2, (const u32 *)counters,
-                           front ? (const u32 *)front->bad : (const u32 *)nullptr);
-        PSS_TRY(mark());
-        PSS_HIP(hipMemcpyAsync(h_small + 8, d_total2, 8, hipMemcpyDeviceToHost, s));
-        PSS_HIP(hipMemcpyAsync(h_small + 10, counters + 4, 4, hipMemcpyDeviceToHost, s));
-    }
-    PSS_HIP(hipMemcpyAsync(h_small, d_total, 8, hipMemcpyDeviceToHost, s));
-    PSS_HIP(hipMemcpyAsync(h_small + 2, counters, 16, hipMemcpyDeviceToHost, s));
-    if (front) PSS_HIP(hipMemcpyAsync(h_small + 6, front->bad, 4, hipMemcpyDeviceToHost, s));
-    PSS_HIP(hipStreamSynchronize(s));
-    const u32 ne = h_small[0];
-    const u32 maxb = h_small[3];
-    if (stats) {
-        stats->buckets = ne;
-        stats->max_bucket = maxb;
-        stats->bad_symbol = front ? h_small[6] : 0u;
-    }
-    if (front && h_small[6]) return PSS_OK;        // a byte the table has no code for: nothing of this sort can be used
-    if (maxb > MSD_MAX_BUCKET) return PSS_OK;      // not this text: the caller takes the LSD path
-    if (!lsd) {
-        PSS_TRY(mark());
-        if (wide) hipLaunchKernelGGL((msd_scatter2_kernel<false, 1024>), dim3((u32)max_ranges2), dim3(1024), 0, s, a);
-        else hipLaunchKernelGGL(msd_scatter_kernel<false>, dim3((u32)max_ranges2), dim3(MSD_BLOCK), 0, s, a);
-        PSS_TRY(mark());
-    }
-    const auto local_sort = msd_local_sort_kernel;
-    const auto local_fast = msd_local_fast_kernel;
-    u32 nt = 0;
-    u32 *fail_list = fail_list_dev;
-    if (one_trip) {
-        nt = h_small[8];
-        if ((size_t)nt > max_tiles) {
-            set_error("msd_suffix_sort: %u tiles planned, tables hold %zu (internal error)", nt, max_tiles);
-            return PSS_EDEVICE;
-        }
-        const u32 nfail = h_small[10];
-        if (stats) stats->slow_tiles = nfail;
-        if (nfail)
-            hipLaunchKernelGGL(local_sort, dim3(nfail), dim3(MSD_BLOCK), 0, s, A[1], (const MsdTile *)tiles_all, rem_bits,
-                               ib, sa_out, (const u32 *)fail_list, fused, em);
-    } else {
-    const TilePlan tp{MSD_WIN, MSD_TILE_CAP, cj};
-    PSS_TRY(device_excl_scan(ctx, InTileHead{cstart, ne, n, tp}, ne, partial, d_total, ranks));
-    hipLaunchKernelGGL(msd_tiles_kernel, dim3(1024), dim3(256), 0, s, cstart, ne, n, ranks, (const u64 *)d_total, tile_first, tp);
-    PSS_HIP(hipMemcpyAsync(h_small, d_total, 8, hipMemcpyDeviceToHost, s));
-    PSS_HIP(hipStreamSynchronize(s));
-    nt = h_small[0];
-    if ((size_t)nt > max_tiles) {       // cannot happen (msd_max_tiles is an upper bound of the plan): never run past the tables
-        set_error("msd_suffix_sort: %u tiles planned, tables hold %zu (internal error)", nt, max_tiles);
-        return PSS_EDEVICE;
-    }
-    PSS_TRY(mark());
-    // counters[4] = tiles the fast kernel declined (their numbers go behind the tile table), [5] = active records
-    fail_list = tile_first + nt + 8;
-    hipLaunchKernelGGL(msd_tile_desc_kernel, dim3((nt + 255) / 256), dim3(256), 0, s, cstart, tile_first, nt, ne, n, tiles_all,
-                       (const u32 *)cj, (const u64 *)nullptr, (const u64 *)nullptr);
-    if (knob("PSS_MSD_SLOW_LOCAL")) {
-        hipLaunchKernelGGL(local_sort, dim3(nt), dim3(MSD_BLOCK), 0, s, A[1], (const MsdTile *)tiles_all, rem_bits, ib,
-                           sa_out, (const u32 *)nullptr, fused, em);
-    } else {
-        MsdTile *tiles = tiles_all;
-        const u32 grid = std::min<u32>(nt, 2u * (u32)ctx->num_cus);
-        hipLaunchKernelGGL(local_fast, dim3(grid), dim3(MSD_BLOCK), 0, s, A[1], (const MsdTile *)tiles, nt, rem_bits, ib,
-                           sa_out, fail_list, counters + 4, fused, em, (const u64 *)nullptr, (const u32 *)nullptr, (const u32 *)nullptr);
-        PSS_TRY(mark());            // (profile mode) the events bracket this launch alone
-        PSS_HIP(hipMemcpyAsync(h_small, counters + 4, 4, hipMemcpyDeviceToHost, s));
-        PSS_HIP(hipStreamSynchronize(s));
-        const u32 nfail = h_small[0];
-        if (stats) stats->slow_tiles = nfail;
-        if (nfail)
-            hipLaunchKernelGGL(local_sort, dim3(nfail), dim3(MSD_BLOCK), 0, s, A[1], (const MsdTile *)tiles_all, rem_bits,
-                               ib, sa_out, (const u32 *)fail_list, fused, em);
-    }
-    if (knob("PSS_MSD_SLOW_LOCAL")) PSS_TRY(mark());
-    }
-    if (fused) {
-        // small groups are settled here and now (msd_finish_kernel); the list is made of what they leave.  The count of
-        // the settled suffixes comes down with the list's length, in the high word of the same sum.
-        const bool finish = knob("PSS_MSD_NO_FINISH") == nullptr;
-        if (finish) {
-            const int ks = std::min(64 / text->code_bits, 16);
-            const MsdFinish fin{text->codes, text->code_bits, ks, text->plus_one,
-                                (u32)(text->drop ? text->key_chars - 1 : text->key_chars), n};
-            hipLaunchKernelGGL(msd_finish_kernel, dim3((nt + 3) / 4), dim3(256), 0, s, (const MsdTile *)tiles_all, blk_cnt, nt,
-                               active->st_pos, active->st_idx, sa_out, fin);
-        }
-        PSS_TRY(device_excl_scan(ctx, InBlkCnt{blk_cnt}, nt, partial, d_total, dst_off));
-        hipLaunchKernelGGL(msd_gather_kernel, dim3((nt + 3) / 4), dim3(256), 0, s, (const MsdTile *)tiles_all, blk_cnt, dst_off, nt,
-                           active->st_pos, active->st_idx, active->pos, active->idx, active->grp);
-        PSS_HIP(hipMemcpyAsync(h_small, d_total, 8, hipMemcpyDeviceToHost, s));
-        PSS_HIP(hipStreamSynchronize(s));
-        active->count = h_small[0];
-        if (stats) stats->finished = h_small[1];
-    }
-    PSS_HIP(hipGetLastError());
-    if (stats) {
-        stats->tiles = nt;
-        stats->lookback = lsd ? 1u : 0u;
-    }
-    if (profile && nev >= 6) {
-        PSS_HIP(hipStreamSynchronize(s));
-        float ms = 0.f;
-        PSS_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
-        if (stats) stats->ms_g1 = ms;
-        PSS_HIP(hipEventElapsedTime(&ms, ev[2], ev[3]));
-        if (stats) stats->ms_g2 = ms;
-        PSS_HIP(hipEventElapsedTime(&ms, ev[4], ev[5]));
-        if (stats) stats->ms_local = ms;
-    }
-    *accepted = true;
-    return PSS_OK;
-}
-
-// ---- sample sort: host ---------------------------------------------------------------------------------------------
-
-struct SsGeometry {
-    u32 B1, B2, os, S;
-    int ib, kc, key_bits;
-    u64 plo, phi;          // radix^(kc - 1)
-};
-static bool ss_geometry(uint32_t n, uint32_t radix, SsGeometry *g)
-{
-    if (n < (1u << 16) || n > (1u << 30) || radix < 2 || radix > 257) return false;
-    int ib = 1;
-    while ((1ull << ib) < (u64)n) ++ib;
-    // symbols per key: the largest kc with radix^kc <= 2^(128 - ib), at most SS_MAX_CHARS
-    const unsigned __int128 limit = (unsigned __int128)1 << (128 - ib);
-    unsigned __int128 pw = 1;
-    int kc = 0;
-    while (kc < SS_MAX_CHARS && pw <= limit / radix) {
-        pw *= radix;
-        ++kc;
-    }
-    if (kc < 2) return false;
-    unsigned __int128 lead = 1;
-    for (int i = 0; i + 1 < kc; ++i) lead *= radix;
-    g->plo = (u64)lead;
-    g->phi = (u64)(lead >> 64);
-    int kb = 0;
-    while (kb < 128 && ((pw - 1) >> kb) != 0) ++kb;      // bits of the largest key
-    g->key_bits = kb;
-    // joint buckets of ~512 elements (a tile holds 4088): B1 x B2 of them, both powers of two <= 1024
-    int lb = 4;
-    while (((u64)512 << lb) < (u64)n && lb < 20) ++lb;
-    const u32 B1 = 1u << ((lb + 1) / 2), B2 = 1u << (lb / 2);
-    // sample members per bucket: the bucket sizes follow a gamma distribution of that shape -- 4 puts a bucket of 512 on
-    // average beyond 4088 with probability 1e-10, an average of 1024 (n = 2^30) needs 8
-    const u32 os = ((u64)n > (u64)768 * B1 * B2) ? 8u : 4u;
-    g->B1 = B1;
-    g->B2 = B2;
-    g->os = os;
-    g->S = os * B1 * B2;
-    g->ib = ib;
-    g->kc = kc;
-    return (u64)g->S * 4 <= (u64)n;
-}
-uint32_t ss_sample_count(uint32_t n)
-{
-    SsGeometry g;
-    return ss_geometry(n, 257, &g) ? g.S : 0u;
-}
-// Everything about the sort that depends on n and the alphabet, in one number (0: the sort does not take this text): two
-// texts with the same tag can be cut by the same sorted sample (sa_build.hip, the plan of the sample sort).
-uint64_t ss_geometry_tag(uint32_t n, uint32_t radix)
-{
-    SsGeometry g;
-    if (!ss_geometry(n, radix, &g)) return 0;
-    return ((uint64_t)g.S << 32) | ((uint64_t)g.B1 << 20) | ((uint64_t)g.B2 << 8) | ((uint64_t)g.ib << 2) | (uint64_t)(g.os == 8) | ((uint64_t)g.kc << 58);
-}
-int ss_key_chars(uint32_t n, uint32_t radix)
-{
-    SsGeometry g;
-    return ss_geometry(n, radix, &g) ? g.kc : 0;
-}
-
-int ss_suffix_sort(DeviceCtx *ctx, const TextKeys *text, uint32_t radix, uint32_t n, const SsBuffers &buf, uint32_t *sa_out,
-                   void *work, uint32_t *h_small, bool profile, SsStats *stats, bool *accepted, MsdActive *active)
-{
-    *accepted = false;
-    hipStream_t s = ctx->stream;
-    SsGeometry g;
-    if (!ss_geometry(n, radix, &g)) return PSS_OK;      // not this text
-    static_assert(SS_SBLOCK == (int)MSD_BINS, "one bin per thread in the scatter passes");
-    const size_t max_ranges2 = (size_t)n / MSD_G2_RANGE + MSD_BINS + 8;
-    const size_t nbk = (size_t)MSD_BINS * MSD_BINS;
-    u8 *w = static_cast<u8 *>(work);
-    size_t o = 0;
-    auto carve = [&](size_t bytes) { u8 *p = w + o; o = round_up(o + bytes, 256); return p; };
-    // (the same carving as msd_suffix_sort: msd_workspace_bytes covers it)
-    u32 *T = reinterpret_cast<u32 *>(carve(max_ranges2 * MSD_BINS * 4));
-    u32 *J1 = reinterpret_cast<u32 *>(carve((MSD_BINS + 8) * 4));
-    u32 *J = reinterpret_cast<u32 *>(carve((nbk + 8) * 4));
-    MsdRange *ranges2 = reinterpret_cast<MsdRange *>(carve(max_ranges2 * sizeof(MsdRange)));
-    u32 *seg_first = reinterpret_cast<u32 *>(carve((MSD_BINS + 8) * 4));
-    u32 *counters = reinterpret_cast<u32 *>(carve(64));
-    u64 *ranks = reinterpret_cast<u64 *>(carve((nbk + 8) * 8));
-    u32 *cstart = reinterpret_cast<u32 *>(carve((nbk + 8) * 4));
-    const size_t max_tiles = msd_max_tiles(n);
-    MsdTile *tiles_all = reinterpret_cast<MsdTile *>(carve((max_tiles + 16) * sizeof(MsdTile)));
-    u32 *tile_first = reinterpret_cast<u32 *>(carve((max_tiles + 16) * 8));
-    u32 *blk_cnt = reinterpret_cast<u32 *>(carve((max_tiles + 8) * 4));
-    u64 *dst_off = reinterpret_cast<u64 *>(carve((max_tiles + 8) * 8));
-    u64 *partial = reinterpret_cast<u64 *>(carve((SC_MAX_BLOCKS + 8) * 8));
-    u64 *d_total = partial + SC_MAX_BLOCKS;
-
-    hipEvent_t ev[8] = {};
-    int nev = 0;
-    struct EvGuard {
-        hipEvent_t *e;
-        int *n;
-        ~EvGuard()
-        {
-            for (int i = 0; i < *n; ++i) (void)hipEventDestroy(e[i]);
-        }
-    } guard{ev, &nev};
-    auto mark = [&]() -> int {
-        if (profile && nev < 8) {
-            PSS_HIP(hipEventCreate(&ev[nev]));
-            PSS_HIP(hipEventRecord(ev[nev], s));
-            ++nev;
-        }
-        return PSS_OK;
-    };
-
-    SsText tx{text->codes, n, text->code_bits, g.kc, text->plus_one, g.ib, radix, g.plo, g.phi};
-    const u32 S = g.S;
-    E16 *E0 = static_cast<E16 *>(buf.E0), *E = static_cast<E16 *>(buf.E);
-    PSS_TRY(mark());                                                                       // [0]
-    // ---- the sample, sorted as 128-bit numbers ----
-    if (buf.sample_in) {
-        E = const_cast<E16 *>(static_cast<const E16 *>(buf.sample_in));      // (read only from here on)
-    } else {
-    hipLaunchKernelGGL(ss_sample_kernel, dim3((S + 255) / 256), dim3(256), 0, s, tx, S, E0, buf.K[0], buf.V[0]);
-    if (S <= 8192) {
-        // (small texts, tests: the device sort's one-workgroup path is not stable, which the second of the chained sorts needs)
-        std::vector<E16> hs(S);
-        PSS_HIP(hipMemcpyAsync(hs.data(), E0, (size_t)S * 16, hipMemcpyDeviceToHost, s));
-        PSS_HIP(hipStreamSynchronize(s));
-        std::sort(hs.begin(), hs.end(), [](const E16 &x, const E16 &y) { return x.hi < y.hi || (x.hi == y.hi && x.lo < y.lo); });
-        PSS_HIP(hipMemcpyAsync(E, hs.data(), (size_t)S * 16, hipMemcpyHostToDevice, s));
-        PSS_HIP(hipStreamSynchronize(s));
-    } else {
-        u64 *K[2] = {buf.K[0], buf.K[1]};
-        u32 *V[2] = {buf.V[0], buf.V[1]};
-        SortStats ss1;
-        int d1 = 0, d2 = 0;
-        PSS_TRY(radix_sort_pairs(ctx, K, V, S, 64, 0xffu, nullptr, 0, buf.sort_work, &d1, false, &ss1));
-        hipLaunchKernelGGL(ss_gather_hi_kernel, dim3((S + 255) / 256), dim3(256), 0, s, E0, (const u32 *)V[d1], S, K[d1]);
-        const int hi_bits = std::min(64, std::max(1, g.key_bits + g.ib - 64));
-        PSS_TRY(radix_sort_pairs(ctx, K, V, S, hi_bits, 0xffu, nullptr, d1, buf.sort_work, &d2, false, &ss1));
-        hipLaunchKernelGGL(ss_gather_elems_kernel, dim3((S + 255) / 256), dim3(256), 0, s, E0, (const u32 *)V[d2], S, E);
-    }
-    if (buf.sample_keep) PSS_HIP(hipMemcpyAsync(buf.sample_keep, E, (size_t)S * 16, hipMemcpyDeviceToDevice, s));
-    }
-    PSS_TRY(mark());                                                                       // [1]
-
-    SsArgs a;
-    memset(&a, 0, sizeof a);
-    a.text = tx;
-    a.sample = E;
-    a.B1 = g.B1;
-    a.B2 = g.B2;
-    a.spb = S / g.B1;
-    a.st2 = g.os;
-    a.zl = (u32)std::max(0, std::min(64 - SS_CELL_BITS, 128 - g.key_bits - g.ib));
-    const u32 num_tiles = (u32)(((u64)n + SS_DTILE1 - 1) / SS_DTILE1);
-    a.tiles_per_range1 = (num_tiles + MSD_G1_RANGES - 1) / MSD_G1_RANGES;
-    a.num_ranges1 = (num_tiles + a.tiles_per_range1 - 1) / a.tiles_per_range1;
-    a.T = T;
-    a.J1 = J1;
-    a.ranges2 = ranges2;
-    a.counters = counters;
-    a.digits = buf.digits;
-    PSS_HIP(hipMemsetAsync(counters, 0, 64, s));
-    // ---- G1: text -> A[0] by the first-level splitters ----
-    hipLaunchKernelGGL(ss_digits1_kernel, dim3(a.num_ranges1), dim3(SS_DBLOCK), 0, s, a);
-    hipLaunchKernelGGL(msd_offsets1_kernel, dim3(MSD_BINS), dim3(256), 0, s, T, a.num_ranges1, seg_first);
-    hipLaunchKernelGGL(msd_offsets1b_kernel, dim3(1), dim3(MSD_BINS), 0, s, (const u32 *)seg_first, J1, n);
-    a.out = static_cast<E16 *>(buf.A[0]);
-    hipLaunchKernelGGL(ss_scatter_kernel<true>, dim3(a.num_ranges1), dim3(SS_SBLOCK), 0, s, a);
-    PSS_TRY(mark());                                                                       // [2]
-    // ---- G2: A[0] -> A[1], every first-level bucket by its own splitters ----
-    hipLaunchKernelGGL(msd_ranges_kernel, dim3(1), dim3(MSD_BINS), 0, s, (const u32 *)J1, ranges2, seg_first, counters);
-    a.in = static_cast<const E16 *>(buf.A[0]);
-    a.out = static_cast<E16 *>(buf.A[1]);
-    hipLaunchKernelGGL(ss_digits2_kernel, dim3((u32)max_ranges2), dim3(SS_DBLOCK), 0, s, a);
-    hipLaunchKernelGGL(msd_offsets_kernel, dim3(MSD_BINS), dim3(MSD_BINS), 0, s, T, (const u32 *)seg_first, (const u32 *)J1, J,
-                       0u, n, MSD_BINS);
-    PSS_TRY(device_excl_scan(ctx, InNonEmpty{J}, nbk, partial, d_total, ranks));
-    hipLaunchKernelGGL(msd_compact_kernel, dim3(1024), dim3(256), 0, s, J, (u32)nbk, ranks, cstart, counters, (u32 *)nullptr);
-    PSS_HIP(hipMemcpyAsync(h_small, d_total, 8, hipMemcpyDeviceToHost, s));
-    PSS_HIP(hipMemcpyAsync(h_small + 2, counters, 16, hipMemcpyDeviceToHost, s));
-    PSS_HIP(hipStreamSynchronize(s));
-    const u32 ne = h_small[0];
-    const u32 maxb = h_small[3];
-    if (stats) {
-        stats->buckets = ne;
-        stats->max_bucket = maxb;
-        stats->b1 = g.B1;
-        stats->b2 = g.B2;
-        stats->samples = S;
-        stats->key_chars = g.kc;
-    }
-    if (maxb > SS_MAX_BUCKET && knob("PSS_SS_DEBUG")) {
-        // diagnostic: where did the crowded bucket come from?  (first-level bucket sizes, the largest joint buckets)
-        std::vector<u32> hj1(MSD_BINS + 1), hj((size_t)nbk + 1);
-        (void)hipMemcpy(hj1.data(), J1, (MSD_BINS + 1) * 4, hipMemcpyDeviceToHost);
-        (void)hipMemcpy(hj.data(), J, ((size_t)nbk + 1) * 4, hipMemcpyDeviceToHost);
-        u32 m1 = 0, a1 = 0;
-        for (u32 i = 0; i < g.B1; ++i) { const u32 c = hj1[i + 1] - hj1[i]; if (c > m1) { m1 = c; a1 = i; } }
-        fprintf(stderr, "[pss] ss declined: n=%u S=%u B1=%u B2=%u kc=%d ib=%d | largest first-level bucket %u (#%u, average %u) | joint buckets above the cap:", n, S,
-                g.B1, g.B2, g.kc, g.ib, m1, a1, n / g.B1);
-        int shown = 0;
-        for (u64 i = 0; i < nbk && shown < 12; ++i) {
-            const u32 c = hj[i + 1] - hj[i];
-            if (c > SS_MAX_BUCKET) { fprintf(stderr, " #%llu:%u@%u", (unsigned long long)i, c, hj[i]); ++shown; }
-        }
-        fprintf(stderr, "\n");
-    }
-    if (maxb > SS_MAX_BUCKET) return PSS_OK;      // (a sampling accident, probability ~1e-10 per bucket: the caller falls back)
-    hipLaunchKernelGGL(ss_scatter_kernel<false>, dim3((u32)max_ranges2), dim3(SS_SBLOCK), 0, s, a);
-    PSS_TRY(mark());                                                                       // [3]
-    // bucket-by-bucket local sort (ss_local_seg_kernel): the plan counts every bucket's length rounded up to eight
-    const char *seg_env = knob("PSS_SS_SEG");
-    const bool seg = !knob("PSS_SS_WINDOW_PLAN") && !(seg_env && atoi(seg_env) == 0);
-    u32 *pstart = nullptr;
-    if (knob("PSS_SS_WINDOW_PLAN")) {
-        const TilePlan tp{SS_WIN, SS_TILE_CAP, nullptr};
-        PSS_TRY(device_excl_scan(ctx, InTileHead{cstart, ne, n, tp}, ne, partial, d_total, ranks));
-        hipLaunchKernelGGL(msd_tiles_kernel, dim3(1024), dim3(256), 0, s, cstart, ne, n, ranks, (const u64 *)d_total, tile_first, tp);
-    } else {
-        // greedy plan (ss_sort_impl.h); its tables live in the first element buffer, which the second scatter has read
-        const size_t row = (size_t)ne + 1;
-        u32 *pl = reinterpret_cast<u32 *>(buf.A[0]);
-        const u32 *starts = cstart;
-        u32 total = n, cap = SS_TILE_CAP;
-        if (seg) {
-            PSS_TRY(device_excl_scan(ctx, InPad8{cstart, ne, n}, ne, partial, d_total, ranks));
-            PSS_HIP(hipMemcpyAsync(h_small, d_total, 8, hipMemcpyDeviceToHost, s));
-            pstart = pl;                                                  // the first row of the tables; read by the local sort too
-            hipLaunchKernelGGL(ss_pad_starts_kernel, dim3((u32)((row + 255) / 256)), dim3(256), 0, s, (const u64 *)ranks, (const u64 *)d_total, ne,
-                               pstart);
-            PSS_HIP(hipStreamSynchronize(s));
-            total = h_small[0];
-            starts = pstart;
-            cap = SS_TILE;
-            pl += round_up(row, 64);
-        }
-        const u32 nseg = (u32)(((u64)total + SS_PLAN_SEG - 1) / SS_PLAN_SEG);
-        u32 levels = 0;
-        while ((1u << levels) < nseg) ++levels;
-        u32 *nxt = pl, *heads = pl + row, *jumps = pl + 2 * row;          // jumps: `levels` rows (at least one)
-        const u32 gb = (u32)((row + 255) / 256);
-        PSS_HIP(hipMemsetAsync(heads, 0, row * 4, s));
-        hipLaunchKernelGGL(ss_plan_next_kernel, dim3(gb), dim3(256), 0, s, starts, ne, total, cap, nxt);
-        hipLaunchKernelGGL(ss_plan_exit_kernel, dim3(gb), dim3(256), 0, s, starts, ne, (const u32 *)nxt, jumps);
-        for (u32 i = 1; i < levels; ++i)
-            hipLaunchKernelGGL(ss_plan_double_kernel, dim3(gb), dim3(256), 0, s, (const u32 *)(jumps + (size_t)(i - 1) * row), (u32)row,
-                               jumps + (size_t)i * row);
-        hipLaunchKernelGGL(ss_plan_mark_kernel, dim3((nseg + 255) / 256), dim3(256), 0, s, starts, ne, (const u32 *)nxt,
-                           (const u32 *)jumps, levels, nseg, heads);
-        PSS_TRY(device_excl_scan(ctx, InU32{heads}, ne, partial, d_total, ranks));
-        hipLaunchKernelGGL(ss_plan_tiles_kernel, dim3(1024), dim3(256), 0, s, (const u32 *)heads, ne, (const u64 *)ranks,
-                           (const u64 *)d_total, tile_first);
-    }
-    PSS_HIP(hipMemcpyAsync(h_small, d_total, 8, hipMemcpyDeviceToHost, s));
-    PSS_HIP(hipStreamSynchronize(s));
-    const u32 nt = h_small[0];
-    if ((size_t)nt > max_tiles) {
-        set_error("ss_suffix_sort: %u tiles planned, tables hold %zu (internal error)", nt, max_tiles);
-        return PSS_EDEVICE;
-    }
-    hipLaunchKernelGGL(msd_tile_desc_kernel, dim3((nt + 255) / 256), dim3(256), 0, s, cstart, tile_first, nt, ne, n, tiles_all,
-                       (const u32 *)nullptr, (const u64 *)nullptr, (const u64 *)nullptr);
-    // Ties go out as flags (bit 31 = "same key as my predecessor", the contract of suffix_sort_flags), not as the records
-    // of the fused first rerank: groups of equal keys cross tile boundaries here, and the flag of a tile's first element
-    // takes a look at the tile before it (ss_boundary_kernel, once every tile is sorted).
-    (void)active;
-    (void)blk_cnt;
-    (void)dst_off;
-    PSS_TRY(mark());                                                                       // [4]
-    if (pstart)
-        hipLaunchKernelGGL(ss_local_seg_kernel, dim3(nt), dim3(SL_BLOCK), 0, s, (const E16 *)buf.A[1], (const MsdTile *)tiles_all, nt, g.ib,
-                           (const u32 *)cstart, (const u32 *)pstart, (const u32 *)tile_first, ne, n, sa_out);
-    else
-        hipLaunchKernelGGL(ss_local_kernel, dim3(nt), dim3(SL_BLOCK), 0, s, (const E16 *)buf.A[1], (const MsdTile *)tiles_all, nt, g.ib,
-                           sa_out);
-    PSS_TRY(mark());                                                                       // [5]
-    hipLaunchKernelGGL(ss_boundary_kernel, dim3((nt + 255) / 256), dim3(256), 0, s, (const MsdTile *)tiles_all, nt, tx, sa_out);
-    PSS_HIP(hipGetLastError());
-    if (stats) stats->tiles = nt;
-    if (profile && nev >= 6 && stats) {
-        PSS_HIP(hipStreamSynchronize(s));
-        float ms = 0.f;
-        PSS_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
-        stats->ms_sample = ms;
-        PSS_HIP(hipEventElapsedTime(&ms, ev[1], ev[2]));
-        stats->ms_g1 = ms;
-        PSS_HIP(hipEventElapsedTime(&ms, ev[2], ev[3]));
-        stats->ms_g2 = ms;
-        PSS_HIP(hipEventElapsedTime(&ms, ev[4], ev[5]));
-        stats->ms_local = ms;
-    }
-    *accepted = true;
-    return PSS_OK;
-}
+#include "msd_driver_impl.h"
 
 }  // namespace pss

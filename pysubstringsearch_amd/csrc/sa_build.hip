@@ -628,7 +628,7 @@ int Build::size_key()
     return PSS_OK;
 }
 
-// The local sorts of both initial sorts hand over the active list of the first rerank (SA slot, suffix, group rank of
+// The local sort of the MSD sort hands over the active list of the first rerank (SA slot, suffix, group rank of
 // every suffix tied with a neighbour) in the buffers round 0 would fill: P[1], the free value buffer, G[1].
 // Staging: the first element buffer (free once the second partition pass has read it).
 int Build::active_handover(MsdActive *act)
@@ -749,8 +749,9 @@ int Build::try_sample_sort(Next *next)
 int Build::sample_sort(Next *next)
 {
     const u32 S = ss_sample_count(n);
-    MsdActive act;
-    PSS_TRY(active_handover(&act));
+    // (ties come back as flags: no active list is handed over.  The rounds' second group-rank buffer is reserved here, as
+    // active_handover reserves it on the MSD route)
+    PSS_TRY(ctx->slot[S_GRP2].reserve((size_t)n * 4));
     SsBuffers sb;
     sb.A[0] = ctx->slot[S_SSA].p;
     sb.A[1] = ctx->slot[S_SSB].p;
@@ -770,7 +771,7 @@ int Build::sample_sort(Next *next)
     TextKeys sk{codes, b, 0, plus_one, 0};
     SsStats sst;
     bool accepted = false;
-    PSS_TRY(ss_suffix_sort(ctx, &sk, radix, n, sb, SA, ctx->slot[S_P0].p, h_small, profile, &sst, &accepted, &act));
+    PSS_TRY(ss_suffix_sort(ctx, &sk, radix, n, sb, SA, ctx->slot[S_P0].p, h_small, profile, &sst, &accepted));
     if (planned && !accepted) {
         // The previous chunk's splitters left a bucket beyond a tile (real files: millions of suffixes with one key --
         // blanks -- sit where the files put them, not where the last chunk had them).

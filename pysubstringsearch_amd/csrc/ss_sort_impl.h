@@ -26,7 +26,7 @@
 //
 // HBM traffic per suffix: (1 + 2) + (1 + 2 + 16) + (16 + 2) + (16 + 2 + 16) + (16 + 4) = 94 bytes.
 
-constexpr int SS_MAX_CHARS = 32;                     // symbols packed into a key at most (byte window of the packers)
+// (SS_MAX_CHARS, SS_WIN and ss_geometry: msd_layout.h)
 constexpr u32 SS_TILE = 4096;                        // elements of one workgroup tile (64 KiB of LDS)
 constexpr int SS_CELL_BITS = 12;                     // ss_digits1: lookup on the top bits of the key before the search
 constexpr u32 SS_CELLS = 1u << SS_CELL_BITS;
@@ -34,15 +34,6 @@ constexpr int SS_SBLOCK = 1024;                      // scatter passes: one work
 constexpr int SS_SIPT = SS_TILE / SS_SBLOCK;         // 4
 constexpr int SS_DBLOCK = 512;                       // digit passes
 constexpr u32 SS_DTILE1 = SS_DBLOCK * 16;            // G1 digits: 16 consecutive suffixes per thread
-// Tile plan (msd_tile_head): the buckets that start inside one window of SS_WIN slots form a tile -- W elements on
-// average, give or take what the buckets at its two ends overhang -- unless that exceeds the tile, in which case the
-// window's last bucket becomes a tile of its own.  The merge sort costs per tile, not per element, so the window is as
-// wide as the overflows allow: at 2^29 (buckets of 512 +- 256) 3072 -> 175 995 tiles, 3456 -> 161 659 (local sort 11.0 ->
-// 10.0 ms), 3584 -> 160 905 but more of them single buckets (10.2 ms).
-#ifndef PSS_SS_WIN
-#define PSS_SS_WIN 3456
-#endif
-constexpr u32 SS_WIN = PSS_SS_WIN;
 constexpr u32 SS_TILE_CAP = 4088;
 constexpr u32 SS_MAX_BUCKET = 4088;
 

@@ -473,6 +473,41 @@ def test_build_plan_rules_on_the_cpu(tmp_path):
     assert r.returncode == 0 and 'build_plan: ok' in r.stdout, r.stdout[-1000:] + r.stderr[-2000:]
 
 
+def test_msd_layout_on_the_cpu(tmp_path):
+    """The workspace of the two initial sorts is described once (csrc/msd_layout.h, plain C++ without HIP: MsdWork) and
+    both host drivers take their pointers from it.  tests/native/msd_layout.cpp restates the eighteen regions as a table
+    of sizes and checks every start, the 256-byte rounding, the end = msd_workspace_bytes at twelve sizes up to 2^31 - 1
+    (four ends pinned as numbers), the thirteen regions the sample sort shares, the tile caps, the fail list's two places
+    behind the tile firsts, the scan totals behind the partial sums and the largest key width in both orders.  It prints
+    ss_geometry for every (n, radix) below, which must be the Python model's (tests/ss_edge_texts.geometry), refusals
+    included, and the packed tag of four accepted rows.  Built with g++ under AddressSanitizer + UBSan against that header
+    alone: no library, no device."""
+    from tests import ss_edge_texts as X
+    csrc = os.path.join(ROOT, 'pysubstringsearch_amd', 'csrc')
+    exe = str(tmp_path / 'msd_layout')
+    r = subprocess.run(['g++', '-O1', '-g', '-std=c++17', '-Wall', '-Wextra', '-fsanitize=address,undefined',
+                        '-fno-sanitize-recover=undefined', '-I' + csrc,
+                        os.path.join(ROOT, 'tests', 'native', 'msd_layout.cpp'), '-o', exe], capture_output=True, text=True)
+    assert r.returncode == 0 and not r.stderr.strip(), r.stderr[-2000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and 'msd_layout: ok' in r.stdout, r.stdout[-1000:] + r.stderr[-2000:]
+    lines = r.stdout.splitlines()
+    want, tags = [], 0
+    for n in (65535, 65536, 1 << 20, 1 << 24, 1 << 30, (1 << 30) + 1):
+        for radix in (1, 2, 28, 257, 258):
+            g = X.geometry(n, radix)
+            if g is None:
+                want.append(f'geometry {n} {radix} refused')
+                continue
+            want.append('geometry %d %d %d %d %d %d %d %d %d' % (n, radix, g['ib'], g['kc'], g['key_bits'], g['B1'], g['B2'], g['os'], g['S']))
+            if radix in (28, 257) and n in (1 << 24, 1 << 30):
+                tag = (g['S'] << 32) | (g['B1'] << 20) | (g['B2'] << 8) | (g['ib'] << 2) | int(g['os'] == 8) | (g['kc'] << 58)
+                want.append(f'tag {n} {radix} {tag}')
+                tags += 1
+    assert tags == 4 and sum('refused' in w for w in want) >= 12 and sum('refused' not in w and w[0] == 'g' for w in want) >= 12
+    assert lines[:-1] == want and lines[-1] == 'msd_layout: ok'
+
+
 def test_host_logic_under_sanitizers(tmp_path):
     """The host side of the library (capi.cpp: container writer / reader, argument checks, packed-result merge;
     common.cpp; corpus.cpp) rebuilt with -fsanitize=address,undefined (`make asan`) and driven through the host tests of
