@@ -232,6 +232,35 @@ int32_t pss_sa_build_device(const void *d_T, void *d_SA, int32_t n, int32_t devi
 int32_t pss_sort_pairs_device(void *d_keys, void *d_vals, uint32_t n, int32_t key_bits, int32_t device,
                               double *ms_scatter);
 
+/* The same sort with its pass mask and its range cap exposed (test / measurement utility, no
+ * reference counterpart): the pairs are ordered by the 8-bit digits p < ceil(key_bits / 8) whose bit
+ * (1 << p) is set in pass_mask, least significant first -- every other bit of a key is ignored.
+ * Stable for n > 4096; up to 4096 pairs equal keys leave in value order.  A pass is cut into at most
+ * max_ranges workgroup ranges (a multiple of 8 in 8 .. 1024; the builder always uses 1024): a small cap
+ * makes a range hold several 4096-pair tiles at a small n.  The result is in the caller's buffers.
+ * PSS_EINVAL before any device is touched: NULL pointers with n > 0, key_bits outside 1 .. 64, a bad cap. */
+int32_t pss_sort_pairs_ex_device(void *d_keys, void *d_vals, uint32_t n, int32_t key_bits, uint32_t pass_mask,
+                                 uint32_t max_ranges, int32_t device);
+
+/* The builder's initial LSD sort of all n suffixes on its own (test / measurement utility, no reference
+ * counterpart).  d_codes: the recoded text on `device`, 16-byte aligned, readable for n + 64 bytes and
+ * padded by the caller.  The key of suffix i is its key_chars symbols of code_bits bits each, first symbol
+ * highest, zero past the end of the text (plus_one: symbol = byte + 1 inside the text), shifted right by
+ * `drop`; the suffixes are sorted by the whole 8-bit digits of it that cover its low key_bits bits, that is
+ * by its low 8 * ceil(key_bits / 8) bits (a build's key has no bits above key_bits; a smaller key_bits gives
+ * every prefix of a build's passes).  Equal keys are left in the order the pass over the text ranks them --
+ * inside a tile of 4096 by (wave, round r of the thread's 16 suffixes, lane), not by index -- which every
+ * later pass keeps.  d_out receives n u32.
+ * carry_flags = 1: the flag-carrying passes -- suffix indices, bit 31 set when the key (those bits of it)
+ * equals the predecessor's.  carry_flags = 0: the plain passes with the text as source, plain indices.
+ * max_ranges: as for pss_sort_pairs_ex_device.
+ * PSS_EINVAL before any device is touched: NULL or misaligned pointers, n >= 2^31, code_bits outside
+ * 1 .. 9, key_chars outside 1 .. 16, key_chars * code_bits > 64, drop outside 0 .. code_bits - 1, key_bits
+ * outside 9 .. 64 with flags or 1 .. 64 without, key_bits > key_chars * code_bits - drop, a bad cap. */
+int32_t pss_suffix_sort_device(const void *d_codes, uint32_t n, int32_t code_bits, int32_t key_chars, int32_t plus_one,
+                               int32_t drop, int32_t key_bits, int32_t carry_flags, uint32_t max_ranges, void *d_out,
+                               int32_t device);
+
 /* ---- Writer (src/lib.rs:42-144; pysubstringsearch/__init__.py:6-41) ----- */
 
 /* Writer::new, src/lib.rs:50-65.  Creates/truncates `path`.  max_chunk_len < 0

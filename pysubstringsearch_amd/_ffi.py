@@ -255,6 +255,8 @@ def _load() -> ctypes.CDLL:
         'pss_sa_build': (i32, [vp, vp, i32, i32]),
         'pss_sa_build_device': (i32, [vp, vp, i32, i32, u32, ctypes.POINTER(SaStats)]),
         'pss_sort_pairs_device': (i32, [vp, vp, u32, i32, i32, ctypes.POINTER(ctypes.c_double)]),
+        'pss_sort_pairs_ex_device': (i32, [vp, vp, u32, i32, u32, u32, i32]),
+        'pss_suffix_sort_device': (i32, [vp, u32, i32, i32, i32, i32, i32, i32, u32, vp, i32]),
         'pss_writer_open': (ctypes.c_int, [cp, i64, i32, pvp]),
         'pss_writer_open_format': (ctypes.c_int, [cp, i64, i32, i32, pvp]),
         'pss_writer_open_multi': (ctypes.c_int, [cp, i64, ctypes.POINTER(i32), i32, i32, pvp]),

@@ -321,6 +321,74 @@ extern "C" int32_t pss_sort_pairs_device(void *d_keys, void *d_vals, uint32_t n,
     });
 }
 
+namespace {
+bool range_cap_ok(uint32_t max_ranges) { return max_ranges >= 8 && max_ranges <= RS_MAX_RANGES && (max_ranges & 7u) == 0; }
+}  // namespace
+
+extern "C" int32_t pss_sort_pairs_ex_device(void *d_keys, void *d_vals, uint32_t n, int32_t key_bits, uint32_t pass_mask,
+                                            uint32_t max_ranges, int32_t device)
+{
+    return guarded([&]() -> int {
+        if ((n && (!d_keys || !d_vals)) || key_bits < 1 || key_bits > 64 || !range_cap_ok(max_ranges)) {
+            set_error("pss_sort_pairs_ex_device: bad arguments");
+            return PSS_EINVAL;
+        }
+        DeviceCtx *ctx;
+        PSS_TRY(get_build_ctx(device, &ctx));
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        if (n == 0) return PSS_OK;
+        PSS_TRY(ctx->slot[1].reserve((size_t)n * 8));
+        PSS_TRY(ctx->slot[3].reserve((size_t)n * 4));
+        PSS_TRY(ctx->slot[9].reserve(radix_sort_workspace_bytes() + 65536));
+        uint64_t *K[2] = {static_cast<uint64_t *>(d_keys), ctx->slot[1].as<uint64_t>()};
+        uint32_t *V[2] = {static_cast<uint32_t *>(d_vals), ctx->slot[3].as<uint32_t>()};
+        SortStats st;
+        int dst = 0;
+        PSS_TRY(radix_sort_pairs(ctx, K, V, n, key_bits, pass_mask, nullptr, 0, ctx->slot[9].p, &dst, false, &st, max_ranges));
+        if (dst != 0) {
+            PSS_HIP(hipMemcpyAsync(d_keys, K[1], (size_t)n * 8, hipMemcpyDeviceToDevice, ctx->stream));
+            PSS_HIP(hipMemcpyAsync(d_vals, V[1], (size_t)n * 4, hipMemcpyDeviceToDevice, ctx->stream));
+        }
+        PSS_HIP(hipStreamSynchronize(ctx->stream));
+        return PSS_OK;
+    });
+}
+
+extern "C" int32_t pss_suffix_sort_device(const void *d_codes, uint32_t n, int32_t code_bits, int32_t key_chars, int32_t plus_one,
+                                          int32_t drop, int32_t key_bits, int32_t carry_flags, uint32_t max_ranges, void *d_out,
+                                          int32_t device)
+{
+    return guarded([&]() -> int {
+        const bool ok = d_codes && d_out && ((uintptr_t)d_codes & 15u) == 0 && n < 0x80000000u && code_bits >= 1 && code_bits <= 9 &&
+                        key_chars >= 1 && key_chars <= 16 && key_chars * code_bits <= 64 && drop >= 0 && drop < code_bits &&
+                        (plus_one == 0 || plus_one == 1) && (carry_flags == 0 || carry_flags == 1) &&
+                        key_bits >= (carry_flags ? 9 : 1) && key_bits <= 64 && key_bits <= key_chars * code_bits - drop &&
+                        range_cap_ok(max_ranges);
+        if (!ok) {
+            set_error("pss_suffix_sort_device: bad arguments");
+            return PSS_EINVAL;
+        }
+        DeviceCtx *ctx;
+        PSS_TRY(get_build_ctx(device, &ctx));
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        if (n == 0) return PSS_OK;
+        // the builder's own key planes, value buffers and sort workspace
+        for (int s = 1; s <= 2; ++s) PSS_TRY(ctx->slot[s].reserve((size_t)n * 8));
+        for (int s = 3; s <= 4; ++s) PSS_TRY(ctx->slot[s].reserve((size_t)n * 4));
+        PSS_TRY(ctx->slot[9].reserve(radix_sort_workspace_bytes() + 65536));
+        uint64_t *K[2] = {ctx->slot[1].as<uint64_t>(), ctx->slot[2].as<uint64_t>()};
+        uint32_t *V[2] = {ctx->slot[3].as<uint32_t>(), ctx->slot[4].as<uint32_t>()};
+        TextKeys tk{static_cast<const uint8_t *>(d_codes), code_bits, key_chars, plus_one, drop};
+        SortStats st;
+        int dst = 0;
+        if (carry_flags) PSS_TRY(suffix_sort_flags(ctx, K, V, n, key_bits, &tk, ctx->slot[9].p, &dst, false, &st, max_ranges));
+        else PSS_TRY(radix_sort_pairs(ctx, K, V, n, key_bits, 0xffffffffu, &tk, 0, ctx->slot[9].p, &dst, false, &st, max_ranges));
+        PSS_HIP(hipMemcpyAsync(d_out, V[dst], (size_t)n * 4, hipMemcpyDeviceToDevice, ctx->stream));
+        PSS_HIP(hipStreamSynchronize(ctx->stream));
+        return PSS_OK;
+    });
+}
+
 #include "capi_writer_impl.h"
 
 #include "capi_reader_impl.h"

@@ -38,7 +38,7 @@ int msd_max_key_bits(uint32_t n);
 
 // Same contract as suffix_sort_flags: sa_out[i] = index of the i-th smallest suffix by the low key_bits
 // of (packed text key >> text->drop), bit 31 = "same key as my predecessor".  The order among equal
-// keys is unspecified (suffix_sort_flags leaves them by index; nothing downstream relies on that).
+// keys is unspecified (suffix_sort_flags leaves them in the order its first pass ranks them; nothing downstream relies on that).
 // *accepted = false (and sa_out untouched) when some joint bucket exceeds what a workgroup sorts in
 // LDS: the caller then uses suffix_sort_flags.  h_small: >= 64 bytes of pinned host memory.  work: msd_workspace_bytes(n).
 // `front` (optional): the codes do not exist yet -- the first histogram pass makes them on its way through the raw text

@@ -39,25 +39,39 @@ struct SortStats {
 // Workspace the sort needs besides the ping-pong buffers.
 size_t radix_sort_workspace_bytes();
 
+// Most ranges (workgroups) a pass is cut into; the workspace is sized for it.
+#ifndef PSS_RS_MAX_RANGES
+#define PSS_RS_MAX_RANGES 1024
+#endif
+constexpr uint32_t RS_MAX_RANGES = PSS_RS_MAX_RANGES;
+
 // Sorts n pairs by the key bits [0, 8*ceil(key_bits/8)), least significant
 // digit first, skipping every pass p whose bit (1<<p) is clear in pass_mask.
 // Input: buffer `src` of the two (keys[i], vals[i]) pairs, or `text` (then the
 // first executed pass reads the text and writes buffer 0).  *dst receives the
 // index of the buffer holding the sorted pairs (== src if no pass ran; with
 // `text` and no pass... not allowed: pass_mask must be non-zero).
-// Stable.  `work` must hold radix_sort_workspace_bytes().
+// Stable -- except that n <= 4096 pairs without a text source go to a one-workgroup sort that
+// orders by the same digits and leaves equal keys in VALUE order, not in arrival order.
+// `work` must hold radix_sort_workspace_bytes().  max_ranges caps the ranges of a pass (a multiple
+// of 8 in 8 .. 1024, else PSS_EINVAL): the builder always takes the default, tests lower it so that
+// a range holds several tiles at a small n.
 int radix_sort_pairs(DeviceCtx *ctx, uint64_t *keys[2], uint32_t *vals[2], uint32_t n, int key_bits,
                      uint32_t pass_mask, const TextKeys *text, int src, void *work, int *dst,
-                     bool profile, SortStats *stats);
+                     bool profile, SortStats *stats, uint32_t max_ranges = RS_MAX_RANGES);
 
-// Initial suffix sort: value(i) = i for all n suffixes, sorted (stably) by the low key_bits of
-// (packed text key >> text->drop).  Every pass stores only the digits it has not consumed yet
+// Initial suffix sort: value(i) = i for all n suffixes, sorted by the whole 8-bit digits that cover the low
+// key_bits of (packed text key >> text->drop).  Suffixes with equal keys are NOT left by index: the pass over
+// the text ranks the 16 suffixes of a thread round by round, so inside a tile equal digits leave by (wave,
+// round, lane); the later passes are stable.  (radix_sort_pairs with a text source does the same.)  Nothing
+// downstream looks at the order inside a group of equal keys.  Every pass stores only the digits it has not consumed yet
 // (8-byte key plane while more than 32 bits remain, then 4 bytes, none in the last pass) and
 // carries in bit 31 of each value whether the element's consumed digits equal its predecessor's;
 // after the last pass that bit says "full key equal to my predecessor's" (tied: not the head of
 // its group).  Needs key_bits > 8 (at least two passes).  Pass p writes buffer p & 1; *dst
-// receives the buffer index of the final values.
+// receives the buffer index of the final values.  max_ranges: as for radix_sort_pairs.
 int suffix_sort_flags(DeviceCtx *ctx, uint64_t *keys[2], uint32_t *vals[2], uint32_t n, int key_bits,
-                      const TextKeys *text, void *work, int *dst, bool profile, SortStats *stats);
+                      const TextKeys *text, void *work, int *dst, bool profile, SortStats *stats,
+                      uint32_t max_ranges = RS_MAX_RANGES);
 
 }  // namespace pss

@@ -51,10 +51,7 @@ constexpr int RS_WAVES = RS_BLOCK / kWave;
 constexpr int RS_IPT = PSS_RS_IPT;
 constexpr int RS_TILE = RS_BLOCK * RS_IPT;   // 4096 pairs per tile
 static_assert(RS_IPT == TK_IPT, "text tiles pack 16 suffixes per thread");
-#ifndef PSS_RS_MAX_RANGES
-#define PSS_RS_MAX_RANGES 1024
-#endif
-constexpr u32 RS_MAX_RANGES = PSS_RS_MAX_RANGES;   // <= 1024 (one thread per range in the scan / fix kernels)
+static_assert(RS_MAX_RANGES <= 1024 && RS_MAX_RANGES % 8 == 0, "one thread per range in the scan / fix kernels");
 
 struct PassArgs {
     const u64 *kin;
@@ -697,9 +694,10 @@ __global__ __launch_bounds__(1024) void fs_fix_kernel(const u32 *first_z, const 
 }
 
 // Tiny inputs (<= one tile): one workgroup, bitonic network in LDS over the
-// whole 64-bit key, ties broken by value (so the order is fully determined and the
-// padding never overtakes a real element).
-__global__ __launch_bounds__(RS_BLOCK) void rs_small_sort_kernel(u64 *keys, u32 *vals, u32 n)
+// digits the call sorts by (`mask`: 0xff at every pass the LSD passes would run), ties
+// broken by value (so the order is fully determined and the padding never overtakes a
+// real element).  Not stable: equal keys leave in value order, not in arrival order.
+__global__ __launch_bounds__(RS_BLOCK) void rs_small_sort_kernel(u64 *keys, u32 *vals, u32 n, u64 mask)
 {
     __shared__ u64 sk[RS_TILE];
     __shared__ u32 sv[RS_TILE];
@@ -718,10 +716,11 @@ __global__ __launch_bounds__(RS_BLOCK) void rs_small_sort_kernel(u64 *keys, u32 
                 if (x > i) {
                     const bool up = (i & k) == 0;
                     const u64 a = sk[i], b = sk[x];
+                    const u64 ma = a & mask, mb = b & mask;
                     const u32 va = sv[i], vb = sv[x];
                     // equal keys order by value: the padding (value 0xffffffff) must stay behind real
                     // elements even when a real key is all ones (16 symbols of the largest 4-bit code)
-                    if ((a > b || (a == b && va > vb)) == up) {
+                    if ((ma > mb || (ma == mb && va > vb)) == up) {
                         sk[i] = b;
                         sk[x] = a;
                         sv[i] = vb;
@@ -754,10 +753,30 @@ size_t radix_sort_workspace_bytes()
     return (size_t)256 * RS_MAX_RANGES * 4 + 256 * 4 * 16 + (size_t)256 * RS_MAX_RANGES * 12 + RS_MAX_RANGES * 4;
 }
 
+// Tiles, tiles per range and ranges (workgroups) of one pass over n elements with at most max_ranges ranges: the
+// fewest tiles per range that fit the cap, the ranges rounded up to a multiple of 8 (the trailing ones are empty).
+struct RsGeometry {
+    u32 num_tiles, tiles_per_range, num_ranges;
+};
+static int rs_geometry(u32 n, u32 max_ranges, RsGeometry *g)
+{
+    if (max_ranges < 8 || max_ranges > RS_MAX_RANGES || (max_ranges & 7u)) {
+        set_error("radix sort: max_ranges %u is not a multiple of 8 in 8 .. %u", max_ranges, RS_MAX_RANGES);
+        return PSS_EINVAL;
+    }
+    g->num_tiles = (u32)(((u64)n + RS_TILE - 1) / RS_TILE);
+    g->tiles_per_range = (g->num_tiles + max_ranges - 1) / max_ranges;
+    const u32 used = g->tiles_per_range ? (g->num_tiles + g->tiles_per_range - 1) / g->tiles_per_range : 0;
+    g->num_ranges = (used + 7u) & ~7u;
+    return PSS_OK;
+}
+
 int radix_sort_pairs(DeviceCtx *ctx, uint64_t *keys[2], uint32_t *vals[2], uint32_t n, int key_bits,
                      uint32_t pass_mask, const TextKeys *text, int src, void *work, int *dst,
-                     bool profile, SortStats *stats)
+                     bool profile, SortStats *stats, uint32_t max_ranges)
 {
+    RsGeometry geo;
+    PSS_TRY(rs_geometry(n, max_ranges, &geo));
     const int passes = (key_bits + 7) / 8;
     int cur = src;
     bool from_text = text != nullptr;
@@ -766,16 +785,16 @@ int radix_sort_pairs(DeviceCtx *ctx, uint64_t *keys[2], uint32_t *vals[2], uint3
         return PSS_OK;
     }
     if (!from_text && n <= (u32)RS_TILE) {
-        hipLaunchKernelGGL(rs_small_sort_kernel, dim3(1), dim3(RS_BLOCK), 0, ctx->stream, keys[src], vals[src], n);
+        u64 digits = 0;
+        for (int p = 0; p < passes && p < 8; ++p)
+            if ((pass_mask >> p) & 1u) digits |= 0xffull << (8 * p);
+        hipLaunchKernelGGL(rs_small_sort_kernel, dim3(1), dim3(RS_BLOCK), 0, ctx->stream, keys[src], vals[src], n, digits);
         PSS_HIP(hipGetLastError());
         if (stats) stats->small_launches += 1;
         *dst = src;
         return PSS_OK;
     }
-    const u32 num_tiles = (u32)(((u64)n + RS_TILE - 1) / RS_TILE);
-    const u32 tpr = (num_tiles + RS_MAX_RANGES - 1) / RS_MAX_RANGES;
-    u32 num_ranges = (num_tiles + tpr - 1) / tpr;
-    num_ranges = (num_ranges + 7u) & ~7u;
+    const u32 num_tiles = geo.num_tiles, tpr = geo.tiles_per_range, num_ranges = geo.num_ranges;
 
     u32 *table = static_cast<u32 *>(work);
     u32 *totals_base = table + (size_t)256 * RS_MAX_RANGES;
@@ -861,17 +880,16 @@ int radix_sort_pairs(DeviceCtx *ctx, uint64_t *keys[2], uint32_t *vals[2], uint3
 
 
 int suffix_sort_flags(DeviceCtx *ctx, uint64_t *keys[2], uint32_t *vals[2], uint32_t n, int key_bits,
-                      const TextKeys *text, void *work, int *dst, bool profile, SortStats *stats)
+                      const TextKeys *text, void *work, int *dst, bool profile, SortStats *stats, uint32_t max_ranges)
 {
     const int passes = (key_bits + 7) / 8;
     if (passes < 2 || text == nullptr || n == 0) {
         set_error("suffix_sort_flags: needs a text source, n > 0 and more than 8 key bits");
         return PSS_EINVAL;
     }
-    const u32 num_tiles = (u32)(((u64)n + RS_TILE - 1) / RS_TILE);
-    const u32 tpr = (num_tiles + RS_MAX_RANGES - 1) / RS_MAX_RANGES;
-    u32 num_ranges = (num_tiles + tpr - 1) / tpr;
-    num_ranges = (num_ranges + 7u) & ~7u;
+    RsGeometry geo;
+    PSS_TRY(rs_geometry(n, max_ranges, &geo));
+    const u32 num_tiles = geo.num_tiles, tpr = geo.tiles_per_range, num_ranges = geo.num_ranges;
 
     u32 *table = static_cast<u32 *>(work);
     u32 *totals_base = table + (size_t)256 * RS_MAX_RANGES;

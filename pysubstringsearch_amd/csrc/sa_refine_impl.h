@@ -502,7 +502,9 @@ static int refine_rounds(DeviceCtx *ctx, const Knobs &knobs, RoundsIO &io, SortS
             hipLaunchKernelGGL(gather_gid_kernel, dim3((nbig + 255) / 256), dim3(256), 0, s, BV[d1], d_bgid, nbig,
                                nbig <= 4096u, BK[d1]);
             if (nbig_groups > 1)
-                PSS_TRY(radix_sort_pairs(ctx, BK, BV, nbig, gid_bits, 0xffffffffu, nullptr, d1, work, &d2, profile, &s2));
+                // (unique keys carry v in their low word: the one-workgroup sort then compares all 64 bits)
+                PSS_TRY(radix_sort_pairs(ctx, BK, BV, nbig, nbig <= 4096u ? 64 : gid_bits, 0xffffffffu, nullptr, d1, work, &d2, profile,
+                                         &s2));
             else d2 = d1;
             hipLaunchKernelGGL(big_writeback_kernel, dim3((nbig + 255) / 256), dim3(256), 0, s, BV[d2], d_bt, K[src],
                                V[src], nbig, K[src ^ 1], V[src ^ 1]);

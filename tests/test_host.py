@@ -371,6 +371,22 @@ def test_cabi_argument_contract_without_gpu():
     assert lib.pss_reader_evict_chunk(None, 0) == _ffi.PSS_EINVAL
     lib.pss_result_free(None)
     assert lib.pss_reader_close(None) == _ffi.PSS_OK and lib.pss_writer_close(None) == _ffi.PSS_OK
+    # the sort utilities of the LSD edge tests: pointers (never dereferenced here), key widths and the range cap
+    buf = np.zeros(64, dtype=np.uint64)
+    p = buf.ctypes.data
+    assert p % 16 == 0
+    assert lib.pss_sort_pairs_ex_device(None, p, 4, 64, 0xff, 8, 0) == _ffi.PSS_EINVAL
+    assert lib.pss_sort_pairs_ex_device(p, None, 4, 64, 0xff, 8, 0) == _ffi.PSS_EINVAL
+    for key_bits, cap in ((0, 8), (65, 8), (64, 0), (64, 7), (64, 12), (64, 1032), (64, 2048)):
+        assert lib.pss_sort_pairs_ex_device(p, p, 4, key_bits, 0xff, cap, 0) == _ffi.PSS_EINVAL, (key_bits, cap)
+
+    def suffix_rc(codes=p, n=4, b=8, k=8, plus_one=0, drop=0, key_bits=64, flags=1, cap=8, out=p):
+        return lib.pss_suffix_sort_device(codes, n, b, k, plus_one, drop, key_bits, flags, cap, out, 0)
+    for bad in (dict(codes=None), dict(out=None), dict(codes=p + 8), dict(n=1 << 31), dict(key_bits=8), dict(key_bits=65),
+                dict(key_bits=0, flags=0), dict(key_bits=65, flags=0), dict(k=0), dict(k=17, b=2, key_bits=16), dict(b=9, k=8),
+                dict(b=0), dict(drop=8), dict(drop=-1), dict(drop=1), dict(b=4, k=4, key_bits=17), dict(flags=2), dict(plus_one=2),
+                dict(cap=0), dict(cap=12), dict(cap=1032)):
+        assert suffix_rc(**bad) == _ffi.PSS_EINVAL, bad
 
 
 def test_merge_packed_random():
