@@ -1,5 +1,5 @@
 // anchor_impl.h -- anchors: a content-defined sample of the text's positions that breaks long ties in ONE round.
-// Included by sa_build.hip (device kernels; the host side, anchor_rank_keys, sits there next to refine_rounds).
+// Included by sa_build.hip (device kernels; the host side is AnchorRound of anchor_driver_impl.h, next to the Rounds of sa_refine_impl.h).
 //
 // Prefix doubling pays log2(longest repeat) rounds over every suffix that is still tied, and inside duplicated
 // stretches of text (copies of a block, a line written over and over) every suffix stays tied until h reaches the end
@@ -39,7 +39,7 @@
 
 namespace pss {
 
-constexpr u32 ANC_TILE = 4096;        // window starts per workgroup pass (256 threads x 16)
+// (ANC_TILE window starts per workgroup pass, 256 threads x 16: rounds_layout.h)
 constexpr u32 ANC_MAX_OMEGA = 224;    // M(s) - s fits a byte
 constexpr u32 ANC_HMAX = 0xffffffffu; // H of a position past the end of the text: never the smallest of a window that starts inside
 

@@ -34,6 +34,28 @@ struct SortStats {
     double fs_ms[9] = {};
     uint64_t fs_launches[9] = {};
     uint64_t fs_elems[9] = {};
+    // What the sorts after the initial one add to a build's totals: launches, elements, time, and the pairs kernel's share
+    // (the text and flag passes belong to the initial sort alone, and the one-workgroup sorts are not totalled).
+    SortStats &operator+=(const SortStats &o)
+    {
+        launches += o.launches;
+        elems += o.elems;
+        ms += o.ms;
+        ms_pairs += o.ms_pairs;
+        pairs_launches += o.pairs_launches;
+        pairs_elems += o.pairs_elems;
+        return *this;
+    }
+    // ... and the same six into the statistics of a build
+    void add_to(pss_sa_stats *st) const
+    {
+        st->sort_launches += launches;
+        st->sort_elems += elems;
+        st->ms_sort += ms;
+        st->ms_pairs += ms_pairs;
+        st->pairs_launches += pairs_launches;
+        st->pairs_elems += pairs_elems;
+    }
 };
 
 // Workspace the sort needs besides the ping-pong buffers.

@@ -18,7 +18,7 @@
 //     reduced string is the end of the text (smaller than everything) in both orders.
 //     Its suffix array SAr comes from the same machinery as every other build: the symbols are
 //     sorted (radix sort of 41-bit keys), then rank rounds over an inverse array resolve the ties
-//     (refine_rounds of sa_build.hip with h0 = 1) -- on S elements instead of n.
+//     (Rounds of sa_refine_impl.h with h0 = 1) -- on S elements instead of n.
 //  3. Expansion.  The suffix at position x inside run k, r = start[k+1] - x bytes before its end, is
 //     c^r followed by the suffix at the head of run k+1.  By the argument above suffixes are ordered by
 //     (c, type, type ? -r : r) first -- a dense number id(x) < n: per class (c, type) the longest run
@@ -488,14 +488,7 @@ int rle_suffix_array(DeviceCtx *ctx, const uint8_t *T, uint32_t n, uint32_t S, u
         V[final_buf] = v_scratch;
     }
     mark(3);
-    if (st && !columns) {
-        st->sort_launches += fs.launches;
-        st->sort_elems += fs.elems;
-        st->ms_sort += fs.ms;
-        st->ms_pairs += fs.ms_pairs;
-        st->pairs_launches += fs.pairs_launches;
-        st->pairs_elems += fs.pairs_elems;
-    }
+    if (st && !columns) fs.add_to(st);
     if (rs) {
         rs->runs = S;
         rs->id_bits = (u32)id_bits;

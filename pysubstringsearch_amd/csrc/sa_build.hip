@@ -39,6 +39,7 @@
 #include "msd_sort.h"
 #include "rle_build.h"
 #include "radix_sort.h"
+#include "rounds_layout.h"
 #include "sa_build.h"
 #include "scan.h"
 #include "text_keys.h"
@@ -203,6 +204,8 @@ __global__ __launch_bounds__(256) void sa_recode_kernel(const u8 *T, u32 n, u32 
 
 #include "sa_refine_impl.h"
 
+#include "anchor_driver_impl.h"
+
 // Suffix array of an INTEGER string of m symbols (rle_build.hip: one symbol per run of the text).  K[cur] / V[cur]:
 // the (symbol key, index) pairs sorted by key; both buffer pairs hold m elements and are scratch afterwards.
 // The end of the string is smaller than every symbol.  SA_out: m entries.  st: rounds / passes are added.
@@ -217,31 +220,13 @@ int suffix_rounds_integer(DeviceCtx *ctx, uint32_t m, uint64_t *K[2], uint32_t *
     const size_t sort_ws = radix_sort_workspace_bytes();
     PSS_TRY(ctx->slot[S_WORK].reserve(sort_ws + 65536));
     u8 *work = ctx->slot[S_WORK].as<u8>();
-    RoundsIO io;
-    io.n = m;
-    io.SA = SA_out;
-    io.K[0] = K[0]; io.K[1] = K[1];
-    io.V[0] = V[0]; io.V[1] = V[1];
-    io.ISA = ctx->slot[S_ISA].as<u32>();
-    io.P[0] = ctx->slot[S_P0].as<u32>(); io.P[1] = ctx->slot[S_P1].as<u32>();
-    io.GRP = ctx->slot[S_GRP].as<u32>();
-    io.codes = nullptr;
-    io.b = 8; io.plus_one = 0; io.key_chars = 1; io.key_drop = 0;
-    io.h0 = 1;
+    RoundsIO io = RoundsIO::for_integers(SmallState(work + sort_ws, ctx->pinned), work, m, SA_out, K, V, ctx->slot[S_ISA].as<u32>(),
+                                         ctx->slot[S_P0].as<u32>(), ctx->slot[S_P1].as<u32>(), ctx->slot[S_GRP].as<u32>());
     io.cur = cur;
-    io.final_buf = -1;
-    io.v_scratch = nullptr;
-    io.ties = false;
-    io.msd_fused = false;
-    io.msd_active = 0;
-    io.no_sparse = false;
-    io.work = work;
-    SmallState(work + sort_ws, ctx->pinned).lend(io);
-    io.profile = false;
     SortStats ss;
     pss_sa_stats local;
     memset(&local, 0, sizeof local);
-    PSS_TRY(refine_rounds(ctx, knobs, io, ss, st ? *st : local));
+    PSS_TRY(Rounds(ctx, knobs, io, ss, st ? *st : local).run());
     return PSS_OK;
 }
 
@@ -824,17 +809,7 @@ int Build::lsd_passes()
 // ---- 2. rerank + compaction, 3. doubling rounds ----
 int Build::run_rounds()
 {
-    RoundsIO io;
-    io.n = n;
-    io.SA = SA;
-    io.K[0] = K[0]; io.K[1] = K[1];
-    io.V[0] = V[0]; io.V[1] = V[1];
-    io.ISA = ISA;
-    io.P[0] = P[0]; io.P[1] = P[1];
-    io.GRP = GRP;
-    io.codes = codes;
-    io.b = b; io.plus_one = plus_one; io.key_chars = key_chars; io.key_drop = key_drop;
-    io.h0 = (u64)(key_drop ? key_chars - 1 : key_chars);
+    RoundsIO io = RoundsIO::for_text(sm, work, n, SA, K, V, ISA, P[0], P[1], GRP, codes, b, plus_one, key_chars, key_drop);
     io.cur = cur;
     io.final_buf = final_buf;
     io.v_scratch = v_scratch;
@@ -842,11 +817,9 @@ int Build::run_rounds()
     io.msd_fused = msd_fused;
     io.msd_active = msd_active;
     io.no_sparse = st.ss != 0;
-    io.work = work;
-    sm.lend(io);
     io.profile = profile;
     io.side = &side;
-    PSS_TRY(refine_rounds(ctx, knobs, io, ss, st));
+    PSS_TRY(Rounds(ctx, knobs, io, ss, st).run());
     side.join();
     if (side.started && st.anchor_side == 0) st.anchor_side = 2;      // started for nothing
     plan.remember_side(logn, b, plain, st.anchor_side == 1 ? side.h_eff : 0);

@@ -42,11 +42,7 @@ __global__ __launch_bounds__(256) void rank_keys_kernel(const u32 *idx, u32 m, u
     }
 }
 
-constexpr int GS_T = 2048;      // elements per workgroup window
-#ifndef PSS_GS_CAP
-#define PSS_GS_CAP 512
-#endif
-constexpr int GS_CAP = PSS_GS_CAP;     // largest group ranked in LDS (= halo on both sides)
+// (GS_T elements per workgroup window, groups of <= GS_CAP members ranked in LDS = the halo on both sides: rounds_layout.h)
 constexpr int GS_LDS = GS_T + 2 * GS_CAP;
 
 // Sorts every group of <= GS_CAP members by key (ties keep their order) into
@@ -377,19 +373,11 @@ __global__ __launch_bounds__(GM_BLOCK) void group_msort32_kernel(const u64 *key,
 // ones of its bin, ties by list position (stable, like group_sort).  A group with a crowded bin (many equal
 // keys) stays flagged and takes the chained sorts as before.  Sorted groups are un-flagged and taken out of
 // the per-window counts big_compact works from.
-constexpr u32 MID_CAP = 4096;
+// (MID_CAP, MID_KMAX and the list's row, MidGroup: rounds_layout.h)
 constexpr int MID_BLOCK = 512;
 constexpr int MID_IPT = MID_CAP / MID_BLOCK;
 constexpr int MID_WAVES = MID_BLOCK / kWave;
 constexpr u32 MID_BINS = 4096, MID_WORDS = MID_BINS / 2;      // 16-bit counters, two per LDS word
-#ifndef PSS_MID_KMAX
-#define PSS_MID_KMAX 512
-#endif
-constexpr u32 MID_KMAX = PSS_MID_KMAX;
-
-struct MidGroup {
-    u32 start, size;
-};
 
 __global__ __launch_bounds__(256) void mid_collect_kernel(const u8 *big, const u32 *grp, u32 m, MidGroup *list, u32 *count)
 {
@@ -741,10 +729,7 @@ __global__ __launch_bounds__(256) void big_writeback_kernel(const u32 *order, co
 // need twelve passes where 32-bit rank keys cost the radix sorts seven.  The passes are sequential but not fast -- a tile
 // is loaded, merged and stored behind three barriers by a workgroup that spends the first microseconds of each on two
 // searches in global memory -- and the traffic they save was not what bounded the build.
-constexpr u32 BG_TILE = 4096;
-struct BigTile {
-    u32 gstart, gsize, t;      // tile t of the group whose members are [gstart, gstart + gsize) of the compacted list
-};
+// (BG_TILE and the tile table's row, BigTile: rounds_layout.h)
 
 __global__ __launch_bounds__(256) void bg_gstart_kernel(const u32 *bgid, u32 nbig, u32 ngroups, u32 *gstart)
 {

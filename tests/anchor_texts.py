@@ -1,4 +1,4 @@
-"""The anchor round (csrc/anchor_impl.h, anchor_rank_keys in csrc/sa_refine_impl.h) restated in numpy, and the texts that
+"""The anchor round (csrc/anchor_impl.h, AnchorRound in csrc/anchor_driver_impl.h) restated in numpy, and the texts that
 put it on its edges (tests/test_anchor_edges_gpu.py).  Everything here runs on the CPU; tests/test_anchor_texts.py runs
 every generator for every size the GPU tests use and holds the model to a plain double loop.
 
@@ -84,7 +84,7 @@ def anchor_count(codes, omega, w):
 
 
 def window_of(depth, forced=None, level0=True):
-    """(omega, w) of anchor_rank_keys for a text whose tied suffixes share `depth` symbols; forced: PSS_ANCHOR_OMEGA."""
+    """(omega, w) of AnchorRound::window for a text whose tied suffixes share `depth` symbols; forced: PSS_ANCHOR_OMEGA."""
     assert level0
     w = 8 if depth >= 28 else 4
     omega = depth - w + 1 if depth >= w else 0
@@ -291,7 +291,7 @@ def tied_at(t, sa, depths, cap=128):
 
 
 def check_ladder(t, sa):
-    """The drain condition of refine_rounds (m * 10 <= m_prev * 6 before every text round after the first) from the key's
+    """The drain condition of Rounds::text_round (m * 10 <= m_prev * 6 before every text round after the first) from the key's
     16 symbols -- or 15, should the key leave out bits of its last one -- to a depth of at least 79, and ties left there:
     the window is then 64 wide whether or not the fifth round runs.  Returns the counts."""
     out = {}

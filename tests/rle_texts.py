@@ -451,7 +451,7 @@ def tiny_runs_case(r, small=False):
 
 def tier_case(k):
     """The group-size tiers of the rank rounds (sa_rounds_impl.h: GS_CAP 512, MID_CAP 4096, two tiles of 4096) in the mode
-    only this path uses: suffix_rounds_integer runs refine_rounds on the REDUCED string, without codes (rank_only) and from
+    only this path uses: suffix_rounds_integer runs the Rounds on the REDUCED string, without codes (rank_only) and from
     h0 = 1.  k units  a^5 b^4 c^3 d^2 x^i y^j x^l z  in random order: the k runs a^5 carry one meta symbol, so do the b^4, c^3
     and d^2 behind them (and the z before them), and only the three digit runs (i, j, l: different for every unit) tell the units apart.  The group
     of k run heads at a^5 is therefore still whole after the first rank round (h = 1 looks at b^4: all tied) and after the

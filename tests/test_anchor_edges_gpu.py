@@ -1,4 +1,4 @@
-"""The anchor round on its edges (csrc/anchor_impl.h, anchor_rank_keys in csrc/sa_refine_impl.h): the three code paths of
+"""The anchor round on its edges (csrc/anchor_impl.h, AnchorRound in csrc/anchor_driver_impl.h): the three code paths of
 anc_select_kernel by window (the plain loop up to 8, anc_window_mins<9> + <8> up to 16, anc_window_mins<17> above) and their
 seams, the host's clamp to 64, tile borders and the end of the text (the partial uint4 of d and of the key fill, hashes
 that read the padding), the refusal below 64 bytes, the limit of n / div anchors from both sides, and a second level of
@@ -195,7 +195,7 @@ def test_on_the_cap(oracle, monkeypatch, div):
 @pytest.mark.parametrize('alpha', A.DEEP_ALPHAS)
 def test_levels(oracle, monkeypatch, alpha, periodic):
     """Copies of n / 8 bytes: the names of the anchors repeat as the text does, the rank rounds over them reach depth 32 with
-    most of them tied, and minimizers of the NAMES (anc_select_kernel<true>, the SYMS branch of anchor_rank_keys) go on top:
+    most of them tied, and minimizers of the NAMES (anc_select_kernel<true>, the `syms` branch of AnchorRound) go on top:
     anchor_levels counts them.  Observed on an MI355X at n = 2^18, with PSS_PERIODIC at its default and at 0 alike: 4 symbols
     (depth 32, window 25, 8-byte hashes, 19 970 anchors) three levels, 39 symbols (depth 16, window 13, 4-byte hashes, 37 552
     anchors) three levels -- so three are asked of all four cases."""

@@ -489,6 +489,26 @@ def test_build_plan_rules_on_the_cpu(tmp_path):
     assert r.returncode == 0 and 'build_plan: ok' in r.stdout, r.stdout[-1000:] + r.stderr[-2000:]
 
 
+def test_rounds_layout_on_the_cpu(tmp_path):
+    """The scratch slots of the rounds and the rules their driver decides by are described once (csrc/rounds_layout.h, plain
+    C++ without HIP) and the staged driver (Rounds, AnchorRound) takes its pointers and its verdicts from there.
+    tests/native/rounds_layout.cpp restates the six layouts as tables of region sizes and checks every start, the rounding,
+    the end, and end <= what the slot reserved before the header existed (the old formulas written out) at sixteen sizes
+    up to 2^32 - 1, with one, two and nbig / 2 groups, with and without the middle tier; the three outcomes of the anchors'
+    sort on both sides of 9 * m4 = 8 n and 2 * m8 = 8 n; and every rule on its edges with the answers written down: the
+    first mode, when a text round gives up, merge sort against chained sorts, the probe's two verdicts, the periodic
+    words, when rank rounds go global, the digit mask, rank_bits / index_bits.  Built with g++ under AddressSanitizer +
+    UBSan against that header alone: no library, no device."""
+    csrc = os.path.join(ROOT, 'pysubstringsearch_amd', 'csrc')
+    exe = str(tmp_path / 'rounds_layout')
+    r = subprocess.run(['g++', '-O1', '-g', '-std=c++17', '-Wall', '-Wextra', '-fsanitize=address,undefined',
+                        '-fno-sanitize-recover=undefined', '-I' + csrc,
+                        os.path.join(ROOT, 'tests', 'native', 'rounds_layout.cpp'), '-o', exe], capture_output=True, text=True)
+    assert r.returncode == 0 and not r.stderr.strip(), r.stderr[-2000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and 'rounds_layout: ok' in r.stdout, r.stdout[-1000:] + r.stderr[-2000:]
+
+
 def test_msd_layout_on_the_cpu(tmp_path):
     """The workspace of the two initial sorts is described once (csrc/msd_layout.h, plain C++ without HIP: MsdWork) and
     both host drivers take their pointers from it.  tests/native/msd_layout.cpp restates the eighteen regions as a table

@@ -282,7 +282,7 @@ def test_rounds_look_up_finished_suffixes(oracle, monkeypatch, mode):
 
 def test_nothing_left(oracle, monkeypatch):
     """Every tie of the text falls to the finisher: the rounds have nothing to do -- no round, no active suffix, which is
-    what a build of a text without any tie reports (the loop of refine_rounds leaves before it counts a round)."""
+    what a build of a text without any tie reports (the loop of Rounds::run leaves before it counts a round)."""
     _env(monkeypatch, FORMATS['cap42'])
     t, _, want = _case(oracle, 'nothing', nothing_left_text)
     f, m = _model('nothing', t, FORMATS['cap42'])

@@ -189,7 +189,7 @@ def test_expand_threads_across_tiny_runs(oracle, monkeypatch, r, small):
 
 @pytest.mark.parametrize('k', E.TIER_KS)
 def test_tiers_of_the_rank_rounds_on_the_reduced_string(oracle, monkeypatch, k):
-    """R.tier_case: groups of exactly k tied run heads that outlive two rank rounds of suffix_rounds_integer (refine_rounds
+    """R.tier_case: groups of exactly k tied run heads that outlive two rank rounds of suffix_rounds_integer (Rounds
     without codes, h0 = 1), k on both sides of GS_CAP = 512, MID_CAP = 4096 and two tiles of 4096.  As in the text path
     (tests/test_sa_edges_gpu.py), big_elems counts the members that stayed with the chained sorts or the segmented merge: the
     largest group is exactly k and the build hands its statistics to the rounds, so it is zero up to MID_CAP and positive
