@@ -583,7 +583,7 @@ int pss_reader_count_terms_batch(pss_reader *r, const uint8_t *tbytes, const uin
  * pss_reader_last_stats: queries = groups, hits = the sum of the drivers' interval hits, entries = what is returned;
  * route = GENERAL | the interval bits (| COUNTS for the count call) -- there is no bit of its own.  The id variant builds
  * the line tables on first use, the other two allocate nothing for them.
- * Out of scope: `?` and character classes; exclusions inside a group; driving an anchored first or last segment through
+ * Out of scope: exclusions inside a group (`?` and byte classes are pss_reader_search_seqc_batch's, below); driving an anchored first or last segment through
  * the anchored search's "\n" + s rewrite (`a*` follows the occurrences of `a`, not the entries that start with it); the
  * fused, resident and mid paths; a device-resident result; the multi-process gather over RCCL (dist.ShardedReader).
  */
@@ -596,6 +596,60 @@ int pss_reader_search_seq_ids_batch(pss_reader *r, const uint8_t *sbytes, const 
 /* counts[g] = entries group g matches; nothing but ngroups counters comes down */
 int pss_reader_count_seq_batch(pss_reader *r, const uint8_t *sbytes, const uint64_t *soffsets, uint32_t nsegs,
                                const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *anchors, uint64_t *counts);
+/*
+ * Wildcard search with byte classes (no reference counterpart): pss_reader_search_seq_batch whose segments hold, beside
+ * literal bytes, positions that accept ONE BYTE OUT OF A SET -- a glob's `?` and `[0-9]`, `[!x]`.  One family of three calls
+ * serves exact bytes and, with PSS_SEQ_FOLD in `flags`, the ASCII fold of pss_reader_search_icase_batch.
+ * The nsegs segments are packed in sbytes / soffsets as ever, ONE BYTE PER POSITION, and `classes` holds one more byte per
+ * position under the same offsets: 0 -- the position is a literal, and sbytes holds its byte --, or k in 1 .. nsets -- the
+ * position accepts the bytes of set k, and sbytes holds 0 there.  `sets` is nsets x 32 bytes, nsets <= 255: byte b is in set
+ * k iff bit (b & 7) of sets[(k - 1) * 32 + (b >> 3)] is set.  No set holds 0x0A (no entry holds one, so a negated set simply
+ * leaves it out), none is empty, and under PSS_SEQ_FOLD every set is closed under the fold: it holds both cases of a letter
+ * or neither.  `?` is the set of the 255 bytes other than 0x0A.  Groups and anchors exactly as for the sequence calls.
+ * The entry [start, end) matches group g when positions p_0 < p_1 < .. exist as pss_reader_search_seq_batch states them,
+ * with "entry[p_j, p_j + |s_j|) == s_j" read position by position: a literal equals the entry's byte (under PSS_SEQ_FOLD:
+ * after fold of both), a class position holds it in its set.  |s_j| is the segment's position count: a class position is
+ * exactly one byte -- of a UTF-8 character one of several.  A window never reaches the closing 0x0A or past n: a set that
+ * holds 0x00 does not match the padding behind a chunk.  A literal 0x0A anywhere in a group makes it match nothing.
+ * The CORE of a segment is its longest run of literal positions, the leftmost on a tie (pss_seqc_cores shows it); a segment
+ * of class positions alone has none.  The search is the sequence search over the CORES of the segments that have one: the
+ * interval search over all (core, chunk) pairs -- under PSS_SEQ_FOLD over the spellings of each core's seed, as
+ * pss_reader_search_seq_icase_batch expands a segment --, per (group, chunk) pair the core with the fewest hits (the lowest
+ * index on a tie) DRIVES, one candidate per entry that holds it, and every candidate entry is walked once, left to right:
+ * each segment at its leftmost place behind the one before it, found by its core and tested at the other positions, the
+ * next occurrence of the core on a miss; a segment without a core is tested place by place.  Leftmost-greedy stays
+ * complete: every segment has a fixed length.  A chunk that lacks a core contributes nothing without a hit being looked at.
+ * Order: group-major, chunk-major; inside a (group, chunk) pair the order the sequence call (under PSS_SEQ_FOLD: its _icase
+ * form) has for the driving core as driver segment -- pss_reader_set_result_order has no effect.  A batch without a class
+ * position returns exactly what the sequence call returns for it.
+ * pss_reader_last_stats: queries = groups, hits = the sum of the driving cores' interval hits (under PSS_SEQ_FOLD: of their
+ * seeds' hits), route = GENERAL | the interval bits (| COUNTS) -- no bit of its own.
+ * PSS_EINVAL (message in pss_last_error, *out / counts untouched): everything the sequence calls refuse (a null `classes`
+ * with nsegs > 0 and a null `sets` with nsets > 0 included); flags other than PSS_SEQ_FOLD; nsets > 255; a class index past
+ * nsets; a nonzero byte in sbytes under a class index; a set that holds 0x0A; an empty set; under PSS_SEQ_FOLD a set not
+ * closed under the fold; a group none of whose segments has a core (nothing in the suffix array can be looked up for it).
+ * The reader is judged last.
+ * Out of scope: driving a segment by anything but its longest literal run (a rare byte pair inside it, a set of few bytes);
+ * groups without a literal byte; classes in all-terms groups, in the search within k mismatches or edits; POSIX classes
+ * such as [:alpha:] (the caller expands them into sets); multi-byte characters; the fused, resident and mid paths; a
+ * device-resident result; the multi-process gather over RCCL (dist.ShardedReader).
+ */
+#define PSS_SEQ_FOLD 1u
+/* packed entry text, one row per group */
+int pss_reader_search_seqc_batch(pss_reader *r, const uint8_t *sbytes, const uint8_t *classes, const uint64_t *soffsets, uint32_t nsegs,
+                                 const uint8_t *sets, uint32_t nsets, const uint64_t *group_offsets, uint32_t ngroups,
+                                 const uint8_t *anchors, uint32_t flags, pss_result **out);
+/* u64 entry ids, packed as pss_reader_search_ids_batch packs them */
+int pss_reader_search_seqc_ids_batch(pss_reader *r, const uint8_t *sbytes, const uint8_t *classes, const uint64_t *soffsets, uint32_t nsegs,
+                                     const uint8_t *sets, uint32_t nsets, const uint64_t *group_offsets, uint32_t ngroups,
+                                     const uint8_t *anchors, uint32_t flags, pss_result **out);
+/* counts[g] = entries group g matches; nothing but ngroups counters comes down */
+int pss_reader_count_seqc_batch(pss_reader *r, const uint8_t *sbytes, const uint8_t *classes, const uint64_t *soffsets, uint32_t nsegs,
+                                const uint8_t *sets, uint32_t nsets, const uint64_t *group_offsets, uint32_t ngroups,
+                                const uint8_t *anchors, uint32_t flags, uint64_t *counts);
+/* core_off[t] / core_len[t] = the core of segment t of a class plane (core_len 0: none), by the rule the calls above apply.
+ * Host only: no device is touched. */
+int pss_seqc_cores(const uint8_t *classes, const uint64_t *soffsets, uint32_t nsegs, uint32_t *core_off, uint32_t *core_len);
 /*
  * Case-insensitive search (no reference counterpart): `grep -i` over the entries.  ASCII only: the bytes 0x41 .. 0x5A (A .. Z)
  * are equivalent to 0x61 .. 0x7A (a .. z), and every other byte -- 0x80 .. 0xFF included, so no letter outside ASCII -- equals

@@ -28,7 +28,7 @@ except ImportError:   # pragma: no cover
     _pssglue = None
 
 __all__ = ['Writer', 'Reader', 'PackedResult', 'IdResult', 'DeviceResult', 'device_count', 'default_devices', 'release_workspace', 'workspace_bytes',
-           'glob_parse', 'glob_escape', 'icase_variants', 'near_pieces']
+           'glob_parse', 'glob_escape', 'glob_cores', 'icase_variants', 'near_pieces']
 
 
 def device_count() -> int:
@@ -86,15 +86,29 @@ def _pack_queries(patterns: typing.Sequence[bytes]):
     return b''.join(patterns), offs
 
 
-def glob_parse(pattern: bytes) -> typing.Tuple[typing.List[bytes], int]:
+def glob_parse(pattern: bytes, classes: bool = False, *, fold: bool = False):
     """``(segments, anchors)`` of a glob pattern as ``Reader.search_glob_ids_batch`` searches it (include/pss.h,
     pss_reader_search_seq_batch).  ``*`` stands for any run of bytes, also none; ``\\`` takes the next byte literally
     (``\\*``, ``\\\\``); adjacent ``*`` are one.  The anchors follow from the pattern's ends: no unescaped ``*`` in front sets
     ``PSS_ANCHOR_START`` (1), none behind sets ``PSS_ANCHOR_END`` (2).  ``ValueError`` for a lone ``\\`` at the end and for a
-    pattern without a literal byte.  Pure Python: no device is touched."""
+    pattern without a literal byte.  Pure Python: no device is touched.
+
+    ``classes=True``: ``?`` is exactly one byte of the entry, ``[set]`` one byte out of ``set`` and ``[!set]`` one byte not in
+    it (only ``!`` negates: ``^`` is a member, as in ``fnmatch``); ``a-z`` inside brackets is an inclusive byte range, a ``]``
+    right behind ``[`` or ``[!`` and a ``-`` first or last are members, and ``\\`` takes the next byte literally inside
+    brackets too.  A segment is then a LIST with one ``bytes`` object per position: the sorted bytes the position accepts --
+    one byte for a literal (so ``[*]`` is a literal), the 255 bytes other than newline for ``?``.  ``0x0A`` is taken out of
+    every set: an entry holds none.  ``ValueError`` also for an unclosed ``[``, an empty set, a descending range and a
+    pattern none of whose segments holds a literal byte (``glob_cores``).  ``fold=True`` (with ``classes``) shows the sets as
+    ``icase=True`` searches them: what is written between the brackets is closed under the ASCII fold before ``!`` negates,
+    so ``[a-c]`` accepts ``B`` and ``[!a]`` rejects ``A``; literals, a set of one byte among them, stay as written (the
+    search folds them), so a pattern has the same cores with and without fold.  ``classes=False`` is the parser as it
+    always was."""
     if not isinstance(pattern, (bytes, bytearray)):
         raise TypeError(f'a glob pattern must be bytes, not {type(pattern).__name__}')
     pattern = bytes(pattern)
+    if classes:
+        return _glob_parse_classes(pattern, bool(fold))
     segments: typing.List[bytes] = []
     cur = bytearray()
     first_star = last_star = False
@@ -126,11 +140,135 @@ def glob_parse(pattern: bytes) -> typing.Tuple[typing.List[bytes], int]:
     return segments, (0 if first_star else _ffi.ANCHOR_START) | (0 if last_star else _ffi.ANCHOR_END)
 
 
-def glob_escape(text: bytes) -> bytes:
-    """``text`` with every ``*`` and ``\\`` escaped: ``glob_parse(glob_escape(x)) == ([x], 3)`` for a non-empty ``x``."""
+def glob_escape(text: bytes, classes: bool = False) -> bytes:
+    """``text`` with every ``*`` and ``\\`` escaped: ``glob_parse(glob_escape(x)) == ([x], 3)`` for a non-empty ``x``.
+    ``classes=True`` also escapes ``?``, ``[`` and ``]``: ``glob_parse(glob_escape(x, classes=True), classes=True)`` is
+    ``([[bytes([b]) for b in x]], 3)``."""
     if not isinstance(text, (bytes, bytearray)):
         raise TypeError(f'glob_escape takes bytes, not {type(text).__name__}')
-    return bytes(text).replace(b'\\', b'\\\\').replace(b'*', b'\\*')
+    out = bytes(text).replace(b'\\', b'\\\\').replace(b'*', b'\\*')
+    if classes:
+        out = out.replace(b'?', b'\\?').replace(b'[', b'\\[').replace(b']', b'\\]')
+    return out
+
+
+_ANY_BYTE = bytes(b for b in range(256) if b != 0x0A)     # what ``?`` accepts
+
+
+def _fold_closed(members: typing.Set[int]) -> typing.Set[int]:
+    """members and, for every ASCII letter among them, the letter's other case."""
+    return members | {b ^ 0x20 for b in members if 0x41 <= (b & 0xDF) <= 0x5A}
+
+
+def _glob_set(pattern: bytes, i: int, fold: bool) -> typing.Tuple[bytes, int]:
+    """(accepted bytes, index behind the closing ``]``) of the bracket expression whose ``[`` stands at pattern[i]."""
+    n = len(pattern)
+    j = i + 1
+    negate = j < n and pattern[j] == 0x21           # '!'
+    if negate:
+        j += 1
+    members: typing.Set[int] = set()
+    first = True
+
+    def item(j):                                    # one member byte at j, escaped or not -> (byte, index behind it)
+        if j >= n:
+            raise ValueError(f'glob pattern {pattern!r}: the [ at byte {i} is not closed')
+        if pattern[j] == 0x5C:
+            if j + 1 >= n:
+                raise ValueError(f'glob pattern {pattern!r} ends in a lone backslash (write it as two)')
+            return pattern[j + 1], j + 2
+        return pattern[j], j + 1
+
+    while True:
+        if j >= n:
+            raise ValueError(f'glob pattern {pattern!r}: the [ at byte {i} is not closed')
+        if pattern[j] == 0x5D and not first:        # ']' (right behind '[' or '[!' it is a member)
+            j += 1
+            break
+        first = False
+        lo, j = item(j)
+        if j + 1 < n and pattern[j] == 0x2D and pattern[j + 1] != 0x5D:     # 'lo-hi' (a '-' in front of ']' is a member)
+            hi, j = item(j + 1)
+            if hi < lo:
+                raise ValueError(f'glob pattern {pattern!r}: the range {bytes([lo])!r}-{bytes([hi])!r} descends')
+            members.update(range(lo, hi + 1))
+        else:
+            members.add(lo)
+    if fold and (negate or len(members) > 1):       # (one byte is a literal, which folds as every literal does: the cores stay
+        members = _fold_closed(members)             # the same with and without fold)
+    if negate:
+        members = set(range(256)) - members
+    members.discard(0x0A)
+    if not members:
+        raise ValueError(f'glob pattern {pattern!r}: the set at byte {i} is empty (no byte of an entry is in it)')
+    return bytes(sorted(members)), j
+
+
+def _glob_parse_classes(pattern: bytes, fold: bool):
+    """``glob_parse(pattern, classes=True)``: segments as lists of byte sets."""
+    segments: typing.List[typing.List[bytes]] = []
+    cur: typing.List[bytes] = []
+    first_star = last_star = False
+    i, n = 0, len(pattern)
+    while i < n:
+        c = pattern[i]
+        if c == 0x2A:                               # '*': closes the segment before it
+            if cur:
+                segments.append(cur)
+                cur = []
+            elif not segments:
+                first_star = True
+            last_star = True
+            i += 1
+            continue
+        last_star = False
+        if c == 0x5C:                               # '\\': the next byte as it is
+            if i + 1 >= n:
+                raise ValueError(f'glob pattern {pattern!r} ends in a lone backslash (write it as two)')
+            cur.append(pattern[i + 1:i + 2])
+            i += 2
+        elif c == 0x3F:                             # '?'
+            cur.append(_ANY_BYTE)
+            i += 1
+        elif c == 0x5B:                             # '['
+            members, i = _glob_set(pattern, i, fold)
+            cur.append(members)
+        else:
+            cur.append(pattern[i:i + 1])
+            i += 1
+    if cur:
+        segments.append(cur)
+    if not any(len(pos) == 1 for seg in segments for pos in seg):
+        raise ValueError(f"glob pattern {pattern!r} has no literal byte: nothing in the suffix array can be looked up for it "
+                         "('*' alone matches every entry, entry_counts counts them)")
+    return segments, (0 if first_star else _ffi.ANCHOR_START) | (0 if last_star else _ffi.ANCHOR_END)
+
+
+def _segment_core(seg: typing.Sequence[bytes]) -> typing.Optional[typing.Tuple[int, bytes]]:
+    """The core of one segment of ``glob_parse(..., classes=True)``: (offset, bytes) of its longest run of literal positions,
+    the leftmost on a tie; None for a segment without one."""
+    best_off = best_len = 0
+    i, n = 0, len(seg)
+    while i < n:
+        if len(seg[i]) != 1:
+            i += 1
+            continue
+        j = i
+        while j < n and len(seg[j]) == 1:
+            j += 1
+        if j - i > best_len:
+            best_off, best_len = i, j - i
+        i = j
+    return (best_off, b''.join(seg[best_off:best_off + best_len])) if best_len else None
+
+
+def glob_cores(pattern: bytes) -> typing.List[typing.Optional[typing.Tuple[int, bytes]]]:
+    """Per segment of ``glob_parse(pattern, classes=True)`` its CORE as ``(offset, bytes)``: the longest run of literal
+    positions, the leftmost on a tie -- what ``Reader.search_glob_ids_batch(..., classes=True)`` looks up in the suffix
+    arrays for the segment (include/pss.h, pss_reader_search_seqc_batch).  A segment without a literal position (``??``,
+    ``[0-9]``) has no core: ``None``.  The rarest core of every (pattern, chunk) pair drives the search, so ``hits`` and the
+    order of the result follow from this rule.  Host only: no device is touched."""
+    return [_segment_core(seg) for seg in glob_parse(pattern, classes=True)[0]]
 
 
 def icase_variants(pattern: bytes, letters: typing.Optional[int] = None) -> typing.Tuple[int, typing.List[bytes]]:
@@ -338,16 +476,33 @@ def _icase_flag(icase) -> bool:
     return icase
 
 
-def _with_icase(folded, note: str):
+def _classes_flag(classes) -> bool:
+    """The ``classes`` keyword of the glob calls: a bool and nothing else, as ``icase``."""
+    if not isinstance(classes, bool):
+        raise TypeError(f"argument 'classes': must be bool, not {type(classes).__name__}")
+    return classes
+
+
+def _with_icase(folded, note: str, classed=None):
     """Decorator of the ten all-terms and glob methods of ``Reader``: adds the keyword-only ``icase: bool = False``.
     ``icase=False`` calls the decorated exact-byte method as it stands -- not one line of its path changes; ``icase=True``
     calls ``folded`` with the same arguments.  ``functools.wraps`` keeps the method's name and appends ``note`` to its
     docstring; like every wrapped function it also keeps the exact-byte method's ``inspect.signature`` (``__wrapped__``) --
-    the keyword itself is declared in ``__init__.pyi`` and shown by ``inspect.signature(m, follow_wrapped=False)``."""
+    the keyword itself is declared in ``__init__.pyi`` and shown by ``inspect.signature(m, follow_wrapped=False)``.
+    ``classed`` (the five glob methods): the wrapper also takes the keyword-only ``classes: bool = False``;
+    ``classes=True`` calls ``classed(self, *args, icase=...)`` -- the pattern language with ``?`` and ``[...]`` -- and
+    ``classes=False`` the two bodies above, exactly as without the keyword."""
     def decorate(exact):
-        @functools.wraps(exact)
-        def method(self, *args, icase: bool = False, **kwargs):
-            return (folded if _icase_flag(icase) else exact)(self, *args, **kwargs)
+        if classed is None:
+            @functools.wraps(exact)
+            def method(self, *args, icase: bool = False, **kwargs):
+                return (folded if _icase_flag(icase) else exact)(self, *args, **kwargs)
+        else:
+            @functools.wraps(exact)
+            def method(self, *args, icase: bool = False, classes: bool = False, **kwargs):
+                if _classes_flag(classes):
+                    return classed(self, *args, icase=_icase_flag(icase), **kwargs)
+                return (folded if _icase_flag(icase) else exact)(self, *args, **kwargs)
         method.__doc__ = (exact.__doc__ or '') + note
         return method
     return decorate
@@ -388,6 +543,73 @@ def _folded_count_glob(self, s):
     return _folded_batch('seq', 'counts')(self, [_utf8(s, 'pattern')])[0]
 
 
+SEQ_MAX_SETS = 255      # distinct byte sets one batch of class globs carries (include/pss.h, pss_reader_search_seqc_batch)
+
+
+def _glob_class_args(patterns, fold: bool):
+    """The arguments of one ``pss_reader_search_seqc_*`` call between the reader and the output: the segments of every
+    pattern (``glob_parse(p, classes=True, fold=fold)``) as literal bytes and class plane, the batch's distinct sets as
+    256-bit memberships, the group offsets, the anchors and the flags word.  Returns ``(args, keep)``; ``keep`` holds the
+    arrays the pointers in ``args`` point into."""
+    import numpy as np
+    if isinstance(patterns, (bytes, bytearray, str)):
+        raise TypeError(f"argument 'patterns': '{type(patterns).__name__}' object cannot be converted to a sequence of glob patterns")
+    lit = bytearray()
+    plane = bytearray()
+    soff, goff = [0], [0]
+    anch: typing.List[int] = []
+    index: typing.Dict[bytes, int] = {}
+    for g, pat in enumerate(patterns):
+        if not isinstance(pat, (bytes, bytearray)):
+            raise TypeError(f'pattern {g}: a glob pattern must be bytes, not {type(pat).__name__}')
+        segs, a = glob_parse(pat, classes=True, fold=fold)
+        for seg in segs:
+            for pos in seg:
+                if len(pos) == 1:
+                    lit.append(pos[0])
+                    plane.append(0)
+                    continue
+                k = index.get(pos)
+                if k is None:
+                    if len(index) == SEQ_MAX_SETS:
+                        raise ValueError(f'pattern {g}: the batch holds more than {SEQ_MAX_SETS} distinct byte sets (the class plane '
+                                         f'names a set in one byte): split the batch')
+                    k = index[pos] = len(index) + 1
+                lit.append(0)
+                plane.append(k)
+            soff.append(len(lit))
+        goff.append(len(soff) - 1)
+        anch.append(a)
+    sets = np.zeros((max(len(index), 1), 32), dtype=np.uint8)
+    for members, k in index.items():
+        m = np.frombuffer(members, dtype=np.uint8)
+        np.bitwise_or.at(sets[k - 1], m >> 3, np.uint8(1) << (m & 7))
+    soffs, goffs = np.array(soff, dtype=np.uint64), np.array(goff, dtype=np.uint64)
+    anchors = np.array(anch if anch else [0], dtype=np.uint8)
+    keep = (bytes(lit), bytes(plane), soffs, sets, goffs, anchors)
+    args = (keep[0], keep[1], soffs.ctypes.data, len(soff) - 1, sets.ctypes.data, len(index), goffs.ctypes.data, len(goff) - 1,
+            anchors.ctypes.data, _ffi.SEQ_FOLD if fold else 0)
+    return args, keep
+
+
+def _classed_batch(form: str):
+    """The ``classes=True`` body of one batched glob method (``form`` 'packed', 'ids' or 'counts'), exact bytes or under fold."""
+    name = {'packed': 'pss_reader_search_seqc_batch', 'ids': 'pss_reader_search_seqc_ids_batch', 'counts': 'pss_reader_count_seqc_batch'}[form]
+
+    def run(self, batch, icase=False):
+        args, keep = _glob_class_args(batch, icase)
+        return self._batch(getattr(_lib, name), args, args[7], form)
+    return run
+
+
+def _classed_search_glob(self, s, icase=False):
+    return _packed_strs(_classed_batch('packed')(self, [_utf8(s, 'pattern')], icase))
+
+
+def _classed_count_glob(self, s, icase=False):
+    return _classed_batch('counts')(self, [_utf8(s, 'pattern')], icase)[0]
+
+
 _ICASE_ALL = """
 
         ``icase=True`` (keyword only): every term is compared under ASCII case folding (``A-Z`` = ``a-z``, every other byte
@@ -400,7 +622,16 @@ _ICASE_GLOB = """
         ``icase=True`` (keyword only): every byte is compared under ASCII case folding (``A-Z`` = ``a-z``, every other byte
         equals only itself): ``grep -i`` for globs.  ``glob_escape(p) + b'*'``, ``b'*' + glob_escape(p)`` and
         ``glob_escape(p)`` are then the case-insensitive "starts with", "ends with" and "equals" (include/pss.h,
-        pss_reader_search_seq_icase_batch).  ``icase=False`` is the call as it always was."""
+        pss_reader_search_seq_icase_batch).  ``icase=False`` is the call as it always was.
+
+        ``classes=True`` (keyword only): ``?`` stands for exactly one byte of the entry and ``[set]`` / ``[!set]`` for one
+        byte in / not in a set of bytes (``glob_parse(p, classes=True)`` shows what a pattern stands for, ``glob_escape(x,
+        classes=True)`` writes a literal).  A class is one BYTE: ``?`` over UTF-8 text counts bytes.  Every piece between two
+        ``*`` is looked up by its CORE, its longest run of literal bytes (``glob_cores``); the rarest core of every (pattern,
+        chunk) pair drives and every candidate entry is walked once, left to right (include/pss.h,
+        pss_reader_search_seqc_batch).  A pattern needs one literal byte; a batch holds at most 255 distinct sets.  Combines
+        with ``icase=True``: a set then accepts both cases of the letters written in it, ``[!a]`` rejects ``A``.
+        ``classes=False``, the default, leaves ``?``, ``[`` and ``]`` the literal bytes they always were."""
 
 
 class Reader:
@@ -816,7 +1047,7 @@ class Reader:
         blob, offs = _pack_queries(segs)
         return blob, offs, np.array(goff, dtype=np.uint64), np.array(anch if anch else [0], dtype=np.uint8)
 
-    @_with_icase(_folded_batch('seq', 'packed'), _ICASE_GLOB)
+    @_with_icase(_folded_batch('seq', 'packed'), _ICASE_GLOB, _classed_batch('packed'))
     def search_glob_batch_packed(self, patterns: typing.Sequence[bytes]) -> 'PackedResult':
         """Extension: per glob pattern (``glob_parse``: literal pieces and ``*``), the entries that hold the pieces IN
         ORDER and without overlap -- the first at the entry's start unless the pattern begins with ``*``, the last at its
@@ -826,23 +1057,23 @@ class Reader:
         (include/pss.h, pss_reader_search_seq_batch).  ``set_result_order`` has no effect."""
         return self._group_batch('pss_reader_search_seq_batch', self._glob_args(patterns), 'packed')
 
-    @_with_icase(_folded_batch('seq', 'ids'), _ICASE_GLOB)
+    @_with_icase(_folded_batch('seq', 'ids'), _ICASE_GLOB, _classed_batch('ids'))
     def search_glob_ids_batch(self, patterns: typing.Sequence[bytes]) -> 'IdResult':
         """Extension: the ids (``search_ids_batch``) of the entries ``search_glob_batch_packed`` returns, in the same
         order; ``counts[g]`` of them belong to pattern g."""
         return self._group_batch('pss_reader_search_seq_ids_batch', self._glob_args(patterns), 'ids')
 
-    @_with_icase(_folded_batch('seq', 'counts'), _ICASE_GLOB)
+    @_with_icase(_folded_batch('seq', 'counts'), _ICASE_GLOB, _classed_batch('counts'))
     def count_glob_bytes(self, patterns: typing.Sequence[bytes]) -> typing.List[int]:
         """Extension: how many entries each glob pattern matches; only the counters come back."""
         return self._group_batch('pss_reader_count_seq_batch', self._glob_args(patterns), 'counts')
 
-    @_with_icase(_folded_search_glob, _ICASE_GLOB)
+    @_with_icase(_folded_search_glob, _ICASE_GLOB, _classed_search_glob)
     def search_glob(self, s: str) -> typing.List[str]:
         """Extension: the entries that match the glob pattern ``s`` (``*`` = any run of bytes, ``\\`` escapes)."""
         return _packed_strs(self.search_glob_batch_packed([_utf8(s, 'pattern')]))
 
-    @_with_icase(_folded_count_glob, _ICASE_GLOB)
+    @_with_icase(_folded_count_glob, _ICASE_GLOB, _classed_count_glob)
     def count_glob(self, s: str) -> int:
         """Extension: how many entries match the glob pattern ``s``."""
         return self.count_glob_bytes([_utf8(s, 'pattern')])[0]

@@ -154,6 +154,7 @@ ROUTES = {
 # Anchors of the anchored search (PSS_ANCHOR_* in include/pss.h): where in the entry the pattern must sit.
 ANCHORS = {'start': 1, 'end': 2, 'entry': 3}
 ANCHOR_START, ANCHOR_END = 1, 2
+SEQ_FOLD = 1        # PSS_SEQ_FOLD: the flags word of the pss_reader_search_seqc_* calls
 
 
 class DeviceResult(ctypes.Structure):
@@ -301,6 +302,10 @@ def _load() -> ctypes.CDLL:
         'pss_reader_search_seq_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, u32, vp, pvp]),
         'pss_reader_search_seq_ids_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, u32, vp, pvp]),
         'pss_reader_count_seq_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, u32, vp, vp]),
+        'pss_reader_search_seqc_batch': (ctypes.c_int, [vp, vp, vp, vp, u32, vp, u32, vp, u32, vp, u32, pvp]),
+        'pss_reader_search_seqc_ids_batch': (ctypes.c_int, [vp, vp, vp, vp, u32, vp, u32, vp, u32, vp, u32, pvp]),
+        'pss_reader_count_seqc_batch': (ctypes.c_int, [vp, vp, vp, vp, u32, vp, u32, vp, u32, vp, u32, vp]),
+        'pss_seqc_cores': (ctypes.c_int, [vp, vp, u32, vp, vp]),
         'pss_reader_search_icase_batch': (ctypes.c_int, [vp, vp, vp, u32, pvp]),
         'pss_reader_search_icase_ids_batch': (ctypes.c_int, [vp, vp, vp, u32, pvp]),
         'pss_reader_count_icase_batch': (ctypes.c_int, [vp, vp, vp, u32, vp]),

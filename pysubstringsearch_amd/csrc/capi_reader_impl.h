@@ -1547,6 +1547,203 @@ extern "C" int pss_reader_count_seq_batch(pss_reader *r, const uint8_t *sbytes, 
     return guarded([&]() -> int { return seq_batch(r, "pss_reader_count_seq_batch", sbytes, soffsets, nsegs, group_offsets, ngroups, anchors, false, SEARCH_COUNTS, nullptr, counts); });
 }
 
+// ---- wildcard search with byte classes: segments of literals, `?` and `[...]` (seq_class_impl.h) ------
+
+namespace {
+
+// The core of one segment from its class plane: offset and length of the longest run of literal positions (plane 0), the
+// leftmost on a tie; length 0 for a segment without a literal position.  The rule of glob_cores in the Python layer.
+void segment_core(const uint8_t *plane, uint64_t len, uint32_t *off, uint32_t *clen)
+{
+    uint64_t best_off = 0, best_len = 0;
+    for (uint64_t i = 0; i < len;) {
+        if (plane[i]) {
+            ++i;
+            continue;
+        }
+        uint64_t j = i;
+        while (j < len && !plane[j]) ++j;
+        if (j - i > best_len) {
+            best_off = i;
+            best_len = j - i;
+        }
+        i = j;
+    }
+    *off = (uint32_t)best_off;
+    *clen = (uint32_t)best_len;
+}
+
+bool set_has(const uint8_t *set, uint32_t b) { return (set[b >> 3] >> (b & 7)) & 1u; }
+
+// The three class calls: the argument checks -- every one a sequence call makes, then the class plane's and the sets' --, the
+// cores of the segments as the terms of a sequence batch, under PSS_SEQ_FOLD expanded into their seeds' spellings, and the
+// segments themselves in the request's class block.  The batch is judged before the reader is, as everywhere.
+int seqc_batch(pss_reader *r, const char *who, const uint8_t *sbytes, const uint8_t *classes, const uint64_t *soffsets, uint32_t nsegs,
+               const uint8_t *sets, uint32_t nsets, const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *anchors, uint32_t flags,
+               SearchMode mode, pss_result **out, uint64_t *counts)
+{
+    if (!out_ok_by_mode(mode, ngroups, out, counts) || !group_offsets || !anchors || (nsegs && (!sbytes || !classes || !soffsets)) ||
+        (nsets && !sets)) {
+        set_error("%s: bad arguments", who);
+        return PSS_EINVAL;
+    }
+    if (flags & ~PSS_SEQ_FOLD) {
+        set_error("%s: flags = %#x (0 or PSS_SEQ_FOLD)", who, (unsigned)flags);
+        return PSS_EINVAL;
+    }
+    if (nsets > 255) {
+        set_error("%s: %u sets (the class plane names a set in one byte: 255 at most)", who, nsets);
+        return PSS_EINVAL;
+    }
+    const bool fold = (flags & PSS_SEQ_FOLD) != 0;
+    for (uint32_t k = 0; k < nsets; ++k) {
+        const uint8_t *set = sets + (size_t)k * 32;
+        bool any = false;
+        for (uint32_t w = 0; w < 32; ++w) any = any || set[w];
+        if (!any) {
+            set_error("%s: set %u is empty (no byte of an entry is in it)", who, k + 1);
+            return PSS_EINVAL;
+        }
+        if (set_has(set, 0x0A)) {
+            set_error("%s: set %u holds 0x0A (no entry holds a newline: leave it out)", who, k + 1);
+            return PSS_EINVAL;
+        }
+        for (uint32_t b = 'A'; fold && b <= 'Z'; ++b)
+            if (set_has(set, b) != set_has(set, b | 0x20)) {
+                set_error("%s: set %u holds one case of '%c' alone: under PSS_SEQ_FOLD a set is closed under the fold", who, k + 1, (int)b);
+                return PSS_EINVAL;
+            }
+    }
+    std::vector<uint32_t> cores((size_t)nsegs * 2 + 2);
+    std::vector<uint8_t> newline((size_t)nsegs + 1);
+    for (uint32_t t = 0; t < nsegs; ++t) {
+        if (soffsets[t + 1] <= soffsets[t]) {
+            set_error("%s: segment %u is empty (two wildcards in a row are one: leave it out)", who, t);
+            return PSS_EINVAL;
+        }
+        const uint64_t len = soffsets[t + 1] - soffsets[t];
+        if (len > 0xffffffffull) {
+            set_error("%s: segment %u has more than 2^32 - 1 bytes (a chunk has fewer)", who, t);
+            return PSS_EINVAL;
+        }
+        const uint8_t *sb = sbytes + soffsets[t], *sp = classes + soffsets[t];
+        bool all_any = true;
+        for (uint64_t i = 0; i < len; ++i) {
+            if (sp[i] > nsets) {
+                set_error("%s: segment %u names set %u at position %llu, and the batch has %u", who, t, (unsigned)sp[i], (unsigned long long)i, nsets);
+                return PSS_EINVAL;
+            }
+            if (sp[i] && sb[i]) {
+                set_error("%s: segment %u holds the byte %#x under a class index at position %llu (a class position's byte is 0)", who, t,
+                          (unsigned)sb[i], (unsigned long long)i);
+                return PSS_EINVAL;
+            }
+            if (!sp[i] && sb[i] == '\n') newline[t] = 1;
+            if (sp[i]) {                                    // (every byte but 0x0A: what `?` stands for)
+                const uint8_t *set = sets + (size_t)(sp[i] - 1) * 32;
+                for (uint32_t w = 0; w < 32 && all_any; ++w) all_any = set[w] == (w == 1 ? 0xfb : 0xff);
+            }
+        }
+        segment_core(sp, len, &cores[2 * (size_t)t], &cores[2 * (size_t)t + 1]);
+        if (!cores[2 * (size_t)t + 1]) cores[2 * (size_t)t] = all_any ? 1u : 0u;
+    }
+    PSS_TRY(group_args(r, who, "segments", group_offsets, ngroups, nsegs, [&](uint32_t g) {
+        if (group_offsets[g + 1] == group_offsets[g]) {
+            set_error("%s: group %u has no segment (a pattern of wildcards alone is not a search)", who, g);
+            return false;
+        }
+        if (anchors[g] > (PSS_ANCHOR_START | PSS_ANCHOR_END)) {
+            set_error("%s: anchors[%u] = %u (0, PSS_ANCHOR_START = 1, PSS_ANCHOR_END = 2 or both)", who, g, (unsigned)anchors[g]);
+            return false;
+        }
+        bool cored = false;
+        for (uint64_t t = group_offsets[g]; t < group_offsets[g + 1] && !cored; ++t) cored = cores[2 * t + 1] != 0;
+        if (!cored) set_error("%s: group %u has no segment with a literal byte: nothing in the suffix array can be looked up for it", who, g);
+        return cored;
+    }));
+    // the cores as terms: their bytes back to back (as the caller wrote them: the expansion folds), offsets, groups, void flags
+    std::vector<uint8_t> cbytes, cvoid, fbytes;
+    std::vector<uint64_t> coff(1, 0), cgoff(1, 0);
+    for (uint32_t g = 0; g < ngroups; ++g) {
+        bool dead = false;
+        for (uint64_t t = group_offsets[g]; t < group_offsets[g + 1]; ++t) dead = dead || newline[t];
+        for (uint64_t t = group_offsets[g]; t < group_offsets[g + 1]; ++t) {
+            const uint32_t co = cores[2 * t], cl = cores[2 * t + 1];
+            if (!cl) continue;
+            cbytes.insert(cbytes.end(), sbytes + soffsets[t] + co, sbytes + soffsets[t] + co + cl);
+            coff.push_back(cbytes.size());
+            cvoid.push_back(dead ? 1 : 0);
+        }
+        cgoff.push_back(coff.size() - 1);
+    }
+    const uint32_t ncores = (uint32_t)(coff.size() - 1);
+    cbytes.push_back(0);                    // (data() of an empty vector may be null)
+    cvoid.push_back(0);
+    const uint64_t stotal = nsegs ? soffsets[nsegs] : 0;
+    const uint8_t *seg_bytes = sbytes;
+    if (fold) {                             // (the literals as they are compared: lower case; a class position's 0 stays)
+        fbytes.assign(sbytes, sbytes + stotal);
+        for (uint8_t &b : fbytes)
+            if ((uint8_t)(b - 'A') < 26) b |= 0x20;
+        fbytes.push_back(0);
+        seg_bytes = fbytes.data();
+    }
+    SeededGroups b;
+    SearchRequest rq{cbytes.data(), coff.data(), ncores, mode, nullptr, cgoff.data(), ngroups, nullptr, anchors};
+    if (fold) {
+        PSS_TRY(icase_expand(who, "core", cbytes.data(), coff.data(), ncores, &b));
+        rq = b.request(ncores, cgoff.data(), ngroups, nullptr, anchors, mode);
+    }
+    rq.class_bytes = seg_bytes;
+    rq.class_plane = classes;
+    rq.class_offsets = soffsets;
+    rq.class_nsegs = nsegs;
+    rq.class_groups = group_offsets;
+    rq.class_cores = cores.data();
+    rq.class_sets = sets;
+    rq.class_nsets = nsets;
+    rq.class_void = cvoid.data();
+    return answer_by_mode(r, rq, out, counts);
+}
+
+}  // namespace
+
+extern "C" int pss_reader_search_seqc_batch(pss_reader *r, const uint8_t *sbytes, const uint8_t *classes, const uint64_t *soffsets, uint32_t nsegs,
+        const uint8_t *sets, uint32_t nsets, const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *anchors, uint32_t flags, pss_result **out)
+{
+    return guarded([&]() -> int { return seqc_batch(r, "pss_reader_search_seqc_batch", sbytes, classes, soffsets, nsegs, sets, nsets, group_offsets, ngroups, anchors, flags, SEARCH_FULL, out, nullptr); });
+}
+
+extern "C" int pss_reader_search_seqc_ids_batch(pss_reader *r, const uint8_t *sbytes, const uint8_t *classes, const uint64_t *soffsets, uint32_t nsegs,
+        const uint8_t *sets, uint32_t nsets, const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *anchors, uint32_t flags, pss_result **out)
+{
+    return guarded([&]() -> int { return seqc_batch(r, "pss_reader_search_seqc_ids_batch", sbytes, classes, soffsets, nsegs, sets, nsets, group_offsets, ngroups, anchors, flags, SEARCH_IDS, out, nullptr); });
+}
+
+extern "C" int pss_reader_count_seqc_batch(pss_reader *r, const uint8_t *sbytes, const uint8_t *classes, const uint64_t *soffsets, uint32_t nsegs,
+        const uint8_t *sets, uint32_t nsets, const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *anchors, uint32_t flags, uint64_t *counts)
+{
+    return guarded([&]() -> int { return seqc_batch(r, "pss_reader_count_seqc_batch", sbytes, classes, soffsets, nsegs, sets, nsets, group_offsets, ngroups, anchors, flags, SEARCH_COUNTS, nullptr, counts); });
+}
+
+extern "C" int pss_seqc_cores(const uint8_t *classes, const uint64_t *soffsets, uint32_t nsegs, uint32_t *core_off, uint32_t *core_len)
+{
+    return guarded([&]() -> int {
+        if (nsegs && (!classes || !soffsets || !core_off || !core_len)) {
+            set_error("pss_seqc_cores: bad arguments");
+            return PSS_EINVAL;
+        }
+        for (uint32_t t = 0; t < nsegs; ++t) {
+            if (soffsets[t + 1] < soffsets[t] || soffsets[t + 1] - soffsets[t] > 0xffffffffull) {
+                set_error("pss_seqc_cores: the segment offsets decrease at segment %u, or it has more than 2^32 - 1 bytes", t);
+                return PSS_EINVAL;
+            }
+            segment_core(classes + soffsets[t], soffsets[t + 1] - soffsets[t], &core_off[t], &core_len[t]);
+        }
+        return PSS_OK;
+    });
+}
+
 // ---- case-insensitive search: group -> terms -> the spellings of a seed (fold_impl.h) --------------
 
 namespace {

@@ -111,6 +111,24 @@ struct SearchRequest {
     const uint8_t *term_bytes = nullptr; const uint64_t *term_offsets = nullptr; uint32_t nterms = 0;
     const uint64_t *seed_offsets = nullptr; const uint32_t *seed_pos = nullptr; const uint8_t *near_budget = nullptr;
     bool near_edits = false;
+    // class_bytes .. class_void, together with group_offsets and seq_anchors: a sequence batch whose segments hold BYTE CLASSES
+    // (`?`, `[...]`) beside literal bytes (seq_class_impl.h).  The nq patterns -- under fold the nterms terms -- are
+    // then the CORES of the segments that have one (a segment's longest run of literal positions), group_offsets index them, and
+    // everything up to the verify step runs over cores as over segments.  The block states the segments themselves, which the
+    // verify step alone reads:
+    //   class_offsets (class_nsegs + 1) cut class_bytes and class_plane into segments, one byte per position: class_plane is 0 at
+    //     a literal position, whose byte class_bytes holds (folded to lower case under fold), else the 1-based index of the
+    //     position's set, and class_bytes 0;
+    //   class_groups (ngroups + 1) cut the segments into the groups, in order;
+    //   class_cores holds two values per segment: the core's offset inside the segment and its length -- or, length 0, a segment
+    //     without a core, and then 1 in the offset's place iff every position accepts every byte (a run of `?`);
+    //   class_sets: class_nsets x 32 bytes, bit b of a set = byte b >> 3, bit b & 7; no set holds 0x0A, none is empty, and under
+    //     fold every set is closed under it;
+    //   class_void (one flag per core): the core's group holds a literal 0x0A somewhere and matches nothing.
+    // The caller has validated all of it (capi_reader_impl.h, seqc_batch).  Not with near_budget.
+    const uint8_t *class_bytes = nullptr, *class_plane = nullptr; const uint64_t *class_offsets = nullptr; uint32_t class_nsegs = 0;
+    const uint64_t *class_groups = nullptr; const uint32_t *class_cores = nullptr;
+    const uint8_t *class_sets = nullptr; uint32_t class_nsets = 0; const uint8_t *class_void = nullptr;
     uint32_t rows() const { return group_offsets ? ngroups : nq; }     // rows of the result: queries, or groups of terms
     bool low_latency = false;            // one query through the resident kernel when it fits (an unanchored SEARCH_FULL batch only)
     // sa_order: the entries of one (query, chunk) pair come out in the reference's order -- suffix-array order of the FIRST hit

@@ -1744,6 +1744,7 @@ static void newline_flags(const u8 *bytes, const u64 *off, u32 n, u8 set, u8 *fl
 #include "entry_scan_impl.h"
 #include "all_terms_impl.h"
 #include "sequence_impl.h"
+#include "seq_class_impl.h"
 #include "seed_impl.h"
 #include "fold_impl.h"
 #include "near_impl.h"
@@ -1791,6 +1792,7 @@ struct Batch {
     // the request, normalised once: nothing below asks for a mode again
     bool counts, device, ids, anchored, terms, sa_order;
     bool seq;                           // terms, and the groups are ordered sequences (sequence_impl.h)
+    bool seqc;                          // seq, and the segments hold byte classes: the terms are their cores (seq_class_impl.h)
     bool seeded;                        // terms looked up through seed queries: group -> terms -> queries (seed_impl.h)
     bool near;                          // ... within k mismatches (near_impl.h); else under fold (fold_impl.h, 4.14)
     bool edits;                         // near, and the budget counts edits: EditMatch in NearMatch's place (edit_impl.h, 4.17)
@@ -1813,6 +1815,7 @@ struct Batch {
     u32 *p_lo = nullptr, *p_cnt = nullptr;          // interval and hits per (row, chunk) pair: d_lo / d_cnt, or the drivers'
     u64 *d_goff = nullptr;                          // all-terms batch: group offsets, term flags, driver term per group pair
     u8 *d_tflags = nullptr, *d_sanch = nullptr;       // (d_sanch: a sequence batch's anchor byte per group)
+    SeqClass d_sc{};                                // a class batch: its segments, behind the anchor bytes (upload_anchors)
     u32 *d_gdrv = nullptr;
     u8 *d_fbytes = nullptr, *d_fvoid = nullptr;     // a seeded batch: the terms as they are verified, their offsets, a void flag
     u64 *d_foff = nullptr, *d_soff = nullptr;       // per term, the queries' offsets per term and positions per query, the seed
@@ -1840,6 +1843,7 @@ struct Batch {
         anchored = rq.anchors != nullptr;
         terms = rq.group_offsets != nullptr;
         seq = terms && rq.seq_anchors != nullptr;
+        seqc = seq && rq.class_bytes != nullptr;
         seeded = terms && rq.seed_offsets != nullptr;
         near = seeded && rq.near_budget != nullptr;
         edits = near && rq.near_edits;
@@ -1864,6 +1868,8 @@ struct Batch {
     }
     int stage_queries(), run_fused(bool *served), launch_interval(), run_mid(bool *done), pick_drivers(), seed_drivers(), run_general(), finish();
     int sa_order_hits(u32 grid, u64 H);
+    size_t anchor_room() const;
+    int upload_anchors();
     int download_result(u64 E, u64 B, const u64 *d_starts, const u8 *d_bytes, bool via_stage);
     void leave_on_device(const u64 *d_starts, const u8 *d_bytes), set_totals(u64 hits, u64 kept, u64 E, u64 B);
 };
@@ -1942,6 +1948,8 @@ int Batch::stage_queries()
         const u32 nt = seeded ? nterm : nq;
         own_tflags.resize(nt);
         newline_flags(seeded ? rq.term_bytes : rq.qbytes, seeded ? rq.term_offsets : rq.qoffsets, nt, kTermVoid, own_tflags.data());
+        for (u32 t = 0; seqc && t < nt; ++t)                        // (a class batch: a literal 0x0A outside the cores voids its group too)
+            if (rq.class_void[t]) own_tflags[t] |= kTermVoid;
         if (seeded) own_fvoid = own_tflags;
         for (u32 t = 0; !seq && t < nt; ++t)                        // (no segment of a sequence batch excludes)
             if (rq.exclude[t]) own_tflags[t] |= kTermExclude;
@@ -2172,12 +2180,52 @@ int Batch::sa_order_hits(u32 grid, u64 H)
     return PSS_OK;
 }
 
+// What a sequence batch keeps behind its term flags in the Q_TERMS slot, in multiples of 64 bytes: one anchor byte per group
+// and, for a class batch, the segments as seqc_verify_kernel reads them (SeqClass) -- offsets, the groups' offsets, the
+// cores, the sets, then bytes and plane, each with 32 zero bytes behind it (entry_scan reads a core up to 16 bytes past its
+// end).  anchor_room() sizes the stretch for pick_drivers' and seed_drivers' layouts alike; upload_anchors() fills it from
+// d_sanch on.
+size_t Batch::anchor_room() const
+{
+    if (!seq) return 0;
+    size_t room = round_up((size_t)nrow, 64);
+    if (seqc) {
+        const size_t ns = rq.class_nsegs, total = rq.class_offsets[ns];
+        room += round_up((ns + 1) * 8, 64) + round_up(((size_t)nrow + 1) * 8, 64) + round_up(ns * 8, 64) +
+                round_up((size_t)rq.class_nsets * 32, 64) + 2 * round_up(total + 32, 64);
+    }
+    return room;
+}
+
+int Batch::upload_anchors()
+{
+    if (!seq) return PSS_OK;
+    PSS_HIP(hipMemcpyAsync(d_sanch, rq.seq_anchors, nrow, hipMemcpyHostToDevice, s));
+    if (!seqc) return PSS_OK;
+    const size_t ns = rq.class_nsegs, total = rq.class_offsets[ns];
+    u8 *p = d_sanch + round_up((size_t)nrow, 64);
+    u8 *at[6];
+    const void *src[6] = {rq.class_offsets, rq.class_groups, rq.class_cores, rq.class_sets, rq.class_bytes, rq.class_plane};
+    const size_t len[6] = {(ns + 1) * 8, ((size_t)nrow + 1) * 8, ns * 8, (size_t)rq.class_nsets * 32, total, total};
+    for (int k = 0; k < 6; ++k) {
+        const size_t zeros = k >= 4 ? 32 : 0;                    // (behind the bytes and behind the plane)
+        at[k] = p;
+        if (len[k]) PSS_HIP(hipMemcpyAsync(p, src[k], len[k], hipMemcpyHostToDevice, s));
+        if (zeros) PSS_HIP(hipMemsetAsync(p + len[k], 0, zeros, s));
+        p += round_up(len[k] + zeros, 64);
+    }
+    u8 *off = at[0], *goff = at[1], *core = at[2], *sets = at[3], *bytes = at[4], *plane = at[5];
+    d_sc = SeqClass{bytes, plane, reinterpret_cast<const u64 *>(off), reinterpret_cast<const u64 *>(goff),
+                    reinterpret_cast<const u32 *>(core), reinterpret_cast<const u32 *>(sets)};
+    return PSS_OK;
+}
+
 // All-terms batch: from the term pairs to the group pairs.  Group offsets and term flags go up, and one lane per (group,
 // chunk) pair picks the pair's driver term; from here on the pipeline runs over the drivers' intervals.
 int Batch::pick_drivers()
 {
     const size_t goff_room = round_up(((size_t)nrow + 1) * 8, 64), flag_room = round_up((size_t)nq, 64);
-    const size_t anch_room = seq ? round_up((size_t)nrow, 64) : 0;        // (a sequence batch: one anchor byte per group)
+    const size_t anch_room = anchor_room();        // (a sequence batch: one anchor byte per group; a class batch: its segments too)
     PSS_TRY(take(Q_TERMS, goff_room + flag_room + anch_room + nrp * 12, d_goff));
     d_tflags = reinterpret_cast<u8 *>(d_goff) + goff_room;
     d_sanch = d_tflags + flag_room;
@@ -2186,7 +2234,7 @@ int Batch::pick_drivers()
     p_cnt = p_lo + nrp;
     PSS_HIP(hipMemcpyAsync(d_goff, rq.group_offsets, ((size_t)nrow + 1) * 8, hipMemcpyHostToDevice, s));
     PSS_HIP(hipMemcpyAsync(d_tflags, own_tflags.data(), nq, hipMemcpyHostToDevice, s));
-    if (seq) PSS_HIP(hipMemcpyAsync(d_sanch, rq.seq_anchors, nrow, hipMemcpyHostToDevice, s));
+    PSS_TRY(upload_anchors());
     hipLaunchKernelGGL(terms_driver_kernel<true>, dim3((u32)((nrp + 255) / 256)), dim3(256), 0, s, nc, d_goff, d_tflags, d_lo, d_cnt, nrp,
                        d_gdrv, p_lo, p_cnt);
     return PSS_OK;
@@ -2206,7 +2254,7 @@ int Batch::seed_drivers()
     const u64 ttotal = rq.term_offsets[nterm];
     const size_t goff_room = round_up(((size_t)nrow + 1) * 8, 64), toff_room = round_up(((size_t)nterm + 1) * 8, 64);
     const size_t over_room = near ? 64 : 0, pos_room = round_up((size_t)nq * 4, 64), flag_room = round_up((size_t)nterm, 64);
-    const size_t budget_room = near ? flag_room : 0, anch_room = seq ? round_up((size_t)nrow, 64) : 0;
+    const size_t budget_room = near ? flag_room : 0, anch_room = anchor_room();
     const size_t byte_room = round_up(ttotal + 32, 64), tcnt_room = round_up((size_t)ntp * 4, 64);
     PSS_TRY(take(Q_TERMS, goff_room + 2 * toff_room + over_room + pos_room + 2 * flag_room + budget_room + anch_room + byte_room +
                               tcnt_room + nrp * 8, d_goff));
@@ -2229,7 +2277,7 @@ int Batch::seed_drivers()
     PSS_HIP(hipMemcpyAsync(d_pos, rq.seed_pos, (size_t)nq * 4, hipMemcpyHostToDevice, s));
     PSS_HIP(hipMemcpyAsync(d_fvoid, own_fvoid.data(), nterm, hipMemcpyHostToDevice, s));
     PSS_HIP(hipMemcpyAsync(d_tflags, own_tflags.data(), nterm, hipMemcpyHostToDevice, s));
-    if (seq) PSS_HIP(hipMemcpyAsync(d_sanch, rq.seq_anchors, nrow, hipMemcpyHostToDevice, s));
+    PSS_TRY(upload_anchors());
     if (near) {
         PSS_HIP(hipMemcpyAsync(d_nk, rq.near_budget, nterm, hipMemcpyHostToDevice, s));
         PSS_HIP(hipMemsetAsync(d_over, 0, 8, s));
@@ -2294,7 +2342,10 @@ int Batch::run_general()
         hipLaunchKernelGGL(dedupe, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, T, nrp, d_hitoff, H, d_start, d_m, d_len, d_gdrv);
         // (every candidate against the group's other terms, or its segments in order: under fold alone -- a near batch is no
         // sequence and has one term per group)
-        if (seq)
+        if (seqc)   // (a class batch under fold: the candidates hold the driving core; every segment is placed by its own core)
+            hipLaunchKernelGGL(seqc_verify_kernel<true>, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, d_sc, d_sanch, nrp, d_hitoff, H, d_start,
+                               d_len);
+        else if (seq)
             hipLaunchKernelGGL(seq_verify_kernel<true>, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, d_fbytes, d_foff, d_goff, d_sanch,
                                nrp, d_hitoff, H, d_start, d_len);
         else if (nterm != nrow)     // (every group has an include term: as many terms as groups are one per group, and no other to look for)
@@ -2305,7 +2356,10 @@ int Batch::run_general()
         hipLaunchKernelGGL(hit_lines_kernel<true>, dim3(grid), dim3(256), 0, s, d_chunks, nc, d_q, d_qoff, nrp, p_lo, d_hitoff, H,
                            (const MidState *)nullptr, d_start, d_len, d_gdrv);
         const u32 vgrid = (u32)std::min<u64>((u64)ctx->num_cus * 16, (H * TG + 255) / 256);
-        if (seq)    // (a sequence batch: every candidate against the group's segments in order, the driver among them)
+        if (seqc)   // (a class batch: the terms are the segments' cores; every candidate against the segments themselves, in order)
+            hipLaunchKernelGGL(seqc_verify_kernel<false>, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, d_sc, d_sanch, nrp, d_hitoff, H, d_start,
+                               d_len);
+        else if (seq)    // (a sequence batch: every candidate against the group's segments in order, the driver among them)
             hipLaunchKernelGGL(seq_verify_kernel<false>, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, d_q, d_qoff, d_goff, d_sanch, nrp,
                                d_hitoff, H, d_start, d_len);
         else
@@ -2405,6 +2459,20 @@ int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, const LineDes
             set_error("search: a seeded batch states its groups, its terms' bytes and offsets, the seed queries' offsets and positions, "
                       "and either exclude flags or sequence anchors; with budgets its groups are one include term each and it has no "
                       "sequence anchors; budgets count edits only where there are budgets");
+            return PSS_EINVAL;
+        }
+    }
+    if (rq.class_bytes || rq.class_plane || rq.class_offsets || rq.class_groups || rq.class_cores || rq.class_sets || rq.class_void ||
+        rq.class_nsegs || rq.class_nsets) {
+        // a class batch is a sequence batch (groups and sequence anchors) that states all of its block, the sets where it names
+        // any; its terms are cores, so there are at most as many of them as segments; budgets are another search
+        const bool ok = rq.class_bytes && rq.class_plane && rq.class_offsets && rq.class_groups && rq.class_cores && rq.class_void &&
+                        (rq.class_sets || !rq.class_nsets) && rq.class_nsets <= 255 && rq.group_offsets && rq.seq_anchors && !rq.near_budget &&
+                        (rq.seed_offsets ? rq.nterms : rq.nq) <= rq.class_nsegs && rq.class_groups[0] == 0 &&
+                        rq.class_groups[rq.ngroups] == rq.class_nsegs;
+        if (!ok) {
+            set_error("search: a class batch is a sequence batch that states its segments' bytes, class plane, offsets, group offsets, "
+                      "cores and void flags, and at most 255 sets; its terms are the segments' cores");
             return PSS_EINVAL;
         }
     }
