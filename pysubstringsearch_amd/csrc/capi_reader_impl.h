@@ -1489,6 +1489,26 @@ extern "C" int pss_reader_count_terms_batch(pss_reader *r, const uint8_t *tbytes
 
 namespace {
 
+// What the sequence calls and the class calls ask of segment t and of group g alike; each states its own error.
+bool segment_ok(const char *who, const uint64_t *soffsets, uint32_t t)
+{
+    if (soffsets[t + 1] > soffsets[t]) return true;
+    set_error("%s: segment %u is empty (two wildcards in a row are one: leave it out)", who, t);
+    return false;
+}
+bool seq_group_ok(const char *who, const uint64_t *group_offsets, const uint8_t *anchors, uint32_t g)
+{
+    if (group_offsets[g + 1] == group_offsets[g]) {
+        set_error("%s: group %u has no segment (a pattern of wildcards alone is not a search)", who, g);
+        return false;
+    }
+    if (anchors[g] > (PSS_ANCHOR_START | PSS_ANCHOR_END)) {
+        set_error("%s: anchors[%u] = %u (0, PSS_ANCHOR_START = 1, PSS_ANCHOR_END = 2 or both)", who, g, (unsigned)anchors[g]);
+        return false;
+    }
+    return true;
+}
+
 // The argument checks of the three sequence calls (out_ok: the call's own output argument is usable).
 int seq_args(const pss_reader *r, const char *who, const uint8_t *sbytes, const uint64_t *soffsets, uint32_t nsegs,
              const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *anchors, bool out_ok)
@@ -1498,21 +1518,8 @@ int seq_args(const pss_reader *r, const char *who, const uint8_t *sbytes, const 
         return PSS_EINVAL;
     }
     for (uint32_t t = 0; t < nsegs; ++t)
-        if (soffsets[t + 1] <= soffsets[t]) {
-            set_error("%s: segment %u is empty (two wildcards in a row are one: leave it out)", who, t);
-            return PSS_EINVAL;
-        }
-    return group_args(r, who, "segments", group_offsets, ngroups, nsegs, [&](uint32_t g) {
-        if (group_offsets[g + 1] == group_offsets[g]) {
-            set_error("%s: group %u has no segment (a pattern of wildcards alone is not a search)", who, g);
-            return false;
-        }
-        if (anchors[g] > (PSS_ANCHOR_START | PSS_ANCHOR_END)) {
-            set_error("%s: anchors[%u] = %u (0, PSS_ANCHOR_START = 1, PSS_ANCHOR_END = 2 or both)", who, g, (unsigned)anchors[g]);
-            return false;
-        }
-        return true;
-    });
+        if (!segment_ok(who, soffsets, t)) return PSS_EINVAL;
+    return group_args(r, who, "segments", group_offsets, ngroups, nsegs, [&](uint32_t g) { return seq_group_ok(who, group_offsets, anchors, g); });
 }
 
 // The six sequence calls, as terms_batch: group -> segments, under icase -> spellings.
@@ -1575,27 +1582,9 @@ void segment_core(const uint8_t *plane, uint64_t len, uint32_t *off, uint32_t *c
 
 bool set_has(const uint8_t *set, uint32_t b) { return (set[b >> 3] >> (b & 7)) & 1u; }
 
-// The three class calls: the argument checks -- every one a sequence call makes, then the class plane's and the sets' --, the
-// cores of the segments as the terms of a sequence batch, under PSS_SEQ_FOLD expanded into their seeds' spellings, and the
-// segments themselves in the request's class block.  The batch is judged before the reader is, as everywhere.
-int seqc_batch(pss_reader *r, const char *who, const uint8_t *sbytes, const uint8_t *classes, const uint64_t *soffsets, uint32_t nsegs,
-               const uint8_t *sets, uint32_t nsets, const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *anchors, uint32_t flags,
-               SearchMode mode, pss_result **out, uint64_t *counts)
+// The sets of a class batch: none empty, none with 0x0A, under fold every one closed under it.
+int seqc_sets_ok(const char *who, const uint8_t *sets, uint32_t nsets, bool fold)
 {
-    if (!out_ok_by_mode(mode, ngroups, out, counts) || !group_offsets || !anchors || (nsegs && (!sbytes || !classes || !soffsets)) ||
-        (nsets && !sets)) {
-        set_error("%s: bad arguments", who);
-        return PSS_EINVAL;
-    }
-    if (flags & ~PSS_SEQ_FOLD) {
-        set_error("%s: flags = %#x (0 or PSS_SEQ_FOLD)", who, (unsigned)flags);
-        return PSS_EINVAL;
-    }
-    if (nsets > 255) {
-        set_error("%s: %u sets (the class plane names a set in one byte: 255 at most)", who, nsets);
-        return PSS_EINVAL;
-    }
-    const bool fold = (flags & PSS_SEQ_FOLD) != 0;
     for (uint32_t k = 0; k < nsets; ++k) {
         const uint8_t *set = sets + (size_t)k * 32;
         bool any = false;
@@ -1614,13 +1603,16 @@ int seqc_batch(pss_reader *r, const char *who, const uint8_t *sbytes, const uint
                 return PSS_EINVAL;
             }
     }
-    std::vector<uint32_t> cores((size_t)nsegs * 2 + 2);
-    std::vector<uint8_t> newline((size_t)nsegs + 1);
+    return PSS_OK;
+}
+
+// The walk over the segments of a class batch: every check of a segment's positions, its core into cores[2 t], cores[2 t + 1]
+// (class_cores of the request) and newline[t] = it holds a literal 0x0A.
+int seqc_segments(const char *who, const uint8_t *sbytes, const uint8_t *classes, const uint64_t *soffsets, uint32_t nsegs, const uint8_t *sets,
+                  uint32_t nsets, uint32_t *cores, uint8_t *newline)
+{
     for (uint32_t t = 0; t < nsegs; ++t) {
-        if (soffsets[t + 1] <= soffsets[t]) {
-            set_error("%s: segment %u is empty (two wildcards in a row are one: leave it out)", who, t);
-            return PSS_EINVAL;
-        }
+        if (!segment_ok(who, soffsets, t)) return PSS_EINVAL;
         const uint64_t len = soffsets[t + 1] - soffsets[t];
         if (len > 0xffffffffull) {
             set_error("%s: segment %u has more than 2^32 - 1 bytes (a chunk has fewer)", who, t);
@@ -1647,52 +1639,83 @@ int seqc_batch(pss_reader *r, const char *who, const uint8_t *sbytes, const uint
         segment_core(sp, len, &cores[2 * (size_t)t], &cores[2 * (size_t)t + 1]);
         if (!cores[2 * (size_t)t + 1]) cores[2 * (size_t)t] = all_any ? 1u : 0u;
     }
+    return PSS_OK;
+}
+
+// The cores as the terms of a sequence batch: their bytes back to back (as the caller wrote them: the expansion folds),
+// offsets, groups, void flags (a group with a literal 0x0A somewhere matches nothing).
+struct CoreTerms {
+    std::vector<uint8_t> bytes, dead;
+    std::vector<uint64_t> off{0}, goff{0};
+    uint32_t n = 0;
+    CoreTerms(const uint8_t *sbytes, const uint64_t *soffsets, const uint64_t *group_offsets, uint32_t ngroups, const uint32_t *cores,
+              const uint8_t *newline)
+    {
+        for (uint32_t g = 0; g < ngroups; ++g) {
+            bool dead_group = false;
+            for (uint64_t t = group_offsets[g]; t < group_offsets[g + 1]; ++t) dead_group = dead_group || newline[t];
+            for (uint64_t t = group_offsets[g]; t < group_offsets[g + 1]; ++t) {
+                const uint32_t co = cores[2 * t], cl = cores[2 * t + 1];
+                if (!cl) continue;
+                bytes.insert(bytes.end(), sbytes + soffsets[t] + co, sbytes + soffsets[t] + co + cl);
+                off.push_back(bytes.size());
+                dead.push_back(dead_group ? 1 : 0);
+            }
+            goff.push_back(off.size() - 1);
+        }
+        n = (uint32_t)(off.size() - 1);
+        bytes.push_back(0);                 // (data() of an empty vector may be null)
+        dead.push_back(0);
+    }
+};
+
+// The three class calls: the argument checks -- every one a sequence call makes, then the class plane's and the sets' --, the
+// cores of the segments as the terms of a sequence batch, under PSS_SEQ_FOLD expanded into their seeds' spellings, and the
+// segments themselves in the request's class block.  The batch is judged before the reader is, as everywhere.
+int seqc_batch(pss_reader *r, const char *who, const uint8_t *sbytes, const uint8_t *classes, const uint64_t *soffsets, uint32_t nsegs,
+               const uint8_t *sets, uint32_t nsets, const uint64_t *group_offsets, uint32_t ngroups, const uint8_t *anchors, uint32_t flags,
+               SearchMode mode, pss_result **out, uint64_t *counts)
+{
+    if (!out_ok_by_mode(mode, ngroups, out, counts) || !group_offsets || !anchors || (nsegs && (!sbytes || !classes || !soffsets)) ||
+        (nsets && !sets)) {
+        set_error("%s: bad arguments", who);
+        return PSS_EINVAL;
+    }
+    if (flags & ~PSS_SEQ_FOLD) {
+        set_error("%s: flags = %#x (0 or PSS_SEQ_FOLD)", who, (unsigned)flags);
+        return PSS_EINVAL;
+    }
+    if (nsets > 255) {
+        set_error("%s: %u sets (the class plane names a set in one byte: 255 at most)", who, nsets);
+        return PSS_EINVAL;
+    }
+    const bool fold = (flags & PSS_SEQ_FOLD) != 0;
+    PSS_TRY(seqc_sets_ok(who, sets, nsets, fold));
+    std::vector<uint32_t> cores((size_t)nsegs * 2 + 2);
+    std::vector<uint8_t> newline((size_t)nsegs + 1);
+    PSS_TRY(seqc_segments(who, sbytes, classes, soffsets, nsegs, sets, nsets, cores.data(), newline.data()));
     PSS_TRY(group_args(r, who, "segments", group_offsets, ngroups, nsegs, [&](uint32_t g) {
-        if (group_offsets[g + 1] == group_offsets[g]) {
-            set_error("%s: group %u has no segment (a pattern of wildcards alone is not a search)", who, g);
-            return false;
-        }
-        if (anchors[g] > (PSS_ANCHOR_START | PSS_ANCHOR_END)) {
-            set_error("%s: anchors[%u] = %u (0, PSS_ANCHOR_START = 1, PSS_ANCHOR_END = 2 or both)", who, g, (unsigned)anchors[g]);
-            return false;
-        }
+        if (!seq_group_ok(who, group_offsets, anchors, g)) return false;
         bool cored = false;
         for (uint64_t t = group_offsets[g]; t < group_offsets[g + 1] && !cored; ++t) cored = cores[2 * t + 1] != 0;
         if (!cored) set_error("%s: group %u has no segment with a literal byte: nothing in the suffix array can be looked up for it", who, g);
         return cored;
     }));
-    // the cores as terms: their bytes back to back (as the caller wrote them: the expansion folds), offsets, groups, void flags
-    std::vector<uint8_t> cbytes, cvoid, fbytes;
-    std::vector<uint64_t> coff(1, 0), cgoff(1, 0);
-    for (uint32_t g = 0; g < ngroups; ++g) {
-        bool dead = false;
-        for (uint64_t t = group_offsets[g]; t < group_offsets[g + 1]; ++t) dead = dead || newline[t];
-        for (uint64_t t = group_offsets[g]; t < group_offsets[g + 1]; ++t) {
-            const uint32_t co = cores[2 * t], cl = cores[2 * t + 1];
-            if (!cl) continue;
-            cbytes.insert(cbytes.end(), sbytes + soffsets[t] + co, sbytes + soffsets[t] + co + cl);
-            coff.push_back(cbytes.size());
-            cvoid.push_back(dead ? 1 : 0);
-        }
-        cgoff.push_back(coff.size() - 1);
-    }
-    const uint32_t ncores = (uint32_t)(coff.size() - 1);
-    cbytes.push_back(0);                    // (data() of an empty vector may be null)
-    cvoid.push_back(0);
-    const uint64_t stotal = nsegs ? soffsets[nsegs] : 0;
+    const CoreTerms c(sbytes, soffsets, group_offsets, ngroups, cores.data(), newline.data());
+    std::vector<uint8_t> fbytes;
     const uint8_t *seg_bytes = sbytes;
     if (fold) {                             // (the literals as they are compared: lower case; a class position's 0 stays)
-        fbytes.assign(sbytes, sbytes + stotal);
+        fbytes.assign(sbytes, sbytes + (nsegs ? soffsets[nsegs] : 0));
         for (uint8_t &b : fbytes)
             if ((uint8_t)(b - 'A') < 26) b |= 0x20;
         fbytes.push_back(0);
         seg_bytes = fbytes.data();
     }
     SeededGroups b;
-    SearchRequest rq{cbytes.data(), coff.data(), ncores, mode, nullptr, cgoff.data(), ngroups, nullptr, anchors};
+    SearchRequest rq{c.bytes.data(), c.off.data(), c.n, mode, nullptr, c.goff.data(), ngroups, nullptr, anchors};
     if (fold) {
-        PSS_TRY(icase_expand(who, "core", cbytes.data(), coff.data(), ncores, &b));
-        rq = b.request(ncores, cgoff.data(), ngroups, nullptr, anchors, mode);
+        PSS_TRY(icase_expand(who, "core", c.bytes.data(), c.off.data(), c.n, &b));
+        rq = b.request(c.n, c.goff.data(), ngroups, nullptr, anchors, mode);
     }
     rq.class_bytes = seg_bytes;
     rq.class_plane = classes;
@@ -1702,7 +1725,7 @@ int seqc_batch(pss_reader *r, const char *who, const uint8_t *sbytes, const uint
     rq.class_cores = cores.data();
     rq.class_sets = sets;
     rq.class_nsets = nsets;
-    rq.class_void = cvoid.data();
+    rq.class_void = c.dead.data();
     return answer_by_mode(r, rq, out, counts);
 }
 

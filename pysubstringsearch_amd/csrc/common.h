@@ -21,6 +21,7 @@
 
 #include "build_plan.h"
 #include "knobs.h"
+#include "search_layout.h"
 
 namespace pss {
 
@@ -137,7 +138,7 @@ struct DeviceCtx {
     void *pinned_dev = nullptr;          // the same memory as the device sees it (zero-copy reads / writes)
     // Pinned staging of the batched search (queries up, results down): copies from / to pageable
     // memory are synchronous and slow to start, DMA from / to pinned memory is not.
-    static constexpr size_t kStageQ = (size_t)2 << 20, kStageR = (size_t)4 << 20;
+    static constexpr size_t kStageQ = SEARCH_STAGE_Q, kStageR = SEARCH_STAGE_R;      // (search_layout.h: the staging rules read them)
     void *search_stage = nullptr;        // kStageQ + kStageR bytes, allocated on first use
     int ensure_search_stage();
     hipEvent_t search_ev[3] = {nullptr, nullptr, nullptr};   // timing events of the search path, created once

@@ -701,7 +701,7 @@ __device__ __forceinline__ void copy_entry(u8 *dst, const u8 *src, u32 l, u8 *ds
 // launch, the buffers are sized for the caps, and the host waits once for the totals and once for the
 // result.  More hits or bytes than the caps raise `flag`; the later kernels then do nothing and the
 // general pipeline runs instead.
-constexpr u32 MID_MAX = 65536;
+// (MID_MAX: search_layout.h, whose route rules read it)
 constexpr u32 MID_BLOCK = 1024;
 struct MidState {
     u64 hits, entries, bytes;
@@ -825,7 +825,7 @@ __global__ __launch_bounds__(256) void hit_lines_kernel(const ChunkDesc *chunks,
 // than the prefix are fetched from the device arena with one copy.  Anything that does not fit
 // (arena full, more than SM_MAX_HITS hits for one pair) sets the overflow flag and the general
 // multi-kernel path runs instead.
-constexpr u32 SM_MAX_VQ = 1024;
+// (SM_MAX_VQ and SM_MAX_PLEN, the longest query the path takes -- it is kept in LDS: search_layout.h, whose route rules read them)
 constexpr u32 SM_MAX_HITS = 1024;
 constexpr u32 SM_ENT_CAP = 65536;
 #ifndef PSS_SM_BYTE_PREFIX
@@ -833,7 +833,6 @@ constexpr u32 SM_ENT_CAP = 65536;
 #endif
 constexpr u32 SM_BYTE_PREFIX = PSS_SM_BYTE_PREFIX;   // result bytes that also go to pinned host memory
 constexpr u32 SM_BYTE_CAP = 8u << 20;
-constexpr u32 SM_MAX_PLEN = 256;       // longest query the path takes (kept in LDS)
 
 struct SmallHeader {   // device memory; all zero between launches (the last wave to finish resets it)
     u32 ent_cursor, byte_cursor, done;
@@ -859,11 +858,11 @@ struct SmallEntry {
 constexpr size_t SM_OFF_FLAGS = 0;                                              // u32 overflow
 constexpr size_t SM_OFF_REC = 64;                                               // 2048 records (one per pair, or per (pair, sub-block))
 constexpr size_t SM_OFF_MAILBOX = DeviceCtx::kResidentMailboxOff;               // resident kernel only: ResidentMailbox
-constexpr size_t SM_OFF_QUERY = 32768;                                          // query bytes, then offsets at + 8192
+// (SM_OFF_QUERY = 32768: query bytes, then offsets at + SM_QUERY_ROOM -- search_layout.h, QueryStage)
 constexpr size_t SM_OFF_BYTES = 65536;                                          // first SM_BYTE_PREFIX result bytes
 constexpr size_t SM_OFF_ENT = SM_OFF_BYTES + SM_BYTE_PREFIX;                    // entry table
 static_assert(SM_OFF_REC + 2048 * sizeof(SmallRecord) <= SM_OFF_QUERY && SM_MAX_VQ <= 2048, "records must fit below the query staging");
-static_assert(SM_OFF_QUERY + 16384 <= SM_OFF_BYTES, "query staging must fit below the result prefix");
+static_assert(SM_OFF_QUERY + 2 * SM_QUERY_ROOM <= SM_OFF_BYTES, "query staging must fit below the result prefix");
 static_assert(SM_OFF_REC + 2048 * sizeof(SmallRecord) <= SM_OFF_MAILBOX && SM_OFF_MAILBOX + sizeof(ResidentMailbox) <= SM_OFF_QUERY,
               "the mailbox sits between the records and the query staging");
 static_assert(sizeof(ResidentMailbox::query) >= SM_MAX_PLEN + 32 && offsetof(ResidentMailbox, query) % 8 == 0,
@@ -970,7 +969,7 @@ __global__ __launch_bounds__(256) void search_small_kernel(const ChunkDesc *chun
 // (a query with 245 hits: 137 -> ~45 us of device time).  Entry order inside the pair stays the
 // suffix-array order of the kept hits.
 constexpr u32 SM_BLOCK = 1024;
-constexpr u32 SM_BLOCK_MAX_VQ = 64;
+// (SM_BLOCK_MAX_VQ: search_layout.h)
 constexpr u32 SM_BLOCK_MAX_HITS = 1024;
 // ... and up to SM_SPREAD workgroups per pair: workgroup k of a pair takes hits [1024 k, 1024 (k + 1)) of its
 // interval -- one hit per thread, one round of dependent loads -- and every workgroup finds the interval
@@ -1527,7 +1526,11 @@ constexpr size_t SM_ARENA_BYTES = SM_ARENA_RHDR + 64;
 #error "search.hip is written for gfx950 (MI355X): the fused search kernels keep ~72 KiB of LDS per workgroup (160 KiB per CU there; gfx90a / gfx942 stop at 64 KiB)"
 #endif
 
-enum SSlot { Q_ORD_K0 = 50, Q_ORD_K1, Q_ORD_V0, Q_ORD_V1, Q_ORD_WORK, Q_BYTES = 10, Q_OFF, Q_LO, Q_CNT, Q_HITOFF, Q_START, Q_LEN, Q_EIDX, Q_BOFF, Q_ENTOFF, Q_OUT, Q_SMALL, Q_QCOUNT, Q_ANCHOR, Q_ARENA = 28, Q_HEAT = 46, Q_LINE_TMP = 47, Q_TERMS = 56 };
+enum SSlot { Q_ORD_K0 = 50, Q_ORD_K1, Q_ORD_V0, Q_SEED_M = Q_ORD_V0, Q_ORD_V1, Q_ORD_WORK, Q_BYTES = 10, Q_OFF, Q_LO, Q_CNT, Q_HITOFF, Q_START, Q_LEN, Q_EIDX, Q_BOFF, Q_ENTOFF, Q_OUT, Q_SMALL, Q_QCOUNT, Q_ANCHOR, Q_ARENA = 28, Q_HEAT = 46, Q_LINE_TMP = 47, Q_TERMS = 56 };
+// (Q_SEED_M: a seeded batch's match starts live in the slot of the suffix-array order's values -- that order is never a seeded batch's)
+static_assert(SEARCH_SCAN_BLOCKS == SC_MAX_BLOCKS, "search_layout.h restates the partial sums of scan.h");
+static_assert(SmallWords::MID_STATE * 8 + sizeof(MidState) <= SmallWords::BYTES, "MidState sits behind the scan's total in Q_SMALL");
+static_assert(sizeof(MidState) <= 4 * 8 && SM_OFF_FLAGS + 64 > PW_NEAR_OVERFLOW * 8, "the pinned words the pipelines read their totals from");
 
 void HostResult::release()
 {
@@ -1767,12 +1770,13 @@ __global__ __launch_bounds__(256) void chunk_hits_kernel(const u32 *cnt, u64 nq,
 // ---- host driver of one batch -------------------------------------------------------------------------------------
 // search_batch_device reads top to bottom: empty batch -> stage_queries -> run_fused? -> launch_interval -> run_mid? ->
 // pick_drivers (an all-terms or a sequence batch) | seed_drivers (a seeded batch: case-insensitive, or within k mismatches)
-// -> run_general -> finish.
-// The stages share one Batch: the request normalised into the few booleans they read, the
-// workspace every route needs, the timing events and the two outputs.
+// -> run_general (scan_hits -> candidates -> scan_kept -> counts_tail | emit_tail) -> finish.
+// The stages share one Batch: the request normalised into the few booleans, counts and route verdicts they read
+// (BatchShape of search_layout.h: nothing below asks for a mode again), the workspace every route needs, the timing
+// events and the two outputs.  Every slot that holds more than one array is carved by a layout of search_layout.h.
 namespace {
 
-struct Batch {
+struct Batch : BatchShape {
     DeviceCtx *ctx;
     hipStream_t s;
     const ChunkDesc *d_chunks;
@@ -1782,24 +1786,7 @@ struct Batch {
     pss_search_stats *st;
     const SearchKnobs &knobs;
     const u32 nq, nc;
-    const u64 nvq;                      // (query, chunk) pairs: what the interval search runs over
-    // An all-terms batch (all_terms_impl.h) has a second pair space: its nq queries are terms, its result rows are the ng
-    // groups, and everything from the first scan on runs over (group, chunk) pairs.  For every other batch the two agree.
-    const u32 nrow;                     // rows of the result: groups of an all-terms batch, else queries
-    const u64 nrp;                      // (row, chunk) pairs: what the scans, the hit kernels and the emit kernels run over
-    u64 qtotal;                         // bytes of the queries as they are searched (an anchored batch: rewritten)
-    size_t off_bytes;
-    // the request, normalised once: nothing below asks for a mode again
-    bool counts, device, ids, anchored, terms, sa_order;
-    bool seq;                           // terms, and the groups are ordered sequences (sequence_impl.h)
-    bool seqc;                          // seq, and the segments hold byte classes: the terms are their cores (seq_class_impl.h)
-    bool seeded;                        // terms looked up through seed queries: group -> terms -> queries (seed_impl.h)
-    bool near;                          // ... within k mismatches (near_impl.h); else under fold (fold_impl.h, 4.14)
-    bool edits;                         // near, and the budget counts edits: EditMatch in NearMatch's place (edit_impl.h, 4.17)
-    const u32 nterm;                    // terms of a seeded batch (else 0) ...
-    const u64 ntp;                      // ... and its (term, chunk) pairs
-    bool tiny;                          // queries and offsets fit the 16 KiB of the pinned scratch
-    bool fused_ok, resident_ok, mid_ok; // routes this batch may take (each may still overflow into the next)
+    const u64 qtotal;                   // bytes of the queries as they are searched (an anchored batch: rewritten)
     // host copy of queries, offsets and anchor flags (stage_queries)
     const u8 *h_q = nullptr, *h_flags = nullptr;
     const u64 *h_off = nullptr;
@@ -1831,33 +1818,19 @@ struct Batch {
     bool timed_route = true, timed_interval = true;     // which of them finish() reads
     std::chrono::steady_clock::time_point t_begin;
 
+    // (an anchored batch searches its rewritten queries: a newline in front of and / or behind every pattern)
     Batch(DeviceCtx *c, const ChunkDesc *chunks, const LineDesc *lines, u32 nchunks, const SearchRequest &r, HostResult *out,
           pss_search_stats *stats)
-        : ctx(c), s(c->stream), d_chunks(chunks), d_lines(lines), rq(r), res(out), st(stats), knobs(search_knobs()), nq(r.nq),
-          nc(nchunks), nvq((u64)r.nq * nchunks), nrow(r.rows()), nrp((u64)r.rows() * nchunks), nterm(r.seed_offsets ? r.nterms : 0u),
-          ntp((u64)(r.seed_offsets ? r.nterms : 0u) * nchunks), e0(c->search_ev[0]), e1(c->search_ev[1]), e2(c->search_ev[2])
+        : Batch(c, chunks, lines, nchunks, r, out, stats, search_knobs(),
+                r.anchors ? anchored_query_bytes(r.qoffsets, r.nq, r.anchors) : r.qoffsets[r.nq])
     {
-        counts = rq.mode == SEARCH_COUNTS;
-        device = rq.mode == SEARCH_DEVICE;
-        ids = rq.mode == SEARCH_IDS;
-        anchored = rq.anchors != nullptr;
-        terms = rq.group_offsets != nullptr;
-        seq = terms && rq.seq_anchors != nullptr;
-        seqc = seq && rq.class_bytes != nullptr;
-        seeded = terms && rq.seed_offsets != nullptr;
-        near = seeded && rq.near_budget != nullptr;
-        edits = near && rq.near_edits;
-        // (counts do not depend on the order; one hit per entry has one order; an all-terms batch keeps its driver's text order)
-        sa_order = rq.sa_order && !counts && !anchored && !terms;
-        // (an anchored batch searches its rewritten queries: a newline in front of and / or behind every pattern)
-        qtotal = anchored ? anchored_query_bytes(rq.qoffsets, nq, rq.anchors) : rq.qoffsets[nq];
-        off_bytes = ((size_t)nq + 1) * 8;
-        tiny = !anchored && qtotal + 32 <= 8192 && off_bytes <= 8192;
-        const bool plain = !anchored && !terms && !sa_order;    // entries that contain the pattern, in text order
-        fused_ok = plain && rq.mode == SEARCH_FULL && tiny && nvq <= SM_MAX_VQ && !knobs.no_small_path;
-        for (u32 i = 0; fused_ok && i < nq; ++i) fused_ok = rq.qoffsets[i + 1] - rq.qoffsets[i] <= SM_MAX_PLEN;
-        resident_ok = fused_ok && rq.low_latency && nq == 1 && nvq <= SM_BLOCK_MAX_VQ && !knobs.no_block_path;
-        mid_ok = plain && (rq.mode == SEARCH_FULL || device) && nvq <= MID_MAX && !knobs.no_mid_pipeline;
+    }
+    Batch(DeviceCtx *c, const ChunkDesc *chunks, const LineDesc *lines, u32 nchunks, const SearchRequest &r, HostResult *out,
+          pss_search_stats *stats, const SearchKnobs &k, u64 searched_bytes)
+        : BatchShape(r, nchunks, searched_bytes, k.no_small_path, k.no_block_path, k.no_mid_pipeline), ctx(c), s(c->stream),
+          d_chunks(chunks), d_lines(lines), rq(r), res(out), st(stats), knobs(k), nq(r.nq), nc(nchunks), qtotal(searched_bytes),
+          e0(c->search_ev[0]), e1(c->search_ev[1]), e2(c->search_ev[2])
+    {
     }
     template <typename T>
     int take(SSlot which, size_t bytes, T *&p)          // room in one slot of the device's grow-only workspace
@@ -1866,10 +1839,21 @@ struct Batch {
         p = ctx->slot[which].as<T>();
         return PSS_OK;
     }
+    // `bytes` from the host up to dst, then `zeros_behind` zero bytes behind them (what a kernel may read past the end of an array)
+    int upload(void *dst, const void *src, size_t bytes, size_t zeros_behind = 0)
+    {
+        if (bytes) PSS_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
+        if (zeros_behind) PSS_HIP(hipMemsetAsync(static_cast<u8 *>(dst) + bytes, 0, zeros_behind, s));
+        return PSS_OK;
+    }
     int stage_queries(), run_fused(bool *served), launch_interval(), run_mid(bool *done), pick_drivers(), seed_drivers(), run_general(), finish();
+    // the stages of run_general: hits -> candidates -> kept hits -> counts | emit
+    int scan_hits(u64 *H), no_hits(), candidates(u64 H, u32 grid), scan_kept(u64 H), counts_tail(u64 H), emit_tail(u64 H, u32 grid);
+    template <bool Fold>
+    void verify(u32 vgrid, u64 H, const u8 *bytes, const u64 *off, const u32 *tcnt);
     int sa_order_hits(u32 grid, u64 H);
-    size_t anchor_room() const;
-    int upload_anchors();
+    ClassBlock class_block() const;
+    int upload_anchors(u8 *at, const ClassBlock &L);
     int download_result(u64 E, u64 B, const u64 *d_starts, const u8 *d_bytes, bool via_stage);
     void leave_on_device(const u64 *d_starts, const u8 *d_bytes), set_totals(u64 hits, u64 kept, u64 E, u64 B);
 };
@@ -1900,44 +1884,46 @@ int empty_batch(DeviceCtx *ctx, const SearchRequest &rq, HostResult *res)
 // into vectors of the batch.
 int Batch::stage_queries()
 {
-    PSS_TRY(take(Q_BYTES, qtotal + 32, d_q));
+    PSS_TRY(take(Q_BYTES, qtotal + SEARCH_PAD, d_q));
     PSS_TRY(take(Q_OFF, off_bytes, d_qoff));
     PSS_TRY(take(Q_LO, nvq * 4, d_lo));
     PSS_TRY(take(Q_CNT, nvq * 4, d_cnt));
     PSS_TRY(take(Q_HITOFF, (std::max(nvq, nrp) + 1) * 8, d_hitoff));
-    PSS_TRY(take(Q_SMALL, SC_MAX_BLOCKS * 8 + 256, d_partial));          // scan partials, totals, MidState
+    PSS_TRY(take(Q_SMALL, SmallWords::BYTES, d_partial));          // scan partials, totals, MidState
     PSS_TRY(take(Q_QCOUNT, (size_t)std::max(nq, nrow) * 8, d_qcount));
-    d_total = d_partial + SC_MAX_BLOCKS;
+    d_total = d_partial + SmallWords::TOTAL;
     p_lo = d_lo;
     p_cnt = d_cnt;
     h_small = static_cast<u64 *>(ctx->pinned);
     t_begin = std::chrono::steady_clock::now();
-    const size_t q_room = round_up(qtotal + 32, 64), o_room = round_up(off_bytes, 64);
-    const size_t staged = anchored ? q_room + o_room + nq : qtotal + 32 + off_bytes + 64;
+    const QueryStage Q(anchored, nq, qtotal, off_bytes);
     u8 *hq = nullptr, *hf = nullptr;
     u64 *ho = nullptr;
     if (tiny) {
-        hq = static_cast<u8 *>(ctx->pinned) + SM_OFF_QUERY;
-        ho = reinterpret_cast<u64 *>(hq + 8192);
-    } else if (staged <= DeviceCtx::kStageQ && !knobs.no_search_stage) {
+        u8 *pinned = static_cast<u8 *>(ctx->pinned);
+        hq = pinned + QueryStage::TINY_Q;
+        ho = reinterpret_cast<u64 *>(pinned + QueryStage::TINY_OFF);
+    } else if (Q.fits() && !knobs.no_search_stage) {
         PSS_TRY(ctx->ensure_search_stage());
-        hq = static_cast<u8 *>(ctx->search_stage);
-        ho = reinterpret_cast<u64 *>(hq + q_room);
-        hf = hq + q_room + o_room;
+        u8 *stage = static_cast<u8 *>(ctx->search_stage);
+        hq = stage + Q.q;
+        ho = reinterpret_cast<u64 *>(stage + Q.off);
+        hf = stage + Q.flags;
     } else if (anchored) {
-        own_q.resize(q_room + nq);
+        own_q.resize(Q.own_bytes);
         own_off.resize((size_t)nq + 1);
         hq = own_q.data();
         ho = own_off.data();
-        hf = hq + q_room;
+        hf = hq + Q.own_flags;
     }
     if (anchored) {
-        PSS_TRY(take(Q_ANCHOR, round_up((size_t)nq, 64) + nvq, d_aflags));         // flags per query, chunk-edge hits per pair
-        d_edge = d_aflags + round_up((size_t)nq, 64);
+        const AnchorFlags A(nq, nvq);               // flags per query, chunk-edge hits per pair
+        PSS_TRY(take(Q_ANCHOR, A.end, d_aflags));
+        d_edge = d_aflags + A.edge;
         anchored_rewrite(rq.qbytes, rq.qoffsets, nq, rq.anchors, hq, ho, hf);
     } else if (hq) {
         memcpy(hq, rq.qbytes, qtotal);
-        memset(hq + qtotal, 0, 32);
+        memset(hq + qtotal, 0, SEARCH_PAD);
         memcpy(ho, rq.qoffsets, off_bytes);
     }
     h_q = hq ? hq : rq.qbytes;
@@ -1987,8 +1973,8 @@ int Batch::run_fused(bool *served)
     // microseconds of host time and two marker packets, so it only takes them when asked: PSS_SEARCH_EVENTS=1)
     const bool timed = knobs.small_path_events;
     if (timed) PSS_HIP(hipEventRecord(e0, s));
-    const u8 *v_q = v_arena + SM_OFF_QUERY;
-    const u64 *v_qoff = reinterpret_cast<const u64 *>(v_arena + SM_OFF_QUERY + 8192);
+    const u8 *v_q = v_arena + QueryStage::TINY_Q;
+    const u64 *v_qoff = reinterpret_cast<const u64 *>(v_arena + QueryStage::TINY_OFF);
     u32 *v_flags = reinterpret_cast<u32 *>(v_arena + SM_OFF_FLAGS);
     SmallRecord *v_rec = reinterpret_cast<SmallRecord *>(v_arena + SM_OFF_REC);
     SmallEntry *v_ent = reinterpret_cast<SmallEntry *>(v_arena + SM_OFF_ENT);
@@ -2083,12 +2069,14 @@ int Batch::download_result(u64 E, u64 B, const u64 *d_starts, const u8 *d_bytes,
     const size_t cnt_bytes = (size_t)nrow * 8;
     PSS_TRY(alloc_host_result(res, E, B, !via_stage && !knobs.no_pinned_results));
     u8 *to_off = reinterpret_cast<u8 *>(res->offsets), *to_bytes = res->bytes, *to_cnt = reinterpret_cast<u8 *>(res->qcount);
-    const bool staged = via_stage && round_up(E * 8, 64) + round_up(B, 64) + cnt_bytes <= DeviceCtx::kStageR && !knobs.no_search_stage;
+    const ResultStage R(E, B, nrow);
+    const bool staged = via_stage && R.fits() && !knobs.no_search_stage;
     if (staged) {
         PSS_TRY(ctx->ensure_search_stage());
-        to_off = static_cast<u8 *>(ctx->search_stage) + DeviceCtx::kStageQ;
-        to_bytes = to_off + round_up(E * 8, 64);
-        to_cnt = to_bytes + round_up(B, 64);
+        u8 *stage = static_cast<u8 *>(ctx->search_stage) + DeviceCtx::kStageQ;
+        to_off = stage + R.offsets;
+        to_bytes = stage + R.bytes;
+        to_cnt = stage + R.counts;
     }
     if (E) PSS_HIP(hipMemcpyAsync(to_off, d_starts, E * 8, hipMemcpyDeviceToHost, s));
     if (B) PSS_HIP(hipMemcpyAsync(to_bytes, d_bytes, B, hipMemcpyDeviceToHost, s));
@@ -2125,7 +2113,7 @@ int Batch::run_mid(bool *done)
     PSS_TRY(take(Q_BOFF, ((size_t)MID_MAX + 1) * 8, d_boff));
     PSS_TRY(take(Q_ENTOFF, ((size_t)MID_MAX + 1) * 8, d_entoff));
     PSS_TRY(take(Q_OUT, byte_cap + 16, d_out));
-    MidState *d_ms = reinterpret_cast<MidState *>(d_total + 8);       // behind the scan partials
+    MidState *d_ms = reinterpret_cast<MidState *>(d_partial + SmallWords::MID_STATE);       // behind the scan partials and their total
     const u32 grid = (u32)ctx->num_cus * 4;
     hipLaunchKernelGGL(mid_hitoff_kernel, dim3(1), dim3(MID_BLOCK), 0, s, d_cnt, (u32)nvq, d_hitoff, d_ms);
     hipLaunchKernelGGL(hit_lines_kernel<false>, dim3(grid), dim3(256), 0, s, d_chunks, nc, d_q, d_qoff, nvq, d_lo, d_hitoff,
@@ -2180,43 +2168,28 @@ int Batch::sa_order_hits(u32 grid, u64 H)
     return PSS_OK;
 }
 
-// What a sequence batch keeps behind its term flags in the Q_TERMS slot, in multiples of 64 bytes: one anchor byte per group
-// and, for a class batch, the segments as seqc_verify_kernel reads them (SeqClass) -- offsets, the groups' offsets, the
-// cores, the sets, then bytes and plane, each with 32 zero bytes behind it (entry_scan reads a core up to 16 bytes past its
-// end).  anchor_room() sizes the stretch for pick_drivers' and seed_drivers' layouts alike; upload_anchors() fills it from
-// d_sanch on.
-size_t Batch::anchor_room() const
+// What a sequence batch keeps behind its term flags in the Q_TERMS slot (ClassBlock of search_layout.h): class_block()
+// sizes the stretch for pick_drivers' and seed_drivers' layouts alike; upload_anchors() fills it from the anchor bytes on.
+ClassBlock Batch::class_block() const
 {
-    if (!seq) return 0;
-    size_t room = round_up((size_t)nrow, 64);
-    if (seqc) {
-        const size_t ns = rq.class_nsegs, total = rq.class_offsets[ns];
-        room += round_up((ns + 1) * 8, 64) + round_up(((size_t)nrow + 1) * 8, 64) + round_up(ns * 8, 64) +
-                round_up((size_t)rq.class_nsets * 32, 64) + 2 * round_up(total + 32, 64);
-    }
-    return room;
+    return ClassBlock(seq, seqc, nrow, rq.class_nsegs, seqc ? rq.class_offsets[rq.class_nsegs] : 0, rq.class_nsets);
 }
 
-int Batch::upload_anchors()
+int Batch::upload_anchors(u8 *at, const ClassBlock &L)
 {
+    d_sanch = at;
     if (!seq) return PSS_OK;
-    PSS_HIP(hipMemcpyAsync(d_sanch, rq.seq_anchors, nrow, hipMemcpyHostToDevice, s));
+    PSS_TRY(upload(at + L.anchors, rq.seq_anchors, nrow));
     if (!seqc) return PSS_OK;
     const size_t ns = rq.class_nsegs, total = rq.class_offsets[ns];
-    u8 *p = d_sanch + round_up((size_t)nrow, 64);
-    u8 *at[6];
-    const void *src[6] = {rq.class_offsets, rq.class_groups, rq.class_cores, rq.class_sets, rq.class_bytes, rq.class_plane};
-    const size_t len[6] = {(ns + 1) * 8, ((size_t)nrow + 1) * 8, ns * 8, (size_t)rq.class_nsets * 32, total, total};
-    for (int k = 0; k < 6; ++k) {
-        const size_t zeros = k >= 4 ? 32 : 0;                    // (behind the bytes and behind the plane)
-        at[k] = p;
-        if (len[k]) PSS_HIP(hipMemcpyAsync(p, src[k], len[k], hipMemcpyHostToDevice, s));
-        if (zeros) PSS_HIP(hipMemsetAsync(p + len[k], 0, zeros, s));
-        p += round_up(len[k] + zeros, 64);
-    }
-    u8 *off = at[0], *goff = at[1], *core = at[2], *sets = at[3], *bytes = at[4], *plane = at[5];
-    d_sc = SeqClass{bytes, plane, reinterpret_cast<const u64 *>(off), reinterpret_cast<const u64 *>(goff),
-                    reinterpret_cast<const u32 *>(core), reinterpret_cast<const u32 *>(sets)};
+    PSS_TRY(upload(at + L.seg_off, rq.class_offsets, (ns + 1) * 8));
+    PSS_TRY(upload(at + L.seg_goff, rq.class_groups, ((size_t)nrow + 1) * 8));
+    PSS_TRY(upload(at + L.cores, rq.class_cores, ns * 8));
+    PSS_TRY(upload(at + L.sets, rq.class_sets, (size_t)rq.class_nsets * 32));
+    PSS_TRY(upload(at + L.bytes, rq.class_bytes, total, SEARCH_PAD));
+    PSS_TRY(upload(at + L.plane, rq.class_plane, total, SEARCH_PAD));
+    d_sc = SeqClass{at + L.bytes, at + L.plane, reinterpret_cast<const u64 *>(at + L.seg_off), reinterpret_cast<const u64 *>(at + L.seg_goff),
+                    reinterpret_cast<const u32 *>(at + L.cores), reinterpret_cast<const u32 *>(at + L.sets)};
     return PSS_OK;
 }
 
@@ -2224,70 +2197,63 @@ int Batch::upload_anchors()
 // chunk) pair picks the pair's driver term; from here on the pipeline runs over the drivers' intervals.
 int Batch::pick_drivers()
 {
-    const size_t goff_room = round_up(((size_t)nrow + 1) * 8, 64), flag_room = round_up((size_t)nq, 64);
-    const size_t anch_room = anchor_room();        // (a sequence batch: one anchor byte per group; a class batch: its segments too)
-    PSS_TRY(take(Q_TERMS, goff_room + flag_room + anch_room + nrp * 12, d_goff));
-    d_tflags = reinterpret_cast<u8 *>(d_goff) + goff_room;
-    d_sanch = d_tflags + flag_room;
-    d_gdrv = reinterpret_cast<u32 *>(d_sanch + anch_room);
-    p_lo = d_gdrv + nrp;
-    p_cnt = p_lo + nrp;
-    PSS_HIP(hipMemcpyAsync(d_goff, rq.group_offsets, ((size_t)nrow + 1) * 8, hipMemcpyHostToDevice, s));
-    PSS_HIP(hipMemcpyAsync(d_tflags, own_tflags.data(), nq, hipMemcpyHostToDevice, s));
-    PSS_TRY(upload_anchors());
+    const TermsLayout L(nrow, nq, nrp, class_block());
+    u8 *base;
+    PSS_TRY(take(Q_TERMS, L.end, base));
+    d_goff = reinterpret_cast<u64 *>(base + L.goff);
+    d_tflags = base + L.tflags;
+    d_gdrv = reinterpret_cast<u32 *>(base + L.gdrv);
+    p_lo = reinterpret_cast<u32 *>(base + L.lo);
+    p_cnt = reinterpret_cast<u32 *>(base + L.cnt);
+    PSS_TRY(upload(d_goff, rq.group_offsets, ((size_t)nrow + 1) * 8));
+    PSS_TRY(upload(d_tflags, own_tflags.data(), nq));
+    PSS_TRY(upload_anchors(base + L.anchors, L.cls));
     hipLaunchKernelGGL(terms_driver_kernel<true>, dim3((u32)((nrp + 255) / 256)), dim3(256), 0, s, nc, d_goff, d_tflags, d_lo, d_cnt, nrp,
                        d_gdrv, p_lo, p_cnt);
     return PSS_OK;
 }
 
 // Seeded batch: from the (query, chunk) pairs over the (term, chunk) pairs to the (group, chunk) pairs.  The terms go up
-// beside their seed queries -- the queries' offsets per term, the terms' bytes (32 zero bytes behind them, as behind the
-// staged queries) and offsets, every query's position inside its term, void flags -- and with them what pick_drivers sends
-// up: group offsets, term flags, anchor bytes.  The anchor bytes have room in a sequence batch alone; the budgets and the
-// overflow flag in a near batch alone.  seed_union_kernel leaves every term's seed hits per chunk in d_tcnt;
-// terms_driver_kernel picks the include term with the fewest of them as the pair's driver.  Neither a term nor a pair has
-// an interval of its own (p_lo is not read).  A near pair past 2^32 - 1 hits raises d_over, whose copy run_general reads
-// with the hit total, before any hit buffer is reserved; a fold batch passes no flag (disjoint intervals: the sum is at
-// most n) and so neither clears nor fetches one.
+// beside their seed queries, and with them what pick_drivers sends up (SeedLayout of search_layout.h).  seed_union_kernel
+// leaves every term's seed hits per chunk in d_tcnt; terms_driver_kernel picks the include term with the fewest of them as
+// the pair's driver.  Neither a term nor a pair has an interval of its own (p_lo is not read).  A near pair past 2^32 - 1
+// hits raises d_over, whose copy (PW_NEAR_OVERFLOW) scan_hits reads with the hit total, before any hit buffer is
+// reserved; a fold batch passes no flag (disjoint intervals: the sum is at most n) and so neither clears nor fetches one.
 int Batch::seed_drivers()
 {
     const u64 ttotal = rq.term_offsets[nterm];
-    const size_t goff_room = round_up(((size_t)nrow + 1) * 8, 64), toff_room = round_up(((size_t)nterm + 1) * 8, 64);
-    const size_t over_room = near ? 64 : 0, pos_room = round_up((size_t)nq * 4, 64), flag_room = round_up((size_t)nterm, 64);
-    const size_t budget_room = near ? flag_room : 0, anch_room = anchor_room();
-    const size_t byte_room = round_up(ttotal + 32, 64), tcnt_room = round_up((size_t)ntp * 4, 64);
-    PSS_TRY(take(Q_TERMS, goff_room + 2 * toff_room + over_room + pos_room + 2 * flag_room + budget_room + anch_room + byte_room +
-                              tcnt_room + nrp * 8, d_goff));
-    d_soff = d_goff + goff_room / 8;
-    d_foff = d_soff + toff_room / 8;
-    u8 *p = reinterpret_cast<u8 *>(d_foff + toff_room / 8);
-    d_over = near ? reinterpret_cast<u64 *>(p) : nullptr;
-    d_pos = reinterpret_cast<u32 *>(p += over_room);
-    d_fvoid = (p += pos_room);
-    d_tflags = (p += flag_room);
-    d_nk = near ? p + flag_room : nullptr;
-    d_sanch = (p += flag_room + budget_room);
-    d_fbytes = (p += anch_room);
-    d_tcnt = reinterpret_cast<u32 *>(p += byte_room);
-    d_gdrv = reinterpret_cast<u32 *>(p + tcnt_room);
-    p_cnt = d_gdrv + nrp;
-    PSS_HIP(hipMemcpyAsync(d_goff, rq.group_offsets, ((size_t)nrow + 1) * 8, hipMemcpyHostToDevice, s));
-    PSS_HIP(hipMemcpyAsync(d_soff, rq.seed_offsets, ((size_t)nterm + 1) * 8, hipMemcpyHostToDevice, s));
-    PSS_HIP(hipMemcpyAsync(d_foff, rq.term_offsets, ((size_t)nterm + 1) * 8, hipMemcpyHostToDevice, s));
-    PSS_HIP(hipMemcpyAsync(d_pos, rq.seed_pos, (size_t)nq * 4, hipMemcpyHostToDevice, s));
-    PSS_HIP(hipMemcpyAsync(d_fvoid, own_fvoid.data(), nterm, hipMemcpyHostToDevice, s));
-    PSS_HIP(hipMemcpyAsync(d_tflags, own_tflags.data(), nterm, hipMemcpyHostToDevice, s));
-    PSS_TRY(upload_anchors());
+    const SeedLayout L(nrow, nterm, nq, ttotal, ntp, nrp, near, class_block());
+    u8 *base;
+    PSS_TRY(take(Q_TERMS, L.end, base));
+    d_goff = reinterpret_cast<u64 *>(base + L.goff);
+    d_soff = reinterpret_cast<u64 *>(base + L.soff);
+    d_foff = reinterpret_cast<u64 *>(base + L.foff);
+    d_over = near ? reinterpret_cast<u64 *>(base + L.over) : nullptr;
+    d_pos = reinterpret_cast<u32 *>(base + L.pos);
+    d_fvoid = base + L.fvoid;
+    d_tflags = base + L.tflags;
+    d_nk = near ? base + L.budget : nullptr;
+    d_fbytes = base + L.fbytes;
+    d_tcnt = reinterpret_cast<u32 *>(base + L.tcnt);
+    d_gdrv = reinterpret_cast<u32 *>(base + L.gdrv);
+    p_cnt = reinterpret_cast<u32 *>(base + L.cnt);
+    PSS_TRY(upload(d_goff, rq.group_offsets, ((size_t)nrow + 1) * 8));
+    PSS_TRY(upload(d_soff, rq.seed_offsets, ((size_t)nterm + 1) * 8));
+    PSS_TRY(upload(d_foff, rq.term_offsets, ((size_t)nterm + 1) * 8));
+    PSS_TRY(upload(d_pos, rq.seed_pos, (size_t)nq * 4));
+    PSS_TRY(upload(d_fvoid, own_fvoid.data(), nterm));
+    PSS_TRY(upload(d_tflags, own_tflags.data(), nterm));
+    PSS_TRY(upload_anchors(base + L.anchors, L.cls));
     if (near) {
-        PSS_HIP(hipMemcpyAsync(d_nk, rq.near_budget, nterm, hipMemcpyHostToDevice, s));
+        PSS_TRY(upload(d_nk, rq.near_budget, nterm));
         PSS_HIP(hipMemsetAsync(d_over, 0, 8, s));
     }
-    PSS_HIP(hipMemsetAsync(d_fbytes + ttotal, 0, 32, s));
-    PSS_HIP(hipMemcpyAsync(d_fbytes, rq.term_bytes, ttotal, hipMemcpyHostToDevice, s));
+    PSS_HIP(hipMemsetAsync(d_fbytes + ttotal, 0, SEARCH_PAD, s));
+    PSS_TRY(upload(d_fbytes, rq.term_bytes, ttotal));
     hipLaunchKernelGGL(seed_union_kernel, dim3((u32)((ntp + 255) / 256)), dim3(256), 0, s, nc, d_soff, d_fvoid, d_cnt, ntp, d_tcnt, d_over);
     hipLaunchKernelGGL(terms_driver_kernel<false>, dim3((u32)((nrp + 255) / 256)), dim3(256), 0, s, nc, d_goff, d_tflags,
                        (const u32 *)nullptr, d_tcnt, nrp, d_gdrv, (u32 *)nullptr, p_cnt);
-    if (near) PSS_HIP(hipMemcpyAsync(h_small + 2, d_over, 8, hipMemcpyDeviceToHost, s));
+    if (near) PSS_HIP(hipMemcpyAsync(h_small + PW_NEAR_OVERFLOW, d_over, 8, hipMemcpyDeviceToHost, s));
     return PSS_OK;
 }
 
@@ -2297,33 +2263,72 @@ int Batch::run_general()
 {
     st->route |= PSS_ROUTE_GENERAL | (sa_order ? PSS_ROUTE_SA_ORDER : 0u) | (counts ? PSS_ROUTE_COUNTS : 0u) |
                    (anchored ? PSS_ROUTE_ANCHORED : 0u);
+    u64 H;
+    PSS_TRY(scan_hits(&H));
+    if (H == 0) return no_hits();
+    const u32 grid = (u32)std::min<u64>((u64)ctx->num_cus * 16, (H + 255) / 256);
+    PSS_TRY(candidates(H, grid));
+    PSS_TRY(scan_kept(H));
+    return counts ? counts_tail(H) : emit_tail(H, grid);
+}
+
+// The hits of every pair scanned into d_hitoff, and their total.
+int Batch::scan_hits(u64 *H)
+{
     PSS_TRY(device_excl_scan(ctx, InU32{p_cnt}, nrp, d_partial, d_total, d_hitoff));
-    PSS_HIP(hipMemcpyAsync(h_small, d_total, 8, hipMemcpyDeviceToHost, s));
+    PSS_HIP(hipMemcpyAsync(h_small + PW_COUNT, d_total, 8, hipMemcpyDeviceToHost, s));
     PSS_HIP(hipStreamSynchronize(s));
-    const u64 H = h_small[0];
-    if (near && h_small[2]) {   // (seed_union_kernel's flag: the one place a pair's 64-bit sum is judged, out of a test's reach and
-                                // checked by reading; nothing is reserved yet)
+    *H = h_small[PW_COUNT];
+    if (near && h_small[PW_NEAR_OVERFLOW]) {   // (seed_union_kernel's flag, fetched by seed_drivers: the one place a pair's 64-bit sum
+                                               // is judged, out of a test's reach and checked by reading; nothing is reserved yet)
         set_error("search: the pieces of one pattern have more than 2^32 - 1 hits in one chunk: more than a batch within k %s takes",
                   edits ? "edits" : "mismatches");
         return PSS_EINVAL;
     }
-    if (H == 0) {
-        PSS_HIP(hipEventRecord(e2, s));
-        if (device) {
-            PSS_HIP(hipMemsetAsync(d_qcount, 0, (size_t)nrow * 8, s));
-            leave_on_device(nullptr, nullptr);
-        }
-        PSS_HIP(hipStreamSynchronize(s));
-        if (!device) PSS_TRY(empty_offsets(res));
-        set_totals(0, 0, 0, 0);
-        return PSS_OK;
+    return PSS_OK;
+}
+
+// No hit at all: zero counts, no entries.
+int Batch::no_hits()
+{
+    PSS_HIP(hipEventRecord(e2, s));
+    if (device) {
+        PSS_HIP(hipMemsetAsync(d_qcount, 0, (size_t)nrow * 8, s));
+        leave_on_device(nullptr, nullptr);
     }
+    PSS_HIP(hipStreamSynchronize(s));
+    if (!device) PSS_TRY(empty_offsets(res));
+    set_totals(0, 0, 0, 0);
+    return PSS_OK;
+}
+
+// Every candidate of a group batch against the group's other terms, or its segments in order: a class batch (the terms
+// are the segments' cores, every segment is placed by its own core), a sequence batch (every candidate against the
+// group's segments in order, the driver among them), an all-terms batch.  bytes / off: the terms as they are verified;
+// tcnt: the hits per (term, chunk) pair.
+template <bool Fold>
+void Batch::verify(u32 vgrid, u64 H, const u8 *bytes, const u64 *off, const u32 *tcnt)
+{
+    if (seqc)
+        hipLaunchKernelGGL(seqc_verify_kernel<Fold>, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, d_sc, d_sanch, nrp, d_hitoff, H, d_start,
+                           d_len);
+    else if (seq)
+        hipLaunchKernelGGL(seq_verify_kernel<Fold>, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, bytes, off, d_goff, d_sanch, nrp, d_hitoff,
+                           H, d_start, d_len);
+    else if (!Fold || nterm != nrow)    // (seeded: every group has an include term -- as many terms as groups are one per group, and
+                                        // no other to look for; a near batch is no sequence and has one term per group)
+        hipLaunchKernelGGL(terms_verify_kernel<Fold>, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, bytes, off, d_goff, d_tflags, tcnt,
+                           d_gdrv, nrp, d_hitoff, H, d_start, d_len);
+}
+
+// The entry of every hit; a hit whose entry another hit of the pair stands for is marked in d_len and dropped by the scans.
+int Batch::candidates(u64 H, u32 grid)
+{
     PSS_TRY(take(Q_START, H * 4, d_start));
     PSS_TRY(take(Q_LEN, H * 4, d_len));
     PSS_TRY(take(Q_EIDX, (H + 1) * 8, d_eidx));
     PSS_TRY(take(Q_BOFF, (H + 1) * 8, d_boff));
-    const u32 grid = (u32)std::min<u64>((u64)ctx->num_cus * 16, (H + 255) / 256);
-    // the entry of every hit; a hit whose entry another hit of the pair stands for is marked in d_len and dropped by the scans
+    const u32 vgrid = (u32)std::min<u64>((u64)ctx->num_cus * 16, (H * TG + 255) / 256);
     if (sa_order)
         PSS_TRY(sa_order_hits(grid, H));
     else if (anchored)
@@ -2333,60 +2338,54 @@ int Batch::run_general()
         // every hit of every seed query against the whole driver term at its match start (under fold, or within the budget inside
         // its entry and as its alignment's first exact piece; under edits: the piece's two sides within the budget); then the
         // survivors against the entry in front of them: one candidate per entry, its leftmost match
-        PSS_TRY(take(Q_ORD_V0, H * 4, d_m));        // (the slot of the suffix-array order's values: that order is never a seeded batch's)
-        const u32 vgrid = (u32)std::min<u64>((u64)ctx->num_cus * 16, (H * TG + 255) / 256);
+        PSS_TRY(take(Q_SEED_M, H * 4, d_m));
         const SeedTerms T{d_fbytes, d_foff, d_soff, d_pos, d_nk};
         auto *hits = edits ? seed_hits_kernel<EditMatch> : near ? seed_hits_kernel<NearMatch> : seed_hits_kernel<FoldMatch>;
         auto *dedupe = edits ? seed_dedupe_kernel<EditMatch> : near ? seed_dedupe_kernel<NearMatch> : seed_dedupe_kernel<FoldMatch>;
         hipLaunchKernelGGL(hits, dim3(grid), dim3(256), 0, s, d_chunks, nc, T, d_lo, d_cnt, nrp, d_hitoff, H, d_start, d_len, d_m, d_gdrv);
         hipLaunchKernelGGL(dedupe, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, T, nrp, d_hitoff, H, d_start, d_m, d_len, d_gdrv);
-        // (every candidate against the group's other terms, or its segments in order: under fold alone -- a near batch is no
-        // sequence and has one term per group)
-        if (seqc)   // (a class batch under fold: the candidates hold the driving core; every segment is placed by its own core)
-            hipLaunchKernelGGL(seqc_verify_kernel<true>, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, d_sc, d_sanch, nrp, d_hitoff, H, d_start,
-                               d_len);
-        else if (seq)
-            hipLaunchKernelGGL(seq_verify_kernel<true>, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, d_fbytes, d_foff, d_goff, d_sanch,
-                               nrp, d_hitoff, H, d_start, d_len);
-        else if (nterm != nrow)     // (every group has an include term: as many terms as groups are one per group, and no other to look for)
-            hipLaunchKernelGGL(terms_verify_kernel<true>, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, d_fbytes, d_foff, d_goff,
-                               d_tflags, d_tcnt, d_gdrv, nrp, d_hitoff, H, d_start, d_len);
+        verify<true>(vgrid, H, d_fbytes, d_foff, d_tcnt);
     } else if (terms) {
-        // candidates: the entries that hold the pair's driver term; then every candidate against the group's other terms
+        // candidates: the entries that hold the pair's driver term
         hipLaunchKernelGGL(hit_lines_kernel<true>, dim3(grid), dim3(256), 0, s, d_chunks, nc, d_q, d_qoff, nrp, p_lo, d_hitoff, H,
                            (const MidState *)nullptr, d_start, d_len, d_gdrv);
-        const u32 vgrid = (u32)std::min<u64>((u64)ctx->num_cus * 16, (H * TG + 255) / 256);
-        if (seqc)   // (a class batch: the terms are the segments' cores; every candidate against the segments themselves, in order)
-            hipLaunchKernelGGL(seqc_verify_kernel<false>, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, d_sc, d_sanch, nrp, d_hitoff, H, d_start,
-                               d_len);
-        else if (seq)    // (a sequence batch: every candidate against the group's segments in order, the driver among them)
-            hipLaunchKernelGGL(seq_verify_kernel<false>, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, d_q, d_qoff, d_goff, d_sanch, nrp,
-                               d_hitoff, H, d_start, d_len);
-        else
-            hipLaunchKernelGGL(terms_verify_kernel<false>, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, d_q, d_qoff, d_goff, d_tflags, d_cnt,
-                               d_gdrv, nrp, d_hitoff, H, d_start, d_len);
+        verify<false>(vgrid, H, d_q, d_qoff, d_cnt);
     } else
         hipLaunchKernelGGL(hit_lines_kernel<false>, dim3(grid), dim3(256), 0, s, d_chunks, nc, d_q, d_qoff, nrp, p_lo,
                            d_hitoff, H, (const MidState *)nullptr, d_start, d_len, (const u32 *)nullptr);
+    return PSS_OK;
+}
+
+// The kept hits scanned into d_eidx; their total is on its way to PW_COUNT.
+int Batch::scan_kept(u64 H)
+{
     PSS_TRY(device_excl_scan(ctx, InKept{d_len}, H, d_partial, d_total, d_eidx));
-    PSS_HIP(hipMemcpyAsync(h_small, d_total, 8, hipMemcpyDeviceToHost, s));
-    if (counts) {
-        // entries per query without materialising one: interval search, dedupe flags, two scans
-        hipLaunchKernelGGL(query_counts_kernel, dim3((nrow + 255) / 256), dim3(256), 0, s, nc, nrow, d_hitoff, d_eidx,
-                           d_qcount, (const MidState *)nullptr);
-        PSS_HIP(hipEventRecord(e2, s));
-        PSS_HIP(hipMemcpyAsync(res->qcount, d_qcount, (size_t)nrow * 8, hipMemcpyDeviceToHost, s));
-        PSS_HIP(hipStreamSynchronize(s));
-        PSS_TRY(empty_offsets(res));
-        set_totals(H, h_small[0], 0, 0);
-        return PSS_OK;
-    }
+    PSS_HIP(hipMemcpyAsync(h_small + PW_COUNT, d_total, 8, hipMemcpyDeviceToHost, s));
+    return PSS_OK;
+}
+
+// Entries per query without materialising one: interval search, dedupe flags, two scans.
+int Batch::counts_tail(u64 H)
+{
+    hipLaunchKernelGGL(query_counts_kernel, dim3((nrow + 255) / 256), dim3(256), 0, s, nc, nrow, d_hitoff, d_eidx,
+                       d_qcount, (const MidState *)nullptr);
+    PSS_HIP(hipEventRecord(e2, s));
+    PSS_HIP(hipMemcpyAsync(res->qcount, d_qcount, (size_t)nrow * 8, hipMemcpyDeviceToHost, s));
+    PSS_HIP(hipStreamSynchronize(s));
+    PSS_TRY(empty_offsets(res));
+    set_totals(H, h_small[PW_COUNT], 0, 0);
+    return PSS_OK;
+}
+
+// The bytes scanned, the result sized by entries and bytes, every kept hit's entry (or its id) and the counts per row.
+int Batch::emit_tail(u64 H, u32 grid)
+{
     if (!ids) {         // (ids: one per kept hit, 8 bytes each -- no byte scan, the entry count alone sizes the result)
         PSS_TRY(device_excl_scan(ctx, InLen{d_len}, H, d_partial, d_total, d_boff));
-        PSS_HIP(hipMemcpyAsync(h_small + 1, d_total, 8, hipMemcpyDeviceToHost, s));
+        PSS_HIP(hipMemcpyAsync(h_small + PW_BYTES, d_total, 8, hipMemcpyDeviceToHost, s));
     }
     PSS_HIP(hipStreamSynchronize(s));
-    const u64 E = h_small[0], B = ids ? E * 8 : h_small[1];
+    const u64 E = h_small[PW_COUNT], B = ids ? E * 8 : h_small[PW_BYTES];
     PSS_TRY(take(Q_ENTOFF, (E + 1) * 8, d_entoff));
     PSS_TRY(take(Q_OUT, B + 16, d_out));
     if (ids)
@@ -2432,49 +2431,22 @@ int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, const LineDes
 {
     if (rq.chunk_hits)
         for (u32 c = 0; c < nc; ++c) rq.chunk_hits[c] = 0;
-    if (rq.mode == SEARCH_IDS && nc && !d_lines) {
-        set_error("search: the ids mode needs the chunks' line tables");
-        return PSS_EINVAL;
-    }
-    if (rq.anchors && (rq.mode == SEARCH_DEVICE || rq.low_latency)) {
-        set_error("search: an anchored batch takes the general pipeline to a host result");
-        return PSS_EINVAL;
-    }
-    if (rq.group_offsets && (rq.anchors || (rq.nq && !rq.exclude && !rq.seq_anchors) || rq.mode == SEARCH_DEVICE || rq.low_latency)) {
+    switch (check_request(rq, nc, d_lines != nullptr)) {       // (the rules: search_layout.h)
+    case REQUEST_OK: break;
+    case REQUEST_IDS_WITHOUT_LINES: set_error("search: the ids mode needs the chunks' line tables"); return PSS_EINVAL;
+    case REQUEST_ANCHORED: set_error("search: an anchored batch takes the general pipeline to a host result"); return PSS_EINVAL;
+    case REQUEST_ALL_TERMS:
         set_error("search: an all-terms batch takes the general pipeline to a host result, and its terms are not anchored");
         return PSS_EINVAL;
-    }
-    if (rq.seed_offsets || rq.seed_pos || rq.near_budget || rq.near_edits) {
-        // a seeded batch carries its groups, its terms and the queries' offsets and positions, and either exclude flags or
-        // sequence anchors; it excludes anchors, SEARCH_DEVICE and low_latency; a budget adds: identity groups of one include
-        // term each, no sequence anchors; near_edits says how a budget is counted and is legal with one alone
-        bool ok = rq.seed_offsets && rq.seed_pos && rq.group_offsets && rq.term_bytes && rq.term_offsets &&
-                  (!rq.nterms || rq.exclude || rq.seq_anchors) && !rq.anchors && rq.mode != SEARCH_DEVICE && !rq.low_latency;
-        ok = ok && (rq.near_budget || !rq.near_edits);
-        if (rq.near_budget) {
-            ok = ok && !rq.seq_anchors && rq.exclude && rq.ngroups == rq.nterms;
-            for (u32 g = 0; ok && g < rq.ngroups; ++g) ok = rq.group_offsets[g] == g && rq.group_offsets[g + 1] == (u64)g + 1;
-        }
-        if (!ok) {
-            set_error("search: a seeded batch states its groups, its terms' bytes and offsets, the seed queries' offsets and positions, "
-                      "and either exclude flags or sequence anchors; with budgets its groups are one include term each and it has no "
-                      "sequence anchors; budgets count edits only where there are budgets");
-            return PSS_EINVAL;
-        }
-    }
-    if (rq.class_bytes || rq.class_plane || rq.class_offsets || rq.class_groups || rq.class_cores || rq.class_sets || rq.class_void ||
-        rq.class_nsegs || rq.class_nsets) {
-        // a class batch is a sequence batch (groups and sequence anchors) that states all of its block, the sets where it names
-        // any; its terms are cores, so there are at most as many of them as segments; budgets are another search
-        const bool ok = rq.class_bytes && rq.class_plane && rq.class_offsets && rq.class_groups && rq.class_cores && rq.class_void &&
-                        (rq.class_sets || !rq.class_nsets) && rq.class_nsets <= 255 && rq.group_offsets && rq.seq_anchors && !rq.near_budget &&
-                        (rq.seed_offsets ? rq.nterms : rq.nq) <= rq.class_nsegs && rq.class_groups[0] == 0 &&
-                        rq.class_groups[rq.ngroups] == rq.class_nsegs;
-        if (!ok) {
-            set_error("search: a class batch is a sequence batch that states its segments' bytes, class plane, offsets, group offsets, "
-                      "cores and void flags, and at most 255 sets; its terms are the segments' cores");
-            return PSS_EINVAL;
-        }
+    case REQUEST_SEEDED:
+        set_error("search: a seeded batch states its groups, its terms' bytes and offsets, the seed queries' offsets and positions, "
+                  "and either exclude flags or sequence anchors; with budgets its groups are one include term each and it has no "
+                  "sequence anchors; budgets count edits only where there are budgets");
+        return PSS_EINVAL;
+    case REQUEST_CLASS:
+        set_error("search: a class batch is a sequence batch that states its segments' bytes, class plane, offsets, group offsets, "
+                  "cores and void flags, and at most 255 sets; its terms are the segments' cores");
+        return PSS_EINVAL;
     }
     const u32 rows = rq.rows();
     memset(st, 0, sizeof *st);

@@ -382,3 +382,66 @@ def run_case(case, tmp_path, set_env):
         return {name: res for (name, _, _), res in zip(FUZZ_BATCHES, got)}
     finally:
         r.close()
+
+
+# ---- rows and term bytes around a multiple of 64 -----------------------------------------------------------------------------
+# The host driver rounds every region of a group batch's workspace to 64 bytes (csrc/search_layout.h): group offsets, flags
+# and anchor bytes per row or term, the terms' bytes with 32 zero bytes behind them.  63, 64 and 65 rows whose term bytes
+# add up to 31, 32 and 33 modulo 64 put every one of those regions on, just under and just over its rounding.
+
+EDGE_ROWS = (63, 64, 65)
+EDGE_BYTES = (31, 32, 33)
+
+
+def edge_chunks():
+    """A few hundred short entries of the filler alphabet in both cases (and five long ones), as one chunk and as three."""
+    rng = np.random.default_rng(6464)
+    lines = [filler(rng, int(rng.integers(0, 21))) for _ in range(300)] + [filler(rng, 80) for _ in range(5)]
+    lines = [bytes(c - 32 if rng.random() < 0.25 else c for c in line) for line in lines]
+    order = rng.permutation(len(lines))
+    lines = [lines[int(i)] for i in order]
+    cut = [b'\n'.join(lines[a:b]) + b'\n' for a, b in ((0, 100), (100, 200), (200, len(lines)))]
+    return lines, ([b''.join(cut)], cut)
+
+
+def edge_groups(rng, lines, rows, total_mod):
+    """`rows` triples (a, b, ab): a and b cut from one entry left to right -- its start and its last byte, so the entry holds
+    both, in order, apart -- and ab, the entry's start as long as both together.  The lengths of all a and b add up to total_mod
+    modulo 64."""
+    long_lines = [line for line in lines if len(line) >= 80]
+    groups, total = [], 0
+    while len(groups) < rows:
+        last = len(groups) == rows - 1
+        line = long_lines[int(rng.integers(0, len(long_lines)))] if last or rng.random() < 0.1 else lines[int(rng.integers(0, len(lines)))]
+        if len(line) < 6:
+            continue
+        first = 2 + int(rng.integers(0, 2))
+        if last:        # (the length that brings the total home: 2 .. 65 bytes)
+            first = (total_mod - total - 1 - 2) % 64 + 2
+        a, b = line[:first], line[-1:]
+        assert len(line) > first + 1
+        groups.append((a, b, line[:first + 1]))
+        total += len(a) + len(b)
+    assert total % 64 == total_mod and len(groups) == rows and all(len(a) + len(b) == len(ab) for a, b, ab in groups)
+    return groups
+
+
+def layout_edges(kind, batch_of, min_ids=1):
+    """EDGE_ROWS x EDGE_BYTES batches of `kind` (batch_of: the triples of edge_groups as the kind's batch) through check() on the
+    one-chunk and on the three-chunk reader: ids, counts and packed text against the brute-force reference."""
+    lines, placements = edge_chunks()
+    rng = np.random.default_rng(31 + 32 + 33)
+    batches = [batch_of(edge_groups(rng, lines, rows, mod)) for rows in EDGE_ROWS for mod in EDGE_BYTES]
+    for chunks in placements:
+        r, ref = device_reader(chunks), kind.ref_cls(chunks)
+        try:
+            for batch in batches:
+                assert len(kind.rows(batch)) in EDGE_ROWS
+                assert check(kind, r, ref, batch).ids.size >= min_ids
+        finally:
+            r.close()
+
+
+def edge_globs(groups, gap=b'*'):
+    """The triples of edge_groups as glob patterns of two segments, every other one anchored at both ends."""
+    return [(a + gap + b) if i % 2 else (b'*' + a + gap + b + b'*') for i, (a, b, _) in enumerate(groups)]

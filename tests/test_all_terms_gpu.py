@@ -420,3 +420,8 @@ def test_conveniences_on_the_readme_example(tmp_path):
             r.search_all(['some', ''])
     finally:
         r.close()
+
+
+def test_rows_and_term_bytes_around_a_multiple_of_64():
+    """63, 64 and 65 groups whose term bytes add up to 31, 32 and 33 modulo 64, on one chunk and on three (search_harness.layout_edges)."""
+    H.layout_edges(H.ALL_TERMS, lambda groups: [[a, b] for a, b, _ in groups], min_ids=63)

@@ -416,3 +416,10 @@ def test_conveniences_on_the_readme_example(tmp_path):
             r.search_glob('some*', classes='yes')
     finally:
         r.close()
+
+
+@pytest.mark.parametrize('kind', [CLASS, CLASS_ICASE], ids=lambda kind: kind.name)
+def test_rows_and_core_bytes_around_a_multiple_of_64(kind):
+    """63, 64 and 65 patterns whose core bytes add up to 31, 32 and 33 modulo 64 -- a class position behind the first core --, on one
+    chunk and on three (search_harness.layout_edges)."""
+    H.layout_edges(kind, lambda groups: H.edge_globs(groups, gap=b'?*'), min_ids=63)

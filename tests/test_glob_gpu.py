@@ -519,3 +519,8 @@ def test_conveniences_on_the_readme_example(tmp_path):
                 r.count_glob(bad)
     finally:
         r.close()
+
+
+def test_rows_and_segment_bytes_around_a_multiple_of_64():
+    """63, 64 and 65 patterns whose segment bytes add up to 31, 32 and 33 modulo 64, on one chunk and on three (search_harness.layout_edges)."""
+    H.layout_edges(H.GLOB, H.edge_globs, min_ids=63)

@@ -509,6 +509,27 @@ def test_rounds_layout_on_the_cpu(tmp_path):
     assert r.returncode == 0 and 'rounds_layout: ok' in r.stdout, r.stdout[-1000:] + r.stderr[-2000:]
 
 
+def test_search_layout_on_the_cpu(tmp_path):
+    """What the host driver of a search batch decides by and carves is described once (csrc/search_layout.h, plain C++ without
+    HIP): the request, the rules it keeps, the routes a batch may take (BatchShape) and the layouts of the Q_TERMS slot of an
+    all-terms / sequence batch and of a seeded one, the class block both embed, Q_ANCHOR, the words of Q_SMALL, the pinned
+    result words and the two stagings.  tests/native/search_layout.cpp restates every layout as a table of region sizes and
+    checks every start, the 64-byte rounding, that no region overlaps the next and end == the reservation written out before
+    the header existed, at 1, 63, 64, 65 and 2^20 + 1 rows, terms and queries, one and five chunks, 1, 31, 32, 33 and 96 term
+    bytes, with and without budgets, sequence anchors and a class block (0, 1, 255 sets; 0 and 33 positions); every route
+    rule on both sides of its edge with the answers written down; one valid request of every kind, and for every clause of
+    every request rule the same request with that clause broken.  Built with g++ under AddressSanitizer + UBSan against that
+    header alone: no library, no device."""
+    csrc = os.path.join(ROOT, 'pysubstringsearch_amd', 'csrc')
+    exe = str(tmp_path / 'search_layout')
+    r = subprocess.run(['g++', '-O1', '-g', '-std=c++17', '-Wall', '-Wextra', '-fsanitize=address,undefined',
+                        '-fno-sanitize-recover=undefined', '-I' + csrc,
+                        os.path.join(ROOT, 'tests', 'native', 'search_layout.cpp'), '-o', exe], capture_output=True, text=True)
+    assert r.returncode == 0 and not r.stderr.strip(), r.stderr[-2000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and 'search_layout: ok' in r.stdout, r.stdout[-1000:] + r.stderr[-2000:]
+
+
 def test_msd_layout_on_the_cpu(tmp_path):
     """The workspace of the two initial sorts is described once (csrc/msd_layout.h, plain C++ without HIP: MsdWork) and
     both host drivers take their pointers from it.  tests/native/msd_layout.cpp restates the eighteen regions as a table

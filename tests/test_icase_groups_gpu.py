@@ -638,3 +638,14 @@ def test_errors(shape_index):
         assert r.count_icase_bytes([b'ab']) == [sum(1 for ln in lines if b'ab' in ln.lower())]
     finally:
         r.close()
+
+
+@pytest.mark.parametrize('kind', [H.ICASE_ALL, H.ICASE_GLOB], ids=lambda kind: kind.name)
+def test_rows_and_term_bytes_around_a_multiple_of_64(kind):
+    """63, 64 and 65 groups whose term bytes add up to 31, 32 and 33 modulo 64, in the other case, on one chunk and on three
+    (search_harness.layout_edges)."""
+    swapped = lambda groups: [(a.swapcase(), b.swapcase(), ab) for a, b, ab in groups]
+    if kind is H.ICASE_ALL:
+        H.layout_edges(kind, lambda groups: [[a, b] for a, b, _ in swapped(groups)], min_ids=63)
+    else:
+        H.layout_edges(kind, lambda groups: H.edge_globs(swapped(groups)), min_ids=63)

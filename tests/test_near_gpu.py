@@ -496,3 +496,9 @@ def test_conveniences_on_the_readme_example(tmp_path):
                 call('abcdef', [1])
     finally:
         r.close()
+
+
+def test_rows_and_pattern_bytes_around_a_multiple_of_64():
+    """63, 64 and 65 patterns whose bytes add up to 31, 32 and 33 modulo 64, budgets 0 and 1 in turn, on one chunk and on three
+    (search_harness.layout_edges)."""
+    H.layout_edges(H.NEAR, lambda groups: ([ab for _, _, ab in groups], [i % 2 for i in range(len(groups))]), min_ids=63)

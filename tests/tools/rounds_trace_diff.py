@@ -1,25 +1,39 @@
-"""Compares two `rocprofv3 --kernel-trace` runs of tests/tools/rounds_check.py (one per library): the dispatches must be the
-same in the same order, each as `kernel grid workgroup lds`.
+"""Compares two `rocprofv3 --kernel-trace` runs of tests/tools/rounds_check.py -- or, with --stages search, of
+tests/tools/search_check.py -- (one per library): the dispatches must be the same in the same order, each as `kernel grid
+workgroup lds`.
 
-    python tests/tools/rounds_trace_diff.py <a_kernel_trace.csv> <b_kernel_trace.csv> [--per-queue] [--summary-a FILE] [--summary-b FILE]
+    python tests/tools/rounds_trace_diff.py <a_kernel_trace.csv> <b_kernel_trace.csv> [--stages rounds|search] [--per-queue]
+                                            [--summary-a FILE] [--summary-b FILE]
 
 Without --per-queue the dispatches of the whole process are ordered by start time (one stream: the side line off).  With it
 they are compared queue by queue, the queues taken in the order of their first dispatch (the side line's helper stream
 runs beside the main one, so the interleaving of the two is a race and the order inside each is not).
 A summary file holds what fits a repository: the number of dispatches, the sha256 of the full sequence and the count per
-kernel.  Exit code 0 = equal, and every stage of the rounds was seen (STAGES)."""
+kernel.  Exit code 0 = equal, and every stage of the driver was seen (STAGES: a stage is seen when a kernel's name starts
+with it)."""
 import argparse
 import collections
 import csv
 import hashlib
 import sys
 
-STAGES = ('build_keys_kernel<true>', 'build_keys_kernel<false>', 'ht_insert_kernel', 'mid_msort_kernel', 'bg_merge_kernel', 'per_keys_kernel',
+STAGES = {}
+STAGES['rounds'] = ('build_keys_kernel<true>', 'build_keys_kernel<false>', 'ht_insert_kernel', 'mid_msort_kernel', 'bg_merge_kernel', 'per_keys_kernel',
           'big_writeback_kernel', 'anc_select_kernel<true>', 'anc_select_kernel<false>', 'probe_repeats_kernel', 'isa_from_sa_kernel')
+# the stages of a search batch (csrc/search.hip, Batch): run_fused, launch_interval, run_mid, pick_drivers, seed_drivers, and of
+# run_general the hit scan, every branch of candidates() with the verify launcher's three ways under both folds, the counts
+# tail and the emit tail
+STAGES['search'] = ('search_block_kernel', 'search_small_kernel', 'search_interval_kernel', 'search_interval_group_kernel',
+                    'search_interval_lane_kernel', 'anchor_edges_kernel', 'mid_hitoff_kernel', 'mid_hit_scans_kernel',
+                    'terms_driver_kernel<true>', 'seed_union_kernel', 'terms_driver_kernel<false>', 'hit_bounds_kernel',
+                    'mark_later_hits_kernel', 'anchored_hits_kernel', 'seed_hits_kernel', 'seed_dedupe_kernel', 'seqc_verify_kernel<true>',
+                    'seqc_verify_kernel<false>', 'seq_verify_kernel<true>', 'seq_verify_kernel<false>', 'terms_verify_kernel<true>',
+                    'terms_verify_kernel<false>', 'hit_lines_kernel<true>', 'hit_lines_kernel<false>', 'query_counts_kernel',
+                    'emit_ids_kernel', 'emit_kernel')
 
 
 def short(name):
-    name = name.replace('pss::', '').replace('void ', '')
+    name = name.replace('pss::', '').replace('(anonymous namespace)::', '').replace('void ', '')
     depth = 0
     for i, c in enumerate(name):      # cut the argument list, keep the template arguments
         if c == '<':
@@ -57,6 +71,7 @@ def main():
     ap.add_argument('a')
     ap.add_argument('b')
     ap.add_argument('--per-queue', action='store_true')
+    ap.add_argument('--stages', default='rounds', choices=sorted(STAGES))
     ap.add_argument('--summary-a')
     ap.add_argument('--summary-b')
     args = ap.parse_args()
@@ -79,7 +94,7 @@ def main():
         for i in range(max(0, first - 2), min(first + 3, max(len(x), len(y)))):
             print('   %d  a: %s\n   %d  b: %s' % (i, x[i] if i < len(x) else '-', i, y[i] if i < len(y) else '-'))
     seen = set(line.split(' grid ')[0] for seq in B for line in seq)
-    missing = [s for s in STAGES if s not in seen]
+    missing = [s for s in STAGES[args.stages] if not any(name.startswith(s) for name in seen)]
     print('stages missing from the trace:', missing if missing else 'none')
     sys.exit(1 if bad or missing else 0)
 

@@ -120,21 +120,28 @@ def time_legs(legs, seen, warmup, reps, rounds, record=search_call_record, befor
     """Every leg of legs = {name: call} warmed up `warmup` times and timed `reps` times with a host clock around the call,
     the legs alternating for `rounds` rounds.  One record per leg and round: median / min / max, then
     record(the call's last return value, seen(name)), seen(name) being the statistics the record is to show -- a dict the
-    legs fill, or a function.  before(name), if given, runs ahead of a leg's calls, untimed."""
+    legs fill, or a function.  before(name), if given, runs ahead of a leg's calls, untimed.  Where those statistics carry
+    ms_host (the library's own host clock around its last search call), its median / min / max over the timed calls are
+    recorded too: what a change to the host driver alone can move."""
     runs = []
     for _ in range(rounds):
         for name, call in legs.items():
             if before is not None:
                 before(name)
-            times = []
+            times, host = [], []
             for i in range(warmup + reps):
                 t0 = time.perf_counter()
                 out = call()
                 t = time.perf_counter() - t0
                 if i >= warmup:
                     times.append(t * 1e3)
+                    st = seen(name) if callable(seen) else seen.get(name)
+                    if st is not None and 'ms_host' in st:
+                        host.append(st['ms_host'])
             st = seen(name) if callable(seen) else seen[name]
             runs.append({'leg': name, **spread(times, reps), **record(out, st)})
+            if host:
+                runs[-1]['ms_host_last_call'] = {k: v for k, v in spread(host, reps).items() if k != 'reps'}
     return runs
 
 
