@@ -791,8 +791,8 @@ int pss_reader_count_seq_icase_batch(pss_reader *r, const uint8_t *sbytes, const
  * bit of its own.  The id variant builds the line tables on first use, the other two allocate nothing for them.
  * The limit: the candidates follow the occurrences of the PIECES -- a short pattern at k = 3 has pieces of a byte or two, and
  * every occurrence of such a piece is verified.
- * Out of scope: insertions and deletions (the search within k edits below has them); k > 3; mismatches under ASCII case folding, inside all-terms groups or wildcard
- * patterns; the fused, mid, resident and device-resident paths (a near batch always takes the general pipeline); the
+ * Out of scope: insertions and deletions (the search within k edits below has them); k > 3; mismatches inside all-terms groups
+ * or wildcard patterns (under ASCII case folding: pss_reader_search_near_icase_batch below); the fused, mid, resident and device-resident paths (a near batch always takes the general pipeline); the
  * multi-process gather over RCCL (dist.ShardedReader); choosing pieces by rarity; a piece driving only where it is present.
  */
 /* packed entry text, one row per pattern; k = nq budgets */
@@ -841,7 +841,8 @@ int pss_near_pieces(const uint8_t *pat, uint64_t len, uint32_t k, uint32_t *offs
  * entries = what is returned, route = GENERAL | the interval bits (| COUNTS); no bit of its own.
  * The limits: near's (every occurrence of every piece is verified), and an entry DENSE with occurrences of a piece: the scan
  * in front of a hit runs both DPs at every such occurrence, lane by lane.
- * Out of scope: edits under ASCII case folding, inside all-terms groups or wildcard patterns; k > 3; a transposition as one
+ * Out of scope: edits inside all-terms groups or wildcard patterns (under ASCII case folding:
+ * pss_reader_search_near_icase_batch below); k > 3; a transposition as one
  * edit; the fused, mid, resident and device-resident paths; choosing pieces by rarity.
  */
 /* packed entry text, one row per pattern; k = nq budgets */
@@ -853,6 +854,49 @@ int pss_reader_search_edit_ids_batch(pss_reader *r, const uint8_t *qbytes, const
 /* counts[q] = entries pattern q matches within k[q] edits; nothing but nq counters comes down */
 int pss_reader_count_edit_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, const uint8_t *k,
                                 uint64_t *counts);
+/*
+ * Search within k mismatches or k edits UNDER ASCII CASE FOLDING (no reference counterpart): the two searches above with one
+ * other rule of equality -- two bytes are equal iff they are equal after folding A-Z to a-z, the rule of
+ * pss_reader_search_icase_batch.  Nothing else folds: `@` and '`', `[` and `{`, 0xC9 and 0xE9 are different bytes, and 0x00 and
+ * 0x80 .. 0xFF match only themselves.  `passw0rd` and `PASSW0RD` are both found for `Password` at k = 1: a case difference costs
+ * nothing.  Arguments, packing, the ids variant and the count call as for the near calls, plus `edits`: 0 counts substituted bytes
+ * (an entry matches iff some window of |p| bytes inside it differs from p in at most k positions under that equality), anything
+ * else counts edits (iff some substring of the entry has Levenshtein distance <= k to p, a substitution of fold-equal bytes
+ * costing 0).  The window or substring lies inside the entry.  k is nq budgets, 0 .. 3.  A pattern that holds 0x0A matches
+ * nothing and no hit is looked at; every entry at most once per pattern.  k = 0 returns exactly what
+ * pss_reader_search_icase_ids_batch returns, order included; for every k the answer contains the exact-byte answer at the same
+ * k, and the edits answer contains the mismatch answer.
+ * PSS_EINVAL: what the near and edit calls name, in the same order; the reader is judged last.
+ * The search: the pattern folded to lower case is the term that is verified; its pieces are near's (pss_near_pieces); each piece
+ * is looked up as a case-insensitive term is, through the spellings of its SEED -- the longest window of the piece with at most f
+ * ASCII letters, leftmost on a tie, f = min(PSS_ICASE_SEED_LETTERS, cap(k)) with cap = 6, 5, 4, 4 for k = 0 .. 3: the largest f
+ * with (k + 1) 2^f <= 64, so a pattern has at most 64 seed queries.  pss_near_seeds shows them.  Every hit of every query is
+ * verified on the device under fold: its piece must be fold-equal over its whole length where the seed puts it; under
+ * mismatches the window must be within budget inside the hit's entry and the piece its first fold-exact one, and no window
+ * within budget may start in front of it in the entry; under edits the candidate (piece, position) must stand, no earlier piece
+ * may stand at the same position, and no candidate may stand in front of it in the entry.
+ * Order: pattern-major, chunk-major inside a pattern; inside one pair by the piece index of the kept hit, then by query (the
+ * spellings ascend bytewise), then in suffix-array order; pss_reader_set_result_order has no effect.  Always the general pipeline.
+ * pss_reader_last_stats: hits = the sum over all seed queries and chunks of their exact occurrences, entries = what is returned.
+ * Out of scope: folding outside ASCII; budgets under fold inside all-terms groups or wildcard patterns; choosing pieces by rarity.
+ */
+/* packed entry text, one row per pattern; k = nq budgets; edits: 0 = mismatches, else edits */
+int pss_reader_search_near_icase_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, const uint8_t *k,
+                                       int edits, pss_result **out);
+/* u64 entry ids, packed as pss_reader_search_ids_batch packs them */
+int pss_reader_search_near_icase_ids_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq,
+                                           const uint8_t *k, int edits, pss_result **out);
+/* counts[q] = entries pattern q matches within k[q] under fold; nothing but nq counters comes down */
+int pss_reader_count_near_icase_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, const uint8_t *k,
+                                      int edits, uint64_t *counts);
+/* The seed queries of ONE pattern under fold, on the host: no reader, no GPU.  piece / pos / lengths (room for 64 values each)
+ * receive per query, in the order of the search, the index of its piece, its position inside the pattern and its length;
+ * *count = the number of queries (at most 64).  out (cap bytes; null: the sizes alone) receives the queries' bytes back to back.
+ * letters: 1 .. 6, or <= 0 for the configured PSS_ICASE_SEED_LETTERS; the cap of k bounds it.
+ * PSS_EINVAL: an empty pattern, k > 3, len <= k, letters > 6, len > 2^32 - 1, a null piece / pos / lengths / count, an out
+ * too small (*count is set). */
+int pss_near_seeds(const uint8_t *pat, uint64_t len, uint32_t k, int32_t letters, uint8_t *out, uint64_t cap, uint32_t *piece,
+                   uint32_t *pos, uint32_t *lengths, uint32_t *count);
 /* For the first `cap` resident chunks, in file order: index in the file and number of entries; *num = resident chunks. */
 int pss_reader_chunk_entries(pss_reader *r, uint64_t *chunk_index, uint64_t *entries, uint64_t cap, uint64_t *num);
 /*

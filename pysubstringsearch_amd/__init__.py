@@ -28,7 +28,7 @@ except ImportError:   # pragma: no cover
     _pssglue = None
 
 __all__ = ['Writer', 'Reader', 'PackedResult', 'IdResult', 'DeviceResult', 'device_count', 'default_devices', 'release_workspace', 'workspace_bytes',
-           'glob_parse', 'glob_escape', 'glob_cores', 'icase_variants', 'near_pieces']
+           'glob_parse', 'glob_escape', 'glob_cores', 'icase_variants', 'near_pieces', 'near_seeds']
 
 
 def device_count() -> int:
@@ -306,6 +306,33 @@ def near_pieces(pattern: bytes, k: int) -> typing.List[typing.Tuple[int, bytes]]
     off, ln, cnt = (ctypes.c_uint32 * 4)(), (ctypes.c_uint32 * 4)(), ctypes.c_uint32()
     _ffi.check(_lib.pss_near_pieces(pattern, len(pattern), k, off, ln, ctypes.byref(cnt)))
     return [(int(off[j]), pattern[off[j]:off[j] + ln[j]]) for j in range(cnt.value)]
+
+
+def near_seeds(pattern: bytes, k: int, letters: typing.Optional[int] = None) -> typing.List[typing.Tuple[int, int, bytes]]:
+    """``[(piece, pos, bytes), ...]``: the seed queries of a pattern as ``Reader.search_near_ids_batch(..., icase=True)``
+    searches it within ``k`` mismatches or edits (include/pss.h, pss_near_seeds), in the order of the search.  Every piece
+    of ``near_pieces(pattern, k)`` is looked up as a case-insensitive term is: through the spellings, ascending, of its
+    SEED -- the piece's longest window with at most ``f`` ASCII letters, the leftmost on a tie.  ``piece`` is the piece's
+    index and ``pos`` the seed's position inside the pattern.  ``f`` is ``letters`` (1 .. 6; ``None`` = the configured
+    ``PSS_ICASE_SEED_LETTERS``) but at most 6, 5, 4, 4 for ``k`` = 0 .. 3, so that a pattern has at most 64 queries.
+    ``ValueError`` as for ``near_pieces``, and for ``letters`` outside 1 .. 6.  Host only: no device is touched."""
+    if not isinstance(pattern, (bytes, bytearray)):
+        raise TypeError(f'a pattern must be bytes, not {type(pattern).__name__}')
+    k = _near_budget(k)
+    if letters is not None and not 1 <= int(letters) <= 6:
+        raise ValueError(f'letters = {letters!r}: 1 .. 6, or None for PSS_ICASE_SEED_LETTERS')
+    pattern = bytes(pattern)
+    want = 0 if letters is None else int(letters)
+    piece, pos, ln, cnt = (ctypes.c_uint32 * 64)(), (ctypes.c_uint32 * 64)(), (ctypes.c_uint32 * 64)(), ctypes.c_uint32()
+    _ffi.check(_lib.pss_near_seeds(pattern, len(pattern), k, want, None, 0, piece, pos, ln, ctypes.byref(cnt)))
+    total = sum(ln[v] for v in range(cnt.value))
+    buf = ctypes.create_string_buffer(max(1, total))
+    _ffi.check(_lib.pss_near_seeds(pattern, len(pattern), k, want, buf, total, piece, pos, ln, ctypes.byref(cnt)))
+    raw, out, at = buf.raw, [], 0
+    for v in range(cnt.value):
+        out.append((int(piece[v]), int(pos[v]), raw[at:at + ln[v]]))
+        at += ln[v]
+    return out
 
 
 def _near_budget(k) -> int:
@@ -1123,13 +1150,16 @@ class Reader:
         return self.count_icase_bytes([_utf8(s, 'substring')])[0]
 
     @staticmethod
-    def _near_args(patterns, k, edits=False):
-        """(blob, offsets, budgets) of one batch within k mismatches, or within k edits (``edits``, a bool).  ``k`` is an int
+    def _near_args(patterns, k, edits=False, icase=False):
+        """(blob, offsets, budgets) of one batch within k mismatches, or within k edits (``edits``, a bool), in exact bytes or
+        under ASCII case folding (``icase``, a bool: the checks are the same).  ``k`` is an int
         for the batch or a sequence with one int per pattern; ``ValueError`` for an empty pattern, a budget outside 0 .. 3,
         a pattern of at most its budget's bytes, or another number of budgets than patterns."""
         import numpy as np
         if not isinstance(edits, bool):
             raise TypeError(f"argument 'edits' must be a bool, not {type(edits).__name__}")
+        if not isinstance(icase, bool):
+            raise TypeError(f"argument 'icase' must be a bool, not {type(icase).__name__}")
         if isinstance(patterns, (bytes, bytearray, str)):
             raise TypeError(f"argument 'patterns': '{type(patterns).__name__}' object cannot be converted to a sequence of patterns")
         patterns = list(patterns)
@@ -1153,7 +1183,18 @@ class Reader:
         blob, offs = _pack_queries([bytes(p) for p in patterns])
         return blob, offs, np.array(budgets, dtype=np.uint8)
 
-    def search_near_batch_packed(self, patterns: typing.Sequence[bytes], k=1, edits: bool = False) -> 'PackedResult':
+    def _near_batch(self, form: str, patterns, k, edits, icase):
+        """One batch within k through the C call of its kind: near, edit, or -- ``icase`` -- either under fold."""
+        blob, offs, ks = self._near_args(patterns, k, edits, icase)
+        if not icase:
+            name = {'packed': 'pss_reader_search_%s_batch', 'ids': 'pss_reader_search_%s_ids_batch', 'counts': 'pss_reader_count_%s_batch'}[form]
+            return self._query_batch(name % ('edit' if edits else 'near'), (blob, offs), form, ks)
+        name = {'packed': 'pss_reader_search_near_icase_batch', 'ids': 'pss_reader_search_near_icase_ids_batch',
+                'counts': 'pss_reader_count_near_icase_batch'}[form]
+        nq = len(offs) - 1
+        return self._batch(getattr(_lib, name), (blob, offs.ctypes.data, nq, ks.ctypes.data, int(edits)), nq, form)
+
+    def search_near_batch_packed(self, patterns: typing.Sequence[bytes], k=1, edits: bool = False, *, icase: bool = False) -> 'PackedResult':
         """Extension: per pattern, the entries that hold it with at most ``k`` bytes SUBSTITUTED (Hamming distance:
         ``passw0rd`` for ``password`` at ``k=1``), as a packed result like ``search_batch_packed``'s.  ``k`` is 0 .. 3, one
         int for the batch or a sequence with one per pattern.  The window lies inside the entry; bytes are exact (nothing
@@ -1166,32 +1207,38 @@ class Reader:
         ``pasword``, ``passsword`` and ``passw0rd`` for ``password`` at ``k=1``).  An entry matches iff some substring of it
         is within ``k`` edits of the pattern; the substring lies inside the entry.  Everything else as above: the same
         pieces, every occurrence of a piece verified on the device (include/pss.h, pss_reader_search_edit_batch).  The
-        answer contains the answer without ``edits`` at the same ``k``."""
-        blob, offs, ks = self._near_args(patterns, k, edits)
-        return self._query_batch('pss_reader_search_edit_batch' if edits else 'pss_reader_search_near_batch', (blob, offs), 'packed', ks)
+        answer contains the answer without ``edits`` at the same ``k``.
 
-    def search_near_ids_batch(self, patterns: typing.Sequence[bytes], k=1, edits: bool = False) -> 'IdResult':
+        ``icase=True`` (keyword only; combines with ``edits``): two bytes are equal iff they are equal after folding ``A-Z``
+        to ``a-z`` -- the rule of ``search_icase_batch_packed``; nothing else folds, ``0x80 .. 0xFF`` match only themselves.
+        A case difference costs nothing: ``passw0rd`` and ``PASSW0RD`` for ``Password`` at ``k=1``.  Everything else as above.
+        Each piece is looked up through the spellings of its seed (``near_seeds``), at most 64 queries per pattern, and
+        every hit is verified under fold on the device (include/pss.h, pss_reader_search_near_icase_batch).  ``k=0`` returns
+        exactly what ``search_icase_ids_batch`` returns; for every ``k`` the answer contains the answer without ``icase``."""
+        return self._near_batch('packed', patterns, k, edits, icase)
+
+    def search_near_ids_batch(self, patterns: typing.Sequence[bytes], k=1, edits: bool = False, *, icase: bool = False) -> 'IdResult':
         """Extension: the ids (``search_ids_batch``) of the entries ``search_near_batch_packed`` returns, in the same
         order; ``counts[q]`` of them belong to pattern q.  ``k=0`` returns exactly what ``search_ids_batch`` returns.
-        ``edits=True``: the entries within ``k`` edits instead (``search_near_batch_packed``); ``k=0`` is the same."""
-        blob, offs, ks = self._near_args(patterns, k, edits)
-        return self._query_batch('pss_reader_search_edit_ids_batch' if edits else 'pss_reader_search_near_ids_batch', (blob, offs), 'ids', ks)
+        ``edits=True``: the entries within ``k`` edits instead (``search_near_batch_packed``); ``k=0`` is the same.
+        ``icase=True``: under ASCII case folding (``search_near_batch_packed``); ``k=0`` returns exactly what
+        ``search_icase_ids_batch`` returns."""
+        return self._near_batch('ids', patterns, k, edits, icase)
 
-    def count_near_bytes(self, patterns: typing.Sequence[bytes], k=1, edits: bool = False) -> typing.List[int]:
-        """Extension: how many entries hold each pattern within ``k`` mismatches (``edits=True``: within ``k`` edits); only
-        the counters come back."""
-        blob, offs, ks = self._near_args(patterns, k, edits)
-        return self._query_batch('pss_reader_count_edit_batch' if edits else 'pss_reader_count_near_batch', (blob, offs), 'counts', ks)
+    def count_near_bytes(self, patterns: typing.Sequence[bytes], k=1, edits: bool = False, *, icase: bool = False) -> typing.List[int]:
+        """Extension: how many entries hold each pattern within ``k`` mismatches (``edits=True``: within ``k`` edits;
+        ``icase=True``: under ASCII case folding); only the counters come back."""
+        return self._near_batch('counts', patterns, k, edits, icase)
 
-    def search_near(self, s: str, k: int = 1, edits: bool = False) -> typing.List[str]:
+    def search_near(self, s: str, k: int = 1, edits: bool = False, *, icase: bool = False) -> typing.List[str]:
         """Extension: the entries that hold ``s`` (UTF-8 encoded) with at most ``k`` BYTES substituted -- with
-        ``edits=True``: inserted, deleted or substituted."""
-        return _packed_strs(self.search_near_batch_packed([_utf8(s, 'substring')], _near_budget(k), edits))
+        ``edits=True``: inserted, deleted or substituted; with ``icase=True``: whatever the case of ASCII letters."""
+        return _packed_strs(self.search_near_batch_packed([_utf8(s, 'substring')], _near_budget(k), edits, icase=icase))
 
-    def count_near(self, s: str, k: int = 1, edits: bool = False) -> int:
+    def count_near(self, s: str, k: int = 1, edits: bool = False, *, icase: bool = False) -> int:
         """Extension: how many entries hold ``s`` (UTF-8 encoded) with at most ``k`` bytes substituted -- with
-        ``edits=True``: inserted, deleted or substituted."""
-        return self.count_near_bytes([_utf8(s, 'substring')], _near_budget(k), edits)[0]
+        ``edits=True``: inserted, deleted or substituted; with ``icase=True``: whatever the case of ASCII letters."""
+        return self.count_near_bytes([_utf8(s, 'substring')], _near_budget(k), edits, icase=icase)[0]
 
     @property
     def entry_counts(self) -> typing.Dict[int, int]:

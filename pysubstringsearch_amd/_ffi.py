@@ -321,6 +321,11 @@ def _load() -> ctypes.CDLL:
         'pss_reader_search_edit_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, pvp]),
         'pss_reader_search_edit_ids_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, pvp]),
         'pss_reader_count_edit_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, vp]),
+        'pss_reader_search_near_icase_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, ctypes.c_int, pvp]),
+        'pss_reader_search_near_icase_ids_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, ctypes.c_int, pvp]),
+        'pss_reader_count_near_icase_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, ctypes.c_int, vp]),
+        'pss_near_seeds': (ctypes.c_int, [vp, u64, u32, i32, vp, u64, ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(u32),
+                                          ctypes.POINTER(u32)]),
         'pss_near_pieces': (ctypes.c_int, [vp, u64, u32, ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(u32)]),
         'pss_icase_variants': (ctypes.c_int, [vp, u64, i32, vp, u64, ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(u32)]),
         'pss_reader_chunk_entries': (ctypes.c_int, [vp, vp, vp, u64, ctypes.POINTER(u64)]),

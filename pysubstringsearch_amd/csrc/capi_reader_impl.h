@@ -1884,12 +1884,80 @@ namespace {
 
 constexpr uint32_t kNearMaxBudget = 3;
 
+// Under fold a piece is looked up as a case-insensitive term is: through the spellings of its seed.  A term keeps at most
+// 64 queries, the bound seed_union_kernel and the hit walk were written for, so the seed of a piece of a pattern with budget
+// k has at most kNearFoldCap[k] letters: the largest f with (k + 1) 2^f <= 64.
+constexpr uint8_t kNearFoldCap[kNearMaxBudget + 1] = {6, 5, 4, 4};
+
+// The seeds of pat[0, len) with budget k < len under fold, piece by piece: emit(piece j, the seed's position inside the
+// PATTERN, its length, its letters).  `letters` is the configured limit (1 .. 6), which the cap of k bounds.
+template <typename Emit>
+void near_fold_seeds(const uint8_t *pat, uint64_t len, uint32_t k, uint32_t letters, Emit emit)
+{
+    uint64_t off[kNearMaxBudget + 2];
+    near_pieces(len, k, off);
+    const uint32_t f = std::min<uint32_t>(letters, kNearFoldCap[k]);
+    for (uint32_t j = 0; j <= k; ++j) {
+        uint64_t so = 0, sl = 0;
+        const uint32_t nl = fold_seed(pat + off[j], off[j + 1] - off[j], f, &so, &sl);
+        emit(j, off[j] + so, sl, nl);
+    }
+}
+
+// A batch that near_plain has judged, under ASCII case folding: the terms are the patterns folded to
+// lower case, and a pattern's seed queries are, piece by piece, the spellings of the piece's seed in ascending order, each
+// at the seed's position inside the pattern.  The queries of one term are piece-major; spellings of one piece have disjoint
+// intervals, but pieces may overlap, nest or repeat, so the batch hands seed_union_kernel the overflow flag as every near
+// batch does.  At k = 0 the queries are exactly those of icase_expand.
+int near_fold_plain(pss_reader *r, const char *who, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, const uint8_t *k,
+                    bool edits, SearchMode mode, pss_result **out, uint64_t *counts)
+{
+    const uint32_t letters = icase_letters(0);
+    const uint64_t total = nq ? qoffsets[nq] : 0;
+    SeededGroups b;
+    b.fbytes.resize(total + 1);
+    for (uint64_t i = 0; i < total; ++i) b.fbytes[i] = (uint8_t)((uint8_t)(qbytes[i] - 'A') < 26 ? qbytes[i] | 0x20 : qbytes[i]);
+    b.voff.assign(1, 0);
+    b.soff.assign(1, 0);
+    b.soff.reserve((size_t)nq + 1);
+    for (uint32_t q = 0; q < nq; ++q) {
+        const uint8_t *pat = qbytes + qoffsets[q];
+        uint64_t nqueries = b.soff.back();
+        near_fold_seeds(pat, qoffsets[q + 1] - qoffsets[q], k[q], letters, [&](uint32_t, uint64_t at, uint64_t sl, uint32_t nl) {
+            const size_t o = b.vbytes.size();
+            b.vbytes.resize(o + (size_t)(sl << nl));
+            fold_spellings(pat + at, sl, nl, b.vbytes.data() + o);
+            for (uint32_t v = 0; v < (1u << nl); ++v) {
+                b.voff.push_back(b.voff.back() + sl);
+                b.pos.push_back((uint32_t)at);
+            }
+            nqueries += 1ull << nl;
+        });
+        if (nqueries > 0xffffffffull) {
+            set_error("%s: the patterns expand to more than the 2^32 - 1 seed queries a batch takes (at pattern %u)", who, q);
+            return PSS_EINVAL;
+        }
+        b.soff.push_back(nqueries);
+    }
+    b.vbytes.push_back(0);                   // (data() of an empty vector may be null)
+    b.pos.push_back(0);
+    b.one_term_each(nq);
+    static const uint8_t no_budget = 0;
+    static const uint64_t no_offset = 0;
+    SearchRequest rq = b.request(nq, b.one_each.data(), nq, b.no_exclude.data(), nullptr, mode);
+    rq.term_offsets = nq ? qoffsets : &no_offset;
+    rq.near_budget = nq ? k : &no_budget;
+    rq.near_edits = edits;
+    rq.near_fold = true;
+    return answer_by_mode(r, rq, out, counts);
+}
+
 // The three calls within k mismatches and the three within k edits (`edits`: what the budget counts, and the one
-// difference of the request): their own argument checks, then every pattern cut into its pieces -- the seed queries of a
+// difference of the request), and the three of either under fold (`fold`: near_fold_plain takes the judged batch): their own argument checks, then every pattern cut into its pieces -- the seed queries of a
 // group of one include term.  The patterns' own bytes and offsets are the caller's.  As for icase_plain, a malformed batch
 // is reported as such with or without a reader: the reader is looked at last.
 int near_plain(pss_reader *r, const char *who, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, const uint8_t *k,
-               bool edits, SearchMode mode, pss_result **out, uint64_t *counts)
+               bool edits, bool fold, SearchMode mode, pss_result **out, uint64_t *counts)
 {
     const char *unit = edits ? "edits" : "mismatches";
     if (!out_ok_by_mode(mode, nq, out, counts) || (nq && (!qbytes || !qoffsets || !k))) {
@@ -1919,6 +1987,7 @@ int near_plain(pss_reader *r, const char *who, const uint8_t *qbytes, const uint
         set_error("%s: bad arguments (no reader)", who);
         return PSS_EINVAL;
     }
+    if (fold) return near_fold_plain(r, who, qbytes, qoffsets, nq, k, edits, mode, out, counts);
     SeededGroups b;
     b.voff.reserve(npieces + 1);
     b.pos.reserve(npieces + 1);
@@ -1985,37 +2054,102 @@ extern "C" int pss_near_pieces(const uint8_t *pat, uint64_t len, uint32_t k, uin
 extern "C" int pss_reader_search_near_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, const uint8_t *k,
                                             pss_result **out)
 {
-    return guarded([&]() -> int { return near_plain(r, "pss_reader_search_near_batch", qbytes, qoffsets, nq, k, false, SEARCH_FULL, out, nullptr); });
+    return guarded([&]() -> int { return near_plain(r, "pss_reader_search_near_batch", qbytes, qoffsets, nq, k, false, false, SEARCH_FULL, out, nullptr); });
 }
 
 extern "C" int pss_reader_search_near_ids_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, const uint8_t *k,
                                                 pss_result **out)
 {
-    return guarded([&]() -> int { return near_plain(r, "pss_reader_search_near_ids_batch", qbytes, qoffsets, nq, k, false, SEARCH_IDS, out, nullptr); });
+    return guarded([&]() -> int { return near_plain(r, "pss_reader_search_near_ids_batch", qbytes, qoffsets, nq, k, false, false, SEARCH_IDS, out, nullptr); });
 }
 
 extern "C" int pss_reader_count_near_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, const uint8_t *k,
                                            uint64_t *counts)
 {
-    return guarded([&]() -> int { return near_plain(r, "pss_reader_count_near_batch", qbytes, qoffsets, nq, k, false, SEARCH_COUNTS, nullptr, counts); });
+    return guarded([&]() -> int { return near_plain(r, "pss_reader_count_near_batch", qbytes, qoffsets, nq, k, false, false, SEARCH_COUNTS, nullptr, counts); });
 }
 
 extern "C" int pss_reader_search_edit_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, const uint8_t *k,
                                             pss_result **out)
 {
-    return guarded([&]() -> int { return near_plain(r, "pss_reader_search_edit_batch", qbytes, qoffsets, nq, k, true, SEARCH_FULL, out, nullptr); });
+    return guarded([&]() -> int { return near_plain(r, "pss_reader_search_edit_batch", qbytes, qoffsets, nq, k, true, false, SEARCH_FULL, out, nullptr); });
 }
 
 extern "C" int pss_reader_search_edit_ids_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, const uint8_t *k,
                                                 pss_result **out)
 {
-    return guarded([&]() -> int { return near_plain(r, "pss_reader_search_edit_ids_batch", qbytes, qoffsets, nq, k, true, SEARCH_IDS, out, nullptr); });
+    return guarded([&]() -> int { return near_plain(r, "pss_reader_search_edit_ids_batch", qbytes, qoffsets, nq, k, true, false, SEARCH_IDS, out, nullptr); });
 }
 
 extern "C" int pss_reader_count_edit_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq, const uint8_t *k,
                                            uint64_t *counts)
 {
-    return guarded([&]() -> int { return near_plain(r, "pss_reader_count_edit_batch", qbytes, qoffsets, nq, k, true, SEARCH_COUNTS, nullptr, counts); });
+    return guarded([&]() -> int { return near_plain(r, "pss_reader_count_edit_batch", qbytes, qoffsets, nq, k, true, false, SEARCH_COUNTS, nullptr, counts); });
+}
+
+/* ---- the same two searches under ASCII case folding ---- */
+
+extern "C" int pss_reader_search_near_icase_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq,
+                                                  const uint8_t *k, int edits, pss_result **out)
+{
+    return guarded([&]() -> int { return near_plain(r, "pss_reader_search_near_icase_batch", qbytes, qoffsets, nq, k, edits != 0, true, SEARCH_FULL, out, nullptr); });
+}
+
+extern "C" int pss_reader_search_near_icase_ids_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq,
+                                                      const uint8_t *k, int edits, pss_result **out)
+{
+    return guarded([&]() -> int { return near_plain(r, "pss_reader_search_near_icase_ids_batch", qbytes, qoffsets, nq, k, edits != 0, true, SEARCH_IDS, out, nullptr); });
+}
+
+extern "C" int pss_reader_count_near_icase_batch(pss_reader *r, const uint8_t *qbytes, const uint64_t *qoffsets, uint32_t nq,
+                                                 const uint8_t *k, int edits, uint64_t *counts)
+{
+    return guarded([&]() -> int { return near_plain(r, "pss_reader_count_near_icase_batch", qbytes, qoffsets, nq, k, edits != 0, true, SEARCH_COUNTS, nullptr, counts); });
+}
+
+extern "C" int pss_near_seeds(const uint8_t *pat, uint64_t len, uint32_t k, int32_t letters, uint8_t *out, uint64_t cap, uint32_t *piece,
+                              uint32_t *pos, uint32_t *lengths, uint32_t *count)
+{
+    return guarded([&]() -> int {
+        if (!pat || !len) {
+            set_error("pss_near_seeds: the pattern is empty (every entry contains the empty pattern)");
+            return PSS_EINVAL;
+        }
+        if (k > kNearMaxBudget) {
+            set_error("pss_near_seeds: a budget of %u: 0 .. %u", k, kNearMaxBudget);
+            return PSS_EINVAL;
+        }
+        if (len <= k) {
+            set_error("pss_near_seeds: a pattern of %llu bytes and a budget of %u (a pattern is longer than its budget)",
+                      (unsigned long long)len, k);
+            return PSS_EINVAL;
+        }
+        if (letters > 6 || len > 0xffffffffull || !piece || !pos || !lengths || !count) {
+            set_error("pss_near_seeds: bad arguments (letters = %d: 1 .. 6, or <= 0 for PSS_ICASE_SEED_LETTERS; a pattern of %llu bytes)",
+                      (int)letters, (unsigned long long)len);
+            return PSS_EINVAL;
+        }
+        uint32_t n = 0;
+        uint64_t bytes = 0;
+        bool fits = true;
+        near_fold_seeds(pat, len, k, icase_letters(letters), [&](uint32_t j, uint64_t at, uint64_t sl, uint32_t nl) {
+            fits = fits && (!out || bytes + (sl << nl) <= cap);
+            if (out && fits) fold_spellings(pat + at, sl, nl, out + bytes);
+            for (uint32_t v = 0; v < (1u << nl); ++v, ++n) {      // (at most 64 in all: the cap)
+                piece[n] = j;
+                pos[n] = (uint32_t)at;
+                lengths[n] = (uint32_t)sl;
+            }
+            bytes += sl << nl;
+        });
+        *count = n;
+        if (!fits) {
+            set_error("pss_near_seeds: %u queries need %llu bytes, more than the %llu bytes of out", n, (unsigned long long)bytes,
+                      (unsigned long long)cap);
+            return PSS_EINVAL;
+        }
+        return PSS_OK;
+    });
 }
 
 namespace {

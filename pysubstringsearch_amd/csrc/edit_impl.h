@@ -13,7 +13,9 @@
 // one of its candidates stands, and the ONE hit kept for it is the standing candidate with the smallest d and, among
 // equal d (one piece a prefix of the other, `aab` + `aa`), the smallest j: EditMatch::at lets a hit stand only when no
 // earlier piece stands at the same d, EditMatch::before asks for a standing candidate in front of d.
-// Bytes are exact (no fold).
+// Bytes are exact (no fold) in the <false> forms below.  The <true> forms compare under ASCII case folding:
+// the pattern is folded to lower case already and the text is folded on load -- fold8 on 8-byte words, one byte in
+// edit_side's fetch --, and a query is a spelling of the seed of a piece, not a piece: see EditMatch<true>.
 //
 // Bounds.  edit_side reads the text one byte at a time, at an index it has checked to lie in [0, n), and stops at the
 // first index that does not or that holds a 0x0A (a WALL): it needs no entry bounds, never reads below 0 and never takes a
@@ -43,7 +45,8 @@ __device__ __forceinline__ u32 edit_cell(u32 left, u32 diag, u32 up, u32 w, u32 
 // as kEditInf.  Row i of the DP (i pattern bytes taken) lives in r0 .. r6, columns t = i - 3 .. i + 3, and w0 .. w6 are
 // the text bytes of those columns; a row shifts the window by one byte.  The loop ends at m or as soon as a whole row
 // is above the budget: at most L trips of 7 cells.
-template <bool kBack>
+// kFold: the text byte is folded to lower case as it is fetched (a newline is none of A-Z: the walls are unchanged).
+template <bool kBack, bool kFold>
 __device__ __forceinline__ u32 edit_side(const u8 *text, u32 n, u32 at, const u8 *pat, u32 m, u32 budget)
 {
     if (m == 0) return 0;
@@ -55,7 +58,8 @@ __device__ __forceinline__ u32 edit_side(const u8 *text, u32 n, u32 at, const u8
     auto next = [&]() -> u32 {
         const bool in = !wall && (kBack ? taken < at : (u64)at + taken < n);
         const u32 idx = in ? (kBack ? at - 1 - taken : at + taken) : 0u;
-        const u32 b = text[idx];
+        const u32 b0 = text[idx];
+        const u32 b = kFold && b0 - 'A' < 26u ? b0 | 0x20u : b0;
         wall = !in || b == '\n';
         taken += wall ? 0u : 1u;
         return wall ? kEditWall : b;
@@ -86,20 +90,23 @@ __device__ __forceinline__ u32 edit_side(const u8 *text, u32 n, u32 at, const u8
 }
 
 // Does the candidate (piece [off, off + len) of pat, exact at d) stand?
+template <bool kFold>
 __device__ __forceinline__ bool edit_stands(const ChunkDesc &ch, const u8 *pat, u32 plen, u32 off, u32 len, u32 d, u32 budget)
 {
-    const u32 lc = edit_side<true>(ch.text, ch.n, d, pat, off, budget);
+    const u32 lc = edit_side<true, kFold>(ch.text, ch.n, d, pat, off, budget);
     if (lc > budget) return false;
-    return edit_side<false>(ch.text, ch.n, d + len, pat + off + len, plen - off - len, budget - lc) <= budget - lc;
+    return edit_side<false, kFold>(ch.text, ch.n, d + len, pat + off + len, plen - off - len, budget - lc) <= budget - lc;
 }
 
 // Is text[d + from, d + len) the piece's bytes [from, len)?  The piece must end inside the text: behind n stands zero
-// padding, which a piece that ends in 0x00 bytes would else be found in.
+// padding, which a piece that ends in 0x00 bytes would else be found in.  kFold: the text word is folded before the xor.
+template <bool kFold>
 __device__ __forceinline__ bool piece_at(const ChunkDesc &ch, u32 d, const u8 *piece, u32 from, u32 len)
 {
     if ((u64)d + len > ch.n) return false;
     for (u32 i = from; i < len; i += 8) {
-        u64 x = load_text8(ch.text + d + i) ^ load_u64_unaligned(piece + i);
+        const u64 tw = load_text8(ch.text + d + i);
+        u64 x = (kFold ? fold8(tw) : tw) ^ load_u64_unaligned(piece + i);
         const u32 rem = len - i;
         if (rem < 8) x &= (1ull << (8 * rem)) - 1ull;
         if (x) return false;
@@ -117,17 +124,21 @@ __device__ __forceinline__ bool piece_at(const ChunkDesc &ch, u32 d, const u8 *p
 // budget and base are group-wide, and everything that depends on gl -- the `p64 <= last` branch, the loop over the word's
 // start positions, the loop over the pieces whose prefix is equal and the DPs inside it -- closes before the ballot.
 // The loop is bounded by last - from, the inner ones by 8, by 4 and by the pattern's length: nothing spins.
+// kFold: both text words are folded before the candidate mask is formed, and the pieces' offsets are computed (piece_off:
+// `pos` is not read, under fold a query is no piece) -- arithmetic on group-wide values, so the invariant stands as it is.
+template <bool kFold>
 __device__ __forceinline__ bool edit_scan(const ChunkDesc &ch, u32 from, u32 last, const u8 *pat, u32 plen, const u32 *pos, u32 budget,
                                           u32 gl, u32 gbase)
 {
     const u32 np = budget + 1;
+    auto off_of = [&](u32 j) -> u32 { return kFold ? piece_off(j, plen, np) : pos[j]; };
     u64 pk[4], pm[4];
 #pragma unroll
     for (u32 j = 0; j < 4; ++j) {                                 // (constant indices: registers)
         pk[j] = 0;
         pm[j] = 0;
         if (j < np) {
-            const u32 off = pos[j], len = (j + 1 < np ? pos[j + 1] : plen) - off;
+            const u32 off = off_of(j), len = (j + 1 < np ? off_of(j + 1) : plen) - off;
             pm[j] = len >= 8 ? ~0ull : (1ull << (8 * len)) - 1ull;
             pk[j] = load_u64_unaligned(pat + off) & pm[j];
         }
@@ -137,7 +148,8 @@ __device__ __forceinline__ bool edit_scan(const ChunkDesc &ch, u32 from, u32 las
         bool found = false;
         if (p64 <= last) {
             const u32 p = (u32)p64;
-            const u64 w = load_text8(ch.text + p), nxt = load_text8(ch.text + p + 8);
+            const u64 w0 = load_text8(ch.text + p), nxt0 = load_text8(ch.text + p + 8);
+            const u64 w = kFold ? fold8(w0) : w0, nxt = kFold ? fold8(nxt0) : nxt0;
             const u32 left = last - p + 1, nv = left < 8 ? left : 8u;        // start positions of this word inside the range
             // bit 4 k + j: the first bytes of piece j stand at start position k of this word (straight-line code: one
             // loop less around the DPs, whose lane masks the scalar registers have to hold)
@@ -152,8 +164,8 @@ __device__ __forceinline__ bool edit_scan(const ChunkDesc &ch, u32 from, u32 las
             while (cand && !found) {                              // (rare: ascending positions, and pieces inside one)
                 const u32 bit = (u32)__builtin_ctz(cand), k = bit >> 2, j = bit & 3;
                 cand &= cand - 1;
-                const u32 off = pos[j], len = (j + 1 < np ? pos[j + 1] : plen) - off;
-                if (piece_at(ch, p + k, pat + off, len < 8 ? len : 8u, len)) found = edit_stands(ch, pat, plen, off, len, p + k, budget);
+                const u32 off = off_of(j), len = (j + 1 < np ? off_of(j + 1) : plen) - off;
+                if (piece_at<kFold>(ch, p + k, pat + off, len < 8 ? len : 8u, len)) found = edit_stands<kFold>(ch, pat, plen, off, len, p + k, budget);
             }
         }
         if ((u32)(__ballot(found) >> gbase) & ((1u << TG) - 1u)) return true;
@@ -162,7 +174,9 @@ __device__ __forceinline__ bool edit_scan(const ChunkDesc &ch, u32 from, u32 las
 }
 
 // The compare of the seeded path (seed_impl.h) within a budget of edits.  The queries v0 .. v1 are the pattern's at most 4
-// pieces, piece w at T.pos[w] inside it; the hit came from piece v, which is exact at di by construction.
+// pieces, piece w at T.pos[w] inside it; the hit came from piece v, which is exact at di by construction.  (The exact-byte
+// form; EditMatch<true> is stated below.)
+template <bool kFold>
 struct EditMatch {
     // An edit moves what stands behind it: the match around a piece hit neither starts at di - pos nor ends at
     // di - pos + L, so the frame rejects nothing, passes di through as m, and m_out[t] is di -- the position the dedupe
@@ -171,7 +185,7 @@ struct EditMatch {
     // The hit stands iff its candidate stands and no piece before v is exact at di and stands there too (the alignment's hit
     // is then THAT piece's).  The earlier pieces are judged first and through the same call as the hit's own: a piece in front
     // of v is exact at di only when it is a prefix of piece v or piece v of it, which one or two loads rule out.
-    static __device__ __forceinline__ void at(const ChunkDesc &ch, const SeedTerms &T, u32 g, u32 v0, u32 v1, u32 v, u32 di, u32 m, u32 plen,
+    static __device__ __forceinline__ void at(const ChunkDesc &ch, const SeedTerms &T, u32 g, u32 v0, u32 v1, u32 v, u32 di, u32 &m, u32 plen,
                                               u32 &ls, u32 &ll)
     {
         const u32 budget = T.budget[g];
@@ -179,8 +193,8 @@ struct EditMatch {
         bool ok = false;
         for (u32 w = v0; w <= v; ++w) {                           // (at most 4 pieces)
             const u32 off = T.pos[w], len = (w + 1 < v1 ? T.pos[w + 1] : plen) - off;
-            if (w < v && !piece_at(ch, di, pat + off, 0, len)) continue;
-            const bool st = edit_stands(ch, pat, plen, off, len, di, budget);
+            if (w < v && !piece_at<false>(ch, di, pat + off, 0, len)) continue;
+            const bool st = edit_stands<false>(ch, pat, plen, off, len, di, budget);
             if (w < v && st) break;
             ok = st;
         }
@@ -189,6 +203,52 @@ struct EditMatch {
     static __device__ __forceinline__ bool before(const ChunkDesc &ch, const SeedTerms &T, u32 g, u32 from, u32 last, u32 plen, u32 gl,
                                                   u32 gbase)
     {
-        return edit_scan(ch, from, last, T.bytes + T.off[g], plen, T.pos + (u32)T.soff[g], T.budget[g], gl, gbase);
+        return edit_scan<false>(ch, from, last, T.bytes + T.off[g], plen, T.pos + (u32)T.soff[g], T.budget[g], gl, gbase);
+    }
+};
+
+// The same compare under ASCII case folding.  The pattern is folded to lower case; its queries are, piece
+// by piece, the spellings of the piece's SEED, so the hit at di says where the seed stands, not where its piece would: with
+// j the piece that holds T.pos[v] (piece_of; the bounds are computed, piece_off) the CANDIDATE position is
+// d = di - (T.pos[v] - off_j).  d < 0 or a piece that ends past n rejects the hit before anything is read.  Then piece j
+// must be fold-equal at d over its whole length (piece_at<true>, with its guard against the zero padding behind n: the
+// seed guarantees only its own bytes), the candidate (d, j) must stand (edit_side compares the folded text byte with the
+// pattern byte; walls as they are), and a piece j' < j that is fold-exact at d and stands there takes the hit.  The
+// position the dedupe looks before is d, not di: at() leaves it in m, and edit_scan<true> asks for a standing candidate in
+// [start, d).  Each candidate (d, j) has exactly one hit -- the seed of piece j stands at d + its offset in exactly one
+// spelling --, so one hit per matching entry survives: the standing candidate with the smallest d and, there, smallest j.
+// Bounds and the group-wide-ballot invariant are the exact form's (above, and seed_dedupe_kernel): edit_side judges every
+// index before it reads, piece_at checks the piece's end against n first, every tail is masked; before() passes group-wide
+// arguments only.  Every loop is bounded by the 4 pieces, by L, by 8 or by 7.  No LDS, no scratch.
+template <>
+struct EditMatch<true> {
+    static constexpr bool kFixedWindow = false;
+    static __device__ __forceinline__ void at(const ChunkDesc &ch, const SeedTerms &T, u32 g, u32, u32, u32 v, u32 di, u32 &m, u32 plen,
+                                              u32 &ls, u32 &ll)
+    {
+        const u32 budget = T.budget[g], np = budget + 1;
+        const u8 *pat = T.bytes + T.off[g];
+        const u32 sp = T.pos[v], j = piece_of(sp, plen, np);
+        const u32 oj = piece_off(j, plen, np), back = sp - oj;
+        if (di < back) return;
+        const u32 d = di - back;
+        if (!piece_at<true>(ch, d, pat + oj, 0, piece_off(j + 1, plen, np) - oj)) return;     // (false where the piece ends past n)
+        bool ok = false;
+        for (u32 w = 0; w <= j; ++w) {                            // (at most 4 pieces)
+            const u32 off = piece_off(w, plen, np), len = piece_off(w + 1, plen, np) - off;
+            if (w < j && !piece_at<true>(ch, d, pat + off, 0, len)) continue;
+            const bool st = edit_stands<true>(ch, pat, plen, off, len, d, budget);
+            if (w < j && st) break;
+            ok = st;
+        }
+        if (ok) {
+            entry_bounds(ch, di, ls, ll);
+            m = d;
+        }
+    }
+    static __device__ __forceinline__ bool before(const ChunkDesc &ch, const SeedTerms &T, u32 g, u32 from, u32 last, u32 plen, u32 gl,
+                                                  u32 gbase)
+    {
+        return edit_scan<true>(ch, from, last, T.bytes + T.off[g], plen, nullptr, T.budget[g], gl, gbase);
     }
 };

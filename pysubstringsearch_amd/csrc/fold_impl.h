@@ -53,7 +53,7 @@ struct FoldMatch {
     static constexpr bool kFixedWindow = true;      // the term stands at m = di - pos or not at all: the frame rejects a window that leaves the chunk
     // The whole term at m under fold (the bytes outside the seed are what is unknown; the term holds no 0x0A, so a match
     // cannot leave its entry), then the entry's bounds.
-    static __device__ __forceinline__ void at(const ChunkDesc &ch, const SeedTerms &T, u32 g, u32, u32, u32, u32 di, u32 m, u32 plen,
+    static __device__ __forceinline__ void at(const ChunkDesc &ch, const SeedTerms &T, u32 g, u32, u32, u32, u32 di, u32 &m, u32 plen,
                                               u32 &ls, u32 &ll)
     {
         if (fold_equal(ch.text, m, T.bytes + T.off[g], plen)) entry_bounds(ch, di, ls, ll);

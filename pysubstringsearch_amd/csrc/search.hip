@@ -2340,8 +2340,13 @@ int Batch::candidates(u64 H, u32 grid)
         // survivors against the entry in front of them: one candidate per entry, its leftmost match
         PSS_TRY(take(Q_SEED_M, H * 4, d_m));
         const SeedTerms T{d_fbytes, d_foff, d_soff, d_pos, d_nk};
-        auto *hits = edits ? seed_hits_kernel<EditMatch> : near ? seed_hits_kernel<NearMatch> : seed_hits_kernel<FoldMatch>;
-        auto *dedupe = edits ? seed_dedupe_kernel<EditMatch> : near ? seed_dedupe_kernel<NearMatch> : seed_dedupe_kernel<FoldMatch>;
+        // (six instantiations: fold; within a budget of mismatches or edits, each in exact bytes or, fold_near, under fold)
+        auto *hits = edits  ? (fold_near ? seed_hits_kernel<EditMatch<true>> : seed_hits_kernel<EditMatch<false>>)
+                     : near ? (fold_near ? seed_hits_kernel<NearMatch<true>> : seed_hits_kernel<NearMatch<false>>)
+                            : seed_hits_kernel<FoldMatch>;
+        auto *dedupe = edits  ? (fold_near ? seed_dedupe_kernel<EditMatch<true>> : seed_dedupe_kernel<EditMatch<false>>)
+                       : near ? (fold_near ? seed_dedupe_kernel<NearMatch<true>> : seed_dedupe_kernel<NearMatch<false>>)
+                              : seed_dedupe_kernel<FoldMatch>;
         hipLaunchKernelGGL(hits, dim3(grid), dim3(256), 0, s, d_chunks, nc, T, d_lo, d_cnt, nrp, d_hitoff, H, d_start, d_len, d_m, d_gdrv);
         hipLaunchKernelGGL(dedupe, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, T, nrp, d_hitoff, H, d_start, d_m, d_len, d_gdrv);
         verify<true>(vgrid, H, d_fbytes, d_foff, d_tcnt);
@@ -2441,7 +2446,8 @@ int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, const LineDes
     case REQUEST_SEEDED:
         set_error("search: a seeded batch states its groups, its terms' bytes and offsets, the seed queries' offsets and positions, "
                   "and either exclude flags or sequence anchors; with budgets its groups are one include term each and it has no "
-                  "sequence anchors; budgets count edits only where there are budgets");
+                  "sequence anchors; budgets count edits, or are counted under fold, only where there are budgets, and under fold no "
+                  "term excludes");
         return PSS_EINVAL;
     case REQUEST_CLASS:
         set_error("search: a class batch is a sequence batch that states its segments' bytes, class plane, offsets, group offsets, "

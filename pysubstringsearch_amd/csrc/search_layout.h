@@ -55,9 +55,14 @@ struct SearchRequest {
     //   and its queries are its k + 1 pieces, left to right.
     //   near_edits, with near_budget alone: the budget counts EDITS -- insertions, deletions and substitutions of single
     //   bytes (edit_impl.h) -- instead of substitutions.  Everything else of the request is near's.
+    //   near_fold, with near_budget alone, with or without near_edits: the budget is counted under ASCII CASE FOLDING
+    //   (DESIGN.md 4.19).  term_bytes holds the patterns folded to lower case; a pattern's queries are, piece by piece, the
+    //   spellings of the piece's seed (ascending), each at the seed's position inside the PATTERN.  A query is then no
+    //   piece: the device computes the pieces' bounds from a pattern's length and budget.  No exclude flag is set.
     const uint8_t *term_bytes = nullptr; const uint64_t *term_offsets = nullptr; uint32_t nterms = 0;
     const uint64_t *seed_offsets = nullptr; const uint32_t *seed_pos = nullptr; const uint8_t *near_budget = nullptr;
     bool near_edits = false;
+    bool near_fold = false;
     // class_bytes .. class_void, together with group_offsets and seq_anchors: a sequence batch whose segments hold BYTE CLASSES
     // (`?`, `[...]`) beside literal bytes (seq_class_impl.h).  The nq patterns -- under fold the nterms terms -- are
     // then the CORES of the segments that have one (a segment's longest run of literal positions), group_offsets index them, and
@@ -115,12 +120,15 @@ enum RequestVerdict {
 
 // A seeded batch carries its groups, its terms and the queries' offsets and positions, and either exclude flags or sequence
 // anchors; it excludes anchors, SEARCH_DEVICE and low_latency; a budget adds: identity groups of one include term each, no
-// sequence anchors; near_edits says how a budget is counted and is legal with one alone.
+// sequence anchors; near_edits says how a budget is counted and is legal with one alone; near_fold says that it is counted
+// under fold, is legal with one alone too, and then no term excludes and there is no class block.
 inline bool seeded_request_ok(const SearchRequest &rq)
 {
     bool ok = rq.seed_offsets && rq.seed_pos && rq.group_offsets && rq.term_bytes && rq.term_offsets &&
               (!rq.nterms || rq.exclude || rq.seq_anchors) && !rq.anchors && rq.mode != SEARCH_DEVICE && !rq.low_latency;
     ok = ok && (rq.near_budget || !rq.near_edits);
+    ok = ok && (!rq.near_fold || (rq.near_budget && !rq.seq_anchors && !rq.class_bytes && rq.exclude));
+    for (uint32_t t = 0; ok && rq.near_fold && t < rq.nterms; ++t) ok = rq.exclude[t] == 0;
     if (rq.near_budget) {
         ok = ok && !rq.seq_anchors && rq.exclude && rq.ngroups == rq.nterms;
         for (uint32_t g = 0; ok && g < rq.ngroups; ++g) ok = rq.group_offsets[g] == g && rq.group_offsets[g + 1] == (uint64_t)g + 1;
@@ -145,7 +153,7 @@ inline RequestVerdict check_request(const SearchRequest &rq, uint32_t nc, bool h
     if (rq.anchors && (rq.mode == SEARCH_DEVICE || rq.low_latency)) return REQUEST_ANCHORED;
     if (rq.group_offsets && (rq.anchors || (rq.nq && !rq.exclude && !rq.seq_anchors) || rq.mode == SEARCH_DEVICE || rq.low_latency))
         return REQUEST_ALL_TERMS;
-    if ((rq.seed_offsets || rq.seed_pos || rq.near_budget || rq.near_edits) && !seeded_request_ok(rq)) return REQUEST_SEEDED;
+    if ((rq.seed_offsets || rq.seed_pos || rq.near_budget || rq.near_edits || rq.near_fold) && !seeded_request_ok(rq)) return REQUEST_SEEDED;
     if ((rq.class_bytes || rq.class_plane || rq.class_offsets || rq.class_groups || rq.class_cores || rq.class_sets || rq.class_void ||
          rq.class_nsegs || rq.class_nsets) &&
         !class_request_ok(rq))
@@ -163,6 +171,7 @@ struct BatchShape {
     bool seeded;                        // terms looked up through seed queries: group -> terms -> queries (seed_impl.h)
     bool near;                          // ... within k mismatches (near_impl.h); else under fold (fold_impl.h, 4.14)
     bool edits;                         // near, and the budget counts edits: EditMatch in NearMatch's place (edit_impl.h, 4.17)
+    bool fold_near;                     // near, and the budget is counted under fold: the <true> forms of either Match (4.19)
     bool sa_order;
     // An all-terms batch (all_terms_impl.h) has a second pair space: its nq queries are terms, its result rows are the ng
     // groups, and everything from the first scan on runs over (group, chunk) pairs.  For every other batch the two agree.
@@ -187,6 +196,7 @@ struct BatchShape {
         seeded = terms && rq.seed_offsets != nullptr;
         near = seeded && rq.near_budget != nullptr;
         edits = near && rq.near_edits;
+        fold_near = near && rq.near_fold;
         // (counts do not depend on the order; one hit per entry has one order; an all-terms batch keeps its driver's text order)
         sa_order = rq.sa_order && !counts && !anchored && !terms;
         nrow = rq.rows();

@@ -75,7 +75,9 @@ __global__ __launch_bounds__(256) void seed_union_kernel(u32 nc, const u64 *soff
 // and m.  That reject is right for a Match with a FIXED WINDOW (Match::kFixedWindow: fold, near).  Under edits
 // (EditMatch) it is wrong -- a deletion left of the piece lets the match start behind di - pos, one right of it lets it
 // end before di - pos + L, so a match flush with the chunk's start or end would be lost --: there the frame passes di
-// through, m is di itself, and what m_out[t] means is "the position the dedupe looks before".
+// through, m is di itself, and what m_out[t] means is "the position the dedupe looks before".  Match::at takes m by
+// reference: a Match whose candidate does not stand where its query was found (EditMatch<true>, DESIGN.md 4.19: the query
+// is the seed of a piece) leaves the candidate's position there; every other Match leaves m alone.
 template <typename Match>
 __global__ __launch_bounds__(256) void seed_hits_kernel(const ChunkDesc *chunks, u32 nc, SeedTerms T, const u32 *lo, const u32 *cnt, u64 ngq,
                                                           const u64 *hit_off, u64 H, u32 *start_out, u32 *len_out, u32 *m_out, const u32 *g_drv)
