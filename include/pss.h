@@ -897,6 +897,40 @@ int pss_reader_count_near_icase_batch(pss_reader *r, const uint8_t *qbytes, cons
  * too small (*count is set). */
 int pss_near_seeds(const uint8_t *pat, uint64_t len, uint32_t k, int32_t letters, uint8_t *out, uint64_t cap, uint32_t *piece,
                    uint32_t *pos, uint32_t *lengths, uint32_t *count);
+/*
+ * MATCH SPANS (no reference counterpart): where in an entry a pattern's best match stands, how long it is and how close, for
+ * rows of (entry id, pattern) -- the third call beside "which entries" (the *_ids_batch calls) and "their text"
+ * (pss_reader_entries_by_id).  12 bytes per row come down; no text does.
+ * Rows id_offsets[q] .. id_offsets[q + 1] of `ids` belong to pattern q (bytes qbytes[qoffsets[q], qoffsets[q + 1]), budget k[q]
+ * = 0 .. 3); out[i] answers ids[i], in the order given.  Repeated ids, and ids of several chunks in any order, are fine.
+ * flags: PSS_SPAN_EDITS -- the budget counts edits, not substituted bytes; PSS_SPAN_ICASE -- bytes are equal as in
+ * pss_reader_search_near_icase_batch (after folding A-Z to a-z, nothing else), else exactly.
+ * Let e be the entry's true bytes (text[start, newline), or text[start, n) for an unterminated last entry) and p the pattern.  A
+ * candidate is a substring e[s, s + l): without EDITS l = |p| and its distance d is the number of differing bytes; with EDITS
+ * any l >= 1 and d = lev(e[s, s + l), p) over bytes.  It counts only if d <= k, and it lies inside the entry by construction
+ * (e holds no newline).  The row's answer is the candidate with the least (d, s, -l): closest first, then leftmost, then
+ * longest -- {start = s, length = l, distance = d}, offsets in BYTES from the entry's first byte.  A row with no candidate is
+ * {-1, 0, -1}: a legal row, not an error, since ids may come from anywhere.  A pattern that holds 0x0A gives {-1, 0, -1} in all
+ * its rows (the search calls' rule).  Hence distance >= 0 exactly for the ids pss_reader_search_near_ids_batch /
+ * _edit_ids_batch / _near_icase_ids_batch return for the same pattern and budget, and without EDITS length == |p|.
+ * "Closest first" is deliberate: the search keeps an entry's LEFTMOST match within budget, but `passw0rd` is not what to
+ * highlight in a line that also holds `password`.
+ * PSS_EINVAL (message in pss_last_error, out untouched), judged before the reader is looked at and before anything is launched,
+ * as the near calls do: an empty pattern; a pattern of at most k bytes; k > 3; unknown flag bits; id_offsets that do not ascend
+ * from 0; null pointers where rows or patterns exist.  Then, with pss_reader_entries_by_id's message: an id of a chunk this
+ * reader does not hold, or a line past the chunk's last entry.  nq = 0, or zero rows, is PSS_OK and writes nothing.
+ * A multi-device reader splits the rows by part and puts the answers back in the order asked; a sharded reader answers for the
+ * chunks it holds.  The scan: one wavefront per row, 64 start positions a step; one wait on the stream.
+ * pss_reader_last_stats is left as it was.
+ * Out of scope: spans of wildcard pieces and of all-terms groups (call once per term); more than one span per entry; spans
+ * straight out of the search calls.
+ */
+typedef struct pss_span { int32_t start, length, distance; } pss_span;
+#define PSS_SPAN_EDITS 1u
+#define PSS_SPAN_ICASE 2u
+int pss_reader_match_spans(pss_reader *r, const uint64_t *ids, const uint64_t *id_offsets /* nq + 1 */, const uint8_t *qbytes,
+                           const uint64_t *qoffsets, uint32_t nq, const uint8_t *k, uint32_t flags,
+                           pss_span *out /* id_offsets[nq] rows, the caller's */);
 /* For the first `cap` resident chunks, in file order: index in the file and number of entries; *num = resident chunks. */
 int pss_reader_chunk_entries(pss_reader *r, uint64_t *chunk_index, uint64_t *entries, uint64_t cap, uint64_t *num);
 /*

@@ -1240,6 +1240,65 @@ class Reader:
         ``edits=True``: inserted, deleted or substituted; with ``icase=True``: whatever the case of ASCII letters."""
         return self.count_near_bytes([_utf8(s, 'substring')], _near_budget(k), edits, icase=icase)[0]
 
+    @staticmethod
+    def _span_ids(ids, counts, npatterns: int):
+        """(ids as uint64, id offsets as uint64) of one span batch; ``ValueError`` when ``counts`` has another length than
+        the patterns or another sum than ``ids`` has entries."""
+        import numpy as np
+        arr = np.ascontiguousarray(np.asarray(ids).reshape(-1) if len(ids) else np.zeros(0, dtype=np.uint64))
+        if arr.dtype != np.uint64:
+            if arr.dtype.kind not in 'iu':
+                raise TypeError('entry ids must be integers')
+            if arr.dtype.kind == 'i' and arr.size and int(arr.min()) < 0:
+                raise ValueError('entry ids are not negative')
+            arr = arr.astype(np.uint64)
+        cnt = np.asarray(counts).reshape(-1) if len(counts) else np.zeros(0, dtype=np.uint64)
+        if cnt.dtype.kind not in 'iu':
+            raise TypeError('counts must be integers')
+        if cnt.dtype.kind == 'i' and cnt.size and int(cnt.min()) < 0:
+            raise ValueError('counts are not negative')
+        if cnt.size != npatterns:
+            raise ValueError(f'{cnt.size} counts for {npatterns} patterns')
+        offs = np.zeros(npatterns + 1, dtype=np.uint64)
+        np.cumsum(cnt.astype(np.uint64), out=offs[1:])
+        if int(offs[-1]) != arr.size:
+            raise ValueError(f'the counts add up to {int(offs[-1])} rows, ids has {arr.size}')
+        return arr, offs
+
+    def match_spans_batch(self, ids, counts, patterns: typing.Sequence[bytes], k=1, edits: bool = False, *, icase: bool = False):
+        """Extension: WHERE and HOW CLOSELY entries match -- for the ids and counts of an ``IdResult`` (``counts[q]`` ids
+        in a row belong to pattern q; any ids will do, repeated or of several chunks) the best match of each entry's pattern
+        as a numpy int32 array ``[len(ids), 3]`` with the columns ``start, length, distance``, row i answering ``ids[i]``.
+        ``patterns``, ``k``, ``edits`` and ``icase`` are ``search_near_ids_batch``'s, argument for argument, with the same
+        checks: the call that explains an answer takes what the call that found it took.
+
+        A candidate is a substring of the entry: without ``edits`` a window of ``len(pattern)`` bytes, its distance the
+        number of differing bytes; with ``edits`` any non-empty substring, its distance the Levenshtein distance over bytes
+        (``icase``: bytes equal after folding ``A-Z`` to ``a-z`` cost nothing).  Among the candidates within ``k`` the row is
+        the CLOSEST, then the leftmost, then the longest -- ``passw0rd password`` is highlighted at ``password``.  An entry
+        with no candidate within ``k`` is ``(-1, 0, -1)``, and so is every row of a pattern that holds a newline; hence
+        ``distance >= 0`` exactly for the ids ``search_near_ids_batch`` returns, and ``length == len(pattern)`` without
+        ``edits``.  Offsets count BYTES from the entry's first byte: slice the entry's bytes,
+        ``entry_bytes[start:start + length]``, not its decoded text, where entries hold UTF-8.
+        ``ValueError`` when ``sum(counts) != len(ids)`` or ``len(counts) != len(patterns)``, and for an id of a chunk this
+        reader does not hold or a line its chunk does not have (``entries_by_id``).  The scan runs on the device, one
+        wavefront per row; 12 bytes per row come down and no text (include/pss.h, pss_reader_match_spans)."""
+        import numpy as np
+        blob, offs, ks = self._near_args(patterns, k, edits, icase)
+        nq = len(offs) - 1
+        arr, id_offs = self._span_ids(ids, counts, nq)
+        out = np.empty((arr.size, 3), dtype=np.int32)
+        flags = (_ffi.SPAN_EDITS if edits else 0) | (_ffi.SPAN_ICASE if icase else 0)
+        _ffi.check(_lib.pss_reader_match_spans(self._handle(), arr.ctypes.data, id_offs.ctypes.data, blob, offs.ctypes.data, nq,
+                                               ks.ctypes.data, flags, out.ctypes.data))
+        return out
+
+    def match_spans(self, ids, pattern, k: int = 1, edits: bool = False, *, icase: bool = False):
+        """Extension: ``match_spans_batch`` for ONE pattern (bytes, or a str that is UTF-8 encoded) and the ids it is asked
+        about: int32 ``[len(ids), 3]``, columns ``start, length, distance`` in bytes."""
+        pat = pattern.encode('utf-8') if isinstance(pattern, str) else pattern
+        return self.match_spans_batch(ids, [len(ids)], [pat], _near_budget(k), edits, icase=icase)
+
     @property
     def entry_counts(self) -> typing.Dict[int, int]:
         """Extension: entries of every chunk this reader holds, keyed by the chunk's index in the index file."""

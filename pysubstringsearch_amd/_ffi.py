@@ -153,6 +153,7 @@ ROUTES = {
 
 # Anchors of the anchored search (PSS_ANCHOR_* in include/pss.h): where in the entry the pattern must sit.
 ANCHORS = {'start': 1, 'end': 2, 'entry': 3}
+SPAN_EDITS, SPAN_ICASE = 1, 2      # pss_reader_match_spans flags (include/pss.h)
 ANCHOR_START, ANCHOR_END = 1, 2
 SEQ_FOLD = 1        # PSS_SEQ_FOLD: the flags word of the pss_reader_search_seqc_* calls
 
@@ -324,6 +325,7 @@ def _load() -> ctypes.CDLL:
         'pss_reader_search_near_icase_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, ctypes.c_int, pvp]),
         'pss_reader_search_near_icase_ids_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, ctypes.c_int, pvp]),
         'pss_reader_count_near_icase_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, ctypes.c_int, vp]),
+        'pss_reader_match_spans': (ctypes.c_int, [vp, vp, vp, vp, vp, u32, vp, u32, vp]),
         'pss_near_seeds': (ctypes.c_int, [vp, u64, u32, i32, vp, u64, ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(u32),
                                           ctypes.POINTER(u32)]),
         'pss_near_pieces': (ctypes.c_int, [vp, u64, u32, ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(u32)]),

@@ -2154,15 +2154,12 @@ extern "C" int pss_near_seeds(const uint8_t *pat, uint64_t len, uint32_t k, int3
 
 namespace {
 
-// ids[0 .. n) of ONE single-device reader: validation on the host (the reader knows every chunk's entry count once the
-// line tables exist), select + copy on the device.
-int reader_entries_single(pss_reader *x, const uint64_t *ids, uint64_t n, HostResult *res)
+// ids[0 .. n) of ONE single-device reader as (resident chunk, line) pairs, validated on the host (the reader knows every
+// chunk's entry count once the line tables exist).
+int reader_resolve_ids(pss_reader *x, const uint64_t *ids, uint64_t n, std::vector<uint32_t> &chunk_of, std::vector<uint32_t> &line_of)
 {
-    std::lock_guard<std::recursive_mutex> lk(x->ctx->mu);
-    PSS_HIP(hipSetDevice(x->device));
-    PSS_TRY(reader_sync_descs(x));
-    PSS_TRY(reader_ensure_lines(x));
-    std::vector<uint32_t> chunk_of(n), line_of(n);
+    chunk_of.resize(n);
+    line_of.resize(n);
     size_t at = 0;                                   // (consecutive ids mostly name the same chunk)
     for (uint64_t i = 0; i < n; ++i) {
         const uint64_t c = ids[i] >> 32;
@@ -2181,7 +2178,43 @@ int reader_entries_single(pss_reader *x, const uint64_t *ids, uint64_t n, HostRe
         chunk_of[i] = (uint32_t)at;
         line_of[i] = line;
     }
+    return PSS_OK;
+}
+
+// ids[0 .. n) of ONE single-device reader: validation on the host, select + copy on the device.
+int reader_entries_single(pss_reader *x, const uint64_t *ids, uint64_t n, HostResult *res)
+{
+    std::lock_guard<std::recursive_mutex> lk(x->ctx->mu);
+    PSS_HIP(hipSetDevice(x->device));
+    PSS_TRY(reader_sync_descs(x));
+    PSS_TRY(reader_ensure_lines(x));
+    std::vector<uint32_t> chunk_of, line_of;
+    PSS_TRY(reader_resolve_ids(x, ids, n, chunk_of, line_of));
     return entries_by_id_device(x->ctx, x->d_descs, x->d_lines, chunk_of.data(), line_of.data(), n, res);
+}
+
+// The judged patterns of a span batch as the device reads them: folded to lower case under ICASE, kSpanPatPad zero bytes
+// behind them, and per pattern whether it holds a newline (then all its rows are no match).
+struct SpanPatterns {
+    std::vector<uint8_t> bytes, has_nl;
+    const uint64_t *off;
+    const uint8_t *k;
+    uint32_t nq;
+    bool edits, fold;
+};
+
+// Rows of ONE single-device reader: ids[i] against pattern pat_of[i]; out[i] answers ids[i].
+int reader_spans_single(pss_reader *x, const uint64_t *ids, const uint32_t *pat_of, uint64_t n, const SpanPatterns &P, pss_span *out)
+{
+    std::lock_guard<std::recursive_mutex> lk(x->ctx->mu);
+    PSS_HIP(hipSetDevice(x->device));
+    PSS_TRY(reader_sync_descs(x));
+    PSS_TRY(reader_ensure_lines(x));
+    std::vector<uint32_t> chunk_of, line_of;
+    PSS_TRY(reader_resolve_ids(x, ids, n, chunk_of, line_of));
+    static_assert(sizeof(pss_span) == 12, "three int32 a row");
+    return match_spans_device(x->ctx, x->d_descs, x->d_lines, chunk_of.data(), line_of.data(), pat_of, n, P.bytes.data(), P.off, P.nq, P.k,
+                              P.has_nl.data(), P.edits, P.fold, reinterpret_cast<int32_t *>(out));
 }
 
 }  // namespace
@@ -2254,6 +2287,101 @@ extern "C" int pss_reader_entries_by_id(pss_reader *r, const uint64_t *ids, uint
         }
         drop.p = nullptr;
         *out = res;
+        return PSS_OK;
+    });
+}
+
+extern "C" int pss_reader_match_spans(pss_reader *r, const uint64_t *ids, const uint64_t *id_offsets, const uint8_t *qbytes,
+                                      const uint64_t *qoffsets, uint32_t nq, const uint8_t *k, uint32_t flags, pss_span *out)
+{
+    return guarded([&]() -> int {
+        const char *who = "pss_reader_match_spans";
+        if (nq && (!id_offsets || !qbytes || !qoffsets || !k)) {
+            set_error("%s: bad arguments", who);
+            return PSS_EINVAL;
+        }
+        const bool edits = (flags & PSS_SPAN_EDITS) != 0, fold = (flags & PSS_SPAN_ICASE) != 0;
+        const char *unit = edits ? "edits" : "mismatches";
+        PSS_TRY(pattern_args(who, qoffsets, nq, [&](uint32_t q, uint64_t len) {
+            if (k[q] > kNearMaxBudget) {
+                set_error("%s: pattern %u has a budget of %u %s: 0 .. %u", who, q, (unsigned)k[q], unit, kNearMaxBudget);
+                return false;
+            }
+            if (len <= k[q]) {
+                set_error("%s: pattern %u has %llu bytes and a budget of %u %s (a pattern is longer than its budget)", who, q,
+                          (unsigned long long)len, (unsigned)k[q], unit);
+                return false;
+            }
+            return true;
+        }));
+        if (flags & ~(PSS_SPAN_EDITS | PSS_SPAN_ICASE)) {
+            set_error("%s: unknown flag bits %#x (PSS_SPAN_EDITS | PSS_SPAN_ICASE)", who, flags);
+            return PSS_EINVAL;
+        }
+        if (nq && id_offsets[0] != 0) {
+            set_error("%s: the id offsets start at %llu, not at 0", who, (unsigned long long)id_offsets[0]);
+            return PSS_EINVAL;
+        }
+        for (uint32_t q = 0; q < nq; ++q)
+            if (id_offsets[q + 1] < id_offsets[q]) {
+                set_error("%s: the id offsets decrease at pattern %u", who, q);
+                return PSS_EINVAL;
+            }
+        const uint64_t n = nq ? id_offsets[nq] : 0;
+        if (n && (!ids || !out)) {
+            set_error("%s: bad arguments (%llu rows without ids or room for the answer)", who, (unsigned long long)n);
+            return PSS_EINVAL;
+        }
+        if (!r) {
+            set_error("%s: bad arguments (no reader)", who);
+            return PSS_EINVAL;
+        }
+        if (n == 0) return PSS_OK;
+        SpanPatterns P;
+        const uint64_t total = qoffsets[nq];
+        P.bytes.assign((size_t)total + kSpanPatPad, 0);
+        for (uint64_t i = 0; i < total; ++i)
+            P.bytes[i] = (uint8_t)(fold && (uint8_t)(qbytes[i] - 'A') < 26 ? qbytes[i] | 0x20 : qbytes[i]);
+        P.has_nl.resize(nq);
+        for (uint32_t q = 0; q < nq; ++q) P.has_nl[q] = memchr(qbytes + qoffsets[q], '\n', (size_t)(qoffsets[q + 1] - qoffsets[q])) ? 1 : 0;
+        P.off = qoffsets;
+        P.k = k;
+        P.nq = nq;
+        P.edits = edits;
+        P.fold = fold;
+        std::vector<uint32_t> pat_of(n);
+        for (uint32_t q = 0; q < nq; ++q)
+            for (uint64_t i = id_offsets[q]; i < id_offsets[q + 1]; ++i) pat_of[i] = q;
+        if (r->parts.empty()) return reader_spans_single(r, ids, pat_of.data(), n, P, out);
+        // every part answers the rows of its chunks (one part after the other), then the answers go back in the order asked
+        std::lock_guard<std::mutex> batch(r->multi_mu);
+        const size_t G = r->parts.size();
+        std::vector<std::vector<uint64_t>> sub(G), row_of(G);
+        std::vector<std::vector<uint32_t>> sub_pat(G);
+        for (uint64_t i = 0; i < n; ++i) {
+            const uint64_t c = ids[i] >> 32;
+            size_t g = 0;
+            for (; g < G; ++g) {
+                const std::vector<uint64_t> &fi = r->parts[g]->reader->file_index;
+                if (std::find(fi.begin(), fi.end(), c) != fi.end()) break;
+            }
+            if (g == G) {
+                set_error("entry id %#llx: this reader does not hold chunk %llu", (unsigned long long)ids[i], (unsigned long long)c);
+                return PSS_EINVAL;
+            }
+            sub[g].push_back(ids[i]);
+            sub_pat[g].push_back(pat_of[i]);
+            row_of[g].push_back(i);
+        }
+        // (into a buffer of its own first: an id that a part refuses must leave `out` untouched)
+        std::vector<pss_span> all(n), part;
+        for (size_t g = 0; g < G; ++g) {
+            if (sub[g].empty()) continue;
+            part.resize(sub[g].size());
+            PSS_TRY(reader_spans_single(r->parts[g]->reader, sub[g].data(), sub_pat[g].data(), sub[g].size(), P, part.data()));
+            for (size_t j = 0; j < part.size(); ++j) all[row_of[g][j]] = part[j];
+        }
+        memcpy(out, all.data(), (size_t)n * sizeof(pss_span));
         return PSS_OK;
     });
 }

@@ -2,6 +2,7 @@
 #pragma once
 #include "common.h"
 #include "search_layout.h"      // SearchMode, SearchRequest, the rules and the layouts of the batch driver
+#include "span_core.h"          // kSpanPatPad: what the host leaves behind the patterns of a span batch
 
 namespace pss {
 
@@ -86,6 +87,14 @@ int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, const LineDes
 // packed result of n "queries" with one entry each, in the order asked.
 int entries_by_id_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, const LineDesc *d_lines, const uint32_t *chunk_of,
                          const uint32_t *line_of, uint64_t n, HostResult *res);
+
+// Match spans of `rows` (resident chunk, line) pairs the caller has validated, row i against pattern pat_of[i] of the nq
+// patterns (span_impl.h): out receives 3 x int32 per row -- start, length, distance, or -1, 0, -1 -- in the order asked.
+// The patterns are folded to lower case already where `fold`, and kSpanPatPad zero bytes follow them; pvoid[q] != 0
+// marks a pattern that holds a newline (all its rows are no match).  One wait on the stream.
+int match_spans_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, const LineDesc *d_lines, const uint32_t *chunk_of, const uint32_t *line_of,
+                       const uint32_t *pat_of, uint64_t rows, const uint8_t *pbytes, const uint64_t *poff, uint32_t nq, const uint8_t *budget,
+                       const uint8_t *pvoid, bool edits, bool fold, int32_t *out);
 
 // Merge of `world` packed results of the same nq queries, all resident on ctx's device, into one (query-major,
 // rank-major inside a query -- pss_merge_packed's order) on the same device.  starts[r] = entry starts (no closing

@@ -25,7 +25,7 @@
 // The entry-level kinds put their own kernels in K2's place (the *_impl.h files included below): anchored_impl.h,
 // all_terms_impl.h, sequence_impl.h, and seed_impl.h -- the one seeded verify path of the case-insensitive search
 // (fold_impl.h), the search within k mismatches (near_impl.h) and the search within k edits (edit_impl.h), which differ in
-// their compare alone.
+// their compare alone.  span_impl.h is no part of the pipeline: a call of its own, for ids that are known already.
 //
 // Output order: query-major, inside a query chunk-major, inside a chunk
 // suffix-array order of the kept hit (the reference's inter-chunk order is
@@ -1752,6 +1752,7 @@ static void newline_flags(const u8 *bytes, const u64 *off, u32 n, u8 set, u8 *fl
 #include "fold_impl.h"
 #include "near_impl.h"
 #include "edit_impl.h"
+#include "span_impl.h"
 
 // Suffix-array hits of the batch per chunk (pair p = query p / nc on chunk p % nc): one workgroup per chunk.
 __global__ __launch_bounds__(256) void chunk_hits_kernel(const u32 *cnt, u64 nq, u32 nc, u64 *out)
