@@ -17,12 +17,9 @@ constexpr int MSD_IPT = 16;
 constexpr uint32_t MSD_TILE = MSD_BLOCK * MSD_IPT;        // 8192 elements
 constexpr uint32_t MSD_TILE2 = 16384;                     // elements of a tile of the wide scatter kernels and the look-back pass
 constexpr uint32_t MSD_WIN = 6144;                        // buckets whose start falls into one window of this size share a tile ...
-#ifndef PSS_LS_WINDOW
-#define PSS_LS_WINDOW 8                                   // (members of its bin every element of the local sort reads unconditionally)
-#endif
-constexpr uint32_t MSD_TILE_CAP = 8184 - PSS_LS_WINDOW;   // ... unless that is more than a tile holds: then the window's last bucket goes alone
-                                                          // (the window's worth of slots behind a tile's last element hold the ranking's
-                                                          //  sentinels, the eight after those the fast kernel's scalars)
+constexpr uint32_t MSD_TILE_CAP = 8176;                   // ... unless that is more than a tile holds: then the window's last bucket goes alone
+                                                          // (the eight slots behind a tile's last element hold the sentinels of the fast
+                                                          //  kernel's ranking window -- at most eight wide --, the eight after those its scalars)
 constexpr uint32_t MSD_MAX_BUCKET = 4088;                 // a bucket must fit a tile on its own (the last eight slots of the LDS tile
                                                           // carry the fast kernel's scalars: MSD_TILE_CAP)
 constexpr int MSD_TAG_BITS = MSD_D + 1;                   // an element entering the local sort carries the low 11 bits of its joint bucket number ...

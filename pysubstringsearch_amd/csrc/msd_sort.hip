@@ -1282,19 +1282,26 @@ __global__ __launch_bounds__(MSD_BLOCK) void msd_local_sort_kernel(const u64 *in
 }
 
 
-// The fast form.  One counting pass on the top 12 bits of (bucket, key) with returning LDS atomics (no
+// The fast form.  One counting pass on the top 13 bits of (bucket, key) with returning LDS atomics (no
 // order to preserve: the whole element, index included, is the sort key, so the result is a total order
 // anyway) leaves bins of a handful of elements; every element then finds its place inside its bin by
 // counting the smaller ones -- neighbouring lanes sit in the same bin, so those LDS reads are broadcasts.
-// A tile with a bin above LS_KMAX elements (many equal or nearly equal keys) is handed to the general
-// kernel instead.
+// A tile with more than LS_KMAX elements under one value of the top LS_DECLINE_BITS bits (many equal or
+// nearly equal keys) is handed to the general kernel instead.
+//
+// ONE array of counters: counts, scanned in place to the bins' starts; the slot atomics then run every start up
+// to its bin's end, which is the next bin's start whether or not either is empty -- the ranking reads the start
+// of bin b from entry b - 1, and a zero halfword in front of the array (the top of the tile's last, never used
+// slot) serves bin 0.  That leaves the 16 KiB behind the tile to 8192 bins instead of 4096 and their copy.
 #ifndef PSS_LS_BIN_BITS
-#define PSS_LS_BIN_BITS 12
+#define PSS_LS_BIN_BITS 13
 #endif
 constexpr int LS_BIN_BITS = PSS_LS_BIN_BITS;
 constexpr u32 LS_BINS = 1u << LS_BIN_BITS;          // 16-bit counters, two per LDS word (a tile has < 8192 elements)
 constexpr u32 LS_WORDS = LS_BINS / 2;
 constexpr u32 LS_KMAX = 64;
+constexpr int LS_DECLINE_BITS = 12;                 // the decline rule does not move with the bins: msd_slow_tiles is observable
+static_assert(LS_BIN_BITS >= LS_DECLINE_BITS && LS_BIN_BITS <= 13, "the counters fill the 16 KiB behind the tile at most");
 #ifndef PSS_LS_GROUP
 #define PSS_LS_GROUP 1
 #endif
@@ -1303,7 +1310,16 @@ constexpr int LS_GROUP = PSS_LS_GROUP;              // rows ranked / written out
 #define PSS_LS_SLOT_GROUP 1
 #endif
 constexpr int LS_SLOT_GROUP = PSS_LS_SLOT_GROUP;    // rows whose slot atomics are in flight together
-constexpr int LS_WINDOW = PSS_LS_WINDOW;                        // members of its bin every element reads unconditionally (bins average 1.3)
+#ifndef PSS_LS_WINDOW
+#define PSS_LS_WINDOW 7
+#endif
+// Members of its bin every element reads unconditionally.  A knob of the ranking alone (the tile plan reserves eight
+// sentinel slots whatever it is).  What counts is the share of WAVES with a lane in a longer bin, which all run the
+// divergent loop: on the bench text (39 symbols in 6-bit codes: most bin numbers cannot occur) an element of a
+// two-bucket tile sees its bin 3.1 long on average at 8192 bins -- tests/tools/local_bins_model.py, DESIGN §4.2.
+constexpr int LS_WINDOW = PSS_LS_WINDOW;
+static_assert(LS_WINDOW >= 1 && LS_WINDOW <= 8 && MSD_TILE_CAP + 8 + 8 <= MSD_TILE, "the sentinels end before the scalars");
+static_assert((LS_KMAX >> (LS_BIN_BITS - LS_DECLINE_BITS)) >= (u32)LS_WINDOW, "bins that are declined together: one of them outgrows the window");
 
 __global__ __launch_bounds__(256) void msd_tile_desc_kernel(const u32 *cstart, const u32 *tile_first, u32 nt, u32 ne, u32 n,
                                                               MsdTile *tiles, const u32 *cj, const u64 *ntp, const u64 *nep)
@@ -1371,12 +1387,13 @@ __global__ __launch_bounds__(MSD_BLOCK, 4) void msd_local_fast_kernel(const u64 
     const MsdEmit *em = fused ? &em_val : nullptr;
     // 80 KiB of LDS to the byte: two workgroups per CU.  One array: the tile, then the counters -- the ranking below reads
     // up to LS_WINDOW - 1 elements past the tile's last slot (masked out afterwards), and those reads must stay inside it.
-    __shared__ __attribute__((aligned(16))) u64 lds_all[MSD_TILE + LS_WORDS];
+    __shared__ __attribute__((aligned(16))) u64 lds_all[MSD_TILE + LS_WORDS / 2];
     u64 *const exch = lds_all;
-    u32 *const hist = reinterpret_cast<u32 *>(lds_all + MSD_TILE);      // counts, then bin starts (hist) / running slots (hist2), packed
-    u32 *const hist2 = hist + LS_WORDS;
+    u32 *const hist = reinterpret_cast<u32 *>(lds_all + MSD_TILE);      // counts, then bin starts, then (after the slot atomics) bin ends, packed
     u32 *const scr = reinterpret_cast<u32 *>(&exch[MSD_TILE - 8]);      // a tile never reaches these slots (MSD_MAX_BUCKET)
     u32 &s_fail = scr[MSD_WAVES + 2];
+    // scr[0 .. 11] are in use; scr[15], the word in front of the counters, stays zero: "the end of bin -1"
+    static_assert(MSD_WAVES + 3 < 15, "the word in front of the counters is nobody's");
     u32 tid = threadIdx.x;
     const u32 stride = gridDim.x;
     u32 t = blockIdx.x;
@@ -1400,6 +1417,7 @@ __global__ __launch_bounds__(MSD_BLOCK, 4) void msd_local_fast_kernel(const u64 
     if (tid == 0) {
         s_fail = 0;
         scr[MSD_WAVES + 3] = 0;            // records the tile has emitted
+        scr[15] = 0;                       // bin 0 starts at 0, for every tile: nothing else writes here
     }
     lds_barrier();
     u32 prev_t = 0;
@@ -1436,7 +1454,7 @@ __global__ __launch_bounds__(MSD_BLOCK, 4) void msd_local_fast_kernel(const u64 
             scr[MSD_WAVES + 3] = 0;
         }
         {
-            // exclusive scan over the bins in place: LS_WPT adjacent words = 2 LS_WPT bins per thread (four words at 4096 bins)
+            // exclusive scan over the bins in place: LS_WPT adjacent words = 2 LS_WPT bins per thread (eight words at 8192 bins)
             constexpr int LS_WPT = LS_WORDS / MSD_BLOCK;
             static_assert(LS_WPT * MSD_BLOCK == (int)LS_WORDS && LS_WPT >= 1, "bins split evenly over the threads");
             u32 c[2 * LS_WPT];
@@ -1461,14 +1479,14 @@ __global__ __launch_bounds__(MSD_BLOCK, 4) void msd_local_fast_kernel(const u64 
 #pragma unroll
             for (int j = 0; j < LS_WPT; ++j) {
                 const u32 lo = ex, hi = ex + c[2 * j];
-                hist[LS_WPT * tid + j] = hist2[LS_WPT * tid + j] = lo | (hi << 16);
+                hist[LS_WPT * tid + j] = lo | (hi << 16);
                 ex = hi + c[2 * j + 1];
             }
         }
         lds_barrier();
-        // (a second returning atomic on the bin's running start hands out the slot: one more LDS atomic per
-        // element, sixteen fewer registers held across the prefetch).  LS_SLOT_GROUP rows have their atomics in flight
-        // together before the first of them is waited for.
+        // (a second returning atomic on the bin's start hands out the slot: one more LDS atomic per element, sixteen
+        // fewer registers held across the prefetch; when all have theirs, the word holds the bin's END).  LS_SLOT_GROUP
+        // rows have their atomics in flight together before the first of them is waited for.
         ls_rows<LS_SLOT_GROUP>(rows, [&](auto full, int g) __attribute__((always_inline)) {
             u32 slot[LS_SLOT_GROUP], sh[LS_SLOT_GROUP];
 #pragma unroll
@@ -1476,7 +1494,7 @@ __global__ __launch_bounds__(MSD_BLOCK, 4) void msd_local_fast_kernel(const u64 
                 if (decltype(full)::value || (g + j) * MSD_BLOCK + tid < count) {
                     const u32 bin = (u32)(e[g + j] >> bin_shift);
                     sh[j] = 16u * (bin & 1u);
-                    slot[j] = atomicAdd(&hist2[bin >> 1], 1u << sh[j]);
+                    slot[j] = atomicAdd(&hist[bin >> 1], 1u << sh[j]);
                 }
             }
 #pragma unroll
@@ -1484,15 +1502,20 @@ __global__ __launch_bounds__(MSD_BLOCK, 4) void msd_local_fast_kernel(const u64 
                 if (decltype(full)::value || (g + j) * MSD_BLOCK + tid < count) exch[(slot[j] >> sh[j]) & 0xffffu] = e[g + j];
             }
         });
-        // sentinels behind the tile: the ranking window of the last bins reads them (count + 7 < the scalars' slots: MSD_TILE_CAP)
+        // sentinels behind the tile, as many as the window is wide: the ranking window of the last bins reads them
+        // (count + LS_WINDOW - 1 < the scalars' slots: MSD_TILE_CAP)
         if (tid < (u32)LS_WINDOW) exch[count + tid] = ~0ull;
         lds_barrier();
         // Place inside the bin = number of smaller elements there (thread <-> position: neighbours share the bin, their
         // reads are broadcasts).  The kernel is bound by the latency of dependent LDS reads, not by their number: every
         // element reads a fixed window of LS_WINDOW members of its bin (no loop, no branch -- a read past the bin is
-        // masked out), LS_GROUP rows at a time with all their reads in flight; a longer bin (rare: bins average 1.3
-        // elements) finishes in a loop.
-        const u16 *const starts16 = reinterpret_cast<const u16 *>(hist);      // starts16[bin] = first slot of the bin
+        // masked out), LS_GROUP rows at a time with all their reads in flight; a longer bin finishes in a loop that the
+        // whole wave waits for (how many waves have one: the comment at LS_WINDOW).
+        // starts16[bin] = the end of bin - 1 = first slot of the bin, starts16[bin + 1] = first slot behind it; starts16[0] is
+        // the zero halfword in front of the counters
+        const u16 *const starts16 = reinterpret_cast<const u16 *>(hist) - 1;
+        // bins that share their top LS_DECLINE_BITS bits: 2^pair_bits neighbours (one where the key is no wider than that)
+        const int pair_bits = (sort_bits > LS_DECLINE_BITS ? sort_bits - LS_DECLINE_BITS : 0) - (sort_bits > LS_BIN_BITS ? sort_bits - LS_BIN_BITS : 0);
         u32 rk[MSD_IPT];
         u32 rank_rows = (u32)__builtin_amdgcn_readfirstlane((int)rows);
         asm volatile("" : "+s"(rank_rows));      // (as in ls_rows)
@@ -1528,15 +1551,16 @@ __global__ __launch_bounds__(MSD_BLOCK, 4) void msd_local_fast_kernel(const u64 
                 }
 #pragma unroll
                 for (int j = 0; j < LS_GROUP; ++j) {
-                    // the window's last member still in my bin: the bin may go on (rare: bins average 1.3 elements) -- only then
-                    // is its length looked up (the bin's end = the next bin's start)
+                    // the window's last member still in my bin: the bin may go on -- only then is its length looked up, and
+                    // that of the bins it shares its top LS_DECLINE_BITS bits with: more than LS_KMAX there decline the
+                    // tile (such a group has a bin longer than the window, so some lane gets here)
                     // (no lane predicate on the row: a lane past the tile ranks whatever its slot holds, and is asked
                     // p < count only in here)
                     if (((y[j][LS_WINDOW - 1] ^ x[j]) >> bin_shift) == 0 && (g + j) * MSD_BLOCK + tid < count) {
                         const u32 bin = (u32)(x[j] >> bin_shift) & (LS_BINS - 1u);
-                        const u32 s1 = bin + 1u < LS_BINS ? (u32)starts16[min(bin + 1u, LS_BINS - 1u)] : count;
-                        const u32 len = s1 - s0[j];
-                        if (len > LS_KMAX) {
+                        const u32 len = (u32)starts16[bin + 1u] - s0[j];
+                        const u32 lo = bin >> pair_bits << pair_bits;
+                        if ((u32)starts16[lo + (1u << pair_bits)] - (u32)starts16[lo] > LS_KMAX) {
                             s_fail = 1;
                         } else {
                             for (u32 q = s0[j] + LS_WINDOW; q < s0[j] + len; ++q) sm[j] += exch[q] < x[j] ? 1u : 0u;
