@@ -651,6 +651,76 @@ int pss_reader_count_seqc_batch(pss_reader *r, const uint8_t *sbytes, const uint
  * Host only: no device is touched. */
 int pss_seqc_cores(const uint8_t *classes, const uint64_t *soffsets, uint32_t nsegs, uint32_t *core_off, uint32_t *core_len);
 /*
+ * Regular-expression search (no reference counterpart): per pattern the entries e -- the bytes [start, end) of a chunk's
+ * text as the all-terms search takes them, the last byte of an unterminated last entry included -- for which Python's
+ * re.search(pattern, e, re.I if PSS_REGEX_ICASE else 0) finds a match.  A pattern is bytes; the syntax is this subset of
+ * `re` over bytes:
+ *   literal bytes; `.` (any byte but 0x0A); escaped punctuation; \t \r \n \f \v \a \0 \xHH; \d \D \w \W \s \S (ASCII);
+ *   [...] and [^...] with ranges, escapes and \d \w \s inside (a raw byte >= 0x80 inside a set is refused: a set is one
+ *   byte, write \xHH); groups ( ) and (?: ), the same thing here; | ; * + ? {m} {m,} {m,n} {,n};
+ *   ^ only as the pattern's first byte and $ only as its last: they anchor at the entry's first and last byte; with either
+ *   the top level must not be a bare alternation (^a|b is refused, ^(a|b) is the way).
+ * Under PSS_REGEX_ICASE only A-Z / a-z fold; a set accepts both cases of the letters written in it and [^a] rejects A.
+ * Refused, each with its position in the message: lazy and possessive quantifiers, back-references, look-around,
+ * \b \B \A \Z, inline flags and other (?...) forms, named groups, ^ / $ elsewhere, octal escapes, a malformed {} (a literal
+ * brace is \{) or [], unbalanced parentheses, groups nested more than 200 deep, an empty pattern, a pattern without a required
+ * literal (below).
+ * Compilation (host only, csrc/regex_compile.h): Glushkov positions with counted repeats unrolled (more than 2048
+ * positions: refused), the 256 bytes partitioned into `classes` classes, and the subset construction of the WHOLE-ENTRY
+ * language [^\n]* R [^\n]* -- the leading part dropped under ^, the trailing one under $ -- without minimization.  More than
+ * PSS_REGEX_MAX_STATES states: refused ("pattern too complex").  State 0 is dead, the accepting states are >= first_accept,
+ * and without $ the one accepting state is `sink`, which absorbs every byte (sink = 0 with $: none).  The table is
+ * u16 T[states][classes]; reading byte b in state s leads to T[s * classes + cls[b]].
+ * The REQUIRED LITERALS of a pattern are byte runs every match holds: maximal runs of positions written as one byte; of a
+ * concatenation its children's and the runs across adjacent literal children, of a group or a repeat with minimum >= 1 the
+ * child's, of an alternation or a repeat with minimum 0 none.  Distinct, the longest first (the leftmost on a tie), one
+ * that lies inside a longer one dropped, at most 8; folded to lower case under PSS_REGEX_ICASE.  A set or class position is
+ * never part of one.
+ * The search: the required literals of pattern g are the include terms of all-terms group g (pss_reader_search_terms_batch;
+ * under PSS_REGEX_ICASE pss_reader_search_terms_icase_batch) -- the rarest of them per (pattern, chunk) pair drives, one
+ * candidate per entry that holds it, entries that lack another literal are dropped --, and every candidate left is walked
+ * once through the pattern's table from the entry's first byte to its last (one lane per candidate), stopping at state 0
+ * and at sink.  A literal that holds 0x0A makes its pattern match nothing: a count of 0, not an error.  Order and
+ * pss_reader_last_stats exactly as the all-terms call has them for those groups (hits = the sum of the drivers' hits; no
+ * route bit of its own); pss_reader_set_result_order has no effect.
+ * PSS_EINVAL (message in pss_last_error, *out / counts untouched), in this order: a null out / counts, a null pbytes /
+ * poffsets with np > 0, flags other than PSS_REGEX_ICASE, offsets that do not start at 0 or that decrease; then the first
+ * pattern that does not compile ("pattern <g>: ..."), tables of more than 64 MiB in one batch; a null reader last.  Nothing
+ * is launched before all of that has passed.
+ * Not built: a table staged in LDS, several lanes per entry, minimization, a cache of compiled patterns (every call
+ * compiles its batch), the fused, resident and mid paths, a device-resident result, dist.ShardedReader.
+ */
+#define PSS_REGEX_ICASE 1u
+#define PSS_REGEX_MAX_STATES 4096u
+typedef struct pss_regex pss_regex;
+typedef struct pss_regex_dfa {
+    uint32_t states, classes;
+    uint64_t table_bytes;
+    uint32_t anchors;                /* PSS_ANCHOR_START | PSS_ANCHOR_END */
+    uint32_t start, first_accept, sink;
+} pss_regex_dfa;
+/* Host only, no device is touched.  *out is freed with pss_regex_free. */
+int pss_regex_compile(const uint8_t *pattern, uint64_t len, uint32_t flags, pss_regex **out);
+void pss_regex_free(pss_regex *rx);
+int pss_regex_info(const pss_regex *rx, pss_regex_dfa *info);
+/* The required literals back to back into out[0, cap) and their *count + 1 offsets into offsets[0, 9); PSS_EINVAL when cap
+ * is too small.  A literal may be longer than its pattern (`a{200}` has one of 200 bytes: an exact {n} of up to 256 bytes is
+ * written out), so ask first: with out = NULL and cap = 0 the call fills offsets and *count alone, and offsets[*count] is the
+ * size the buffer needs. */
+int pss_regex_literals(const pss_regex *rx, uint8_t *out, uint64_t cap, uint64_t *offsets, uint32_t *count);
+/* The device's walk on the host: 1 = bytes[0, len), taken as one entry (it holds no 0x0A), matches, 0 = it does not,
+ * PSS_EINVAL for a null argument. */
+int pss_regex_match(const pss_regex *rx, const uint8_t *bytes, uint64_t len);
+/* packed entry text, one row per pattern */
+int pss_reader_search_regex_batch(pss_reader *r, const uint8_t *pbytes, const uint64_t *poffsets, uint32_t np, uint32_t flags,
+                                  pss_result **out);
+/* u64 entry ids, packed as pss_reader_search_ids_batch packs them */
+int pss_reader_search_regex_ids_batch(pss_reader *r, const uint8_t *pbytes, const uint64_t *poffsets, uint32_t np, uint32_t flags,
+                                      pss_result **out);
+/* counts[g] = entries pattern g matches; nothing but np counters comes down */
+int pss_reader_count_regex_batch(pss_reader *r, const uint8_t *pbytes, const uint64_t *poffsets, uint32_t np, uint32_t flags,
+                                 uint64_t *counts);
+/*
  * Case-insensitive search (no reference counterpart): `grep -i` over the entries.  ASCII only: the bytes 0x41 .. 0x5A (A .. Z)
  * are equivalent to 0x61 .. 0x7A (a .. z), and every other byte -- 0x80 .. 0xFF included, so no letter outside ASCII -- equals
  * only itself; fold(b) maps A .. Z to a .. z.  An entry is the bytes [start, end) of a chunk's text, end = its closing 0x0A or

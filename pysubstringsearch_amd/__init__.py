@@ -28,7 +28,8 @@ except ImportError:   # pragma: no cover
     _pssglue = None
 
 __all__ = ['Writer', 'Reader', 'PackedResult', 'IdResult', 'DeviceResult', 'device_count', 'default_devices', 'release_workspace', 'workspace_bytes',
-           'glob_parse', 'glob_escape', 'glob_cores', 'icase_variants', 'near_pieces', 'near_seeds']
+           'glob_parse', 'glob_escape', 'glob_cores', 'icase_variants', 'near_pieces', 'near_seeds',
+           'regex_literals', 'regex_info', 'regex_match', 'regex_escape']
 
 
 def device_count() -> int:
@@ -291,6 +292,77 @@ def icase_variants(pattern: bytes, letters: typing.Optional[int] = None) -> typi
                                        ctypes.byref(cnt)))
     raw = buf.raw
     return int(off.value), [raw[i * ln.value:(i + 1) * ln.value] for i in range(cnt.value)]
+
+
+class _Regex:
+    """One compiled pattern (``pss_regex_compile``), freed with the object."""
+
+    def __init__(self, pattern, icase) -> None:
+        pattern = _regex_bytes(pattern)
+        flags = _ffi.REGEX_ICASE if _icase_flag(icase) else 0
+        self.handle = ctypes.c_void_p()
+        _ffi.check(_lib.pss_regex_compile(pattern, len(pattern), flags, ctypes.byref(self.handle)))
+
+    def __del__(self):
+        if getattr(self, 'handle', None):
+            _lib.pss_regex_free(self.handle)
+            self.handle = None
+
+
+def _regex_bytes(pattern) -> bytes:
+    """A regex pattern as bytes: ``bytes`` as they are, ``str`` UTF-8 encoded."""
+    if isinstance(pattern, str):
+        return _utf8(pattern, 'pattern')
+    if not isinstance(pattern, (bytes, bytearray)):
+        raise TypeError(f"argument 'pattern': must be bytes or str, not {type(pattern).__name__}")
+    return bytes(pattern)
+
+
+def regex_literals(pattern, icase: bool = False) -> typing.List[bytes]:
+    """The REQUIRED LITERALS of a regex pattern, as ``Reader.search_regex_ids_batch`` looks them up: byte runs every match
+    holds, the longest first (the leftmost on a tie), at most 8, folded to lower case under ``icase``.  The rarest of them
+    per (pattern, chunk) drives the search.  ``ValueError`` for a pattern the search refuses (include/pss.h,
+    pss_regex_compile).  Host only."""
+    rx = _Regex(pattern, icase)
+    offs = (ctypes.c_uint64 * 9)()
+    count = ctypes.c_uint32()
+    _ffi.check(_lib.pss_regex_literals(rx.handle, None, 0, offs, ctypes.byref(count)))       # the sizes: a literal may outgrow its pattern
+    cap = max(int(offs[count.value]), 1)
+    out = ctypes.create_string_buffer(cap)
+    _ffi.check(_lib.pss_regex_literals(rx.handle, out, cap, offs, ctypes.byref(count)))
+    return [out.raw[offs[i]:offs[i + 1]] for i in range(count.value)]
+
+
+def regex_info(pattern, icase: bool = False) -> dict:
+    """What a regex pattern compiles to: ``states`` and ``classes`` of its DFA, ``table_bytes``, ``anchors`` (1 = ``^``,
+    2 = ``$``), the ``start`` state, ``first_accept`` (the accepting states are the ones from it on; 0 is dead) and ``sink``
+    (the one absorbing accepting state of a pattern without ``$``; 0: none).  Host only."""
+    rx = _Regex(pattern, icase)
+    info = _ffi.RegexDfa()
+    _ffi.check(_lib.pss_regex_info(rx.handle, ctypes.byref(info)))
+    return {k: int(getattr(info, k)) for k, _ in info._fields_}
+
+
+def regex_match(pattern, data: bytes, icase: bool = False) -> bool:
+    """Does ``data``, taken as ONE ENTRY (it holds no newline), match the regex pattern?  The walk the device makes, on
+    the host: ``re.search(pattern, data, re.I if icase else 0) is not None`` for every pattern of the subset."""
+    rx = _Regex(pattern, icase)
+    if not isinstance(data, (bytes, bytearray)):
+        raise TypeError(f"argument 'data': must be bytes, not {type(data).__name__}")
+    data = bytes(data)
+    rc = _lib.pss_regex_match(rx.handle, data, len(data))
+    if rc < 0:
+        _ffi.check(rc)
+    return bool(rc)
+
+
+_REGEX_SPECIAL = frozenset(b'\\.^$*+?{}[]()|')
+
+
+def regex_escape(text: bytes) -> bytes:
+    """``text`` as a regex pattern that matches exactly these bytes (``str`` is UTF-8 encoded first)."""
+    text = _regex_bytes(text)
+    return b''.join(b'\\' + bytes([b]) if b in _REGEX_SPECIAL else (b'\\n' if b == 0x0A else bytes([b])) for b in text)
 
 
 def near_pieces(pattern: bytes, k: int) -> typing.List[typing.Tuple[int, bytes]]:
@@ -1104,6 +1176,47 @@ class Reader:
     def count_glob(self, s: str) -> int:
         """Extension: how many entries match the glob pattern ``s``."""
         return self.count_glob_bytes([_utf8(s, 'pattern')])[0]
+
+    def _regex_batch(self, form: str, patterns, icase):
+        """One ``pss_reader_search_regex_*`` call over ``patterns`` (each ``bytes``, or ``str`` UTF-8 encoded)."""
+        flags = _ffi.REGEX_ICASE if _icase_flag(icase) else 0
+        if isinstance(patterns, (bytes, bytearray, str)):
+            raise TypeError(f"argument 'patterns': '{type(patterns).__name__}' object cannot be converted to a sequence of regex patterns")
+        blob, offs = _pack_queries([_regex_bytes(p) for p in patterns])
+        name = {'packed': 'pss_reader_search_regex_batch', 'ids': 'pss_reader_search_regex_ids_batch',
+                'counts': 'pss_reader_count_regex_batch'}[form]
+        np_ = len(offs) - 1
+        return self._batch(getattr(_lib, name), (blob, offs.ctypes.data, np_, flags), np_, form)
+
+    def search_regex_batch_packed(self, patterns: typing.Sequence[bytes], *, icase: bool = False) -> 'PackedResult':
+        """Extension: per regular expression, the entries ``e`` with ``re.search(pattern, e, re.I if icase else 0)`` as a
+        packed result like ``search_batch_packed``'s with one row per pattern.  The syntax is a subset of ``re`` over bytes:
+        literals, ``.``, escapes, ``\\d \\w \\s`` and their complements, sets, groups, ``|``, ``* + ? {m,n}``, ``^`` as the first
+        and ``$`` as the last byte (the entry's two ends); lazy and possessive quantifiers, back-references, look-around,
+        ``\\b``, inline flags and named groups are a ``ValueError`` that names the position, and so is a pattern without a
+        REQUIRED LITERAL (``regex_literals``): the literals are looked up as an all-terms group, the rarest per (pattern,
+        chunk) drives, and every candidate entry is walked once through the pattern's DFA on the device (``regex_info``;
+        include/pss.h, pss_reader_search_regex_batch).  A ``str`` pattern is UTF-8 encoded; ``icase`` folds ``A-Z`` / ``a-z``
+        only.  A literal holding a newline matches nothing.  Always the general pipeline; ``set_result_order`` has no
+        effect."""
+        return self._regex_batch('packed', patterns, icase)
+
+    def search_regex_ids_batch(self, patterns: typing.Sequence[bytes], *, icase: bool = False) -> 'IdResult':
+        """Extension: the ids (``search_ids_batch``) of the entries ``search_regex_batch_packed`` returns, in the same
+        order; ``counts[g]`` of them belong to pattern g."""
+        return self._regex_batch('ids', patterns, icase)
+
+    def count_regex_bytes(self, patterns: typing.Sequence[bytes], *, icase: bool = False) -> typing.List[int]:
+        """Extension: how many entries each regular expression matches; only the counters come back."""
+        return self._regex_batch('counts', patterns, icase)
+
+    def search_regex(self, s: str, *, icase: bool = False) -> typing.List[str]:
+        """Extension: the entries that match the regular expression ``s`` (``search_regex_batch_packed``)."""
+        return _packed_strs(self.search_regex_batch_packed([s], icase=icase))
+
+    def count_regex(self, s: str, *, icase: bool = False) -> int:
+        """Extension: how many entries match the regular expression ``s``."""
+        return self.count_regex_bytes([s], icase=icase)[0]
 
     @staticmethod
     def _icase_args(patterns):

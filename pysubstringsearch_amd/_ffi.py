@@ -156,6 +156,14 @@ ANCHORS = {'start': 1, 'end': 2, 'entry': 3}
 SPAN_EDITS, SPAN_ICASE = 1, 2      # pss_reader_match_spans flags (include/pss.h)
 ANCHOR_START, ANCHOR_END = 1, 2
 SEQ_FOLD = 1        # PSS_SEQ_FOLD: the flags word of the pss_reader_search_seqc_* calls
+REGEX_ICASE = 1     # PSS_REGEX_ICASE: the flags word of pss_regex_compile and the pss_reader_search_regex_* calls
+REGEX_MAX_STATES = 4096
+
+
+class RegexDfa(ctypes.Structure):
+    """pss_regex_dfa (include/pss.h): what pss_regex_info says about a compiled pattern."""
+    _fields_ = [('states', ctypes.c_uint32), ('classes', ctypes.c_uint32), ('table_bytes', ctypes.c_uint64),
+                ('anchors', ctypes.c_uint32), ('start', ctypes.c_uint32), ('first_accept', ctypes.c_uint32), ('sink', ctypes.c_uint32)]
 
 
 class DeviceResult(ctypes.Structure):
@@ -307,6 +315,14 @@ def _load() -> ctypes.CDLL:
         'pss_reader_search_seqc_ids_batch': (ctypes.c_int, [vp, vp, vp, vp, u32, vp, u32, vp, u32, vp, u32, pvp]),
         'pss_reader_count_seqc_batch': (ctypes.c_int, [vp, vp, vp, vp, u32, vp, u32, vp, u32, vp, u32, vp]),
         'pss_seqc_cores': (ctypes.c_int, [vp, vp, u32, vp, vp]),
+        'pss_regex_compile': (ctypes.c_int, [vp, u64, u32, pvp]),
+        'pss_regex_free': (None, [vp]),
+        'pss_regex_info': (ctypes.c_int, [vp, ctypes.POINTER(RegexDfa)]),
+        'pss_regex_literals': (ctypes.c_int, [vp, vp, u64, vp, ctypes.POINTER(u32)]),
+        'pss_regex_match': (ctypes.c_int, [vp, vp, u64]),
+        'pss_reader_search_regex_batch': (ctypes.c_int, [vp, vp, vp, u32, u32, pvp]),
+        'pss_reader_search_regex_ids_batch': (ctypes.c_int, [vp, vp, vp, u32, u32, pvp]),
+        'pss_reader_count_regex_batch': (ctypes.c_int, [vp, vp, vp, u32, u32, vp]),
         'pss_reader_search_icase_batch': (ctypes.c_int, [vp, vp, vp, u32, pvp]),
         'pss_reader_search_icase_ids_batch': (ctypes.c_int, [vp, vp, vp, u32, pvp]),
         'pss_reader_count_icase_batch': (ctypes.c_int, [vp, vp, vp, u32, vp]),

@@ -13,6 +13,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <deque>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -22,6 +23,7 @@
 #include "radix_sort.h"
 #include "sa_build.h"
 #include "search.h"
+#include "regex_compile.h"
 
 using namespace pss;
 

@@ -1767,6 +1767,184 @@ extern "C" int pss_seqc_cores(const uint8_t *classes, const uint64_t *soffsets, 
     });
 }
 
+// ---- regular-expression search: pattern -> its required literals as an all-terms group + its DFA (regex_compile.h, -----
+// ---- regex_impl.h) -----------------------------------------------------------------------------------
+
+struct pss_regex {
+    RegexDfa dfa;
+};
+
+namespace {
+
+// One pattern compiled, its refusal stated as the entry point's (g < 0: the call has one pattern and names none).
+int regex_compile_as(const char *who, int64_t g, const uint8_t *pat, uint64_t len, uint32_t flags, RegexDfa *d)
+{
+    std::string why;
+    if (regex_compile(pat, len, flags, d, &why)) return PSS_OK;
+    if (g < 0)
+        set_error("%s: %s", who, why.c_str());
+    else
+        set_error("%s: pattern %lld: %s", who, (long long)g, why.c_str());
+    return PSS_EINVAL;
+}
+
+// The three regex calls: arguments, then the patterns -- each compiled, its required literals the include terms of its
+// group, its header, class map and table behind those of the patterns before it --, the reader last (terms_args).  Under
+// PSS_REGEX_ICASE the literals (folded already) are expanded into their seeds' spellings as a case-insensitive all-terms
+// batch expands its terms.  Everything lives in this frame, so it outlives the batch on every part of a multi-device reader.
+int regex_batch(pss_reader *r, const char *who, const uint8_t *pbytes, const uint64_t *poffsets, uint32_t np, uint32_t flags,
+                SearchMode mode, pss_result **out, uint64_t *counts)
+{
+    if (!out_ok_by_mode(mode, np, out, counts) || (np && (!pbytes || !poffsets))) {
+        set_error("%s: bad arguments", who);
+        return PSS_EINVAL;
+    }
+    if (flags & ~PSS_REGEX_ICASE) {
+        set_error("%s: flags = %u (PSS_REGEX_ICASE = 1 or nothing)", who, flags);
+        return PSS_EINVAL;
+    }
+    if (np && poffsets[0] != 0) {
+        set_error("%s: the pattern offsets start at %llu, not at 0", who, (unsigned long long)poffsets[0]);
+        return PSS_EINVAL;
+    }
+    for (uint32_t g = 0; g < np; ++g)
+        if (poffsets[g + 1] < poffsets[g]) {
+            set_error("%s: the pattern offsets decrease at pattern %u", who, g);
+            return PSS_EINVAL;
+        }
+    std::vector<uint8_t> tbytes, cls;
+    std::vector<uint64_t> toffsets(1, 0), goff(1, 0);
+    std::vector<uint32_t> hdr;
+    std::vector<uint16_t> tables;
+    for (uint32_t g = 0; g < np; ++g) {
+        RegexDfa d;
+        PSS_TRY(regex_compile_as(who, g, pbytes + poffsets[g], poffsets[g + 1] - poffsets[g], flags, &d));
+        if ((tables.size() + d.table.size()) * 2 > REGEX_MAX_TABLE_BYTES) {
+            set_error("%s: the tables of the batch pass 64 MiB at pattern %u: split the batch", who, g);
+            return PSS_EINVAL;
+        }
+        for (const std::string &lit : d.literals) {
+            tbytes.insert(tbytes.end(), lit.begin(), lit.end());
+            toffsets.push_back(tbytes.size());
+        }
+        goff.push_back(toffsets.size() - 1);
+        const uint32_t h[REGEX_HDR_WORDS] = {(uint32_t)tables.size(), d.nstates, d.ncls, d.start, d.first_accept, d.sink, d.anchors, 0};
+        hdr.insert(hdr.end(), h, h + REGEX_HDR_WORDS);
+        cls.insert(cls.end(), d.cls, d.cls + 256);
+        tables.insert(tables.end(), d.table.begin(), d.table.end());
+    }
+    const uint32_t nterms = (uint32_t)(toffsets.size() - 1);        // (at most 8 per pattern)
+    tbytes.push_back(0);                                            // (data() of an empty vector may be null)
+    const std::vector<uint8_t> no_exclude((size_t)nterms + 1, 0);
+    PSS_TRY(terms_args(r, who, tbytes.data(), toffsets.data(), nterms, goff.data(), np, no_exclude.data(), true));
+    SeededGroups b;
+    SearchRequest rq{tbytes.data(), toffsets.data(), nterms, mode, nullptr, goff.data(), np, no_exclude.data()};
+    if (flags & PSS_REGEX_ICASE) {
+        PSS_TRY(icase_expand(who, "literal", tbytes.data(), toffsets.data(), nterms, &b));
+        rq = b.request(nterms, goff.data(), np, no_exclude.data(), nullptr, mode);
+    }
+    if (np) {
+        rq.regex_hdr = hdr.data();
+        rq.regex_cls = cls.data();
+        rq.regex_tables = tables.data();
+        rq.regex_table_words = tables.size();
+    }
+    return answer_by_mode(r, rq, out, counts);
+}
+
+}  // namespace
+
+extern "C" int pss_regex_compile(const uint8_t *pattern, uint64_t len, uint32_t flags, pss_regex **out)
+{
+    return guarded([&]() -> int {
+        if (!out || (len && !pattern) || (flags & ~PSS_REGEX_ICASE)) {
+            set_error("pss_regex_compile: bad arguments");
+            return PSS_EINVAL;
+        }
+        std::unique_ptr<pss_regex> rx(new pss_regex);
+        PSS_TRY(regex_compile_as("pss_regex_compile", -1, pattern, len, flags, &rx->dfa));
+        *out = rx.release();
+        return PSS_OK;
+    });
+}
+
+extern "C" void pss_regex_free(pss_regex *rx) { delete rx; }
+
+extern "C" int pss_regex_info(const pss_regex *rx, pss_regex_dfa *info)
+{
+    return guarded([&]() -> int {
+        if (!rx || !info) {
+            set_error("pss_regex_info: bad arguments");
+            return PSS_EINVAL;
+        }
+        const RegexDfa &d = rx->dfa;
+        *info = pss_regex_dfa{d.nstates, d.ncls, d.table_bytes(), d.anchors, d.start, d.first_accept, d.sink};
+        return PSS_OK;
+    });
+}
+
+extern "C" int pss_regex_literals(const pss_regex *rx, uint8_t *out, uint64_t cap, uint64_t *offsets, uint32_t *count)
+{
+    return guarded([&]() -> int {
+        if (!rx || !offsets || !count || (cap && !out)) {
+            set_error("pss_regex_literals: bad arguments");
+            return PSS_EINVAL;
+        }
+        uint64_t total = 0;
+        for (const std::string &lit : rx->dfa.literals) total += lit.size();
+        if (!out) {                                  // the sizes alone: what the buffer of the next call has to hold
+            uint32_t k = 0;
+            offsets[0] = 0;
+            for (const std::string &lit : rx->dfa.literals) { offsets[k + 1] = offsets[k] + lit.size(); ++k; }
+            *count = k;
+            return PSS_OK;
+        }
+        if (total > cap) {
+            set_error("pss_regex_literals: the literals have %llu bytes, the buffer %llu", (unsigned long long)total, (unsigned long long)cap);
+            return PSS_EINVAL;
+        }
+        uint64_t at = 0;
+        uint32_t k = 0;
+        offsets[0] = 0;
+        for (const std::string &lit : rx->dfa.literals) {
+            memcpy(out + at, lit.data(), lit.size());
+            at += lit.size();
+            offsets[++k] = at;
+        }
+        *count = k;
+        return PSS_OK;
+    });
+}
+
+extern "C" int pss_regex_match(const pss_regex *rx, const uint8_t *bytes, uint64_t len)
+{
+    return guarded([&]() -> int {
+        if (!rx || (len && !bytes)) {
+            set_error("pss_regex_match: bad arguments");
+            return PSS_EINVAL;
+        }
+        return regex_match(rx->dfa, bytes, len) ? 1 : 0;
+    });
+}
+
+extern "C" int pss_reader_search_regex_batch(pss_reader *r, const uint8_t *pbytes, const uint64_t *poffsets, uint32_t np, uint32_t flags,
+                                             pss_result **out)
+{
+    return guarded([&]() -> int { return regex_batch(r, "pss_reader_search_regex_batch", pbytes, poffsets, np, flags, SEARCH_FULL, out, nullptr); });
+}
+
+extern "C" int pss_reader_search_regex_ids_batch(pss_reader *r, const uint8_t *pbytes, const uint64_t *poffsets, uint32_t np, uint32_t flags,
+                                                 pss_result **out)
+{
+    return guarded([&]() -> int { return regex_batch(r, "pss_reader_search_regex_ids_batch", pbytes, poffsets, np, flags, SEARCH_IDS, out, nullptr); });
+}
+
+extern "C" int pss_reader_count_regex_batch(pss_reader *r, const uint8_t *pbytes, const uint64_t *poffsets, uint32_t np, uint32_t flags,
+                                            uint64_t *counts)
+{
+    return guarded([&]() -> int { return regex_batch(r, "pss_reader_count_regex_batch", pbytes, poffsets, np, flags, SEARCH_COUNTS, nullptr, counts); });
+}
+
 // ---- case-insensitive search: group -> terms -> the spellings of a seed (fold_impl.h) --------------
 
 namespace {

@@ -1748,6 +1748,7 @@ static void newline_flags(const u8 *bytes, const u64 *off, u32 n, u8 set, u8 *fl
 #include "all_terms_impl.h"
 #include "sequence_impl.h"
 #include "seq_class_impl.h"
+#include "regex_impl.h"
 #include "seed_impl.h"
 #include "fold_impl.h"
 #include "near_impl.h"
@@ -1804,6 +1805,7 @@ struct Batch : BatchShape {
     u64 *d_goff = nullptr;                          // all-terms batch: group offsets, term flags, driver term per group pair
     u8 *d_tflags = nullptr, *d_sanch = nullptr;       // (d_sanch: a sequence batch's anchor byte per group)
     SeqClass d_sc{};                                // a class batch: its segments, behind the anchor bytes (upload_anchors)
+    RegexTables d_rx{};                             // a regex batch: its headers, class maps and tables (upload_regex)
     u32 *d_gdrv = nullptr;
     u8 *d_fbytes = nullptr, *d_fvoid = nullptr;     // a seeded batch: the terms as they are verified, their offsets, a void flag
     u64 *d_foff = nullptr, *d_soff = nullptr;       // per term, the queries' offsets per term and positions per query, the seed
@@ -1855,6 +1857,8 @@ struct Batch : BatchShape {
     int sa_order_hits(u32 grid, u64 H);
     ClassBlock class_block() const;
     int upload_anchors(u8 *at, const ClassBlock &L);
+    RegexBlock regex_block() const { return RegexBlock(regex, nrow, rq.regex_table_words); }
+    int upload_regex(u8 *at, const RegexBlock &L);
     int download_result(u64 E, u64 B, const u64 *d_starts, const u8 *d_bytes, bool via_stage);
     void leave_on_device(const u64 *d_starts, const u8 *d_bytes), set_totals(u64 hits, u64 kept, u64 E, u64 B);
 };
@@ -2194,11 +2198,22 @@ int Batch::upload_anchors(u8 *at, const ClassBlock &L)
     return PSS_OK;
 }
 
+// A regex batch's block (RegexBlock of search_layout.h) behind the sequence's, for pick_drivers' and seed_drivers' layouts alike.
+int Batch::upload_regex(u8 *at, const RegexBlock &L)
+{
+    if (!regex) return PSS_OK;
+    PSS_TRY(upload(at + L.hdr, rq.regex_hdr, (size_t)nrow * REGEX_HDR_WORDS * 4));
+    PSS_TRY(upload(at + L.cls, rq.regex_cls, (size_t)nrow * 256));
+    PSS_TRY(upload(at + L.tables, rq.regex_tables, (size_t)rq.regex_table_words * 2));
+    d_rx = RegexTables{reinterpret_cast<const u32 *>(at + L.hdr), at + L.cls, reinterpret_cast<const u16 *>(at + L.tables)};
+    return PSS_OK;
+}
+
 // All-terms batch: from the term pairs to the group pairs.  Group offsets and term flags go up, and one lane per (group,
 // chunk) pair picks the pair's driver term; from here on the pipeline runs over the drivers' intervals.
 int Batch::pick_drivers()
 {
-    const TermsLayout L(nrow, nq, nrp, class_block());
+    const TermsLayout L(nrow, nq, nrp, class_block(), regex_block());
     u8 *base;
     PSS_TRY(take(Q_TERMS, L.end, base));
     d_goff = reinterpret_cast<u64 *>(base + L.goff);
@@ -2209,6 +2224,7 @@ int Batch::pick_drivers()
     PSS_TRY(upload(d_goff, rq.group_offsets, ((size_t)nrow + 1) * 8));
     PSS_TRY(upload(d_tflags, own_tflags.data(), nq));
     PSS_TRY(upload_anchors(base + L.anchors, L.cls));
+    PSS_TRY(upload_regex(base + L.regex, L.rx));
     hipLaunchKernelGGL(terms_driver_kernel<true>, dim3((u32)((nrp + 255) / 256)), dim3(256), 0, s, nc, d_goff, d_tflags, d_lo, d_cnt, nrp,
                        d_gdrv, p_lo, p_cnt);
     return PSS_OK;
@@ -2223,7 +2239,7 @@ int Batch::pick_drivers()
 int Batch::seed_drivers()
 {
     const u64 ttotal = rq.term_offsets[nterm];
-    const SeedLayout L(nrow, nterm, nq, ttotal, ntp, nrp, near, class_block());
+    const SeedLayout L(nrow, nterm, nq, ttotal, ntp, nrp, near, class_block(), regex_block());
     u8 *base;
     PSS_TRY(take(Q_TERMS, L.end, base));
     d_goff = reinterpret_cast<u64 *>(base + L.goff);
@@ -2245,6 +2261,7 @@ int Batch::seed_drivers()
     PSS_TRY(upload(d_fvoid, own_fvoid.data(), nterm));
     PSS_TRY(upload(d_tflags, own_tflags.data(), nterm));
     PSS_TRY(upload_anchors(base + L.anchors, L.cls));
+    PSS_TRY(upload_regex(base + L.regex, L.rx));
     if (near) {
         PSS_TRY(upload(d_nk, rq.near_budget, nterm));
         PSS_HIP(hipMemsetAsync(d_over, 0, 8, s));
@@ -2305,8 +2322,8 @@ int Batch::no_hits()
 
 // Every candidate of a group batch against the group's other terms, or its segments in order: a class batch (the terms
 // are the segments' cores, every segment is placed by its own core), a sequence batch (every candidate against the
-// group's segments in order, the driver among them), an all-terms batch.  bytes / off: the terms as they are verified;
-// tcnt: the hits per (term, chunk) pair.
+// group's segments in order, the driver among them), an all-terms batch -- and, behind that, a regex batch's walk of every
+// candidate left (regex_impl.h).  bytes / off: the terms as they are verified; tcnt: the hits per (term, chunk) pair.
 template <bool Fold>
 void Batch::verify(u32 vgrid, u64 H, const u8 *bytes, const u64 *off, const u32 *tcnt)
 {
@@ -2320,6 +2337,10 @@ void Batch::verify(u32 vgrid, u64 H, const u8 *bytes, const u64 *off, const u32 
                                         // no other to look for; a near batch is no sequence and has one term per group)
         hipLaunchKernelGGL(terms_verify_kernel<Fold>, dim3(vgrid), dim3(256), 0, s, d_chunks, nc, bytes, off, d_goff, d_tflags, tcnt,
                            d_gdrv, nrp, d_hitoff, H, d_start, d_len);
+    if (regex) {        // the candidates that hold every required literal, each through its pattern's DFA: one lane per candidate
+        const u32 rgrid = (u32)std::min<u64>((u64)ctx->num_cus * 16, (H + 255) / 256);
+        hipLaunchKernelGGL(regex_verify_kernel, dim3(rgrid), dim3(256), 0, s, d_chunks, nc, d_rx, nrp, d_hitoff, H, d_start, d_len);
+    }
 }
 
 // The entry of every hit; a hit whose entry another hit of the pair stands for is marked in d_len and dropped by the scans.
@@ -2453,6 +2474,10 @@ int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, const LineDes
     case REQUEST_CLASS:
         set_error("search: a class batch is a sequence batch that states its segments' bytes, class plane, offsets, group offsets, "
                   "cores and void flags, and at most 255 sets; its terms are the segments' cores");
+        return PSS_EINVAL;
+    case REQUEST_REGEX:
+        set_error("search: a regex batch is an all-terms batch without an exclude term that states its headers, class maps and tables, "
+                  "every table inside the tables and at most 64 MiB of them; it takes the general pipeline to a host result");
         return PSS_EINVAL;
     }
     const u32 rows = rq.rows();

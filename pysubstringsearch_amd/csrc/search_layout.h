@@ -81,6 +81,17 @@ struct SearchRequest {
     const uint8_t *class_bytes = nullptr, *class_plane = nullptr; const uint64_t *class_offsets = nullptr; uint32_t class_nsegs = 0;
     const uint64_t *class_groups = nullptr; const uint32_t *class_cores = nullptr;
     const uint8_t *class_sets = nullptr; uint32_t class_nsets = 0; const uint8_t *class_void = nullptr;
+    // regex_hdr .. regex_table_words, together with group_offsets and exclude: the groups are the REQUIRED LITERALS of ngroups
+    // regular expressions (regex_compile.h) -- an all-terms batch, plain or seeded under fold, whose exclude flags
+    // are all zero -- and every candidate the all-terms verify step leaves is walked through its group's DFA (regex_impl.h):
+    //   regex_hdr: REGEX_HDR_WORDS words per group -- the offset of its table inside regex_tables in u16 units, nstates, ncls,
+    //     start, first_accept, sink, anchors, 0;
+    //   regex_cls: 256 bytes per group, the class of every byte (< ncls);
+    //   regex_tables: regex_table_words u16 in all, per group nstates x ncls of them, every one < nstates.
+    // The caller has compiled all of it (capi_reader_impl.h, regex_batch).  Not with anchors, seq_anchors, a class block, budgets,
+    // SEARCH_DEVICE or low_latency.
+    const uint32_t *regex_hdr = nullptr; const uint8_t *regex_cls = nullptr; const uint16_t *regex_tables = nullptr;
+    uint64_t regex_table_words = 0;
     uint32_t rows() const { return group_offsets ? ngroups : nq; }     // rows of the result: queries, or groups of terms
     bool low_latency = false;            // one query through the resident kernel when it fits (an unanchored SEARCH_FULL batch only)
     // sa_order: the entries of one (query, chunk) pair come out in the reference's order -- suffix-array order of the FIRST hit
@@ -105,6 +116,10 @@ constexpr size_t SM_QUERY_ROOM = 8192;          // ... that many at most with th
 constexpr size_t SEARCH_STAGE_Q = (size_t)2 << 20, SEARCH_STAGE_R = (size_t)4 << 20;      // pinned staging: queries up | results down
 constexpr uint32_t SEARCH_SCAN_BLOCKS = 1024;   // SC_MAX_BLOCKS of scan.h (which needs HIP): partial sums of a device_excl_scan
 constexpr size_t SEARCH_PAD = 32;               // zero bytes behind every byte array a kernel reads past the end of
+constexpr uint32_t REGEX_HDR_WORDS = 8;         // u32 per group of a regex batch: table offset, nstates, ncls, start, first_accept, sink, anchors, 0
+enum RegexHdr { RX_TABLE = 0, RX_NSTATES = 1, RX_NCLS = 2, RX_START = 3, RX_FIRST_ACCEPT = 4, RX_SINK = 5, RX_ANCHORS = 6 };
+constexpr uint32_t REGEX_STATES_MAX = 4096;     // PSS_REGEX_MAX_STATES
+constexpr uint64_t REGEX_TABLE_WORDS_MAX = (uint64_t)32 << 20;      // 64 MiB of u16 in one batch
 
 // ---- the rules a request keeps -------------------------------------------------------------------------------------
 // The C ABI validates a batch before it builds a request, so these state what search_batch_device relies on; it turns a
@@ -116,6 +131,7 @@ enum RequestVerdict {
     REQUEST_ALL_TERMS,              // groups with anchors, without exclude flags or sequence anchors, with SEARCH_DEVICE or low_latency
     REQUEST_SEEDED,
     REQUEST_CLASS,
+    REQUEST_REGEX,
 };
 
 // A seeded batch carries its groups, its terms and the queries' offsets and positions, and either exclude flags or sequence
@@ -146,6 +162,29 @@ inline bool class_request_ok(const SearchRequest &rq)
            rq.class_groups[rq.ngroups] == rq.class_nsegs;
 }
 
+// A regex batch is an all-terms batch (groups and exclude flags, none set) that states its headers, class maps and tables;
+// every group's table lies inside the tables, its numbers inside its table, every class of its map below ncls and every entry
+// of its table below nstates -- all that regex_verify_kernel's reads rest on (one pass over what goes up anyway).
+inline bool regex_request_ok(const SearchRequest &rq)
+{
+    bool ok = rq.regex_hdr && rq.regex_cls && rq.regex_tables && rq.group_offsets && rq.exclude && !rq.anchors && !rq.seq_anchors &&
+              !rq.class_bytes && !rq.near_budget && rq.mode != SEARCH_DEVICE && !rq.low_latency &&
+              rq.regex_table_words <= REGEX_TABLE_WORDS_MAX;
+    const uint32_t nt = rq.seed_offsets ? rq.nterms : rq.nq;
+    for (uint32_t t = 0; ok && t < nt; ++t) ok = rq.exclude[t] == 0;
+    for (uint32_t g = 0; ok && g < rq.ngroups; ++g) {
+        const uint32_t *h = rq.regex_hdr + (size_t)g * REGEX_HDR_WORDS;
+        ok = h[RX_NSTATES] >= 1 && h[RX_NSTATES] <= REGEX_STATES_MAX && h[RX_NCLS] >= 1 && h[RX_NCLS] <= 256 &&
+             (uint64_t)h[RX_TABLE] + (uint64_t)h[RX_NSTATES] * h[RX_NCLS] <= rq.regex_table_words && h[RX_START] < h[RX_NSTATES] &&
+             h[RX_FIRST_ACCEPT] >= 1 && h[RX_FIRST_ACCEPT] <= h[RX_NSTATES] && h[RX_SINK] < h[RX_NSTATES] && h[RX_ANCHORS] <= 3;
+        const uint8_t *cls = rq.regex_cls + (size_t)g * 256;
+        for (uint32_t b = 0; ok && b < 256; ++b) ok = cls[b] < h[RX_NCLS];
+        const uint16_t *tab = rq.regex_tables + h[RX_TABLE];
+        for (size_t i = 0, n = ok ? (size_t)h[RX_NSTATES] * h[RX_NCLS] : 0; ok && i < n; ++i) ok = tab[i] < h[RX_NSTATES];
+    }
+    return ok;
+}
+
 // nc: resident chunks; have_lines: their line tables were built.
 inline RequestVerdict check_request(const SearchRequest &rq, uint32_t nc, bool have_lines)
 {
@@ -158,6 +197,7 @@ inline RequestVerdict check_request(const SearchRequest &rq, uint32_t nc, bool h
          rq.class_nsegs || rq.class_nsets) &&
         !class_request_ok(rq))
         return REQUEST_CLASS;
+    if ((rq.regex_hdr || rq.regex_cls || rq.regex_tables || rq.regex_table_words) && !regex_request_ok(rq)) return REQUEST_REGEX;
     return REQUEST_OK;
 }
 
@@ -172,6 +212,7 @@ struct BatchShape {
     bool near;                          // ... within k mismatches (near_impl.h); else under fold (fold_impl.h, 4.14)
     bool edits;                         // near, and the budget counts edits: EditMatch in NearMatch's place (edit_impl.h, 4.17)
     bool fold_near;                     // near, and the budget is counted under fold: the <true> forms of either Match (4.19)
+    bool regex;                         // terms, and every candidate is walked through its group's DFA (regex_impl.h, 4.21)
     bool sa_order;
     // An all-terms batch (all_terms_impl.h) has a second pair space: its nq queries are terms, its result rows are the ng
     // groups, and everything from the first scan on runs over (group, chunk) pairs.  For every other batch the two agree.
@@ -197,6 +238,7 @@ struct BatchShape {
         near = seeded && rq.near_budget != nullptr;
         edits = near && rq.near_edits;
         fold_near = near && rq.near_fold;
+        regex = terms && rq.regex_hdr != nullptr;
         // (counts do not depend on the order; one hit per entry has one order; an all-terms batch keeps its driver's text order)
         sa_order = rq.sa_order && !counts && !anchored && !terms;
         nrow = rq.rows();
@@ -256,17 +298,38 @@ struct ClassBlock {
     }
 };
 
+// What a regex batch keeps behind the sequence's block in Q_TERMS, as regex_verify_kernel reads it (RegexTables): the
+// headers, the class maps, the tables.  Offsets from its own start; nothing at all (end = 0) where the batch is no regex
+// batch.  Both Q_TERMS layouts embed it.
+struct RegexBlock {
+    size_t hdr = 0, cls = 0, tables = 0, end = 0;
+    RegexBlock() = default;
+    RegexBlock(bool regex, uint32_t nrow, uint64_t table_words)
+    {
+        if (!regex) return;
+        search_detail::Carver carve;
+        hdr = carve((size_t)nrow * REGEX_HDR_WORDS * 4);
+        cls = carve((size_t)nrow * 256);
+        tables = carve((size_t)table_words * 2);
+        end = carve.o;
+    }
+};
+
 // Slot Q_TERMS of an all-terms or a sequence batch of nq terms in nrow groups: group offsets, term flags, the sequence's
-// block, then per (group, chunk) pair the driver term, its interval and its hits -- three arrays back to back.
+// block, a regex batch's block, then per (group, chunk) pair the driver term, its interval and its hits -- three arrays
+// back to back.
 struct TermsLayout {
     ClassBlock cls;             // at `anchors`
-    size_t goff, tflags, anchors, gdrv, lo, cnt, end;
-    TermsLayout(uint32_t nrow, uint32_t nq, uint64_t nrp, const ClassBlock &block) : cls(block)
+    RegexBlock rx;              // at `regex`
+    size_t goff, tflags, anchors, regex, gdrv, lo, cnt, end;
+    TermsLayout(uint32_t nrow, uint32_t nq, uint64_t nrp, const ClassBlock &block, const RegexBlock &rblock = RegexBlock())
+        : cls(block), rx(rblock)
     {
         search_detail::Carver carve;
         goff = carve(((size_t)nrow + 1) * 8);
         tflags = carve(nq);
         anchors = carve(cls.end);
+        regex = carve(rx.end);
         gdrv = carve.o;
         lo = gdrv + (size_t)nrp * 4;
         cnt = lo + (size_t)nrp * 4;
@@ -276,15 +339,17 @@ struct TermsLayout {
 
 // Slot Q_TERMS of a seeded batch: nq seed queries of nterm terms (term_total bytes) in nrow groups.  The queries' offsets
 // per term, the terms' offsets, a near batch's overflow word, every query's position inside its term, void flags and term
-// flags per term, a near batch's budgets, the sequence's block, the terms' bytes (SEARCH_PAD zero bytes behind them), the
-// seed hits per (term, chunk) pair, then per (group, chunk) pair the driver term and its hits, back to back.  `over` and
-// `budget` have room in a near batch alone (elsewhere they coincide with their neighbours and are not used).
+// flags per term, a near batch's budgets, the sequence's block, a regex batch's block, the terms' bytes (SEARCH_PAD zero
+// bytes behind them), the seed hits per (term, chunk) pair, then per (group, chunk) pair the driver term and its hits, back
+// to back.  `over` and `budget` have room in a near batch alone (elsewhere they coincide with their neighbours and are
+// not used).
 struct SeedLayout {
     ClassBlock cls;             // at `anchors`
-    size_t goff, soff, foff, over, pos, fvoid, tflags, budget, anchors, fbytes, tcnt, gdrv, cnt, end;
+    RegexBlock rx;              // at `regex`
+    size_t goff, soff, foff, over, pos, fvoid, tflags, budget, anchors, regex, fbytes, tcnt, gdrv, cnt, end;
     SeedLayout(uint32_t nrow, uint32_t nterm, uint32_t nq, uint64_t term_total, uint64_t ntp, uint64_t nrp, bool near,
-               const ClassBlock &block)
-        : cls(block)
+               const ClassBlock &block, const RegexBlock &rblock = RegexBlock())
+        : cls(block), rx(rblock)
     {
         search_detail::Carver carve;
         goff = carve(((size_t)nrow + 1) * 8);
@@ -296,6 +361,7 @@ struct SeedLayout {
         tflags = carve(nterm);
         budget = carve(near ? nterm : 0);
         anchors = carve(cls.end);
+        regex = carve(rx.end);
         fbytes = carve((size_t)term_total + SEARCH_PAD);
         tcnt = carve((size_t)ntp * 4);
         gdrv = carve.o;
