@@ -968,6 +968,63 @@ int pss_reader_count_near_icase_batch(pss_reader *r, const uint8_t *qbytes, cons
 int pss_near_seeds(const uint8_t *pat, uint64_t len, uint32_t k, int32_t letters, uint8_t *out, uint64_t cap, uint32_t *piece,
                    uint32_t *pos, uint32_t *lengths, uint32_t *count);
 /*
+ * ANY-OF search (no reference counterpart): `grep -e error -e warn -e fatal` over the entries -- per SET of alternatives the
+ * entries that contain at least one of them.  An entry is the bytes [start, end) of a chunk's text as the all-terms search takes
+ * them, the last byte of an unterminated last entry included.  Bytes are exact; under PSS_ANY_ICASE the rule is
+ * pss_reader_search_icase_batch's: A-Z and a-z fold and nothing else does.  Every entry comes at most once per set.
+ * Arguments: nalts alternatives back to back in abytes, cut by aoffsets (nalts + 1); set g is the alternatives set_offsets[g] ..
+ * set_offsets[g + 1] (nsets + 1 offsets, the last = nalts).  One row per set, packed as pss_reader_search_terms_batch packs its
+ * groups; flags is 0 or PSS_ANY_ICASE.
+ * Normalisation (host only, csrc/any_terms.h; pss_any_alternatives shows its result), in this order: under PSS_ANY_ICASE every
+ * alternative is folded to lower case; duplicates go; an alternative that holds 0x0A goes -- it occurs in no entry, and it
+ * voids itself, not its set --; an alternative that holds another one as a substring goes (it asks nothing more of an entry);
+ * the rest is sorted ascending bytewise.  What is left is prefix-free: no two alternatives can start at one text position.  A
+ * set whose alternatives all held 0x0A matches nothing: a count of 0, not an error.
+ * The search: a set is ONE term of a seeded batch (the case-insensitive and the near searches are the others), its alternatives
+ * back to back.  Exact: every alternative is one query at position 0.  Under PSS_ANY_ICASE every alternative is looked up through
+ * the spellings of its SEED, the longest window with at most F ASCII letters, leftmost on a tie, F = min(PSS_ICASE_SEED_LETTERS,
+ * floor(log2(64 / alternatives))): a set keeps the at most 64 queries the seeded kernels are written for, and F >= 1 is what caps
+ * a set at PSS_ANY_MAX_ALTS_ICASE.  Every hit is verified on the device (under fold its alternative over its whole length where
+ * the seed puts it) and kept iff no alternative of the set starts in front of it in its entry: the entry's leftmost match.
+ * Order: set-major, chunk-major inside a set, inside one pair the set's queries one interval behind the other -- exact: by
+ * alternative (ascending), then in suffix-array order, which for a normalised set IS suffix-array order of each entry's leftmost
+ * match of any alternative, so a set of one alternative returns what pss_reader_search_ids_batch returns under the default order;
+ * under fold: by alternative, then spelling (ascending), then suffix-array order of the seed occurrence, so a set of one
+ * alternative returns what pss_reader_search_icase_ids_batch returns.  pss_reader_set_result_order has no effect.  Always the
+ * general pipeline, no route bit of its own.  pss_reader_last_stats: hits = the sum over all queries and chunks of their exact
+ * occurrences, entries = what is returned.
+ * PSS_EINVAL (message in pss_last_error, *out / counts untouched), in this order: a null out / counts; a null abytes / aoffsets
+ * with nalts > 0 or a null set_offsets with nsets > 0; flags other than PSS_ANY_ICASE; alternative offsets that do not start at
+ * 0 or that decrease, set offsets that do not start at 0, that decrease or that do not end at nalts; then the first bad set as
+ * "set <g>: ...": a set without an alternative, an empty alternative, one of more than 2^32 - 1 bytes, more than
+ * PSS_ANY_MAX_ALTS alternatives after normalisation (PSS_ANY_MAX_ALTS_ICASE under PSS_ANY_ICASE); a null reader last.  Nothing
+ * is launched before all of that has passed.
+ * Not built: any-of clauses inside all-terms groups or wildcard patterns; an alternation driving pss_reader_search_regex_batch
+ * (it would hand this path its required set); budgets on alternatives; spans of alternatives; the fused, resident and mid
+ * paths, a device-resident result, dist.ShardedReader; a one-pass multi-pattern scan (Aho-Corasick, a first-byte bitmap);
+ * seed letters budgeted per alternative.
+ */
+#define PSS_ANY_ICASE 1u
+#define PSS_ANY_MAX_ALTS 64u
+#define PSS_ANY_MAX_ALTS_ICASE 32u
+/* packed entry text, one row per set */
+int pss_reader_search_any_batch(pss_reader *r, const uint8_t *abytes, const uint64_t *aoffsets, uint32_t nalts,
+                                const uint64_t *set_offsets, uint32_t nsets, uint32_t flags, pss_result **out);
+/* u64 entry ids, packed as pss_reader_search_ids_batch packs them */
+int pss_reader_search_any_ids_batch(pss_reader *r, const uint8_t *abytes, const uint64_t *aoffsets, uint32_t nalts,
+                                    const uint64_t *set_offsets, uint32_t nsets, uint32_t flags, pss_result **out);
+/* counts[g] = entries set g matches; nothing but nsets counters comes down */
+int pss_reader_count_any_batch(pss_reader *r, const uint8_t *abytes, const uint64_t *aoffsets, uint32_t nalts,
+                               const uint64_t *set_offsets, uint32_t nsets, uint32_t flags, uint64_t *counts);
+/* ONE set normalised, on the host: no reader, no GPU.  out (cap bytes: aoffsets[nalts] always suffice) receives the alternatives
+ * left back to back, offsets (room for nalts + 1) their *count + 1 offsets, seed_pos / seed_len (room for nalts each) per
+ * alternative the position and length of what is looked up inside it: 0 and its length, or under PSS_ANY_ICASE its seed
+ * (pss_icase_variants of those bytes with the set's F gives the queries).  letters: 1 .. 6, or <= 0 for the configured
+ * PSS_ICASE_SEED_LETTERS; the set's size bounds it.
+ * PSS_EINVAL: a null out / offsets / seed_pos / seed_len / count, letters > 6, then what the calls above name for one set. */
+int pss_any_alternatives(const uint8_t *abytes, const uint64_t *aoffsets, uint32_t nalts, uint32_t flags, int32_t letters,
+                         uint8_t *out, uint64_t cap, uint64_t *offsets, uint32_t *seed_pos, uint32_t *seed_len, uint32_t *count);
+/*
  * MATCH SPANS (no reference counterpart): where in an entry a pattern's best match stands, how long it is and how close, for
  * rows of (entry id, pattern) -- the third call beside "which entries" (the *_ids_batch calls) and "their text"
  * (pss_reader_entries_by_id).  12 bytes per row come down; no text does.

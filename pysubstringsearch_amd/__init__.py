@@ -28,7 +28,7 @@ except ImportError:   # pragma: no cover
     _pssglue = None
 
 __all__ = ['Writer', 'Reader', 'PackedResult', 'IdResult', 'DeviceResult', 'device_count', 'default_devices', 'release_workspace', 'workspace_bytes',
-           'glob_parse', 'glob_escape', 'glob_cores', 'icase_variants', 'near_pieces', 'near_seeds',
+           'glob_parse', 'glob_escape', 'glob_cores', 'icase_variants', 'near_pieces', 'near_seeds', 'any_alternatives',
            'regex_literals', 'regex_info', 'regex_match', 'regex_escape']
 
 
@@ -405,6 +405,54 @@ def near_seeds(pattern: bytes, k: int, letters: typing.Optional[int] = None) -> 
         out.append((int(piece[v]), int(pos[v]), raw[at:at + ln[v]]))
         at += ln[v]
     return out
+
+
+def _any_set(alts, where: str) -> typing.List[bytes]:
+    """One any-of set as a list of ``bytes``: ``TypeError`` for a bare ``bytes`` / ``str`` in the sequence's place (it would
+    be read as its characters) and for a member that is not ``bytes``, ``ValueError`` for an empty set or alternative."""
+    if isinstance(alts, (bytes, bytearray, str)):
+        raise TypeError(f"{where}: '{type(alts).__name__}' object cannot be converted to a sequence of alternatives")
+    alts = list(alts)
+    for a in alts:
+        if not isinstance(a, (bytes, bytearray)):
+            raise TypeError(f'{where}: an alternative must be bytes, not {type(a).__name__}')
+        if len(a) == 0:
+            raise ValueError(f'{where}: an empty alternative (every entry contains it)')
+    if not alts:
+        raise ValueError(f'{where}: no alternative (a set without one matches nothing: leave it out)')
+    return [bytes(a) for a in alts]
+
+
+def any_alternatives(terms: typing.Sequence[bytes], icase: bool = False,
+                     letters: typing.Optional[int] = None) -> typing.List[typing.Tuple[bytes, int, bytes]]:
+    """``[(alternative, seed_position, seed_bytes), ...]``: one any-of set as ``Reader.search_any_ids_batch`` asks the
+    device for it (include/pss.h, pss_any_alternatives).  The set is NORMALISED: under ``icase`` folded to lower case
+    (``A-Z`` alone), duplicates dropped, every alternative with a newline dropped (it occurs in no entry; it voids itself,
+    not its set), every alternative that holds another one as a substring dropped, the rest ascending bytewise -- what is
+    left is prefix-free.  Exact: every alternative is one query, ``seed_position`` 0 and ``seed_bytes`` the alternative.
+    Under ``icase`` an alternative is looked up through the spellings (``icase_variants``) of its SEED ``seed_bytes`` at
+    ``seed_position`` inside it: the longest window with at most ``F`` ASCII letters, the leftmost on a tie, ``F`` =
+    ``letters`` (1 .. 6; ``None`` = the configured ``PSS_ICASE_SEED_LETTERS``) but at most ``floor(log2(64 / len(result)))``,
+    so that a set has at most 64 queries.  ``ValueError`` for an empty set, an empty alternative, more than 64 alternatives
+    after normalisation (32 under ``icase``) and ``letters`` outside 1 .. 6; ``TypeError`` for a member that is not
+    ``bytes`` and an ``icase`` that is not a bool.  Host only: no device is touched."""
+    import numpy as np
+    flags = _ffi.ANY_ICASE if _icase_flag(icase) else 0
+    alts = _any_set(terms, 'any_alternatives')
+    if letters is not None and not 1 <= int(letters) <= 6:
+        raise ValueError(f'letters = {letters!r}: 1 .. 6, or None for PSS_ICASE_SEED_LETTERS')
+    blob, offs = _pack_queries(alts)
+    n = len(alts)
+    out = ctypes.create_string_buffer(max(1, len(blob)))
+    ooff, pos, ln = np.zeros(n + 1, dtype=np.uint64), np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
+    cnt = ctypes.c_uint32()
+    _ffi.check(_lib.pss_any_alternatives(blob, offs.ctypes.data, n, flags, 0 if letters is None else int(letters), out, len(blob),
+                                         ooff.ctypes.data, pos.ctypes.data, ln.ctypes.data, ctypes.byref(cnt)))
+    raw, res = out.raw, []
+    for j in range(cnt.value):
+        alt = raw[int(ooff[j]):int(ooff[j + 1])]
+        res.append((alt, int(pos[j]), alt[int(pos[j]):int(pos[j]) + int(ln[j])]))
+    return res
 
 
 def _near_budget(k) -> int:
@@ -1217,6 +1265,63 @@ class Reader:
     def count_regex(self, s: str, *, icase: bool = False) -> int:
         """Extension: how many entries match the regular expression ``s``."""
         return self.count_regex_bytes([s], icase=icase)[0]
+
+    def _any_batch(self, form: str, sets, icase):
+        """One ``pss_reader_search_any_*`` call over ``sets``, a sequence of sequences of ``bytes``."""
+        import numpy as np
+        flags = _ffi.ANY_ICASE if _icase_flag(icase) else 0
+        if isinstance(sets, (bytes, bytearray, str)):
+            raise TypeError(f"argument 'sets': '{type(sets).__name__}' object cannot be converted to a sequence of sets")
+        alts: typing.List[bytes] = []
+        soff = [0]
+        for g, one in enumerate(sets):
+            alts += _any_set(one, f'set {g}')
+            soff.append(len(alts))
+        blob, offs = _pack_queries(alts)
+        soff = np.array(soff, dtype=np.uint64)
+        name = {'packed': 'pss_reader_search_any_batch', 'ids': 'pss_reader_search_any_ids_batch',
+                'counts': 'pss_reader_count_any_batch'}[form]
+        ns = len(soff) - 1
+        return self._batch(getattr(_lib, name), (blob, offs.ctypes.data, len(alts), soff.ctypes.data, ns, flags), ns, form)
+
+    def search_any_batch_packed(self, sets: typing.Sequence[typing.Sequence[bytes]], *, icase: bool = False) -> 'PackedResult':
+        """Extension: per SET of alternatives, the entries that contain AT LEAST ONE of them (``grep -e a -e b``), as a
+        packed result like ``search_batch_packed``'s with one row per set.  "Contains" is what ``search`` means -- exact
+        bytes -- or, with ``icase=True``, what ``search_icase`` means: only ``A-Z`` / ``a-z`` fold.  Every entry comes at
+        most once per set.  The set is normalised on the host (``any_alternatives``: duplicates, alternatives with a
+        newline and alternatives that hold another one go; at most 64 are left, 32 under ``icase``, else ``ValueError``),
+        its alternatives -- under ``icase`` the spellings of their seeds -- are looked up as the queries of one term, and
+        the device keeps the hit of every entry's leftmost match (include/pss.h, pss_reader_search_any_batch).  A set
+        whose alternatives all hold a newline matches nothing.  Inside a (set, chunk) pair the entries come by alternative
+        (ascending), then spelling, then in suffix-array order: a set of one alternative returns what ``search_ids_batch``
+        (``icase``: ``search_icase_ids_batch``) returns, order included.  Always the general pipeline;
+        ``set_result_order`` has no effect.  ``ValueError`` for an empty set or alternative, ``TypeError`` for a member
+        that is not ``bytes`` and an ``icase`` that is not a bool."""
+        return self._any_batch('packed', sets, icase)
+
+    def search_any_ids_batch(self, sets: typing.Sequence[typing.Sequence[bytes]], *, icase: bool = False) -> 'IdResult':
+        """Extension: the ids (``search_ids_batch``) of the entries ``search_any_batch_packed`` returns, in the same
+        order; ``counts[g]`` of them belong to set g."""
+        return self._any_batch('ids', sets, icase)
+
+    def count_any_bytes(self, sets: typing.Sequence[typing.Sequence[bytes]], *, icase: bool = False) -> typing.List[int]:
+        """Extension: how many entries each set matches; only the counters come back."""
+        return self._any_batch('counts', sets, icase)
+
+    @staticmethod
+    def _str_any(terms):
+        if isinstance(terms, (str, bytes, bytearray)):
+            raise TypeError(f"argument 'terms': '{type(terms).__name__}' object cannot be converted to a sequence of 'PyString'")
+        return [[_utf8(t, 'terms') for t in terms]]
+
+    def search_any(self, terms: typing.Sequence[str], *, icase: bool = False) -> typing.List[str]:
+        """Extension: the entries that contain at least one of ``terms`` (``search_any_batch_packed``); with
+        ``icase=True`` whatever the case of ASCII letters."""
+        return _packed_strs(self.search_any_batch_packed(self._str_any(terms), icase=icase))
+
+    def count_any(self, terms: typing.Sequence[str], *, icase: bool = False) -> int:
+        """Extension: how many entries contain at least one of ``terms``."""
+        return self.count_any_bytes(self._str_any(terms), icase=icase)[0]
 
     @staticmethod
     def _icase_args(patterns):

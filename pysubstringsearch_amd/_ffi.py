@@ -158,6 +158,8 @@ ANCHOR_START, ANCHOR_END = 1, 2
 SEQ_FOLD = 1        # PSS_SEQ_FOLD: the flags word of the pss_reader_search_seqc_* calls
 REGEX_ICASE = 1     # PSS_REGEX_ICASE: the flags word of pss_regex_compile and the pss_reader_search_regex_* calls
 REGEX_MAX_STATES = 4096
+ANY_ICASE = 1       # PSS_ANY_ICASE: the flags word of the pss_reader_search_any_* calls and of pss_any_alternatives
+ANY_MAX_ALTS, ANY_MAX_ALTS_ICASE = 64, 32
 
 
 class RegexDfa(ctypes.Structure):
@@ -341,6 +343,10 @@ def _load() -> ctypes.CDLL:
         'pss_reader_search_near_icase_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, ctypes.c_int, pvp]),
         'pss_reader_search_near_icase_ids_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, ctypes.c_int, pvp]),
         'pss_reader_count_near_icase_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, ctypes.c_int, vp]),
+        'pss_reader_search_any_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, u32, u32, pvp]),
+        'pss_reader_search_any_ids_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, u32, u32, pvp]),
+        'pss_reader_count_any_batch': (ctypes.c_int, [vp, vp, vp, u32, vp, u32, u32, vp]),
+        'pss_any_alternatives': (ctypes.c_int, [vp, vp, u32, u32, i32, vp, u64, vp, vp, vp, ctypes.POINTER(u32)]),
         'pss_reader_match_spans': (ctypes.c_int, [vp, vp, vp, vp, vp, u32, vp, u32, vp]),
         'pss_near_seeds': (ctypes.c_int, [vp, u64, u32, i32, vp, u64, ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(u32),
                                           ctypes.POINTER(u32)]),

@@ -24,6 +24,7 @@
 #include "sa_build.h"
 #include "search.h"
 #include "regex_compile.h"
+#include "any_terms.h"
 
 using namespace pss;
 

@@ -2330,6 +2330,205 @@ extern "C" int pss_near_seeds(const uint8_t *pat, uint64_t len, uint32_t k, int3
     });
 }
 
+// ---- any-of search: set -> its normalised alternatives as one term -> the alternatives, or the spellings of their seeds ----
+// ---- (any_terms.h, any_impl.h) ---------------------------------------------------------------------------
+
+namespace {
+
+// Set g = alternatives first .. last of the batch, judged and normalised (any_terms.h): no set is empty, no alternative is
+// empty or has more than 2^32 - 1 bytes, and at most 64 alternatives are left, 32 under fold.
+int any_set(const char *who, uint64_t g, const uint8_t *abytes, const uint64_t *aoffsets, uint64_t first, uint64_t last, bool fold, AnySet *set)
+{
+    if (first == last) {
+        set_error("%s: set %llu: no alternative (a set without one matches nothing: leave it out)", who, (unsigned long long)g);
+        return PSS_EINVAL;
+    }
+    for (uint64_t a = first; a < last; ++a) {
+        const uint64_t len = aoffsets[a + 1] - aoffsets[a];
+        if (len == 0 || len > 0xffffffffull) {
+            set_error(len ? "%s: set %llu: alternative %llu has more than 2^32 - 1 bytes (a chunk has fewer)"
+                          : "%s: set %llu: alternative %llu is empty (every entry contains it)",
+                      who, (unsigned long long)g, (unsigned long long)(a - first));
+            return PSS_EINVAL;
+        }
+    }
+    *set = any_normalise(abytes, aoffsets, first, last, fold);
+    const uint32_t cap = fold ? ANY_MAX_ALTS_FOLD : ANY_MAX_ALTS;
+    if (set->alts.size() > cap) {
+        set_error("%s: set %llu: %llu alternatives after normalisation, more than the %u a set takes%s", who, (unsigned long long)g,
+                  (unsigned long long)set->alts.size(), cap, fold ? " under PSS_ANY_ICASE" : "");
+        return PSS_EINVAL;
+    }
+    return PSS_OK;
+}
+
+// The seed of one alternative of a normalised set of n under fold (letters: the configured limit).
+uint32_t any_seed(const std::string &alt, uint32_t n, uint32_t letters, uint64_t *so, uint64_t *sl)
+{
+    return fold_seed(reinterpret_cast<const uint8_t *>(alt.data()), alt.size(), any_seed_letters(n, letters), so, sl);
+}
+
+// The flags and offsets of the any-of calls, in the documented order (the output argument is the caller's to judge first).
+int any_args(const char *who, const uint8_t *abytes, const uint64_t *aoffsets, uint32_t nalts, const uint64_t *set_offsets, uint32_t nsets,
+             uint32_t flags)
+{
+    if ((nalts && (!abytes || !aoffsets)) || (nsets && !set_offsets)) {
+        set_error("%s: bad arguments", who);
+        return PSS_EINVAL;
+    }
+    if (flags & ~PSS_ANY_ICASE) {
+        set_error("%s: flags = %u (PSS_ANY_ICASE = 1 or nothing)", who, flags);
+        return PSS_EINVAL;
+    }
+    if (nalts && aoffsets[0] != 0) {
+        set_error("%s: the alternative offsets start at %llu, not at 0", who, (unsigned long long)aoffsets[0]);
+        return PSS_EINVAL;
+    }
+    for (uint32_t a = 0; a < nalts; ++a)
+        if (aoffsets[a + 1] < aoffsets[a]) {
+            set_error("%s: the alternative offsets decrease at alternative %u", who, a);
+            return PSS_EINVAL;
+        }
+    if (nsets && set_offsets[0] != 0) {
+        set_error("%s: the set offsets start at %llu, not at 0", who, (unsigned long long)set_offsets[0]);
+        return PSS_EINVAL;
+    }
+    for (uint32_t g = 0; g < nsets; ++g)
+        if (set_offsets[g + 1] < set_offsets[g]) {
+            set_error("%s: the set offsets decrease at set %u", who, g);
+            return PSS_EINVAL;
+        }
+    if (nsets && set_offsets[nsets] != nalts) {
+        set_error("%s: the set offsets end at %llu, not at the %u alternatives", who, (unsigned long long)set_offsets[nsets], nalts);
+        return PSS_EINVAL;
+    }
+    return PSS_OK;
+}
+
+// The three any-of calls: their own argument checks, then every set as a group of one include term -- its normalised
+// alternatives back to back -- whose seed queries are the alternatives themselves or, under fold, alternative by
+// alternative the spellings of its seed.  The reader is looked at last, as for the other seeded calls.
+int any_batch(pss_reader *r, const char *who, const uint8_t *abytes, const uint64_t *aoffsets, uint32_t nalts, const uint64_t *set_offsets,
+              uint32_t nsets, uint32_t flags, SearchMode mode, pss_result **out, uint64_t *counts)
+{
+    if (!out_ok_by_mode(mode, nsets, out, counts)) {
+        set_error("%s: bad arguments", who);
+        return PSS_EINVAL;
+    }
+    PSS_TRY(any_args(who, abytes, aoffsets, nalts, set_offsets, nsets, flags));
+    const bool fold = (flags & PSS_ANY_ICASE) != 0;
+    const uint32_t letters = icase_letters(0);
+    SeededGroups b;
+    std::vector<uint64_t> talts(1, 0), aoff(1, 0);
+    std::vector<uint32_t> qalt;
+    b.voff.assign(1, 0);
+    b.soff.assign(1, 0);
+    b.foff.assign(1, 0);
+    for (uint32_t g = 0; g < nsets; ++g) {
+        AnySet set;
+        PSS_TRY(any_set(who, g, abytes, aoffsets, set_offsets[g], set_offsets[g + 1], fold, &set));
+        const uint32_t n = (uint32_t)set.alts.size();
+        for (const std::string &alt : set.alts) {
+            const uint32_t j = (uint32_t)(aoff.size() - 1);
+            b.fbytes.insert(b.fbytes.end(), alt.begin(), alt.end());
+            aoff.push_back(b.fbytes.size());
+            uint64_t so = 0, sl = alt.size();
+            const uint32_t nl = fold ? any_seed(alt, n, letters, &so, &sl) : 0;
+            const size_t o = b.vbytes.size();
+            b.vbytes.resize(o + (size_t)(sl << nl));
+            if (fold)
+                fold_spellings(reinterpret_cast<const uint8_t *>(alt.data()) + so, sl, nl, b.vbytes.data() + o);
+            else
+                memcpy(b.vbytes.data() + o, alt.data(), alt.size());
+            for (uint32_t v = 0; v < (1u << nl); ++v) {          // (exact: one query, the alternative itself at 0)
+                b.voff.push_back(b.voff.back() + sl);
+                b.pos.push_back((uint32_t)so);
+                qalt.push_back(j);
+            }
+        }
+        if (b.voff.size() - 1 > 0xffffffffull || aoff.size() - 1 > 0xffffffffull) {
+            set_error("%s: the sets expand to more than the 2^32 - 1 seed queries a batch takes (at set %u)", who, g);
+            return PSS_EINVAL;
+        }
+        talts.push_back(aoff.size() - 1);
+        b.foff.push_back(b.fbytes.size());
+        b.soff.push_back(b.voff.size() - 1);
+    }
+    if (!r) {
+        set_error("%s: bad arguments (no reader)", who);
+        return PSS_EINVAL;
+    }
+    b.fbytes.push_back(0);                   // (data() of an empty vector may be null)
+    b.vbytes.push_back(0);
+    b.pos.push_back(0);
+    qalt.push_back(0);
+    b.one_term_each(nsets);
+    SearchRequest rq = b.request(nsets, b.one_each.data(), nsets, b.no_exclude.data(), nullptr, mode);
+    rq.any_term_alts = talts.data();
+    rq.any_alt_offsets = aoff.data();
+    rq.any_query_alt = qalt.data();
+    rq.any_nalts = (uint32_t)(aoff.size() - 1);
+    rq.any_fold = fold;
+    return answer_by_mode(r, rq, out, counts);
+}
+
+}  // namespace
+
+extern "C" int pss_reader_search_any_batch(pss_reader *r, const uint8_t *abytes, const uint64_t *aoffsets, uint32_t nalts,
+                                           const uint64_t *set_offsets, uint32_t nsets, uint32_t flags, pss_result **out)
+{
+    return guarded([&]() -> int { return any_batch(r, "pss_reader_search_any_batch", abytes, aoffsets, nalts, set_offsets, nsets, flags, SEARCH_FULL, out, nullptr); });
+}
+
+extern "C" int pss_reader_search_any_ids_batch(pss_reader *r, const uint8_t *abytes, const uint64_t *aoffsets, uint32_t nalts,
+                                               const uint64_t *set_offsets, uint32_t nsets, uint32_t flags, pss_result **out)
+{
+    return guarded([&]() -> int { return any_batch(r, "pss_reader_search_any_ids_batch", abytes, aoffsets, nalts, set_offsets, nsets, flags, SEARCH_IDS, out, nullptr); });
+}
+
+extern "C" int pss_reader_count_any_batch(pss_reader *r, const uint8_t *abytes, const uint64_t *aoffsets, uint32_t nalts,
+                                          const uint64_t *set_offsets, uint32_t nsets, uint32_t flags, uint64_t *counts)
+{
+    return guarded([&]() -> int { return any_batch(r, "pss_reader_count_any_batch", abytes, aoffsets, nalts, set_offsets, nsets, flags, SEARCH_COUNTS, nullptr, counts); });
+}
+
+extern "C" int pss_any_alternatives(const uint8_t *abytes, const uint64_t *aoffsets, uint32_t nalts, uint32_t flags, int32_t letters,
+                                    uint8_t *out, uint64_t cap, uint64_t *offsets, uint32_t *seed_pos, uint32_t *seed_len, uint32_t *count)
+{
+    return guarded([&]() -> int {
+        const char *who = "pss_any_alternatives";
+        if (!out || !offsets || !seed_pos || !seed_len || !count || letters > 6) {
+            set_error("%s: bad arguments (letters = %d: 1 .. 6, or <= 0 for PSS_ICASE_SEED_LETTERS)", who, (int)letters);
+            return PSS_EINVAL;
+        }
+        const uint64_t one_set[2] = {0, nalts};
+        PSS_TRY(any_args(who, abytes, aoffsets, nalts, one_set, 1, flags));
+        const bool fold = (flags & PSS_ANY_ICASE) != 0;
+        AnySet set;
+        PSS_TRY(any_set(who, 0, abytes, aoffsets, 0, nalts, fold, &set));
+        uint64_t total = 0;
+        for (const std::string &alt : set.alts) total += alt.size();
+        if (total > cap) {
+            set_error("%s: the alternatives need %llu bytes, more than the %llu bytes of out", who, (unsigned long long)total,
+                      (unsigned long long)cap);
+            return PSS_EINVAL;
+        }
+        const uint32_t n = (uint32_t)set.alts.size();
+        offsets[0] = 0;
+        for (uint32_t j = 0; j < n; ++j) {
+            const std::string &alt = set.alts[j];
+            memcpy(out + offsets[j], alt.data(), alt.size());
+            offsets[j + 1] = offsets[j] + alt.size();
+            uint64_t so = 0, sl = alt.size();
+            if (fold) any_seed(alt, n, icase_letters(letters), &so, &sl);
+            seed_pos[j] = (uint32_t)so;
+            seed_len[j] = (uint32_t)sl;
+        }
+        *count = n;
+        return PSS_OK;
+    });
+}
+
 namespace {
 
 // ids[0 .. n) of ONE single-device reader as (resident chunk, line) pairs, validated on the host (the reader knows every

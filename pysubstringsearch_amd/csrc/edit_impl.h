@@ -201,7 +201,7 @@ struct EditMatch {
         if (ok) entry_bounds(ch, di, ls, ll);
     }
     static __device__ __forceinline__ bool before(const ChunkDesc &ch, const SeedTerms &T, u32 g, u32 from, u32 last, u32 plen, u32 gl,
-                                                  u32 gbase)
+                                                  u32 gbase, u32)
     {
         return edit_scan<false>(ch, from, last, T.bytes + T.off[g], plen, T.pos + (u32)T.soff[g], T.budget[g], gl, gbase);
     }
@@ -247,7 +247,7 @@ struct EditMatch<true> {
         }
     }
     static __device__ __forceinline__ bool before(const ChunkDesc &ch, const SeedTerms &T, u32 g, u32 from, u32 last, u32 plen, u32 gl,
-                                                  u32 gbase)
+                                                  u32 gbase, u32)
     {
         return edit_scan<true>(ch, from, last, T.bytes + T.off[g], plen, nullptr, T.budget[g], gl, gbase);
     }

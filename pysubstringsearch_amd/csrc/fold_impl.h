@@ -61,7 +61,7 @@ struct FoldMatch {
     // Does a folded occurrence of the term START in text[from, last]?  entry_scan under fold, for the TG lanes of one
     // group together.
     static __device__ __forceinline__ bool before(const ChunkDesc &ch, const SeedTerms &T, u32 g, u32 from, u32 last, u32 plen, u32 gl,
-                                                  u32 gbase)
+                                                  u32 gbase, u32)
     {
         return entry_scan<true, false>(ch, from, last, T.bytes + T.off[g], plen, gl, gbase) != kNone;
     }

@@ -145,7 +145,7 @@ struct NearMatch {
         }
     }
     static __device__ __forceinline__ bool before(const ChunkDesc &ch, const SeedTerms &T, u32 g, u32 from, u32 last, u32 plen, u32 gl,
-                                                  u32 gbase)
+                                                  u32 gbase, u32)
     {
         return near_scan<false>(ch, from, last, T.bytes + T.off[g], plen, T.budget[g], gl, gbase);
     }
@@ -193,7 +193,7 @@ struct NearMatch<true> {
         }
     }
     static __device__ __forceinline__ bool before(const ChunkDesc &ch, const SeedTerms &T, u32 g, u32 from, u32 last, u32 plen, u32 gl,
-                                                  u32 gbase)
+                                                  u32 gbase, u32)
     {
         return near_scan<true>(ch, from, last, T.bytes + T.off[g], plen, T.budget[g], gl, gbase);
     }

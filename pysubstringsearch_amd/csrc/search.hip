@@ -1751,6 +1751,7 @@ static void newline_flags(const u8 *bytes, const u64 *off, u32 n, u8 set, u8 *fl
 #include "regex_impl.h"
 #include "seed_impl.h"
 #include "fold_impl.h"
+#include "any_impl.h"
 #include "near_impl.h"
 #include "edit_impl.h"
 #include "span_impl.h"
@@ -1813,6 +1814,8 @@ struct Batch : BatchShape {
     u32 *d_m = nullptr;                             // the budget per pattern and the flag of a pair whose pieces' hits pass
     u8 *d_nk = nullptr;                             // 2^32 - 1 (both null under fold)
     u64 *d_over = nullptr;
+    AnyAlts h_any{};                                // an any-of batch: the block's three pointers as they go up (seed_drivers), and
+    const AnyAlts *d_any = nullptr;                 // where they went
     // ... and of the mid and the general pipeline, sized by each: entry bounds per hit, the scans over them, the result
     u32 *d_start = nullptr, *d_len = nullptr;
     u64 *d_eidx = nullptr, *d_boff = nullptr, *d_entoff = nullptr;
@@ -2239,13 +2242,14 @@ int Batch::pick_drivers()
 int Batch::seed_drivers()
 {
     const u64 ttotal = rq.term_offsets[nterm];
-    const SeedLayout L(nrow, nterm, nq, ttotal, ntp, nrp, near, class_block(), regex_block());
+    const bool summed = near || any;      // (the queries' intervals may overlap or repeat: the pair's sum is judged)
+    const SeedLayout L(nrow, nterm, nq, ttotal, ntp, nrp, summed, class_block(), regex_block(), AnyBlock(any, nterm, rq.any_nalts, nq));
     u8 *base;
     PSS_TRY(take(Q_TERMS, L.end, base));
     d_goff = reinterpret_cast<u64 *>(base + L.goff);
     d_soff = reinterpret_cast<u64 *>(base + L.soff);
     d_foff = reinterpret_cast<u64 *>(base + L.foff);
-    d_over = near ? reinterpret_cast<u64 *>(base + L.over) : nullptr;
+    d_over = summed ? reinterpret_cast<u64 *>(base + L.over) : nullptr;
     d_pos = reinterpret_cast<u32 *>(base + L.pos);
     d_fvoid = base + L.fvoid;
     d_tflags = base + L.tflags;
@@ -2262,16 +2266,24 @@ int Batch::seed_drivers()
     PSS_TRY(upload(d_tflags, own_tflags.data(), nterm));
     PSS_TRY(upload_anchors(base + L.anchors, L.cls));
     PSS_TRY(upload_regex(base + L.regex, L.rx));
-    if (near) {
-        PSS_TRY(upload(d_nk, rq.near_budget, nterm));
-        PSS_HIP(hipMemsetAsync(d_over, 0, 8, s));
+    if (near) PSS_TRY(upload(d_nk, rq.near_budget, nterm));
+    if (summed) PSS_HIP(hipMemsetAsync(d_over, 0, 8, s));
+    if (any) {          // the block behind everything else: its pointers (h_any lives as long as the batch), then what they point at
+        u8 *at = base + L.any;
+        h_any = AnyAlts{reinterpret_cast<const u64 *>(at + L.alts.talts), reinterpret_cast<const u64 *>(at + L.alts.aoff),
+                        reinterpret_cast<const u32 *>(at + L.alts.qalt)};
+        d_any = reinterpret_cast<const AnyAlts *>(at + L.alts.hdr);
+        PSS_TRY(upload(at + L.alts.hdr, &h_any, sizeof h_any));
+        PSS_TRY(upload(at + L.alts.talts, rq.any_term_alts, ((size_t)nterm + 1) * 8));
+        PSS_TRY(upload(at + L.alts.aoff, rq.any_alt_offsets, ((size_t)rq.any_nalts + 1) * 8));
+        PSS_TRY(upload(at + L.alts.qalt, rq.any_query_alt, (size_t)nq * 4));
     }
     PSS_HIP(hipMemsetAsync(d_fbytes + ttotal, 0, SEARCH_PAD, s));
     PSS_TRY(upload(d_fbytes, rq.term_bytes, ttotal));
     hipLaunchKernelGGL(seed_union_kernel, dim3((u32)((ntp + 255) / 256)), dim3(256), 0, s, nc, d_soff, d_fvoid, d_cnt, ntp, d_tcnt, d_over);
     hipLaunchKernelGGL(terms_driver_kernel<false>, dim3((u32)((nrp + 255) / 256)), dim3(256), 0, s, nc, d_goff, d_tflags,
                        (const u32 *)nullptr, d_tcnt, nrp, d_gdrv, (u32 *)nullptr, p_cnt);
-    if (near) PSS_HIP(hipMemcpyAsync(h_small + PW_NEAR_OVERFLOW, d_over, 8, hipMemcpyDeviceToHost, s));
+    if (summed) PSS_HIP(hipMemcpyAsync(h_small + PW_NEAR_OVERFLOW, d_over, 8, hipMemcpyDeviceToHost, s));
     return PSS_OK;
 }
 
@@ -2297,6 +2309,10 @@ int Batch::scan_hits(u64 *H)
     PSS_HIP(hipMemcpyAsync(h_small + PW_COUNT, d_total, 8, hipMemcpyDeviceToHost, s));
     PSS_HIP(hipStreamSynchronize(s));
     *H = h_small[PW_COUNT];
+    if (any && h_small[PW_NEAR_OVERFLOW]) {    // (the same flag: alternatives that share a seed under fold)
+        set_error("search: the alternatives of one set have more than 2^32 - 1 hits in one chunk: more than an any-of batch takes");
+        return PSS_EINVAL;
+    }
     if (near && h_small[PW_NEAR_OVERFLOW]) {   // (seed_union_kernel's flag, fetched by seed_drivers: the one place a pair's 64-bit sum
                                                // is judged, out of a test's reach and checked by reading; nothing is reserved yet)
         set_error("search: the pieces of one pattern have more than 2^32 - 1 hits in one chunk: more than a batch within k %s takes",
@@ -2361,12 +2377,16 @@ int Batch::candidates(u64 H, u32 grid)
         // its entry and as its alignment's first exact piece; under edits: the piece's two sides within the budget); then the
         // survivors against the entry in front of them: one candidate per entry, its leftmost match
         PSS_TRY(take(Q_SEED_M, H * 4, d_m));
-        const SeedTerms T{d_fbytes, d_foff, d_soff, d_pos, d_nk};
-        // (six instantiations: fold; within a budget of mismatches or edits, each in exact bytes or, fold_near, under fold)
-        auto *hits = edits  ? (fold_near ? seed_hits_kernel<EditMatch<true>> : seed_hits_kernel<EditMatch<false>>)
+        SeedTerms T{d_fbytes, d_foff, d_soff, d_pos, {d_nk}};
+        if (any) T.any = d_any;
+        // (eight instantiations: fold; within a budget of mismatches or edits, each in exact bytes or, fold_near, under fold; any
+        // of a set, in exact bytes or, any_fold, under fold)
+        auto *hits = any    ? (any_fold ? seed_hits_kernel<AnyMatch<true>> : seed_hits_kernel<AnyMatch<false>>)
+                     : edits  ? (fold_near ? seed_hits_kernel<EditMatch<true>> : seed_hits_kernel<EditMatch<false>>)
                      : near ? (fold_near ? seed_hits_kernel<NearMatch<true>> : seed_hits_kernel<NearMatch<false>>)
                             : seed_hits_kernel<FoldMatch>;
-        auto *dedupe = edits  ? (fold_near ? seed_dedupe_kernel<EditMatch<true>> : seed_dedupe_kernel<EditMatch<false>>)
+        auto *dedupe = any    ? (any_fold ? seed_dedupe_kernel<AnyMatch<true>> : seed_dedupe_kernel<AnyMatch<false>>)
+                       : edits  ? (fold_near ? seed_dedupe_kernel<EditMatch<true>> : seed_dedupe_kernel<EditMatch<false>>)
                        : near ? (fold_near ? seed_dedupe_kernel<NearMatch<true>> : seed_dedupe_kernel<NearMatch<false>>)
                               : seed_dedupe_kernel<FoldMatch>;
         hipLaunchKernelGGL(hits, dim3(grid), dim3(256), 0, s, d_chunks, nc, T, d_lo, d_cnt, nrp, d_hitoff, H, d_start, d_len, d_m, d_gdrv);
@@ -2478,6 +2498,11 @@ int search_batch_device(DeviceCtx *ctx, const ChunkDesc *d_chunks, const LineDes
     case REQUEST_REGEX:
         set_error("search: a regex batch is an all-terms batch without an exclude term that states its headers, class maps and tables, "
                   "every table inside the tables and at most 64 MiB of them; it takes the general pipeline to a host result");
+        return PSS_EINVAL;
+    case REQUEST_ANY:
+        set_error("search: an any-of batch is a seeded batch of one include term per group, without budgets, sequence anchors, classes "
+                  "or tables, that states its terms' alternatives, their offsets and every query's alternative; every query lies "
+                  "inside its alternative, and in exact bytes is its alternative");
         return PSS_EINVAL;
     }
     const u32 rows = rq.rows();

@@ -92,6 +92,20 @@ struct SearchRequest {
     // SEARCH_DEVICE or low_latency.
     const uint32_t *regex_hdr = nullptr; const uint8_t *regex_cls = nullptr; const uint16_t *regex_tables = nullptr;
     uint64_t regex_table_words = 0;
+    // any_term_alts .. any_nalts, together with the seeded block and no budgets: an ANY-OF batch (any_impl.h).  The
+    // groups are the ngroups = nterms SETS, one include term each (identity group_offsets, zero exclude flags); term_bytes holds
+    // a set's ALTERNATIVES back to back -- normalised (any_terms.h): no 0x0A, none a substring of another, ascending; folded to
+    // lower case where the queries are spellings --, and a query belongs to one alternative, no longer to the whole term:
+    //   any_term_alts (nterms + 1): the alternatives of set t are any_term_alts[t] .. any_term_alts[t + 1];
+    //   any_alt_offsets (any_nalts + 1): alternative j is term_bytes[any_alt_offsets[j], any_alt_offsets[j + 1]), not empty;
+    //   any_query_alt (nq): the alternative query v was taken from; seed_pos[v] is its position inside THAT alternative.
+    // any_fold: the alternatives are compared under ASCII case folding -- they are folded to lower case, and a query is a
+    // spelling of its alternative's seed; else a query is its alternative, at position 0.
+    // A set may have no alternative left (all of them held a 0x0A): it has no query and matches nothing.  Not with anchors,
+    // seq_anchors, a class block, budgets, a regex block, SEARCH_DEVICE or low_latency.
+    const uint64_t *any_term_alts = nullptr, *any_alt_offsets = nullptr; const uint32_t *any_query_alt = nullptr;
+    uint32_t any_nalts = 0;
+    bool any_fold = false;
     uint32_t rows() const { return group_offsets ? ngroups : nq; }     // rows of the result: queries, or groups of terms
     bool low_latency = false;            // one query through the resident kernel when it fits (an unanchored SEARCH_FULL batch only)
     // sa_order: the entries of one (query, chunk) pair come out in the reference's order -- suffix-array order of the FIRST hit
@@ -132,6 +146,7 @@ enum RequestVerdict {
     REQUEST_SEEDED,
     REQUEST_CLASS,
     REQUEST_REGEX,
+    REQUEST_ANY,
 };
 
 // A seeded batch carries its groups, its terms and the queries' offsets and positions, and either exclude flags or sequence
@@ -185,6 +200,39 @@ inline bool regex_request_ok(const SearchRequest &rq)
     return ok;
 }
 
+// An any-of batch is a seeded batch of identity groups without an exclude term that states all of its block, and nothing of
+// another search.  The offsets are monotone and end where their tables end: the alternatives tile every term, the queries
+// are dealt out term by term.  Every query's alternative is one of its term's, and the query fits into it behind its
+// position -- all that AnyMatch's reads rest on (any_impl.h): the window it compares is the alternative's, found from the
+// query's hit by a position that cannot leave it.
+inline bool any_request_ok(const SearchRequest &rq)
+{
+    bool ok = rq.any_term_alts && rq.any_alt_offsets && rq.any_query_alt && rq.seed_offsets && rq.seed_pos && rq.group_offsets &&
+              rq.term_bytes && rq.term_offsets && rq.exclude && (rq.qoffsets || !rq.nq) && !rq.anchors && !rq.seq_anchors &&
+              !rq.class_bytes && !rq.near_budget && !rq.near_edits && !rq.near_fold && !rq.regex_hdr && rq.mode != SEARCH_DEVICE &&
+              !rq.low_latency && rq.ngroups == rq.nterms;
+    if (!ok) return false;
+    const uint32_t nt = rq.nterms, na = rq.any_nalts;
+    ok = rq.any_term_alts[0] == 0 && rq.any_term_alts[nt] == na && rq.any_alt_offsets[0] == 0 && rq.term_offsets[0] == 0 &&
+         rq.any_alt_offsets[na] == rq.term_offsets[nt] && rq.seed_offsets[0] == 0 && rq.seed_offsets[nt] == rq.nq;
+    for (uint32_t j = 0; ok && j < na; ++j)
+        ok = rq.any_alt_offsets[j] < rq.any_alt_offsets[j + 1] && rq.any_alt_offsets[j + 1] - rq.any_alt_offsets[j] <= 0xffffffffull;
+    for (uint32_t t = 0; ok && t < nt; ++t) {
+        const uint64_t j0 = rq.any_term_alts[t], j1 = rq.any_term_alts[t + 1], v0 = rq.seed_offsets[t], v1 = rq.seed_offsets[t + 1];
+        ok = rq.group_offsets[t] == t && rq.group_offsets[t + 1] == (uint64_t)t + 1 && rq.exclude[t] == 0 && j0 <= j1 && j1 <= na &&
+             v0 <= v1 && v1 <= rq.nq && rq.term_offsets[t] <= rq.term_offsets[t + 1] && rq.any_alt_offsets[j0] == rq.term_offsets[t] &&
+             rq.any_alt_offsets[j1] == rq.term_offsets[t + 1];
+        for (uint64_t v = v0; ok && v < v1; ++v) {
+            const uint64_t j = rq.any_query_alt[v];
+            ok = j >= j0 && j < j1 && rq.qoffsets[v] <= rq.qoffsets[v + 1] &&
+                 (uint64_t)rq.seed_pos[v] + (rq.qoffsets[v + 1] - rq.qoffsets[v]) <= rq.any_alt_offsets[j + 1] - rq.any_alt_offsets[j];
+            // (exact bytes: nothing is compared behind the lookup, so the query IS the alternative)
+            ok = ok && (rq.any_fold || (rq.seed_pos[v] == 0 && rq.qoffsets[v + 1] - rq.qoffsets[v] == rq.any_alt_offsets[j + 1] - rq.any_alt_offsets[j]));
+        }
+    }
+    return ok;
+}
+
 // nc: resident chunks; have_lines: their line tables were built.
 inline RequestVerdict check_request(const SearchRequest &rq, uint32_t nc, bool have_lines)
 {
@@ -198,6 +246,7 @@ inline RequestVerdict check_request(const SearchRequest &rq, uint32_t nc, bool h
         !class_request_ok(rq))
         return REQUEST_CLASS;
     if ((rq.regex_hdr || rq.regex_cls || rq.regex_tables || rq.regex_table_words) && !regex_request_ok(rq)) return REQUEST_REGEX;
+    if ((rq.any_term_alts || rq.any_alt_offsets || rq.any_query_alt || rq.any_nalts || rq.any_fold) && !any_request_ok(rq)) return REQUEST_ANY;
     return REQUEST_OK;
 }
 
@@ -213,6 +262,8 @@ struct BatchShape {
     bool edits;                         // near, and the budget counts edits: EditMatch in NearMatch's place (edit_impl.h, 4.17)
     bool fold_near;                     // near, and the budget is counted under fold: the <true> forms of either Match (4.19)
     bool regex;                         // terms, and every candidate is walked through its group's DFA (regex_impl.h, 4.21)
+    bool any;                           // seeded, and a term is a set of alternatives: AnyMatch, exact or under fold (any_impl.h, 4.22)
+    bool any_fold;                      // any, under fold: the queries are spellings of the alternatives' seeds
     bool sa_order;
     // An all-terms batch (all_terms_impl.h) has a second pair space: its nq queries are terms, its result rows are the ng
     // groups, and everything from the first scan on runs over (group, chunk) pairs.  For every other batch the two agree.
@@ -239,6 +290,8 @@ struct BatchShape {
         edits = near && rq.near_edits;
         fold_near = near && rq.near_fold;
         regex = terms && rq.regex_hdr != nullptr;
+        any = seeded && rq.any_term_alts != nullptr;
+        any_fold = any && rq.any_fold;
         // (counts do not depend on the order; one hit per entry has one order; an all-terms batch keeps its driver's text order)
         sa_order = rq.sa_order && !counts && !anchored && !terms;
         nrow = rq.rows();
@@ -315,6 +368,24 @@ struct RegexBlock {
     }
 };
 
+// What an any-of batch keeps behind everything else in Q_TERMS, as AnyMatch reads it (AnyAlts of seed_impl.h): the three
+// pointers themselves, the alternatives of every term, the alternatives' offsets into the terms' bytes, every query's
+// alternative.  Offsets from its own start; nothing at all (end = 0) where the batch is no any-of batch.
+struct AnyBlock {
+    size_t hdr = 0, talts = 0, aoff = 0, qalt = 0, end = 0;
+    AnyBlock() = default;
+    AnyBlock(bool any, uint32_t nterm, uint32_t nalts, uint32_t nq)
+    {
+        if (!any) return;
+        search_detail::Carver carve;
+        hdr = carve(3 * sizeof(void *));
+        talts = carve(((size_t)nterm + 1) * 8);
+        aoff = carve(((size_t)nalts + 1) * 8);
+        qalt = carve((size_t)nq * 4);
+        end = carve.o;
+    }
+};
+
 // Slot Q_TERMS of an all-terms or a sequence batch of nq terms in nrow groups: group offsets, term flags, the sequence's
 // block, a regex batch's block, then per (group, chunk) pair the driver term, its interval and its hits -- three arrays
 // back to back.
@@ -341,15 +412,17 @@ struct TermsLayout {
 // per term, the terms' offsets, a near batch's overflow word, every query's position inside its term, void flags and term
 // flags per term, a near batch's budgets, the sequence's block, a regex batch's block, the terms' bytes (SEARCH_PAD zero
 // bytes behind them), the seed hits per (term, chunk) pair, then per (group, chunk) pair the driver term and its hits, back
-// to back.  `over` and `budget` have room in a near batch alone (elsewhere they coincide with their neighbours and are
-// not used).
+// to back, then an any-of batch's block.  `over` and `budget` have room in a near batch alone (elsewhere they coincide
+// with their neighbours and are not used); an any-of batch is carved as a near batch for the sake of `over` and leaves
+// `budget` unused.  `any` is the next multiple of 64 behind the hits where there is a block, else `end` is where it always was.
 struct SeedLayout {
     ClassBlock cls;             // at `anchors`
     RegexBlock rx;              // at `regex`
-    size_t goff, soff, foff, over, pos, fvoid, tflags, budget, anchors, regex, fbytes, tcnt, gdrv, cnt, end;
+    AnyBlock alts;              // at `any`
+    size_t goff, soff, foff, over, pos, fvoid, tflags, budget, anchors, regex, fbytes, tcnt, gdrv, cnt, any, end;
     SeedLayout(uint32_t nrow, uint32_t nterm, uint32_t nq, uint64_t term_total, uint64_t ntp, uint64_t nrp, bool near,
-               const ClassBlock &block, const RegexBlock &rblock = RegexBlock())
-        : cls(block), rx(rblock)
+               const ClassBlock &block, const RegexBlock &rblock = RegexBlock(), const AnyBlock &ablock = AnyBlock())
+        : cls(block), rx(rblock), alts(ablock)
     {
         search_detail::Carver carve;
         goff = carve(((size_t)nrow + 1) * 8);
@@ -366,7 +439,11 @@ struct SeedLayout {
         tcnt = carve((size_t)ntp * 4);
         gdrv = carve.o;
         cnt = gdrv + (size_t)nrp * 4;
-        end = cnt + (size_t)nrp * 4;
+        any = end = cnt + (size_t)nrp * 4;
+        if (alts.end) {
+            any = search_detail::up64(end);
+            end = any + alts.end;
+        }
     }
 };
 

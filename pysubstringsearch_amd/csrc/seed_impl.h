@@ -16,6 +16,9 @@
 // the Match's: FoldMatch compares under ASCII case folding, NearMatch exact bytes within a budget of mismatches.  A third,
 // EditMatch (edit_impl.h), allows insertions and deletions too: it has no fixed window, so for it m is di
 // itself, Match::at asks whether the CANDIDATE (piece, di) stands and Match::before whether one stands in front of di.
+// A fourth, AnyMatch (any_impl.h), takes a term that is a SET of alternatives back to back: a query belongs
+// to one alternative, Match::at verifies that one where the query's position puts it and Match::before asks whether ANY
+// alternative starts in front of it -- windows of several lengths, which is why before() is handed the entry's length.
 // A term that holds a 0x0A occurs in no entry and is flagged void: its pairs count no hit.
 //
 // Bounds, for both kernels and the two kinds with a fixed window (edit_impl.h states its own: it walks byte by byte and
@@ -30,12 +33,23 @@
 // The terms of a seeded batch on the device (Batch::seed_drivers): bytes / off are the terms back to back and their
 // nterms + 1 offsets, soff the nterms + 1 offsets into the queries, pos the position of every QUERY inside its term,
 // budget the mismatches allowed per term -- null under fold.
+// An any-of batch (any_impl.h) has no budgets and puts its own block in their place: `any` points at the
+// three pointers of AnyAlts on the device (AnyBlock of search_layout.h), so that SeedTerms keeps its size and every kernel
+// its arguments.
+struct AnyAlts {
+    const u64 *talts;       // nterms + 1: the alternatives of term g are talts[g] .. talts[g + 1]
+    const u64 *aoff;        // alternatives + 1: alternative j is bytes[aoff[j], aoff[j + 1])
+    const u32 *qalt;        // per query: the alternative it was taken from (pos[v] is its position inside THAT)
+};
 struct SeedTerms {
     const u8 *bytes;
     const u64 *off;
     const u64 *soff;
     const u32 *pos;
-    const u8 *budget;
+    union {
+        const u8 *budget;
+        const AnyAlts *any;
+    };
 };
 
 // One lane per (term, chunk) pair: the hits of the pair are the hits of its queries, one interval behind the other.
@@ -123,13 +137,15 @@ __global__ __launch_bounds__(256) void seed_dedupe_kernel(const ChunkDesc *chunk
     const u32 lane = lane_id(), gl = lane & (TG - 1), gbase = lane & ~(TG - 1);
     const u64 step = (u64)gridDim.x * blockDim.x / TG;
     for (u64 t = ((u64)blockIdx.x * blockDim.x + threadIdx.x) / TG; t < H; t += step) {
-        if (len[t] == kSkip) continue;
+        const u32 l = len[t];
+        if (l == kSkip) continue;
         const u32 s = start[t], m = mpos[t];
         if (m <= s) continue;                                    // (the match stands at the entry's start: nothing starts before it)
         const u64 a = pair_of_hit(hit_off, ngq, t);
         const u32 g = g_drv[a];
         const ChunkDesc ch = chunks[(u32)(a % nc)];
-        const bool dup = Match::before(ch, T, g, s, m - 1, (u32)(T.off[g + 1] - T.off[g]), gl, gbase);
+        // (l, the entry's length as entry_bounds left it: AnyMatch alone asks for it -- its windows have several lengths)
+        const bool dup = Match::before(ch, T, g, s, m - 1, (u32)(T.off[g + 1] - T.off[g]), gl, gbase, l);
         if (dup && gl == 0) len[t] = kSkip;
     }
 }
